@@ -15,9 +15,18 @@ on the HIP kernels of libwsi_hip.so; inputs are resident in HBM when the timed r
 `python bench.py --gpus N` starts its own N ranks as fresh child processes (the parent never touches a GPU); under
 `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` it uses the ranks it was given.
 
-Prints ONE JSON line with `roofline` (dominant kernel, HIP events on the launch stream, live in the timed region),
-`roofline_layer1`, `roofline_bf16` (the same dominant kernel timed in single-pass bf16, outside the timed region)
-and `cpu_baseline` (the CPU oracle timed on this box's host cores over a bounded sample of the same tiles).
+Prints ONE JSON line: `metric`, `value`, `unit`, `ms_per_step` (wall time of one timed step), `dtype`, ... .  A plain run
+sets up, warms up, times --steps steps and prints the line.  Everything measured or checked beside the headline runs only
+with --full, after the timed region: `kernels` / `kernel_leg` and the `roofline*` objects (HIP events on the launch stream,
+one pass of the same steps with one batch in flight), `roofline_bf16` (the dominant kernel in single-pass bf16),
+`cpu_baseline` (the CPU oracle on the host cores over a bounded sample of the same tiles), `contract`, the `parity` leg
+(the other precision mode), the `api` leg (the reference-named drop-in API) and cfg5's `postprocess` leg; without --full
+those keys are null / empty.
+
+--dump-outputs DIR writes the arrays the last timed step returned (rank 0) as DIR/<name>.npy, float64 for float64 and
+32/64-bit integer arrays, float32 otherwise, at most DUMP_BYTES in all: an array over its share of that is replaced by a
+fixed sample of its flattened values, the same positions for the same shape in every run (see dump_outputs).  Inputs and
+weights are seeded, so two builds given the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -41,6 +50,7 @@ KIND_NAMES = {1: 'conv3x3_s1', 5: 'conv3x3_s1_layer1', 2: 'conv3x3_s2', 3: 'conv
               6: 'unet_decoder_conv3x3', 7: 'unet_glue', 8: 'unet_head_1x1', 10: 'unet_tail_fused'}
 SEG_DECODER_GFLOP = 6.04                  # decoder 3x3 convs per 256x256 tile over REAL channels (encoder trunk 3.63 + stem 0.31)
 SEG_TILE_GFLOP = 3.63 + 0.31 + 6.04
+DUMP_BYTES = 48 << 20                     # --dump-outputs: all files together (.npy headers aside)
 
 
 def parse_args():
@@ -71,6 +81,11 @@ def parse_args():
     ap.add_argument('--no-bf16-leg', action='store_true', help='skip the single-pass bf16 timing of the dominant kernel')
     ap.add_argument('--no-parity-leg', action='store_true', help='skip the parity-mode leg after the timed region')
     ap.add_argument('--no-api-leg', action='store_true', help="skip the `api` leg (cfg3 / seg, one GPU): the same slide through the reference-named drop-in API with ITS defaults")
+    ap.add_argument('--full', action='store_true', help='after the timed region, also run the legs beside the headline: per-kernel HIP events and '
+                         'rooflines, bf16 leg, CPU baseline, contract check, other-precision leg, API leg, cfg5 post-process leg (the --no-* '
+                         'switches above then skip single legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step returned as DIR/<name>.npy (float32 / float64, a fixed sample of large arrays)')
     return ap.parse_args()
 
 
@@ -129,6 +144,47 @@ def collect_prof(lib, np, cap, dt):
             per_kind[name] = {'launches': int(sel.sum()), 'avg_ms': tms / int(sel.sum()),
                               'tflops': tfl / (tms * 1e-3) / 1e12, 'share_of_step': (tms * 1e-3 / dt) if dt else None}
     return per_kind
+
+
+def output_arrays(out, prefix=''):
+    """(name, array) pairs of what a step returned: dict entries, nested dicts and the public attributes of result objects
+    (postprocess.TumorBed) as '<key>.<attr>', Python numbers as 0-d arrays; None and strings are skipped."""
+    import numpy as np
+    import torch
+    items = out.items() if isinstance(out, dict) else [(k, v) for k, v in vars(out).items() if not k.startswith('_')]
+    for k, v in items:
+        name = prefix + str(k)
+        if isinstance(v, (torch.Tensor, np.ndarray)):
+            yield name, v
+        elif isinstance(v, (bool, int, float)):
+            yield name, np.asarray(v, np.float64)
+        elif isinstance(v, dict) or (v is not None and not isinstance(v, str) and hasattr(v, '__dict__')):
+            yield from output_arrays(v, name + '.')
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: every array of `out` as path/<name>.npy.  float64 and 32/64-bit integers are written as float64, the
+    rest (fp32, u8 maps, bool) as float32.  Smallest first, each array may take an equal share of what the ones before it
+    left of DUMP_BYTES; a larger one is written as the 1-d sample of its flattened values at the sorted, de-duplicated
+    positions np.unique(default_rng(0).integers(0, n, k)), which depend only on the shapes."""
+    import numpy as np
+    import torch
+    arrays = []
+    for name, a in output_arrays(out):
+        t = torch.as_tensor(a)
+        dt = torch.float64 if t.dtype in (torch.float64, torch.int32, torch.int64) else torch.float32
+        arrays.append((t.numel() * (8 if dt == torch.float64 else 4), name, t, dt))
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BYTES
+    for i, (_, name, t, dt) in enumerate(sorted(arrays, key=lambda e: (e[0], e[1]))):
+        k = left // (len(arrays) - i) // (8 if dt == torch.float64 else 4)
+        if t.numel() > k:
+            flat = t.reshape(-1)
+            idx = np.unique(np.random.default_rng(0).integers(0, flat.numel(), k))
+            t = flat[torch.from_numpy(idx).to(flat.device)]
+        a = t.to(dt).cpu().numpy()
+        left -= a.nbytes
+        np.save(os.path.join(path, name + '.npy'), a)
 
 
 def run_rank(args):
@@ -289,7 +345,7 @@ def run_rank(args):
     for _ in range(args.warmup):
         step()
     fence()
-    prof_on = not args.no_prof
+    prof_on = args.full and not args.no_prof
     per_rank_units = (units_per_step + world - 1) // world
     nb = max(1, -(-per_rank_units // (args.batch * (16 if args.workload == 'cfg4' else 1))))
     launches_per_step = (64 if args.workload == 'seg' else 24) * nb
@@ -315,6 +371,8 @@ def run_rank(args):
     dt = time.perf_counter() - t0
     if gc_off:
         gc.enable()
+    if args.dump_outputs and rank == 0:                     # before any leg below runs the engine again
+        dump_outputs(out, args.dump_outputs)
     if os.environ.get('WSI_BENCH_STEP_TIMES') == '1' and rank == 0:
         print('step enqueue returns (ms): %s | fence %.1f' % (' '.join('%.1f' % (m * 1e3) for m in step_marks), dt * 1e3), file=sys.stderr)
     # Per-kernel leg (roofline objects): the SAME steps once more, right after the timed region, with ONE batch in flight and HIP
@@ -452,7 +510,7 @@ def run_rank(args):
 
     # ------------------------------------------------------------------------------- CPU baseline (rank 0, N = 1)
     cpu_baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload not in ('cfg4', 'seg'):
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.workload not in ('cfg4', 'seg'):
         from oracle import resnet_oracle as R                 # the checker, never the thing measured above
         avail = len(os.sched_getaffinity(0)) if hasattr(os, 'sched_getaffinity') else (os.cpu_count() or 1)
         res = {}
@@ -487,7 +545,7 @@ def run_rank(args):
     # tests/test_gpu_margin.py's output), and - when the headline mode is not `parity` - a parity-mode leg of the same step,
     # timed after the timed region
     contract = parity_leg = None
-    if rank == 0 and args.workload not in ('cfg4', 'seg'):
+    if rank == 0 and args.full and args.workload not in ('cfg4', 'seg'):
         fam = None
         fpath = next((q for q in (os.path.join(ROOT, 'profiles', f) for f in ('r05_margin_families.json', 'r04_margin_families.json', 'r03_margin_families.json')) if os.path.exists(q)),
                      os.path.join(ROOT, 'profiles', 'r05_margin_families.json'))
@@ -497,7 +555,7 @@ def run_rank(args):
                     'max_abs_logit_diff_vs_oracle': cpu_baseline['max_abs_logit_diff_vs_gpu'] if cpu_baseline else None,
                     'oracle_sample_tiles': oracle_sample[1] if cpu_baseline else None,
                     'families_max': (fam or {}).get(args.mode), 'families_source': os.path.relpath(fpath, ROOT) if fam else None}
-    if rank == 0 and world == 1 and planes != PARITY and not args.no_parity_leg and args.workload in ('cfg2', 'cfg3'):
+    if rank == 0 and world == 1 and args.full and planes != PARITY and not args.no_parity_leg and args.workload in ('cfg2', 'cfg3'):
         eng.release_workspaces()
         engp = TrunkEngine(sd, dev, planes=PARITY, head=(cls['fc.0.weight'], cls['fc.0.bias']), max_batch=args.batch, streams=args.streams)
 
@@ -525,7 +583,7 @@ def run_rank(args):
     # a utils.dataset.Dataset_wsis over the slide, utils.eval.predict_tumorbed(model, dataset, ep, mode='cls') - every default
     # left alone (precision='auto': per-slide probe; batch and streams: the engine's own sizing).  Timed after the timed region.
     api = None
-    if rank == 0 and world == 1 and args.workload == 'cfg3' and not args.no_api_leg:
+    if rank == 0 and world == 1 and args.full and args.workload == 'cfg3' and not args.no_api_leg:
         import tempfile
         import myargs
         import resnets_shift
@@ -634,7 +692,7 @@ def run_rank(args):
         del model, net, head
         torch.cuda.empty_cache()
 
-    if rank == 0 and world == 1 and args.workload == 'seg' and not args.no_api_leg:
+    if rank == 0 and world == 1 and args.full and args.workload == 'seg' and not args.no_api_leg:
         # The dense path through the reference-named API: utils.eval.predict_tumorbed(model, dataset, ep, mode='seg') with the model a
         # UNetSeg (the smp.Unet drop-in) over a utils.dataset.Dataset_wsis of the SAME slide (/root/reference/utils/eval.py:196-215).
         # r05: that call takes the engine's fused tile path (utils.eval._dense_batches); `generic_iterator_path` times the loop the
@@ -737,7 +795,7 @@ def run_rank(args):
         del model
         torch.cuda.empty_cache()
 
-    if args.workload == 'seg' and rank == 0:
+    if args.workload == 'seg' and rank == 0 and args.full:
         # roofline of the seg path's dominant kernels = the ten 3x3 convs of the decoder (same conv3x3s1 kernels as the trunk on PF
         # tensors): algorithmic FLOPs over REAL channels (6.04 GFLOP per tile) / their summed HIP-event time in the kernel leg
         k6, k10 = per_kind.get('unet_decoder_conv3x3'), per_kind.get('unet_tail_fused')
@@ -830,7 +888,7 @@ def run_rank(args):
         if args.workload == 'cfg4':
             line['roofline'] = wl.roofline(per_kind)
             line['roofline_layer1'] = None
-        if args.workload == 'cfg5':
+        if args.workload == 'cfg5' and args.full:
             # the post-process leg alone (outside the timed region): HIP events around 5 repetitions on the last step's heat map
             from wsi_segmentation_pipeline_amd import postprocess as PP
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)

@@ -2,7 +2,7 @@
 # A/B of bench --batch caps on one box: tools/ab_batch.sh 6200 6656 ...  (each twice, interleaved; cfg3 default bench)
 for rep in 1 2; do
   for m in "$@"; do
-    python3 bench.py --batch $m --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
+    python3 bench.py --batch $m --full --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
     python3 - $m <<'P'
 import json, sys
 d = json.load(open('/tmp/ab_line.json'))

@@ -5,7 +5,7 @@ L=wsi_segmentation_pipeline_amd/lib/libwsi_hip.so
 for rep in 1 2; do
   for f in $A $B; do
     cp $f $L
-    python3 bench.py "$@" --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
+    python3 bench.py "$@" --full --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
     python3 - $f <<'P'
 import json, sys
 d = json.load(open('/tmp/ab_line.json'))

@@ -2,7 +2,7 @@
 # A/B of wsi_conv_set_mode values on one box: tools/ab_mode.sh 1 8193 [more...]  (each value twice, interleaved; cfg3 default bench)
 for rep in 1 2; do
   for m in "$@"; do
-    python3 bench.py --s2 $m --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
+    python3 bench.py --s2 $m --full --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
     python3 - $m <<'P'
 import json, sys
 d = json.load(open('/tmp/ab_line.json'))

@@ -3,7 +3,7 @@
 W=$1; shift
 for rep in 1 2; do
   for m in "$@"; do
-    python3 bench.py --workload $W --s2 $m --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
+    python3 bench.py --workload $W --s2 $m --full --no-cpu-baseline --no-parity-leg --no-bf16-leg 2>/dev/null > /tmp/ab_line.json
     python3 - $m <<'P'
 import json, sys
 d = json.load(open('/tmp/ab_line.json'))

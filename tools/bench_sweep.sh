@@ -1,11 +1,14 @@
 #!/bin/bash
 # usage: tools/bench_sweep.sh tag "args1" "args2" ...   -> one summary line per arg set
+# (logs under $SWEEP_LOGS, default bench_sweep_logs/)
 tag=$1; shift
+logs=${SWEEP_LOGS:-bench_sweep_logs}
+mkdir -p "$logs"
 i=0
 for a in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 python bench.py --steps 2 --warmup 1 --no-cpu-baseline $a > gpurun_out/bench_${tag}_$i.log 2>&1
-  python - "$a" gpurun_out/bench_${tag}_$i.log <<'PY'
+  timeout -k 10 300 python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline $a > "$logs/bench_${tag}_$i.log" 2>&1
+  python - "$a" "$logs/bench_${tag}_$i.log" <<'PY'
 import json, sys
 ls=[x for x in open(sys.argv[2]) if x.startswith("{")]
 if not ls:
