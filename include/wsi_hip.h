@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 6            /* r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w */
+#define WSI_HIP_ABI_VERSION 7            /* wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -376,6 +376,13 @@ size_t wsi_unet_tail_prepack_bytes(void);
 int wsi_unet_tail_prepack(const float* w1, const float* bn1_weight, const float* bn1_bias, const float* bn1_mean, const float* bn1_var,
                           const float* w2, const float* bn2_weight, const float* bn2_bias, const float* bn2_mean, const float* bn2_var,
                           float eps, const float* head_w, const float* head_b, int cin, int cmid, int classes, void* out);
+/* Bands per image of the fused tail (host, pure): the power of two b dividing h with h / b >= 8 (1 when h < 8) that best fills whole
+ * rounds of `cus` workgroups for n images of a low-resolution map h rows high; -EINVAL for n, h or cus <= 0.  The dispatch uses it with
+ * the device's CU count. */
+int wsi_unet_tail_bands(int n, int h, int cus);
+/* Polls of the fused tail's LDS ring hand-over that ran out (2^20 polls; the slot is overwritten anyway, so the logits of that band
+ * may be wrong with rc 0): *out = the count since the last reset (out may be NULL), reset != 0 clears it.  Synchronous; for tests. */
+int wsi_unet_tail_timeouts(unsigned long long* out, int reset);
 size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes);
 int wsi_unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
 int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,

@@ -234,3 +234,19 @@ def test_unet_tail_prepack_is_the_polyphase_sum(lib):
                 v = (frags[48 + t * 2, lane, j] + frags[48 + t * 2 + 1, lane, j]) * fl[32 + c]
                 exp = w2f[c, ci, dy, dx] if 0 <= dy <= 2 else 0.0
                 assert abs(v - exp) <= 2e-6 * np.abs(w2f).max(), (t, row, ci)
+
+
+def test_unet_tail_bands_rule(lib):
+    """wsi_unet_tail_bands (the fused tail's bands per image, csrc/tail.hip): a power of two dividing h with h / b >= 8 (one band when
+    h < 8); on 256 CUs the shipped batch of 512 tiles of 256 x 256 (h = 128 low-resolution rows) runs ONE band per image and a single
+    image 16; every count 1 .. 16 is reached by some batch <= 512 (tests/test_gpu_unet_tail_edges.py runs each of them)."""
+    f = lib.wsi_unet_tail_bands
+    for cus in (1, 80, 256, 304):
+        for h in list(range(1, 130)) + [256, 384, 512]:
+            for n in (1, 2, 3, 5, 16, 31, 32, 33, 64, 100, 255, 256, 257, 512, 1008, 1009, 4096):
+                b = f(n, h, cus)
+                assert b >= 1 and b & (b - 1) == 0 and h % b == 0, (n, h, cus, b)
+                assert h // b >= 8 or (h < 8 and b == 1), (n, h, cus, b)
+    assert f(512, 128, 256) == 1 and f(1, 128, 256) == 16
+    assert {f(n, 128, 256) for n in range(1, 513)} == {1, 2, 4, 8, 16}
+    assert f(0, 128, 256) == -22 and f(1, 0, 256) == -22 and f(1, 128, 0) == -22

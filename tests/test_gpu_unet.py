@@ -255,8 +255,10 @@ def test_fused_decoder_tail_agrees_with_the_three_launch_path_and_the_spec(dev, 
         return
     assert 0 < d <= 2e-5 * max(scale, 1.0)                                # another rounding of the same conv, not the same bits
     with torch.no_grad():
-        ref = U.unet_forward(sd, x[:1])
-    assert float((fused[:1].cpu() - ref).abs().max()) <= 1e-3 * max(1.0, float(ref.abs().max()) / 16.0)
+        ref = U.unet_forward(sd, x)                                   # every image of the batch, not only the first
+    err = (fused.cpu() - ref).abs().amax((1, 2, 3))
+    print('fused tail vs spec %s: max |dlogit| per image %s' % (shape, ['%.2e' % float(e) for e in err]))
+    assert float(err.max()) <= 1e-3 * max(1.0, float(ref.abs().max()) / 16.0), int(err.argmax())
 
 
 @pytest.mark.parametrize('shape', [(3, 64, 64), (2, 128, 192), (3, 256, 256), (2, 96, 160)])

@@ -484,6 +484,25 @@ def test_batch_sizes_respect_cap_and_cover():
         assert sum(sz) == n and max(sz) <= cap and min(sz) > 0
 
 
+@pytest.mark.parametrize('cap', [1, 2, 3, 7, 64, 100, 512, 1008])
+def test_equal_batches_keep_the_split_and_handle_empty(cap):
+    """unet.equal_batches (the dense U-Net's calls, forward_tiles and utils/eval.py _dense_batches): for n = 0 .. 3000 the batches
+    tile [0, n) without an empty one, start where the formula both call sites used did (the split does not change), and hold at
+    most ceil(1.25 cap) tiles; n = 0 gives no batch (the formula's step was 0 there: range() raised)."""
+    import math
+    from wsi_segmentation_pipeline_amd.unet import equal_batches
+    assert equal_batches(0, cap) == []
+    bound = math.ceil(1.25 * cap)
+    for n in range(1, 3001):
+        got = equal_batches(n, cap)
+        assert got[0][0] == 0 and got[-1][1] == n, (n, cap)
+        assert all(b0[1] == b1[0] for b0, b1 in zip(got, got[1:])), (n, cap)
+        assert all(b > a for a, b in got), (n, cap)
+        assert max(b - a for a, b in got) <= bound, (n, cap)
+        old = list(range(0, n, -(-n // max(1, math.ceil(n / cap - 0.25)))))
+        assert [a for a, _ in got] == old, (n, cap)
+
+
 # ------------------------------------------------------------------------------ precision='auto': one decision per slide and world
 class _FakeTrunk:
     """Stands in for a TrunkEngine on the CPU: logits = per-slide, per-mode constants, calls are recorded."""

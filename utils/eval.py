@@ -90,18 +90,19 @@ def _dense_batches(model, it, scan, dev, forward):
     no fp32 round trip of the five encoder maps between `encoder` and `decoder`) in ITS batch size - the reference's
     `batch_size` flag (30 tiles, myargs.py) leaves the chip mostly idle.  Any other model, a resized scan or a host iterator:
     `forward(batch_image)` over the iterator, as the reference writes it (utils/eval.py:52-60, :196-215)."""
-    from wsi_segmentation_pipeline_amd.unet import UNetSeg
+    from wsi_segmentation_pipeline_amd.unet import UNetSeg, equal_batches
     ds = getattr(it, 'dataset', None)
     if isinstance(model, UNetSeg) and args.scan_resize == 1 and hasattr(it, 'span') and hasattr(scan, 'device_level'):
         eng = model.hip_engine(dev)
         level = scan.device_level(args.scan_level, dev)
         lo, hi = it.span
         ph, pw = ds.params.ph, ds.params.pw
-        nb = max(1, int(np.ceil((hi - lo) / eng._batch(ph, pw) - 0.25)))     # (a quarter over the tuned batch still runs as ONE batch)
-        mb = -(-(hi - lo) // nb)                             # equal batches: no short last batch
+        batches = equal_batches(hi - lo, eng._batch(ph, pw))    # none for an empty span (a rank with no tiles still joins the gather)
+        if not batches:
+            return
         xy_dev = S._upload(ds.tile_xy[lo:hi], torch.int32, dev)     # one asynchronous upload: the host keeps enqueuing batches ahead of the GPU
-        for i in range(0, hi - lo, mb):
-            yield np.ascontiguousarray(ds.tile_xy[lo + i:min(lo + i + mb, hi)]), eng.forward_tiles(level, xy_dev[i:i + mb], ph, pw)
+        for a, b in batches:
+            yield np.ascontiguousarray(ds.tile_xy[lo + a:lo + b]), eng.forward_tiles(level, xy_dev[a:b], ph, pw)
         return
     for batch_x, batch_y, batch_image in it:
         yield np.stack((batch_x.numpy(), batch_y.numpy()), 1), forward(batch_image.to(dev))

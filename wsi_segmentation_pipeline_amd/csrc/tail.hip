@@ -232,6 +232,17 @@ extern "C" int wsi_study_tail_stamps(unsigned long long* out16, int reset) {
 #else
 #define TSTAMP(...)
 #endif
+// Polls of the py = 1 waves that gave up (2^20 sleeps) and overwrote a ring slot B(t - 1) might still read: wrong logits with rc 0.
+// Incremented on that path only (a vector global atomic); read by the tests through wsi_unet_tail_timeouts.
+__device__ unsigned long long g_tail_timeouts;
+extern "C" int wsi_unet_tail_timeouts(unsigned long long* out, int reset) {
+    if (out && hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tail_timeouts), sizeof(g_tail_timeouts)) != hipSuccess) return WSI_EFAULT;
+    if (reset) {
+        const unsigned long long z = 0;
+        if (hipMemcpyToSymbol(HIP_SYMBOL(g_tail_timeouts), &z, sizeof(z)) != hipSuccess) return WSI_EFAULT;
+    }
+    return WSI_OK;
+}
 template <int WT>                                              // low-resolution width / 32: 1, 2 or 4
 __global__ __launch_bounds__(WT == 4 ? 512 : 256, WT == 4 ? 2 : 1) void unet_tail2_kernel(TailArgs a) {
     extern __shared__ __attribute__((aligned(128))) char smem[];
@@ -326,8 +337,10 @@ __global__ __launch_bounds__(WT == 4 ? 512 : 256, WT == 4 ? 2 : 1) void unet_tai
                 if (py == 1) {                                 // row 2t + 1 takes the slot of row 2t - 4: wait for B(t - 1)'s reads of it (the conv2
                     const int need = NC2 * (t - k0);           // waves request them right after their epilogue of B(t - 2))
                     TSTAMP(const unsigned long long tp0 = __builtin_readcyclecounter();)
-                    for (int spin = 0; spin < (1 << 20) && *(volatile int*)flag < need; ++spin) __builtin_amdgcn_s_sleep(1);
+                    int spin = 0;
+                    for (; spin < (1 << 20) && *(volatile int*)flag < need; ++spin) __builtin_amdgcn_s_sleep(1);
                     asm volatile("" ::: "memory");
+                    if (spin == (1 << 20) && lane == 0) atomicAdd(&g_tail_timeouts, 1ull);
                     TSTAMP(ts[3] += __builtin_readcyclecounter() - tp0;)
                 }
                 TSTAMP(tq = __builtin_readcyclecounter();)
@@ -466,8 +479,11 @@ __global__ __launch_bounds__(WT == 4 ? 512 : 256, WT == 4 ? 2 : 1) void unet_tai
 #pragma unroll
                         for (int ti = 0; ti < TPW; ++ti) xload(xq[(tp + 2) % 3][ti], ti, tp + 2);
                     }
-                    if (tp == 0 && lane == 0)                  // taps 0-2 (conv1 row 2j - 2) are requested: count them off behind the reads
-                        __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (tp == 0) {                             // taps 0-2 (conv1 row 2j - 2) are requested: count them off behind the reads
+                        asm volatile("" ::: "memory");         // (compiler barrier only: the reads stay ahead of the add in program order,
+                        if (lane == 0)                         // and LDS runs a wave's operations in that order - no s_waitcnt needed)
+                            __hip_atomic_fetch_add(flag, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    }
                     // lo x hi, hi x lo, hi x hi (conv_dev.h mfma_step<2>), the tiles alternating MFMA by MFMA: a dependent MFMA waits out
                     // its predecessor's passes, two chains hide that
 #pragma unroll
@@ -498,20 +514,11 @@ int g_unet_tail_form = 2;                                      // A/B: wsi_conv_
 size_t wsi_unet_tail_lds_bytes(int w) { return (size_t)4 * (w + 2) * 128 + (size_t)4 * (2 * w + 2) * 64 + 132 * 4; }
 size_t wsi_unet_tail2_lds_bytes(int w) { return (size_t)4 * (w + 2) * 128 + (size_t)5 * (2 * w + 2) * 64 + 128 + 256; }
 
-int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w, int classes, float* logits, hipStream_t st) {
-    if (!x4 || !blob || !logits || n <= 0 || h <= 0 || w % 32 || w < 32 || w > 128 || classes < 1 || classes > 4) return WSI_EINVAL;
-    if ((size_t)pf_alloc_pixels(n, h, w) * 128 > (size_t)0x7fffffff) return WSI_EINVAL;     // 32-bit buffer offsets
-    TailArgs a;
-    a.in = (const char*)x4; a.gl = pf_geom(n, h, w, 32); a.blob = (const char*)blob; a.out = logits; a.classes = classes;
-    // Bands per image: one workgroup per CU runs a whole band, so the grid should fill whole rounds of the chip's CUs (528 images in
-    // one band each = three rounds on 256 CUs, the last one 6 % full) while every band pays two overlap steps: pick the power of two
-    // that maximises (fill of the last round) x rows / (rows + 2), bands of at least 8 low-resolution rows
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+// Bands per image: one workgroup per CU runs a whole band, so the grid should fill whole rounds of the chip's CUs (528 images in
+// one band each = three rounds on 256 CUs, the last one 6 % full) while every band pays two overlap steps: pick the power of two
+// that maximises (fill of the last round) x rows / (rows + 2), bands of at least 8 low-resolution rows (h < 8: one band)
+extern "C" int wsi_unet_tail_bands(int n, int h, int cus) {
+    if (n <= 0 || h <= 0 || cus <= 0) return WSI_EINVAL;
     int bands = 1;
     double best = 0.0;
     for (int b = 1; h % b == 0 && h / b >= 8; b *= 2) {
@@ -519,6 +526,21 @@ int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w
         const double score = (double)wgs / (double)(rounds * cus) * (double)(h / b) / (double)(h / b + 2);
         if (score > best * 1.02) { best = score; bands = b; }      // (ties and near-ties: the fewer bands)
     }
+    return bands;
+}
+
+int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w, int classes, float* logits, hipStream_t st) {
+    if (!x4 || !blob || !logits || n <= 0 || h <= 0 || w % 32 || w < 32 || w > 128 || classes < 1 || classes > 4) return WSI_EINVAL;
+    if ((size_t)pf_alloc_pixels(n, h, w) * 128 > (size_t)0x7fffffff) return WSI_EINVAL;     // 32-bit buffer offsets
+    TailArgs a;
+    a.in = (const char*)x4; a.gl = pf_geom(n, h, w, 32); a.blob = (const char*)blob; a.out = logits; a.classes = classes;
+    static int cus = 0;
+    if (!cus) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        cus = (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+    }
+    const int bands = wsi_unet_tail_bands(n, h, cus);
     a.bands = bands; a.rows_per_band = h / bands;
     if (g_unet_tail_form == 2 && (w == 32 || w == 64 || w == 128)) {
         const size_t lds2 = wsi_unet_tail2_lds_bytes(w);

@@ -46,6 +46,8 @@ SIGNATURES = {
     'wsi_prepack_conv': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _i, _i, _vp, _vp]),
     'wsi_unet_tail_prepack_bytes': (_sz, []),
     'wsi_unet_tail_prepack': (_i, [_vp] * 10 + [_f, _vp, _vp, _i, _i, _i, _vp]),
+    'wsi_unet_tail_bands': (_i, [_i, _i, _i]),
+    'wsi_unet_tail_timeouts': (_i, [C.POINTER(C.c_ulonglong), _i]),
     'wsi_prepack_stem_bytes': (_sz, [_i]),
     'wsi_prepack_stem': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _vp, _vp]),
     'wsi_prepack_stem_u8': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp]),
@@ -137,7 +139,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-ABI_VERSION = 6                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
+ABI_VERSION = 7                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
 
 
 def load():

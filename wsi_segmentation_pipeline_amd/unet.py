@@ -32,6 +32,16 @@ def _pad64(c):
     return (c + 63) // 64 * 64
 
 
+def equal_batches(n, cap):
+    """[(start, stop)] of the U-Net calls for n tiles at a tuned batch of `cap`: ceil(n / cap - 0.25) equal batches (no short last
+    one; a quarter over `cap` still runs as ONE call, so a call holds at most ceil(1.25 cap) tiles).  [] for n = 0."""
+    n, cap = int(n), max(1, int(cap))
+    if n <= 0:
+        return []
+    mb = -(-n // max(1, int(np.ceil(n / cap - 0.25))))
+    return [(i, min(i + mb, n)) for i in range(0, n, mb)]
+
+
 def decoder_key_shapes(classes):
     """[(key, shape, kind)] of the decoder in state-dict order."""
     out, cprev = [], 512
@@ -197,8 +207,9 @@ class UNetEngine:
         _require_gpu(slide_u8, 'slide')
         tile_xy = tile_xy.to(self.device, torch.int32).contiguous()
         n = tile_xy.shape[0]
-        mb = -(-n // max(1, int(np.ceil(n / self._batch(ph, pw) - 0.25))))    # equal batches, no short last one; a quarter over the tuned size is still one
-        parts = [self._run(min(mb, n - i), ph, pw, None, slide_u8, tile_xy[i:i + mb], True, False)[0] for i in range(0, n, mb)]
+        if n == 0:
+            return torch.empty((0, self.classes, ph, pw), dtype=torch.float32, device=self.device)
+        parts = [self._run(b - a, ph, pw, None, slide_u8, tile_xy[a:b], True, False)[0] for a, b in equal_batches(n, self._batch(ph, pw))]
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
     def decode(self, enc):
