@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 7            /* wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w) */
+#define WSI_HIP_ABI_VERSION 8            /* wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w)) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -112,6 +112,11 @@ int wsi_conv3x3_up_concat_bn_act(const void* up_pf, const void* skip_pf, void* o
 int wsi_conv3x3s2_ds_fused(const void* in_pf, void* out_conv_pf, void* out_ds_pf, const void* wpk3, const float* bias3,
                            const void* wpk1, const float* bias1, int n, int h_in, int w_in, int cin, int cout, int planes,
                            void* stream);
+/* Images per launch of wsi_conv3x3s2_ds_fused's phase-slab kernel for an (n, h_in, w_in, cin) input: n when the whole PF input is
+ * under 4 GiB (the kernel's byte offsets are 32-bit), else the largest count whose PF input is; 0 when one image is too large;
+ * -EINVAL for n, h_in, w_in or cin <= 0 or planes outside 1-3.  A larger batch runs as consecutive image sub-ranges of this size
+ * (the last one shorter), bit-identical to one launch.  Pure host arithmetic. */
+int wsi_s2_slab_images(int n, int h_in, int w_in, int cin, int planes);
 /* Phase-split tensors: the four phase images (y&1, x&1) of an (n,h,w,c) tensor, each a PF tensor of geometry
  * (n,h/2,w/2,c), concatenated (wsi_pf_split_bytes = 4 * wsi_pf_bytes(n,h/2,w/2,c,planes); zero-fill once like a PF
  * buffer).  A stride-1 conv can WRITE its output in this form (wsi_conv3x3_bn_act_split; h, w even; planes >= 2) and

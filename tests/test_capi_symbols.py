@@ -250,3 +250,27 @@ def test_unet_tail_bands_rule(lib):
     assert f(512, 128, 256) == 1 and f(1, 128, 256) == 16
     assert {f(n, 128, 256) for n in range(1, 513)} == {1, 2, 4, 8, 16}
     assert f(0, 128, 256) == -22 and f(1, 0, 256) == -22 and f(1, 128, 0) == -22
+
+
+def test_s2_slab_images_rule(lib):
+    """wsi_s2_slab_images (images per launch of the stride-2 block entry's phase-slab kernel, csrc/capi.hip): the whole batch when its
+    PF input is under 4 GiB, else the largest count that is, so consecutive launches of that many images (the last one shorter) cover
+    the batch and each reads less than 4 GiB.  The layer-2 entry of 512 x 512 patches reads 128 x 128 x 64 maps: 1008 images per
+    launch at 4 bytes per channel (modes 2 and 3), 2016 at 2 (mode 1)."""
+    f, pf = lib.wsi_s2_slab_images, lib.wsi_pf_bytes
+    lim = 0xffffffff
+    assert f(1008, 128, 128, 64, 2) == f(1008, 128, 128, 64, 3) == 1008
+    assert f(1009, 128, 128, 64, 2) == f(1009, 128, 128, 64, 3) == 1008
+    assert f(2016, 128, 128, 64, 1) == 2016 and f(2017, 128, 128, 64, 1) == 2016
+    for planes in (1, 2, 3):
+        for hw, cin in ((64, 64), (72, 64), (96, 64), (128, 64), (192, 64), (256, 64), (32, 128), (16, 256)):
+            for n in (1, 2, 450, 451, 1000, 1008, 1009, 1550, 2016, 2017, 3148, 3149, 3970, 3971, 6162, 24648):
+                per = f(n, hw, hw, cin, planes)
+                assert 1 <= per <= n, (planes, hw, n, per)
+                assert pf(per, hw, hw, cin, planes) < lim, (planes, hw, n, per)
+                assert per == n or pf(per + 1, hw, hw, cin, planes) >= lim, (planes, hw, n, per)
+                sizes = [min(per, n - i) for i in range(0, n, per)]   # the launches of wsi_conv3x3s2_ds_fused
+                assert sum(sizes) == n and min(sizes) >= 1 and max(sizes) == per
+    assert f(1, 8192, 8192, 64, 3) == 0                          # one image over 4 GiB: no slab launch at all
+    assert f(0, 128, 128, 64, 3) == -22 and f(1, 0, 128, 64, 3) == -22 and f(1, 128, 128, 0, 3) == -22
+    assert f(1, 128, 128, 64, 0) == -22 and f(1, 128, 128, 64, 4) == -22

@@ -174,7 +174,7 @@ def test_golden_tile_logits_256(dev, sd, golden_dir):
 @pytest.mark.parametrize('shape', [(1, 32, 32), (1, 64, 64), (3, 96, 160), (2, 160, 64), (1, 512, 512), (5, 256, 256)])
 def test_edge_patch_shapes_vs_oracle(dev, sd, shape, planes):
     """Smallest / non-square / large patches and ragged batch sizes through every stage (the 1x1 maps of
-    32x32 patches, the gather fallback of 512x512 ones) against the CPU oracle."""
+    32x32 patches; the layer-2 entry of 512x512 ones on the phase-slab kernel with PMAX = 130, modes 2 and 3) against the CPU oracle."""
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
     n, h, w = shape
     u8 = W.make_u8_patches(100 + h + w, (n, 3, h, w))

@@ -634,6 +634,21 @@ int wsi_conv3x3_up_concat_bn_act(const void* up_pf, const void* skip_pf, void* o
                        nullptr, 0, nullptr, nullptr, 0, up_pf, c_up);
 }
 
+// the phase-slab kernel's byte offsets into its input are 32-bit (conv.hip launch_s2slab refuses a PF input of 4 GiB or more)
+int wsi_s2_slab_images(int n, int h_in, int w_in, int cin, int planes) {
+    if (n <= 0 || h_in <= 0 || w_in <= 0 || cin <= 0 || planes < 1 || planes > 3) return WSI_EINVAL;
+    const unsigned long long pix = (unsigned long long)cin * (planes == 1 ? PFmt<1>::BPC : PFmt<2>::BPC);
+    auto fits = [&](int m) { return (unsigned long long)pf_alloc_pixels(m, h_in, w_in) * pix < 0xffffffffull; };
+    if (fits(n)) return n;
+    if (!fits(1)) return 0;
+    int lo = 1, hi = n;                                // fits(lo), !fits(hi)
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        (fits(mid) ? lo : hi) = mid;
+    }
+    return lo;
+}
+
 int wsi_conv3x3s2_ds_fused(const void* in_pf, void* out_conv_pf, void* out_ds_pf, const void* wpk3, const float* bias3,
                            const void* wpk1, const float* bias1, int n, int h_in, int w_in, int cin, int cout, int planes,
                            void* stream) {
@@ -647,8 +662,23 @@ int wsi_conv3x3s2_ds_fused(const void* in_pf, void* out_conv_pf, void* out_ds_pf
     a.stride = 2; a.ksize = 3; a.relu = 1; a.flags = 0;
     a.out2 = out_ds_pf; a.wpk2 = wpk1; a.bias2 = bias1;
     a.in_split_pixels = 0; a.out_split_pixels = 0;
-    int rc = wsi_s2_dispatch(a, planes, (hipStream_t)stream);
-    if (rc == WSI_EINVAL) {                             // e.g. maps wider than 33: two per-tap gather launches
+    // the phase-slab kernel over image sub-ranges whose PF input is under 4 GiB (wsi_s2_slab_images): views that start at image n0,
+    // so a view's front guard lies in image n0 - 1's zero pads, and every output image reads its own input image only
+    const int per = wsi_s2_slab_images(n, h_in, w_in, cin, planes);
+    const size_t bpc = planes == 1 ? PFmt<1>::BPC : PFmt<2>::BPC;
+    const size_t in_img = (size_t)(h_in + 1) * (w_in + 1) * cin * bpc, out_img = (size_t)(h_in / 2 + 1) * (w_in / 2 + 1) * cout * bpc;
+    int rc = WSI_EINVAL;
+    for (int n0 = 0; per > 0 && n0 < n; n0 += per) {
+        const int nn = n - n0 < per ? n - n0 : per;
+        a.in = (const char*)in_pf + n0 * in_img;
+        a.out = (char*)out_conv_pf + n0 * out_img;
+        a.out2 = (char*)out_ds_pf + n0 * out_img;
+        a.gi = pf_geom_fd(nn, h_in, w_in, cin);
+        a.go = pf_geom_fd(nn, h_in / 2, w_in / 2, cout);
+        rc = wsi_s2_dispatch(a, planes, (hipStream_t)stream);
+        if (rc) break;
+    }
+    if (rc == WSI_EINVAL) {                             // e.g. maps wider than 33 in speed mode: two per-tap gather launches
         rc = conv_common(in_pf, out_conv_pf, nullptr, wpk3, bias3, n, h_in, w_in, cin, cout, 2, 3, 1, planes, stream, 0);
         if (!rc) rc = conv_common(in_pf, out_ds_pf, nullptr, wpk1, bias1, n, h_in, w_in, cin, cout, 2, 1, 0, planes, stream, 0);
     }

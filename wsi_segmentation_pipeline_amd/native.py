@@ -57,6 +57,7 @@ SIGNATURES = {
     'wsi_conv3x3_bn_act': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'wsi_conv3x3_bn_act_cfg': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'wsi_conv3x3s2_ds_fused': (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'wsi_s2_slab_images': (_i, [_i, _i, _i, _i, _i]),
     'wsi_pf_split_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'wsi_conv3x3_bn_act_split': (_i, [_vp] * 5 + [_i] * 7 + [_vp]),
     'wsi_conv3x3_up_concat_bn_act': (_i, [_vp] * 5 + [_i] * 8 + [_vp]),
@@ -139,7 +140,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-ABI_VERSION = 7                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
+ABI_VERSION = 8                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
 
 
 def load():
