@@ -83,11 +83,15 @@ int wsi_stem_conv7x7_bn_relu_maxpool(const float* in_f32, const uint8_t* slide, 
                                      const float* stem_bias_u8, const float* norm_mean_std /* HOST: mean[3], std[3] */,
                                      int n, int h, int w, float* scratch, void* out_pf, int planes, void* stream);
 
-/* tuning / A-B hook: fused = 1 (default) runs the single fused stem+maxpool kernel (no fp32
- * intermediate; scratch unused), fused = 0 the two-kernel form, fused = 2 the fused kernel with the table
- * look-up arithmetic even when u8 weights are supplied, fused = 3 the integer stem in its one-strip launch form (digit
- * planes in registers instead of shared in LDS; bit-identical); rows_per_seg = pooled rows per workgroup of the
- * fused kernel (default 32).  Process-wide. */
+/* tuning / A-B hook, process-wide: which stem launch form runs (`fused`, one of the values below) and how many pooled
+ * rows one workgroup of the fused kernel takes (`rows_per_seg` > 0, default 64).  All four forms agree to the precision
+ * mode's rounding; FUSED and FUSED_ONE_STRIP are bit-identical. */
+enum {
+    WSI_STEM_MODE_UNFUSED = 0,          /* two kernels: stem conv into the fp32 scratch, then the max pool */
+    WSI_STEM_MODE_FUSED = 1,            /* default: one fused stem+maxpool kernel (no fp32 intermediate; scratch unused) */
+    WSI_STEM_MODE_FUSED_LUT = 2,        /* the fused kernel with the table look-up arithmetic even when u8 weights are supplied */
+    WSI_STEM_MODE_FUSED_ONE_STRIP = 3   /* the integer stem, one strip per workgroup: digit planes in registers, not shared in LDS */
+};
 int wsi_stem_set_mode(int fused, int rows_per_seg);
 
 /* ---- conv + folded BN (+ residual) (+ ReLU) (resnets_shift.py:49-65, 19-27) -------------------
@@ -129,24 +133,34 @@ int wsi_conv3x3_bn_act_split(const void* in_pf, void* out_split, const void* res
 int wsi_conv3x3s2_ds_fused_split(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3,
                                  const float* bias3, const void* wpk1, const float* bias1, int n, int h_in, int w_in,
                                  int cin, int cout, int planes, void* stream);
-/* A-B hook: s2_slab = 1 (default) routes stride-2 3x3 convs to the phase-slab kernel (64-pixel tiles) and lets
- * the trunk fuse the downsample branch; 3 = the same with 128-pixel tiles; 0 = per-tap gather kernel + separate
- * 1x1 launch.  Flags added to the value: +8 XCD-aware workgroup order, +16 / +32 use the wide stride-1 kernel only
- * from 256 channels / never (default: from 128), +128 the trunk keeps ordinary PF between stages (no phase-split
- * hand-over to the wide stride-2 kernel), +256 / +512 XCD-contiguous pixel-tile ranges off / 64-channel layer only
- * (default: every stride-1 layer), +2048 the strided blocks' 1x1 downsample as its own tensor + residual instead of an extra K
- * segment of the block's second conv (mode 3), +4096 layer-1 kernel without paired-tile LDS addressing, +16384 the trunk keeps
- * 128-byte lines for the stem output and the layer-1 tensors (mode 3 default: 96-byte lines there - the hi6 plane is rebuilt
- * in LDS by the layer-1 kernel; bit-identical results), +32768 the wide stride-2 kernel with 128 instead of 256 output channels
- * per workgroup on the layer-3 / layer-4 entries (mode 3; bit-identical), +1024 the 64-channel layer 1 on the r03 slab3 kernel instead of
- * the row-stacked kernel (mode 3, 64-wide maps; results equal to a few ulps of the fp32 sums: another summation order), +65536 the
- * U-Net decoder blocks write the upsampled + concatenated tensor before their first conv instead of reading both sources in it
- * (bit-identical), +131072 the wide stride-1 kernel keeps the 9-pixel slab pitch on 8 x 8 maps (r05 default: 8-pixel slab rows, no LDS
- * bank conflicts; bit-identical), +1048576 the 64-channel layer 1 on the persistent producer-fed kernel (r05 study route: bit-identical,
- * measured 30-45 % slower than the row-stacked kernel), +2097152 the U-Net decoder's last block and head as three launches even when
- * the fused-tail weights are present (planes 2; results equal to fp32 rounding of the summed polyphase weights, not bit-identical).
- * Process-wide. */
-int wsi_conv_set_mode(int s2_slab);
+/* A-B hook, process-wide: mode = one base value (the low three bits) plus any of the switch bits below.  The default is
+ * WSI_CONV_MODE_S2_SLAB alone; every other bit is ignored. */
+enum {
+    /* base: how stride-2 3x3 convs run */
+    WSI_CONV_MODE_S2_GATHER = 0,            /* per-tap gather kernel + separate 1x1 downsample launch */
+    WSI_CONV_MODE_S2_SLAB = 1,              /* default: phase-slab kernel (64-pixel tiles); the trunk fuses the downsample branch */
+    WSI_CONV_MODE_S2_SLAB_128 = 3,          /* the same with 128-pixel tiles */
+    /* switches */
+    WSI_CONV_MODE_XCD_ORDER = 8,            /* XCD-aware workgroup order for multi-channel-block launches */
+    WSI_CONV_MODE_WIDE_FROM_256 = 16,       /* wide stride-1 kernel only from 256 channels (default: from 128); wins over WIDE_NEVER */
+    WSI_CONV_MODE_WIDE_NEVER = 32,          /* never the wide stride-1 kernel */
+    WSI_CONV_MODE_S2_ABLATE = 64,           /* study builds only: stride-2 kernel without weight loads (wrong results by design) */
+    WSI_CONV_MODE_NO_S2_SPLIT = 128,        /* the trunk keeps ordinary PF between stages (no phase-split hand-over to the wide stride-2 kernel) */
+    WSI_CONV_MODE_XCD_RANGES_OFF = 256,     /* no XCD-contiguous pixel-tile ranges (default: every stride-1 layer); wins over XCD_RANGES_L1 */
+    WSI_CONV_MODE_XCD_RANGES_L1 = 512,      /* XCD-contiguous pixel-tile ranges on the 64-channel layer only */
+    WSI_CONV_MODE_L1_SLAB3 = 1024,          /* 64-channel layer 1 on the slab3 kernel, not the row-stacked one (mode 3, 64-wide maps; equal to a few ulps: another summation order) */
+    WSI_CONV_MODE_NO_DS_FOLD = 2048,        /* strided blocks' 1x1 downsample as its own tensor + residual, not an extra K segment of the block's second conv (mode 3) */
+    WSI_CONV_MODE_NO_SLAB_PAIR = 4096,      /* layer-1 slab3 kernel without paired-tile LDS addressing */
+    WSI_CONV_MODE_L1_LINES128 = 16384,      /* the trunk keeps 128-byte lines for stem output and layer-1 tensors (mode 3 default: 96-byte lines; bit-identical) */
+    WSI_CONV_MODE_S2_NT2 = 32768,           /* wide stride-2 kernel with 128, not 256, output channels per workgroup (mode 3; bit-identical) */
+    WSI_CONV_MODE_UNET_CONCAT_PASS = 65536, /* U-Net decoder blocks write the upsampled + concatenated tensor before their first conv (bit-identical) */
+    WSI_CONV_MODE_WIDE_NO_D8 = 131072,      /* wide stride-1 kernel keeps the 9-pixel slab pitch on 8 x 8 maps (r05 default: 8-pixel rows; bit-identical) */
+    WSI_CONV_MODE_L1_PERSISTENT = 1048576,  /* 64-channel layer 1 on the persistent producer-fed kernel (r05 study route: bit-identical, 30-45 % slower) */
+    WSI_CONV_MODE_UNET_NO_TAIL = 2097152,   /* U-Net decoder's last block and head as three launches even with fused-tail weights (planes 2; equal to fp32 rounding) */
+    WSI_CONV_MODE_UNET_TAIL_FORM1 = 4194304,/* the fused U-Net tail in its first form (every wave does both convs), not the specialised one */
+    WSI_CONV_MODE_UNET_X0_UNFUSED = 8388608 /* U-Net skip x0 from a separate unfused stem conv, not stored by the fused stem kernel (planes 2, u8 input) */
+};
+int wsi_conv_set_mode(int mode);
 /* tuning hook: same as wsi_conv3x3_bn_act with an explicit tile configuration for the stride-1
  * kernel (cfg index into the table in csrc/conv.hip; -1 = tuned default; -22 if not applicable) */
 int wsi_conv3x3_bn_act_cfg(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,

@@ -30,6 +30,20 @@ def test_header_symbols_exported(lib):
     assert int(re.search(r'#define WSI_HIP_ABI_VERSION (\d+)', hdr).group(1)) == native.ABI_VERSION == lib.wsi_hip_abi_version()
 
 
+def test_mode_names_match_header():
+    """native.ConvMode / StemMode mirror the WSI_CONV_MODE_* / WSI_STEM_MODE_* enumerators of the header, name for name and value for
+    value; apart from the 0 / 1 / 3 base values every conv mode constant is one bit of its own."""
+    hdr = open(os.path.join(ROOT, 'include', 'wsi_hip.h')).read()
+    hdr = re.sub(r'/\*.*?\*/', '', hdr, flags=re.S)
+    for prefix, enum_cls in (('WSI_CONV_MODE_', native.ConvMode), ('WSI_STEM_MODE_', native.StemMode)):
+        in_header = {m.group(1): int(m.group(2)) for m in re.finditer(prefix + r'(\w+)\s*=\s*(\d+)', hdr)}
+        assert in_header == {name: int(m) for name, m in enum_cls.__members__.items()}, prefix
+    M = native.ConvMode
+    assert (int(M.S2_GATHER), int(M.S2_SLAB), int(M.S2_SLAB_128)) == (0, 1, 3)
+    bits = [int(m) for name, m in M.__members__.items() if name not in ('S2_GATHER', 'S2_SLAB', 'S2_SLAB_128')]
+    assert len(bits) >= 18 and all(b > 7 and b & (b - 1) == 0 for b in bits) and len(set(bits)) == len(bits)
+
+
 def test_pf_layout_helpers(lib):
     # pixel (n,y,x) -> (W+2) + n*(H+1)*(W+1) + y*(W+1) + x
     assert lib.wsi_pf_pixel_index(0, 0, 0, 8, 8) == 10

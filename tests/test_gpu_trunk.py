@@ -63,17 +63,13 @@ def test_u8_slide_path_equals_f32_path(dev, sd):
     with torch.no_grad():
         taps = {}
         R.trunk(sd, x, taps)
-    lib = native.load()
     for planes in (2, 3):
         eng = TrunkEngine(sd, dev, planes=planes)
         sl, xyd = torch.from_numpy(slide).to(dev), torch.from_numpy(xy).to(dev)
         b = eng.forward_f32(x.to(dev), feat=True)[0].clone()
         a = eng.forward_tiles(sl, xyd, 64, 64, feat=True, logits=False)[0].clone()
-        try:
-            native.check(lib.wsi_stem_set_mode(2, 32), 'stem mode')
+        with native.stem_mode(native.StemMode.FUSED_LUT, 32):
             a_lut = eng.forward_tiles(sl, xyd, 64, 64, feat=True, logits=False)[0].clone()
-        finally:
-            lib.wsi_stem_set_mode(1, 64)
         if planes == 2:
             assert torch.equal(a_lut, b)
         scale = float(b.abs().max())
@@ -197,18 +193,12 @@ def test_unfused_reference_kernels_agree(dev, sd):
     the same logits as the fused defaults."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     u8 = W.make_u8_patches(77, (6, 3, 128, 128))
     x = R.normalize_u8(u8).to(dev)
     eng = TrunkEngine(sd, dev, planes=2, head=(sd['fc0.weight'], sd['fc0.bias']))
     base = eng.forward_f32(x, logits=True)[1].clone()
-    try:
-        native.check(lib.wsi_stem_set_mode(0, 32), 'stem mode')
-        native.check(lib.wsi_conv_set_mode(0), 'conv mode')
+    with native.stem_mode(native.StemMode.UNFUSED, 32), native.conv_mode(base=native.ConvMode.S2_GATHER):
         alt = eng.forward_f32(x, logits=True)[1].clone()
-    finally:
-        lib.wsi_stem_set_mode(1, 64)
-        lib.wsi_conv_set_mode(1)
     assert float((alt - base).abs().max()) <= 1e-4
 
 
@@ -218,7 +208,6 @@ def test_integer_stem_forms_bit_identical(dev, sd):
     bit-identical pooled outputs, including an odd number of strips (a half-filled last workgroup) and short segments."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     rng = np.random.default_rng(17)
     slide = torch.from_numpy(rng.integers(0, 256, (700, 900, 3), dtype=np.uint8)).to(dev)
     for planes in (2, 3):
@@ -226,13 +215,10 @@ def test_integer_stem_forms_bit_identical(dev, sd):
         for tile, n in ((256, 3), (64, 5), (192, 1)):                   # 5 strips x 2 segments x 3; 1 strip x 1 x 5; 4 strips x 2 segments
             xy = torch.from_numpy(rng.integers(-30, 600, (n, 2)).astype(np.int32)).to(dev)
             for rows in (32, 7):
-                try:
-                    native.check(lib.wsi_stem_set_mode(1, rows), 'stem mode')
+                with native.stem_mode(native.StemMode.FUSED, rows):
                     a = eng.forward_tiles(slide, xy, tile, tile, logits=False, tap=0).clone()
-                    native.check(lib.wsi_stem_set_mode(3, rows), 'stem mode')
+                with native.stem_mode(native.StemMode.FUSED_ONE_STRIP, rows):
                     b = eng.forward_tiles(slide, xy, tile, tile, logits=False, tap=0).clone()
-                finally:
-                    lib.wsi_stem_set_mode(1, 64)
                 assert torch.equal(a, b), (planes, tile, n, rows)
 
 
@@ -241,22 +227,21 @@ def test_ab_switches_agree(dev, sd):
     orders, 128-pixel stride-2 tiles) gives the same logits up to summation order."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     u8 = W.make_u8_patches(78, (5, 3, 128, 128))
     x = R.normalize_u8(u8).to(dev)
     for planes, tol in ((3, 2e-4), (2, 2e-5)):
         eng = TrunkEngine(sd, dev, planes=planes, head=(sd['fc0.weight'], sd['fc0.bias']))
         base = eng.forward_f32(x, logits=True)[1].clone()
-        try:
-            # (+2048: the strided blocks' downsample as its own tensor + residual instead of folded into the second conv; +4096:
-            #  layer-1 kernel without paired-tile addressing - that one must not change a bit)
-            for mode in (3, 1 + 8, 1 + 16, 1 + 32, 1 + 128, 1 + 256, 1 + 512, 3 + 32 + 128 + 256, 1 + 2048, 1 + 2048 + 4096, 1 + 16384, 1 + 32768):
-                native.check(lib.wsi_conv_set_mode(mode), 'conv mode')
+        # (NO_DS_FOLD: the strided blocks' downsample as its own tensor + residual instead of folded into the second conv;
+        #  NO_SLAB_PAIR: layer-1 kernel without paired-tile addressing - that one must not change a bit)
+        M = native.ConvMode
+        for mode in (M.S2_SLAB_128, M.S2_SLAB | M.XCD_ORDER, M.S2_SLAB | M.WIDE_FROM_256, M.S2_SLAB | M.WIDE_NEVER, M.S2_SLAB | M.NO_S2_SPLIT,
+                     M.S2_SLAB | M.XCD_RANGES_OFF, M.S2_SLAB | M.XCD_RANGES_L1, M.S2_SLAB_128 | M.WIDE_NEVER | M.NO_S2_SPLIT | M.XCD_RANGES_OFF,
+                     M.S2_SLAB | M.NO_DS_FOLD, M.S2_SLAB | M.NO_DS_FOLD | M.NO_SLAB_PAIR, M.S2_SLAB | M.L1_LINES128, M.S2_SLAB | M.S2_NT2):
+            with native.conv_mode(base=mode):
                 alt = eng.forward_f32(x, logits=True)[1].clone()
-                err = float((alt - base).abs().max())
-                assert err <= tol, (planes, mode, err)
-        finally:
-            lib.wsi_conv_set_mode(1)
+            err = float((alt - base).abs().max())
+            assert err <= tol, (planes, int(mode), err)
 
 
 def test_forward_is_bit_deterministic(dev, sd):
@@ -310,19 +295,15 @@ def test_paired_tile_addressing_is_bit_identical(dev, sd):
     without the residual; and 64x64 tiles (16-wide layer 1: PAIR not applicable) still run."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     g = torch.Generator(device=dev).manual_seed(9)
     slide = torch.randint(0, 256, (256 * 2, 256 * 3, 3), dtype=torch.uint8, device=dev, generator=g)
     xy = torch.tensor([[256 * (i % 3), 256 * (i // 3)] for i in range(6)], dtype=torch.int32, device=dev)
     eng = TrunkEngine(sd, dev, planes=3, head=(sd['fc0.weight'], sd['fc0.bias']), max_batch=6)
     base = [t.clone() for t in eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)]
-    try:
-        native.check(lib.wsi_conv_set_mode(1 + 4096), 'conv mode')
+    with native.conv_mode(native.ConvMode.NO_SLAB_PAIR):
         alt = eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)
         for a, b in zip(alt, base):
             assert torch.equal(a, b)
-    finally:
-        lib.wsi_conv_set_mode(1)
     small = torch.randint(0, 256, (64, 64 * 5, 3), dtype=torch.uint8, device=dev, generator=g)
     xy5 = torch.tensor([[64 * i, 0] for i in range(5)], dtype=torch.int32, device=dev)
     assert bool(torch.isfinite(eng.forward_tiles(small, xy5, 64, 64, logits=True)[1]).all())
@@ -336,7 +317,6 @@ def test_96_byte_layer1_lines_are_bit_identical(dev, sd):
     stage-0 buffers) and tap runs (128-byte lines in the SAME buffers, whose pad bytes sit elsewhere) stays exact."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     g = torch.Generator(device=dev).manual_seed(19)
     eng = TrunkEngine(sd, dev, planes=3, head=(sd['fc0.weight'], sd['fc0.bias']), max_batch=7)
     for th, tw, n in ((256, 256, 7), (64, 64, 5), (128, 192, 3)):
@@ -350,12 +330,9 @@ def test_96_byte_layer1_lines_are_bit_identical(dev, sd):
         new = run()
         tap1 = eng.forward_tiles(slide, xy, th, tw, logits=False, tap=1).clone()      # 128-byte lines in the buffers the full run left in 96
         again = run()                                                              # ... and back
-        try:
-            native.check(lib.wsi_conv_set_mode(1 + 16384), 'conv mode')
+        with native.conv_mode(native.ConvMode.L1_LINES128):
             old = run()
             tap1_old = eng.forward_tiles(slide, xy, th, tw, logits=False, tap=1).clone()
-        finally:
-            lib.wsi_conv_set_mode(1)
         for a, b, c in zip(new, old, again):
             assert torch.equal(a, b) and torch.equal(a, c), (th, tw)
         assert torch.equal(tap1, tap1_old)
@@ -367,20 +344,16 @@ def test_256_cout_stride2_workgroups_are_bit_identical(dev, sd):
     on 256x256 tiles (dense 16x16 / 8x8 output maps) and 64x64 crops (4x4 / 2x2: the non-dense form)."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     g = torch.Generator(device=dev).manual_seed(23)
     eng = TrunkEngine(sd, dev, planes=3, head=(sd['fc0.weight'], sd['fc0.bias']), max_batch=9)
     for t, n in ((256, 9), (64, 7)):
         slide = torch.randint(0, 256, (t * 3, t * 3, 3), dtype=torch.uint8, device=dev, generator=g)
         xy = torch.tensor([[t * (i % 3), t * (i // 3)] for i in range(n)], dtype=torch.int32, device=dev)
         new = [v.clone() for v in eng.forward_tiles(slide, xy, t, t, feat=True, logits=True, fmap=True)]
-        try:
-            native.check(lib.wsi_conv_set_mode(1 + 32768), 'conv mode')
+        with native.conv_mode(native.ConvMode.S2_NT2):
             old = eng.forward_tiles(slide, xy, t, t, feat=True, logits=True, fmap=True)
             for a, b in zip(new, old):
                 assert torch.equal(a, b), t
-        finally:
-            lib.wsi_conv_set_mode(1)
 
 
 def test_eight_pixel_slab_rows_are_bit_identical(dev, sd):
@@ -391,7 +364,6 @@ def test_eight_pixel_slab_rows_are_bit_identical(dev, sd):
     strided block (layer4.0.conv2 carries the folded 1x1 downsample in mx)."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     g = torch.Generator(device=dev).manual_seed(29)
     for planes in (3, 2, 1):
         eng = TrunkEngine(sd, dev, planes=planes, head=(sd['fc0.weight'], sd['fc0.bias']), max_batch=16)
@@ -399,13 +371,10 @@ def test_eight_pixel_slab_rows_are_bit_identical(dev, sd):
             slide = torch.randint(0, 256, (256 * 3, 256 * 3, 3), dtype=torch.uint8, device=dev, generator=g)
             xy = torch.tensor([[256 * (i % 3), 256 * (i // 3)] for i in range(n)], dtype=torch.int32, device=dev)
             new = [v.clone() for v in eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)]
-            try:
-                native.check(lib.wsi_conv_set_mode(1 + 131072), 'conv mode')
+            with native.conv_mode(native.ConvMode.WIDE_NO_D8):
                 old = eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)
                 for a, b in zip(new, old):
                     assert torch.equal(a, b), (planes, n)
-            finally:
-                lib.wsi_conv_set_mode(1)
 
 
 def test_persistent_layer1_kernel_is_bit_identical(dev, sd):
@@ -415,17 +384,13 @@ def test_persistent_layer1_kernel_is_bit_identical(dev, sd):
     (1, 3, 9 tiles) and a ragged split over the eight XCD ranges (17)."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.engine import TrunkEngine
-    lib = native.load()
     g = torch.Generator(device=dev).manual_seed(31)
     eng = TrunkEngine(sd, dev, planes=3, head=(sd['fc0.weight'], sd['fc0.bias']), max_batch=64)
     slide = torch.randint(0, 256, (256 * 7, 256 * 6, 3), dtype=torch.uint8, device=dev, generator=g)
     for n in (40, 17, 9, 3, 1):
         xy = torch.tensor([[256 * (i % 6), 256 * (i // 6)] for i in range(n)], dtype=torch.int32, device=dev)
         new = [v.clone() for v in eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)]
-        try:
-            native.check(lib.wsi_conv_set_mode(1 + 1048576), 'conv mode')
+        with native.conv_mode(native.ConvMode.L1_PERSISTENT):
             old = eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)
             for a, b in zip(new, old):
                 assert torch.equal(a, b), n
-        finally:
-            lib.wsi_conv_set_mode(1)

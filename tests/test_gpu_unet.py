@@ -229,20 +229,16 @@ def test_fused_decoder_tail_agrees_with_the_three_launch_path_and_the_spec(dev, 
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
     n, h, w = shape
-    lib = native.load()
     u8 = W.make_u8_patches(90 + h + w, (n, 3, h, w))
     x = R.normalize_u8(u8)
     sd = _scaled_to_logit(sd, x[:1] if h * w > 128 * 192 else x)
     eng = UNetEngine(sd, dev, planes=2)
     assert eng.dw.tail_w
     fused = eng.forward_f32(x.to(dev))[0]
-    try:
-        lib.wsi_conv_set_mode(1 + 4194304)                                # the first form of the kernel (all waves do both convs)
+    with native.conv_mode(native.ConvMode.UNET_TAIL_FORM1):                   # the first form of the kernel (all waves do both convs)
         form1 = eng.forward_f32(x.to(dev))[0]
-        lib.wsi_conv_set_mode(1 + 2097152)
+    with native.conv_mode(native.ConvMode.UNET_NO_TAIL):
         plain = eng.forward_f32(x.to(dev))[0]
-    finally:
-        lib.wsi_conv_set_mode(1)
     assert torch.equal(fused, eng.forward_f32(x.to(dev))[0])             # (the specialised form synchronises through an LDS counter: same bits every run)
     d12 = float((fused - form1).abs().max())
     assert d12 <= 2e-6 * max(float(plain.abs().max()), 1.0), d12          # same weights, same products; the head sums in another order
@@ -270,7 +266,6 @@ def test_stem_kernel_stores_the_half_resolution_skip_itself(dev, sd, shape):
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
     n, h, w = shape
-    lib = native.load()
     rng = np.random.default_rng(h + w)
     slide_np = rng.integers(0, 256, (h + 40, 2 * w + 24, 3), dtype=np.uint8)
     slide = torch.from_numpy(slide_np).to(dev)
@@ -280,11 +275,8 @@ def test_stem_kernel_stores_the_half_resolution_skip_itself(dev, sd, shape):
     sd = _scaled_to_logit(sd, x[:1])
     eng = UNetEngine(sd, dev, planes=2)
     fused = eng.forward_tiles(slide, xy, h, w)
-    lib.wsi_conv_set_mode(1 + 8388608)
-    try:
+    with native.conv_mode(native.ConvMode.UNET_X0_UNFUSED):
         plain = eng.forward_tiles(slide, xy, h, w)
-    finally:
-        lib.wsi_conv_set_mode(1)
     d = float((fused - plain).abs().max())
     print('x0 from the pool kernel vs the unfused stem conv %s: max |dlogit| %.3g' % (shape, d))
     assert 0 < d <= 2e-4
@@ -298,7 +290,6 @@ def test_fused_decoder_tail_with_fewer_classes(dev, classes):
     """The fused tail pads the head to four classes in its weight blob and stores only the real ones: 1-3 classes against the three launches."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
-    lib = native.load()
     sdc = W.make_unet_state_dict(9, classes)
     x = R.normalize_u8(W.make_u8_patches(77 + classes, (2, 3, 64, 128)))
     sdc = _scaled_to_logit(sdc, x)
@@ -306,11 +297,8 @@ def test_fused_decoder_tail_with_fewer_classes(dev, classes):
     assert eng.dw.tail_w
     fused = eng.forward_f32(x.to(dev))[0]
     assert tuple(fused.shape) == (2, classes, 64, 128)
-    lib.wsi_conv_set_mode(1 + 2097152)
-    try:
+    with native.conv_mode(native.ConvMode.UNET_NO_TAIL):
         plain = eng.forward_f32(x.to(dev))[0]
-    finally:
-        lib.wsi_conv_set_mode(1)
     d = float((fused - plain).abs().max())
     assert 0 < d <= 2e-5 * max(float(plain.abs().max()), 1.0), d
     with torch.no_grad():

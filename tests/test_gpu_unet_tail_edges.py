@@ -20,10 +20,11 @@ import torch.multiprocessing as mp
 from oracle import resnet_oracle as R
 from oracle import unet_oracle as U
 from oracle import weights as W
+from wsi_segmentation_pipeline_amd import native
 
 pytestmark = pytest.mark.gpu
 
-FORM1, THREE_LAUNCHES = 1 + 4194304, 1 + 2097152           # wsi_conv_set_mode A/B switches (include/wsi_hip.h)
+FORM1, THREE_LAUNCHES = native.ConvMode.UNET_TAIL_FORM1, native.ConvMode.UNET_NO_TAIL      # wsi_conv_set_mode A/B switches (include/wsi_hip.h)
 SPEC_TOL = 1e-3                                            # absolute, logits scaled to |logit| 16 (the contract of the dense path)
 _SPEC = {}                                                 # (th, tw, x, y) -> float64 spec logits of that tile
 
@@ -120,13 +121,10 @@ def _check_case(lib, sh, n, bands):
     xy = torch.from_numpy(xy_np)
     _timeouts(lib)
     fused = eng.forward_tiles(sh.level, xy, th, tw)
-    try:
-        lib.wsi_conv_set_mode(FORM1)
+    with native.conv_mode(FORM1):
         form1 = eng.forward_tiles(sh.level, xy, th, tw)
-        lib.wsi_conv_set_mode(THREE_LAUNCHES)
+    with native.conv_mode(THREE_LAUNCHES):
         plain = eng.forward_tiles(sh.level, xy, th, tw)
-    finally:
-        lib.wsi_conv_set_mode(1)
     again = eng.forward_tiles(sh.level, xy, th, tw)
     assert tuple(fused.shape) == (n, 4, th, tw)
     assert torch.equal(fused, again)                                 # the LDS counter hand-over: same bits every run
@@ -209,11 +207,8 @@ def test_tail_at_its_32_bit_limit(dev, lib):
             xy = torch.from_numpy(xy_np)
             _timeouts(lib)
             fused = sh.eng.forward_tiles(sh.level, xy, 256, 256)
-            lib.wsi_conv_set_mode(THREE_LAUNCHES)
-            try:
+            with native.conv_mode(THREE_LAUNCHES):
                 plain = sh.eng.forward_tiles(sh.level, xy, 256, 256)
-            finally:
-                lib.wsi_conv_set_mode(1)
             d = float((fused - plain).abs().max())
             scale = float(plain.abs().max())
             errs = []

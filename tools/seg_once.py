@@ -12,7 +12,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument('--mode', default='parity')
 ap.add_argument('--n', type=int, default=128)
 ap.add_argument('--reps', type=int, default=2)
-ap.add_argument('--set-mode', type=int, default=0)
+ap.add_argument('--set-mode', type=int, default=0, help='sum of native.ConvMode switch bits, added to ConvMode.S2_SLAB')
 a = ap.parse_args()
 dev = torch.device('cuda:0')
 usd = W.make_unet_state_dict(5, classes=4)
@@ -20,7 +20,7 @@ for key in ('decoder.final_conv.weight', 'decoder.final_conv.bias'):
     usd[key] = usd[key] * (8.0 / 216.0)
 eng = UNetEngine(usd, dev, planes={'parity': PARITY, 'mx': MX, 'speed': SPEED}[a.mode], max_batch=a.n)
 if a.set_mode:
-    native.load().wsi_conv_set_mode(1 + a.set_mode)
+    native.load().wsi_conv_set_mode(native.ConvMode.S2_SLAB | a.set_mode)
 side = 1
 while side * side < a.n:
     side += 1

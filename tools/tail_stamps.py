@@ -20,7 +20,7 @@ eng = UNetEngine(usd, dev, planes=PARITY, max_batch=n)
 lib = native.load()
 lib.wsi_study_tail_stamps.argtypes = [C.c_void_p, C.c_int]
 if len(sys.argv) > 2:
-    lib.wsi_conv_set_mode(1 + int(sys.argv[2]))
+    lib.wsi_conv_set_mode(native.ConvMode.S2_SLAB | int(sys.argv[2]))        # argv[2]: sum of ConvMode switch bits, e.g. int(ConvMode.UNET_TAIL_FORM1)
 side = 1
 while side * side < n:
     side += 1

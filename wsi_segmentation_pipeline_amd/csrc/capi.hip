@@ -124,6 +124,8 @@ size_t wsi_resample_scratch_bytes_impl(const wsi_resample_plan* p, int n);
 int wsi_resample_tiles_impl(const wsi_resample_plan* p, const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, int N,
                             uint8_t* out, void* scratch, hipStream_t st);
 
+ConvRoutes g_routes;                                  // the one instance of the route switches (common.h), at their defaults
+
 extern "C" {
 
 int wsi_hip_abi_version(void) { return WSI_HIP_ABI_VERSION; }
@@ -467,37 +469,50 @@ int wsi_normalize_u8_lut(const float mean[3], const float std_[3], float* lut_ou
 }
 
 // ------------------------------------------------------------------------------------ single ops
-static int g_stem_fused = 1, g_stem_rows = 64;       // fused stem+maxpool kernel; pooled rows per workgroup (r05 sweep: 16 / 32 / 64 -> 6.41 / 6.16 / 6.08 ms per 6 162 tiles)
-extern int g_stem_shared_weights;                     // stem.hip
-static int g_stem_u8x = 1;                            // exact-u8 arithmetic when the caller supplies its weights (A/B: fused = 2 disables)
-
 int wsi_stem_set_mode(int fused, int rows_per_seg) {
     if (rows_per_seg <= 0) return WSI_EINVAL;
-    g_stem_fused = fused ? 1 : 0; g_stem_rows = rows_per_seg; g_stem_u8x = fused != 2;
-    g_stem_shared_weights = fused != 3;                // 3: integer stem in its one-strip form (weights in registers), A/B
+    g_routes.stem_fused = fused != WSI_STEM_MODE_UNFUSED; g_routes.stem_rows = rows_per_seg;
+    g_routes.stem_u8x = fused != WSI_STEM_MODE_FUSED_LUT;
+    g_routes.stem_shared_weights = fused != WSI_STEM_MODE_FUSED_ONE_STRIP;
     return WSI_OK;
 }
 
+// Where a batch's tiles come from: f32 NCHW images (in_f32), or a u8 RGB slide + one (x, y) corner per tile + the normalisation
+// table.  The C-ABI entries fill it once; n images of h x w travel beside it.
+struct TileSource {
+    const float* in_f32;
+    const uint8_t* slide;
+    long long pitch; int SH, SW;                      // bytes per slide row; slide height and width in pixels
+    const int* tile_xy;
+    const float* lut;
+    bool valid() const { return in_f32 || (slide && tile_xy && lut); }
+    TileSource from_image(int n0, int h, int w) const {           // the same source, starting at image n0
+        return {in_f32 ? in_f32 + (size_t)n0 * 3 * h * w : nullptr, slide, pitch, SH, SW, tile_xy ? tile_xy + 2 * n0 : nullptr, lut};
+    }
+};
+// the stem's view of a source; the caller adds weights and outputs
+static StemArgs stem_args(const TileSource& src, const void* wpk, const float* bias, float* scratch, int n, int h, int w) {
+    StemArgs a;
+    a.mode = src.in_f32 ? 0 : 1;
+    a.in_f32 = src.in_f32; a.slide = src.slide; a.slide_pitch = src.pitch; a.SH = src.SH; a.SW = src.SW;
+    a.origins = src.tile_xy; a.lut = src.lut; a.wpk = wpk; a.bias = bias; a.out = scratch;
+    a.N = n; a.H = h; a.W = w; a.wpk_u8 = nullptr; a.bias_u8 = nullptr;
+    return a;
+}
+
 // out96 (trunk, mode 3): the pooled map is written in 96-byte lines (common.h CONV_OUT96) for a layer-1 kernel that reads them
-static int stem_run(const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes,
-                    int slide_h, int slide_w, const int* tile_xy, const float* lut,
-                    const void* stem_wpk, const float* stem_bias, const void* stem_wpk_u8,
+static int stem_run(const TileSource& src, const void* stem_wpk, const float* stem_bias, const void* stem_wpk_u8,
                     const float* stem_bias_u8, const float* norm_mean_std, int n, int h, int w,
                     float* scratch, void* out_pf, int planes, void* stream, int out96, long long plane96 = 0, void* x0_pf = nullptr) {
     if (!stem_wpk || !stem_bias || !scratch || !out_pf || n <= 0 || h % 16 || w % 4) return WSI_EINVAL;
-    if (!in_f32 && (!slide || !tile_xy || !lut)) return WSI_EINVAL;
-    StemArgs a;
-    a.mode = in_f32 ? 0 : 1;
-    a.in_f32 = in_f32; a.slide = slide; a.slide_pitch = slide_pitch_bytes; a.SH = slide_h; a.SW = slide_w;
-    a.origins = tile_xy; a.lut = lut; a.wpk = stem_wpk; a.bias = stem_bias; a.out = scratch;
-    a.N = n; a.H = h; a.W = w;
-    a.wpk_u8 = nullptr; a.bias_u8 = nullptr;
+    if (!src.valid()) return WSI_EINVAL;
+    StemArgs a = stem_args(src, stem_wpk, stem_bias, scratch, n, h, w);
     // integer stem for u8 slide input (the transform is inside the packed weights; norm_mean_std is kept in the signature
     // for ABI stability and as the caller's statement of which transform those weights carry)
-    if (stem_wpk_u8 && stem_bias_u8 && norm_mean_std && !in_f32 && g_stem_u8x) { a.wpk_u8 = stem_wpk_u8; a.bias_u8 = stem_bias_u8; }
+    if (stem_wpk_u8 && stem_bias_u8 && norm_mean_std && !src.in_f32 && g_routes.stem_u8x) { a.wpk_u8 = stem_wpk_u8; a.bias_u8 = stem_bias_u8; }
     if (out96 && planes != 3) return WSI_EINVAL;
-    if (x0_pf && !(a.wpk_u8 && g_stem_fused && planes == 2)) return WSI_EINVAL;       // (the x0 output: integer fused stem, fp16-pair lines)
-    if (g_stem_fused || planes == 3) return wsi_stem_pool_dispatch(a, out_pf, planes, g_stem_rows, (hipStream_t)stream, out96, plane96, x0_pf);
+    if (x0_pf && !(a.wpk_u8 && g_routes.stem_fused && planes == 2)) return WSI_EINVAL;       // (the x0 output: integer fused stem, fp16-pair lines)
+    if (g_routes.stem_fused || planes == 3) return wsi_stem_pool_dispatch(a, out_pf, planes, g_routes.stem_rows, (hipStream_t)stream, out96, plane96, x0_pf);
     int rc = wsi_stem_dispatch(a, planes, (hipStream_t)stream);
     if (rc) return rc;
     return wsi_maxpool_dispatch(scratch, out_pf, n, h / 2, w / 2, planes, (hipStream_t)stream);
@@ -508,79 +523,101 @@ int wsi_stem_conv7x7_bn_relu_maxpool(const float* in_f32, const uint8_t* slide, 
                                      const void* stem_wpk, const float* stem_bias, const void* stem_wpk_u8,
                                      const float* stem_bias_u8, const float* norm_mean_std, int n, int h, int w,
                                      float* scratch, void* out_pf, int planes, void* stream) {
-    return stem_run(in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut, stem_wpk, stem_bias, stem_wpk_u8, stem_bias_u8,
+    return stem_run({in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, stem_wpk, stem_bias, stem_wpk_u8, stem_bias_u8,
                     norm_mean_std, n, h, w, scratch, out_pf, planes, stream, 0);
 }
-
-static int g_s2_slab = 1;                             // stride-2 convs: phase-slab kernel (1) or per-tap gather kernel (0)
-static int g_s2_split = 1;                            // trunk: phase-split stage outputs + wide stride-2 kernel (A/B: wsi_conv_set_mode +128 off)
-static int g_ds_fold = 1;                             // trunk, mode 3: the strided blocks' 1x1 downsample runs inside their second conv (A/B: +2048 off)
 
 #ifdef WSI_STUDY
 static void* g_study_debug = nullptr;                 // study builds: device buffer handed to stamped kernels through ConvArgs.out2
 extern "C" int wsi_study_set_debug(void* dev_buf) { g_study_debug = dev_buf; return WSI_OK; }
 #endif
 
-static int conv_common(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias, int n,
-                       int h_in, int w_in, int cin, int cout, int stride, int ksize, int relu, int planes, void* stream,
-                       int cfg = -1, int split_out = 0, long long split_pixels = 0, const void* in2 = nullptr, int in2_c = 0,
-                       const void* wpk2 = nullptr, const float* bias2 = nullptr, int line_flags = 0, const void* in_up = nullptr, int up_c = 0,
-                       long long plane96 = 0) {
-    if ((!in_pf && !(in_up && up_c == cin)) || !out_pf || !wpk || !bias || in_pf == out_pf || in_up == out_pf || n <= 0) return WSI_EINVAL;
-    // 96-byte lines (CONV_IN96 / OUT96 / RESID96): mode 3, stride-1 3x3, 64 channels in and out (the slab3 kernel), no phase split
-    if (line_flags && (planes != 3 || stride != 1 || ksize != 3 || cin != 64 || cout != 64 || (split_out && (line_flags & CONV_OUT96)) ||
-                       (line_flags & ~(CONV_IN96 | CONV_OUT96 | CONV_RESID96)) || ((line_flags & CONV_RESID96) && !resid_pf)))
-        return WSI_EINVAL;
-    if ((stride != 1 && stride != 2) || h_in % stride || w_in % stride) return WSI_EINVAL;
+// One host conv call: conv (3x3 or 1x1) + folded BN bias (+ residual) (+ ReLU) over PF tensors.  The first block is what every
+// call states; the rest is optional and null / zero when unused.
+struct ConvCall {
+    const void* in;                  // PF (h, w, cin)
+    void* out;                       // PF (h / stride, w / stride, cout)
+    const void* resid = nullptr;     // PF shaped like out
+    const void* wpk; const float* bias;
+    int n, h, w, cin, cout, stride, ksize, relu, planes;
+    void* stream;
+    int cfg = -1;                    // stride-1 tile configuration (conv.hip); -1 = tuned default, 0 on a stride-2 conv = gather kernel
+    // write `out` phase-split (common.h ConvArgs.out_split_pixels), the phase images split_pixels apart (0 = the tight distance for n images)
+    int split_out = 0; long long split_pixels = 0;
+    // extra K segment, the folded 1x1 downsample (common.h ConvArgs.in2): its input, channels, packed weights and bias
+    const void* in2 = nullptr; int in2_c = 0; const void* wpk2 = nullptr; const float* bias2 = nullptr;
+    int line_flags = 0;              // CONV_IN96 / OUT96 / RESID96
+    // fused nearest x2 upsample + concat input (common.h ConvArgs.in_up): the half-size tensor and its channels; `in` is then the skip
+    // tensor (null when up_c == cin)
+    const void* in_up = nullptr; int up_c = 0;
+    long long plane96 = 0;           // bytes between the line planes of 96-byte-line tensors (0 = the tight distance for n images)
+};
+
+// the ConvArgs every launch starts from: tensors, geometry, no flags, no second output, no phase split
+static ConvArgs conv_args(const ConvCall& c) {
     ConvArgs a;
-    a.in = in_pf; a.out = out_pf; a.resid = resid_pf; a.wpk = wpk; a.bias = bias;
-    a.gi = pf_geom_fd(n, h_in, w_in, cin);
-    a.go = pf_geom_fd(n, h_in / stride, w_in / stride, cout);
-    a.stride = stride; a.ksize = ksize; a.relu = relu & 1; a.flags = 0;
-    a.plane96 = line_flags ? (plane96 > 0 ? plane96 : (long long)pf_alloc_pixels(n, h_in, w_in) * 96) : 0;   // line-planar 96-byte tensors (common.h)
+    a.in = c.in; a.out = c.out; a.resid = c.resid; a.wpk = c.wpk; a.bias = c.bias;
+    a.gi = pf_geom_fd(c.n, c.h, c.w, c.cin);
+    a.go = pf_geom_fd(c.n, c.h / c.stride, c.w / c.stride, c.cout);
+    a.stride = c.stride; a.ksize = c.ksize; a.relu = c.relu & 1; a.flags = 0;
+    a.out2 = nullptr; a.wpk2 = nullptr; a.bias2 = nullptr;
+    a.in_split_pixels = 0; a.out_split_pixels = 0;
+    return a;
+}
+
+static int conv_common(const ConvCall& c) {
+    const hipStream_t st = (hipStream_t)c.stream;
+    int cfg = c.cfg;
+    if ((!c.in && !(c.in_up && c.up_c == c.cin)) || !c.out || !c.wpk || !c.bias || c.in == c.out || c.in_up == c.out || c.n <= 0) return WSI_EINVAL;
+    // 96-byte lines (CONV_IN96 / OUT96 / RESID96): mode 3, stride-1 3x3, 64 channels in and out (the slab3 kernel), no phase split
+    if (c.line_flags && (c.planes != 3 || c.stride != 1 || c.ksize != 3 || c.cin != 64 || c.cout != 64 || (c.split_out && (c.line_flags & CONV_OUT96)) ||
+                         (c.line_flags & ~(CONV_IN96 | CONV_OUT96 | CONV_RESID96)) || ((c.line_flags & CONV_RESID96) && !c.resid)))
+        return WSI_EINVAL;
+    if ((c.stride != 1 && c.stride != 2) || c.h % c.stride || c.w % c.stride) return WSI_EINVAL;
+    ConvArgs a = conv_args(c);
+    a.plane96 = c.line_flags ? (c.plane96 > 0 ? c.plane96 : (long long)pf_alloc_pixels(c.n, c.h, c.w) * 96) : 0;   // line-planar 96-byte tensors (common.h)
 #ifdef WSI_STUDY
     // study builds accept the r01 ablation masks of tools/tune_conv.py in `relu` (2 no stores, 64 dispatch only, 128 no main
     // loop, 256 non-temporal, bits 10-13 weight copies, 512 / 16384 XCD orders, 65536 residual read directly)
-    if (relu & 2) a.flags |= CONV_ABL_NO_STORE;
-    if (relu & 64) a.flags |= CONV_ABL_DISPATCH_ONLY;
-    if (relu & 128) a.flags |= CONV_ABL_NO_MAINLOOP;
-    if (relu & 256) a.flags |= CONV_NONTEMPORAL;
-    if (relu & 512) a.flags |= CONV_XCD_ORDER;
-    if (relu & 16384) a.flags |= CONV_XCD_RANGES;
-    if (relu & 65536) a.flags |= CONV_RESID_DIRECT;
-    a.flags |= ((relu >> 10) & 15) << CONV_WCOPIES_SHIFT;
+    if (c.relu & 2) a.flags |= CONV_ABL_NO_STORE;
+    if (c.relu & 64) a.flags |= CONV_ABL_DISPATCH_ONLY;
+    if (c.relu & 128) a.flags |= CONV_ABL_NO_MAINLOOP;
+    if (c.relu & 256) a.flags |= CONV_NONTEMPORAL;
+    if (c.relu & 512) a.flags |= CONV_XCD_ORDER;
+    if (c.relu & 16384) a.flags |= CONV_XCD_RANGES;
+    if (c.relu & 65536) a.flags |= CONV_RESID_DIRECT;
+    a.flags |= ((c.relu >> 10) & 15) << CONV_WCOPIES_SHIFT;
 #else
-    if (relu & ~1) return WSI_EINVAL;
+    if (c.relu & ~1) return WSI_EINVAL;
 #endif
-    a.flags |= line_flags;
-    a.out2 = nullptr; a.wpk2 = nullptr; a.bias2 = nullptr;
-    if (in_up) {                                       // fused nearest x2 upsample + concat input (common.h ConvArgs.in_up): stride-1 3x3, slab3 kernels
-        if (stride != 1 || ksize != 3 || h_in % 2 || w_in % 2 || up_c <= 0 || up_c > cin || resid_pf || in2 || line_flags || split_out) return WSI_EINVAL;
-        a.in_up = in_up; a.up_c = up_c; a.gup = pf_geom_fd(n, h_in / 2, w_in / 2, up_c);
+    a.flags |= c.line_flags;
+    if (c.in_up) {                                     // fused nearest x2 upsample + concat input (common.h ConvArgs.in_up): stride-1 3x3, slab3 kernels
+        if (c.stride != 1 || c.ksize != 3 || c.h % 2 || c.w % 2 || c.up_c <= 0 || c.up_c > c.cin || c.resid || c.in2 || c.line_flags || c.split_out) return WSI_EINVAL;
+        a.in_up = c.in_up; a.up_c = c.up_c; a.gup = pf_geom_fd(c.n, c.h / 2, c.w / 2, c.up_c);
     }
-    if (in2) {                                         // extra K segment (common.h ConvArgs.in2): mode 3, stride-1 3x3, wide kernel only
-        if (planes != 3 || stride != 1 || ksize != 3 || resid_pf || !wpk2 || !bias2 || in2_c <= 0 || in2_c % 32 || cout % 128 || cfg >= 0) return WSI_EINVAL;
-        a.in2 = in2; a.in2_c = in2_c; a.wpk2 = wpk2; a.bias2 = bias2;
+    if (c.in2) {                                       // extra K segment (common.h ConvArgs.in2): mode 3, stride-1 3x3, wide kernel only
+        if (c.planes != 3 || c.stride != 1 || c.ksize != 3 || c.resid || !c.wpk2 || !c.bias2 || c.in2_c <= 0 || c.in2_c % 32 || c.cout % 128 || cfg >= 0) return WSI_EINVAL;
+        a.in2 = c.in2; a.in2_c = c.in2_c; a.wpk2 = c.wpk2; a.bias2 = c.bias2;
         cfg = 60;
     }
 #ifdef WSI_STUDY
     if (cfg == 75 || cfg == 76) a.out2 = g_study_debug;
 #endif
-    a.in_split_pixels = 0;
     // distance between the four phase images: the caller's (a workspace planned for more images) or the tight one
-    a.out_split_pixels = split_out ? (split_pixels ? split_pixels : pf_alloc_pixels(n, h_in / 2, w_in / 2)) : 0;
-    if (split_out && (stride != 1 || ksize != 3 || h_in % 2 || w_in % 2 || planes < 2)) return WSI_EINVAL;
-    if (ksize == 3 && stride == 2 && cout % 128 == 0 && cfg != 0 && g_s2_slab) {
-        const int rc = wsi_s2_dispatch(a, planes, (hipStream_t)stream);
+    a.out_split_pixels = c.split_out ? (c.split_pixels ? c.split_pixels : pf_alloc_pixels(c.n, c.h / 2, c.w / 2)) : 0;
+    if (c.split_out && (c.stride != 1 || c.ksize != 3 || c.h % 2 || c.w % 2 || c.planes < 2)) return WSI_EINVAL;
+    if (c.ksize == 3 && c.stride == 2 && c.cout % 128 == 0 && cfg != 0 && g_routes.s2_slab) {
+        const int rc = wsi_s2_dispatch(a, c.planes, st);
         if (rc != WSI_EINVAL) return rc;               // EINVAL: shape outside the slab kernel's range -> gather kernel
     }
-    return wsi_conv_dispatch(a, planes, cfg, (hipStream_t)stream);
+    return wsi_conv_dispatch(a, c.planes, cfg, st);
 }
 
 int wsi_conv3x3_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,
                        int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes,
                        void* stream) {
-    return conv_common(in_pf, out_pf, resid_pf, wpk, bias, n, h_in, w_in, cin, cout, stride, 3, relu, planes, stream);
+    return conv_common({.in = in_pf, .out = out_pf, .resid = resid_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin,
+                        .cout = cout, .stride = stride, .ksize = 3, .relu = relu, .planes = planes, .stream = stream});
 }
 
 size_t wsi_pf_split_bytes(int n, int h, int w, int c, int planes) {
@@ -590,17 +627,17 @@ size_t wsi_pf_split_bytes(int n, int h, int w, int c, int planes) {
 
 int wsi_conv3x3_bn_act_split(const void* in_pf, void* out_split, const void* resid_pf, const void* wpk, const float* bias,
                              int n, int h, int w, int cin, int cout, int relu, int planes, void* stream) {
-    return conv_common(in_pf, out_split, resid_pf, wpk, bias, n, h, w, cin, cout, 1, 3, relu, planes, stream, -1, 1);
+    return conv_common({.in = in_pf, .out = out_split, .resid = resid_pf, .wpk = wpk, .bias = bias, .n = n, .h = h, .w = w, .cin = cin,
+                        .cout = cout, .stride = 1, .ksize = 3, .relu = relu, .planes = planes, .stream = stream, .split_out = 1});
 }
 
-static int s2_split_common(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3,
-                           const float* bias3, const void* wpk1, const float* bias1, int n, int h_in, int w_in,
-                           int cin, int cout, int planes, void* stream, long long split_pixels);
-
-int wsi_conv3x3s2_ds_fused_split(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3,
-                                 const float* bias3, const void* wpk1, const float* bias1, int n, int h_in, int w_in,
-                                 int cin, int cout, int planes, void* stream) {
-    return s2_split_common(in_split, out_conv_pf, out_ds_pf, wpk3, bias3, wpk1, bias1, n, h_in, w_in, cin, cout, planes, stream, 0);
+// the ConvArgs of a stride-2 3x3 conv + ReLU with the 1x1 downsample branch as second output (out_ds_pf null: the 3x3 conv alone)
+static ConvArgs s2_ds_args(const void* in, void* out_conv_pf, void* out_ds_pf, const void* wpk3, const float* bias3, const void* wpk1,
+                           const float* bias1, int n, int h_in, int w_in, int cin, int cout) {
+    ConvArgs a = conv_args({.in = in, .out = out_conv_pf, .wpk = wpk3, .bias = bias3, .n = n, .h = h_in, .w = w_in, .cin = cin, .cout = cout,
+                            .stride = 2, .ksize = 3, .relu = 1});
+    a.out2 = out_ds_pf; a.wpk2 = out_ds_pf ? wpk1 : nullptr; a.bias2 = out_ds_pf ? bias1 : nullptr;
+    return a;
 }
 
 static int s2_split_common(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3,
@@ -610,28 +647,29 @@ static int s2_split_common(const void* in_split, void* out_conv_pf, void* out_ds
     if (!in_split || !out_conv_pf || !wpk3 || !bias3 || (out_ds_pf && (!wpk1 || !bias1)) || n <= 0 || h_in % 2 || w_in % 2)
         return WSI_EINVAL;
     if (in_split == out_conv_pf || in_split == out_ds_pf || out_conv_pf == out_ds_pf) return WSI_EINVAL;
-    ConvArgs a;
-    a.in = in_split; a.out = out_conv_pf; a.resid = nullptr; a.wpk = wpk3; a.bias = bias3;
-    a.gi = pf_geom_fd(n, h_in, w_in, cin);
-    a.go = pf_geom_fd(n, h_in / 2, w_in / 2, cout);
-    a.stride = 2; a.ksize = 3; a.relu = 1; a.flags = 0;
-    a.out2 = out_ds_pf; a.wpk2 = out_ds_pf ? wpk1 : nullptr; a.bias2 = out_ds_pf ? bias1 : nullptr;
-    a.out_split_pixels = 0;
+    ConvArgs a = s2_ds_args(in_split, out_conv_pf, out_ds_pf, wpk3, bias3, wpk1, bias1, n, h_in, w_in, cin, cout);
     a.in_split_pixels = split_pixels ? split_pixels : pf_alloc_pixels(n, h_in / 2, w_in / 2);
     return wsi_s2_dispatch(a, planes, (hipStream_t)stream);      // EINVAL outside the wide kernel's range (output maps wider than 33)
+}
+
+int wsi_conv3x3s2_ds_fused_split(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3,
+                                 const float* bias3, const void* wpk1, const float* bias1, int n, int h_in, int w_in,
+                                 int cin, int cout, int planes, void* stream) {
+    return s2_split_common(in_split, out_conv_pf, out_ds_pf, wpk3, bias3, wpk1, bias1, n, h_in, w_in, cin, cout, planes, stream, 0);
 }
 
 int wsi_conv3x3_bn_act_cfg(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,
                            int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes, int cfg,
                            void* stream) {
-    return conv_common(in_pf, out_pf, resid_pf, wpk, bias, n, h_in, w_in, cin, cout, stride, 3, relu, planes, stream, cfg);
+    return conv_common({.in = in_pf, .out = out_pf, .resid = resid_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin,
+                        .cout = cout, .stride = stride, .ksize = 3, .relu = relu, .planes = planes, .stream = stream, .cfg = cfg});
 }
 
 int wsi_conv3x3_up_concat_bn_act(const void* up_pf, const void* skip_pf, void* out_pf, const void* wpk, const float* bias, int n, int h, int w,
                                  int c_up, int c_skip, int cout, int relu, int planes, void* stream) {
     if (!up_pf || c_up <= 0 || c_skip < 0 || (c_skip > 0 && !skip_pf)) return WSI_EINVAL;
-    return conv_common(c_skip ? skip_pf : nullptr, out_pf, nullptr, wpk, bias, n, h, w, c_up + c_skip, cout, 1, 3, relu, planes, stream, -1, 0, 0,
-                       nullptr, 0, nullptr, nullptr, 0, up_pf, c_up);
+    return conv_common({.in = c_skip ? skip_pf : nullptr, .out = out_pf, .wpk = wpk, .bias = bias, .n = n, .h = h, .w = w, .cin = c_up + c_skip,
+                        .cout = cout, .stride = 1, .ksize = 3, .relu = relu, .planes = planes, .stream = stream, .in_up = up_pf, .up_c = c_up});
 }
 
 // the phase-slab kernel's byte offsets into its input are 32-bit (conv.hip launch_s2slab refuses a PF input of 4 GiB or more)
@@ -655,13 +693,7 @@ int wsi_conv3x3s2_ds_fused(const void* in_pf, void* out_conv_pf, void* out_ds_pf
     if (!in_pf || !out_conv_pf || !out_ds_pf || !wpk3 || !bias3 || !wpk1 || !bias1 || n <= 0 || h_in % 2 || w_in % 2)
         return WSI_EINVAL;
     if (in_pf == out_conv_pf || in_pf == out_ds_pf || out_conv_pf == out_ds_pf) return WSI_EINVAL;
-    ConvArgs a;
-    a.in = in_pf; a.out = out_conv_pf; a.resid = nullptr; a.wpk = wpk3; a.bias = bias3;
-    a.gi = pf_geom_fd(n, h_in, w_in, cin);
-    a.go = pf_geom_fd(n, h_in / 2, w_in / 2, cout);
-    a.stride = 2; a.ksize = 3; a.relu = 1; a.flags = 0;
-    a.out2 = out_ds_pf; a.wpk2 = wpk1; a.bias2 = bias1;
-    a.in_split_pixels = 0; a.out_split_pixels = 0;
+    ConvArgs a = s2_ds_args(in_pf, out_conv_pf, out_ds_pf, wpk3, bias3, wpk1, bias1, n, h_in, w_in, cin, cout);
     // the phase-slab kernel over image sub-ranges whose PF input is under 4 GiB (wsi_s2_slab_images): views that start at image n0,
     // so a view's front guard lies in image n0 - 1's zero pads, and every output image reads its own input image only
     const int per = wsi_s2_slab_images(n, h_in, w_in, cin, planes);
@@ -679,43 +711,43 @@ int wsi_conv3x3s2_ds_fused(const void* in_pf, void* out_conv_pf, void* out_ds_pf
         if (rc) break;
     }
     if (rc == WSI_EINVAL) {                             // e.g. maps wider than 33 in speed mode: two per-tap gather launches
-        rc = conv_common(in_pf, out_conv_pf, nullptr, wpk3, bias3, n, h_in, w_in, cin, cout, 2, 3, 1, planes, stream, 0);
-        if (!rc) rc = conv_common(in_pf, out_ds_pf, nullptr, wpk1, bias1, n, h_in, w_in, cin, cout, 2, 1, 0, planes, stream, 0);
+        ConvCall c = {.in = in_pf, .out = out_conv_pf, .wpk = wpk3, .bias = bias3, .n = n, .h = h_in, .w = w_in, .cin = cin, .cout = cout,
+                      .stride = 2, .ksize = 3, .relu = 1, .planes = planes, .stream = stream, .cfg = 0};
+        rc = conv_common(c);
+        c.out = out_ds_pf; c.wpk = wpk1; c.bias = bias1; c.ksize = 1; c.relu = 0;       // the 1x1 downsample branch: same input, no ReLU
+        if (!rc) rc = conv_common(c);
     }
     return rc;
 }
 
-extern int g_s2_small_tiles, g_xcd_order, g_wide_min_c, g_s2_ablate, g_xcd_ranges, g_slab_pair;
-extern int g_l1_lines96, g_s2_nt4, g_l1_rows, g_wide_d8, g_l1p;
-extern int g_unet_fuse_up;
-extern int g_unet_tail;
-extern int g_unet_tail_form;
-extern int g_unet_x0_fused;
-int wsi_conv_set_mode(int s2_slab) {
-    g_s2_split = (s2_slab & 128) ? 0 : 1;
-    g_ds_fold = (s2_slab & 2048) ? 0 : 1;
-    g_slab_pair = (s2_slab & 4096) ? 0 : 1;
-    g_l1_rows = (s2_slab & 1024) ? 0 : 1;
-    g_unet_fuse_up = (s2_slab & 65536) ? 0 : 1;
-    g_unet_tail = (s2_slab & 2097152) ? 0 : 1;
-    g_unet_tail_form = (s2_slab & 4194304) ? 1 : 2;
-    g_unet_x0_fused = (s2_slab & 8388608) ? 0 : 1;
-    g_l1_lines96 = (s2_slab & 16384) ? 0 : 1;
-    g_s2_nt4 = (s2_slab & 32768) ? 0 : 1;
-    g_wide_d8 = (s2_slab & 131072) ? 0 : 1;
-    g_l1p = (s2_slab & 1048576) ? 1 : 0;                  // A/B: persistent producer-fed layer-1 kernel (conv.hip conv3x3s1_l1p_kernel, r05)              // A/B: 8-pixel slab rows of the wide kernel on 8 x 8 maps (r05)
-    g_xcd_ranges = (s2_slab & 256) ? 0 : (s2_slab & 512) ? 1 : 2;          // +256: off, +512: 64-channel layer only
-    g_s2_ablate = (s2_slab & 64) ? 1 : 0;                 // bottleneck study only: stride-2 kernel without weight loads (wrong results)
-    g_xcd_order = (s2_slab & 8) ? 1 : 0;
-    g_wide_min_c = (s2_slab & 16) ? 256 : (s2_slab & 32) ? (1 << 30) : 128;      // +16: wide kernel from 256 channels, +32: never
-    s2_slab &= 7;
-    g_s2_slab = s2_slab ? 1 : 0; g_s2_small_tiles = s2_slab != 3;
+int wsi_conv_set_mode(int mode) {
+    ConvRoutes& r = g_routes;
+    const int base = mode & 7;                              // WSI_CONV_MODE_S2_GATHER / S2_SLAB / S2_SLAB_128 (2 and 4-7 act as S2_SLAB)
+    r.s2_slab = base != WSI_CONV_MODE_S2_GATHER;
+    r.s2_small_tiles = base != WSI_CONV_MODE_S2_SLAB_128;
+    r.xcd_order = (mode & WSI_CONV_MODE_XCD_ORDER) ? 1 : 0;
+    r.wide_min_c = (mode & WSI_CONV_MODE_WIDE_FROM_256) ? 256 : (mode & WSI_CONV_MODE_WIDE_NEVER) ? (1 << 30) : 128;
+    r.s2_ablate = (mode & WSI_CONV_MODE_S2_ABLATE) ? 1 : 0;
+    r.s2_split = (mode & WSI_CONV_MODE_NO_S2_SPLIT) ? 0 : 1;
+    r.xcd_ranges = (mode & WSI_CONV_MODE_XCD_RANGES_OFF) ? 0 : (mode & WSI_CONV_MODE_XCD_RANGES_L1) ? 1 : 2;
+    r.l1_rows = (mode & WSI_CONV_MODE_L1_SLAB3) ? 0 : 1;
+    r.ds_fold = (mode & WSI_CONV_MODE_NO_DS_FOLD) ? 0 : 1;
+    r.slab_pair = (mode & WSI_CONV_MODE_NO_SLAB_PAIR) ? 0 : 1;
+    r.l1_lines96 = (mode & WSI_CONV_MODE_L1_LINES128) ? 0 : 1;
+    r.s2_nt4 = (mode & WSI_CONV_MODE_S2_NT2) ? 0 : 1;
+    r.unet_fuse_up = (mode & WSI_CONV_MODE_UNET_CONCAT_PASS) ? 0 : 1;
+    r.wide_d8 = (mode & WSI_CONV_MODE_WIDE_NO_D8) ? 0 : 1;
+    r.l1p = (mode & WSI_CONV_MODE_L1_PERSISTENT) ? 1 : 0;
+    r.unet_tail = (mode & WSI_CONV_MODE_UNET_NO_TAIL) ? 0 : 1;
+    r.unet_tail_form = (mode & WSI_CONV_MODE_UNET_TAIL_FORM1) ? 1 : 2;
+    r.unet_x0_fused = (mode & WSI_CONV_MODE_UNET_X0_UNFUSED) ? 0 : 1;
     return WSI_OK;
 }
 
 int wsi_conv1x1_bn(const void* in_pf, void* out_pf, const void* wpk, const float* bias, int n, int h_in, int w_in,
                    int cin, int cout, int stride, int planes, void* stream) {
-    return conv_common(in_pf, out_pf, nullptr, wpk, bias, n, h_in, w_in, cin, cout, stride, 1, 0, planes, stream);
+    return conv_common({.in = in_pf, .out = out_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin, .cout = cout,
+                        .stride = stride, .ksize = 1, .relu = 0, .planes = planes, .stream = stream});
 }
 
 int wsi_avgpool_fc(const void* in_pf, int n, int h, int w, int c, const float* fc_w, const float* fc_b, int k,
@@ -936,24 +968,29 @@ int wsi_prof_end(float* ms_out, int* kind_out, double* flops_out, int cap) {
     return n;
 }
 
-static inline int prof_open(hipStream_t st, int kind, double flops) {
-    if (!g_prof.enabled || g_prof.count >= g_prof.cap) return -1;
-    const int i = g_prof.count++;
-    g_prof.kind[i] = kind; g_prof.flops[i] = flops;
-    (void)hipEventRecord(g_prof.ev[2 * i], st);
-    return i;
-}
-static inline void prof_close(hipStream_t st, int i) { if (i >= 0) (void)hipEventRecord(g_prof.ev[2 * i + 1], st); }
+// One record: an event on `st` when the scope opens and one when it closes, so a scope holds exactly the launch it times
+// (an early `return rc` inside it closes first).  Kinds and FLOP conventions: trunk_run, unet_decoder_run.
+struct ProfScope {
+    const hipStream_t st;
+    int i = -1;                                        // record index, -1 = not recording
+    ProfScope(hipStream_t st, int kind, double flops) : st(st) {
+        if (!g_prof.enabled || g_prof.count >= g_prof.cap) return;
+        i = g_prof.count++;
+        g_prof.kind[i] = kind; g_prof.flops[i] = flops;
+        (void)hipEventRecord(g_prof.ev[2 * i], st);
+    }
+    ~ProfScope() { if (i >= 0) (void)hipEventRecord(g_prof.ev[2 * i + 1], st); }
+    void relabel(int kind) { if (i >= 0) g_prof.kind[i] = kind; }
+};
+// 2*M*N*K of a conv over real output pixels (padding taps counted)
+static inline double conv_flops(int n, int ho, int wo, int ci, int co, int taps) { return 2.0 * n * ho * wo * (double)co * ci * taps; }
 
 // ------------------------------------------------------------------------------------ trunk
-static int g_chunk_stem = 0, g_chunk_l1 = 0;   // sub-batch sizes (images); 0 = whole batch (measured r01: no gain)
-
 // Layer-1 tensors of a full mode-3 trunk run live in 96-byte lines (common.h CONV_IN96): the pad positions of a PF buffer sit at
 // other BYTES than in the 128-byte layout, and pads are only ever zero because nobody writes them - so a workspace remembers
 // which layout its three stage-0 buffers last held, and a run in the other layout zero-fills them first (taps and the U-Net
 // encoder keep the 128-byte layout; a workspace that only ever runs one kind of call never pays).  -1 = all zero (after
 // wsi_trunk_workspace_init), otherwise 2 * planes + (1 if stage 0 holds 96-byte lines); an unknown workspace counts as dirty.
-int g_l1_lines96 = 1;                           // A/B: wsi_conv_set_mode +16384 disables
 static std::mutex g_ws_mutex;
 struct WsTag { int layout; size_t bytes; };                  // bytes: what wsi_trunk_workspace_init planned (0 = never initialised here)
 static std::unordered_map<const void*, WsTag> g_ws_layout;
@@ -981,7 +1018,7 @@ int wsi_trunk_workspace_release(void* workspace) {
 int wsi_trunk_set_chunks(int stem_chunk, int layer1_chunk) {
     if (stem_chunk < 0 || layer1_chunk < 0) return WSI_EINVAL;
     if (stem_chunk && layer1_chunk && layer1_chunk % stem_chunk) return WSI_EINVAL;
-    g_chunk_stem = stem_chunk; g_chunk_l1 = layer1_chunk;
+    g_routes.chunk_stem = stem_chunk; g_routes.chunk_l1 = layer1_chunk;
     return WSI_OK;
 }
 struct TrunkPlan {
@@ -1032,38 +1069,38 @@ int wsi_trunk_workspace_init(void* workspace, int n, int h, int w, int planes, v
 // come from the plan, so one workspace serves every batch size up to cap (image i sits at the same place whatever n is;
 // what images >= n still hold from an earlier, larger batch is never read: the zero row / column that close image
 // n-1 belong to its own block).
-static int trunk_run(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide, long long pitch, int slide_h,
-                     int slide_w, const int* tile_xy, const float* lut, int n, int cap, int h, int w, void* workspace,
+static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, int cap, int h, int w, void* workspace,
                      int stop_after, hipStream_t st, const TrunkPlan& p, size_t& last_off, int& last_stage,
                      bool allow_split = true, size_t* stage_off = nullptr, char* x0_out = nullptr) {
     char* ws = (char*)workspace;
     const int planes = wt->planes;
     int rc = WSI_OK;
-    // kind: 1 = 3x3 stride-1 of layers 2-4 (wide kernel), 5 = 3x3 stride-1 of the 64-channel layer 1 (slab3 kernel),
-    // 2 = 3x3 stride-2 (+ fused downsample), 3 = 1x1 downsample, 4 = stem+maxpool;
-    // flops = 2*M*N*K over real output pixels (padding taps counted)
-#define PROF_CONV(kind, NN, HO, WO, CI, CO, KK, call)                                                \
-    do {                                                                                            \
-        const int pi_ = prof_open(st, kind, 2.0 * (NN) * (HO) * (WO) * (double)(CO) * (CI) * (KK));  \
-        rc = (call);                                                                                \
-        prof_close(st, pi_);                                                                        \
-        if (rc) return rc;                                                                          \
-    } while (0)
+    // ProfScope kinds: 1 = 3x3 stride-1 of layers 2-4 (wide kernel), 5 = 3x3 stride-1 of the 64-channel layer 1 (slab3 kernel),
+    // 2 = 3x3 stride-2 (+ fused downsample), 3 = 1x1 downsample, 4 = stem+maxpool
+    // conv wi of the trunk (3x3, stride 1, ReLU) on n0 images of an H x W map with C channels in and out; call sites name what differs
+    auto conv3 = [&](const void* in, void* out, const void* resid, int wi, int n0, int H, int W, int C) {
+        return ConvCall{.in = in, .out = out, .resid = resid, .wpk = wt->conv_w[wi], .bias = wt->conv_b[wi], .n = n0, .h = H, .w = W, .cin = C,
+                        .cout = C, .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
+    };
+    auto run = [&](int kind, const ConvCall& c) {      // one conv launch = one profiler record
+        ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
+        return conv_common(c);
+    };
     const size_t bpc = planes == 1 ? PFmt<1>::BPC : PFmt<2>::BPC;     // bytes per channel: 2 (speed) or 4 (parity, mx)
     // ---- stem + maxpool + layer1 run in sub-batches so that the 4 MB/patch fp32 stem scratch and
     //      the 1 MB/patch layer-1 tensors stay resident in the 256 MiB Infinity Cache; the deeper
     //      (small-map) stages run on the whole batch to fill the chip.
-    const int cs = g_chunk_stem > 0 ? g_chunk_stem : n, c1 = g_chunk_l1 > 0 ? g_chunk_l1 : n;
+    const int cs = g_routes.chunk_stem > 0 ? g_routes.chunk_stem : n, c1 = g_routes.chunk_l1 > 0 ? g_routes.chunk_l1 : n;
     const int H1 = p.sh[0], W1 = p.sw[0];
     const int do_l1 = stop_after != 0;
     // stage s writes its output phase-split when the next stage's entry can read it with the wide stride-2 kernel:
     // full runs only (taps unpack ordinary PF), split precision, next output maps <= 33 wide, whole-batch stages
-    auto can_split = [&](int s) { return allow_split && g_s2_split && g_s2_slab && stop_after >= 8 && planes >= 2 && s < 3 && p.sw[s + 1] <= 33; };
+    auto can_split = [&](int s) { return allow_split && g_routes.s2_split && g_routes.s2_slab && stop_after >= 8 && planes >= 2 && s < 3 && p.sw[s + 1] <= 33; };
     const bool split0 = can_split(0);                  // (a layer-1 sub-batch writes its images' slice of each phase image)
     // r03: a full mode-3 run keeps stem output and layer-1 tensors in 96-byte lines (layer 1 is HBM-bound: 25 % fewer bytes);
     // the last layer-1 conv writes the ordinary (or phase-split) 128-byte form every other kernel reads
     // (only with the phase-split hand-over to layer 2: an ordinary 128-byte output would land in a buffer that held 96-byte lines)
-    const bool l96 = g_l1_lines96 && planes == 3 && split0;
+    const bool l96 = g_routes.l1_lines96 && planes == 3 && split0;
     // the tag is recorded for EVERY planes value (r03 advisor finding: a planes 1 / 2 run used to leave a stale '96-byte lines' tag,
     // and a later mx run on the same workspace then skipped the zero-fill): tag = 2 * planes + (96-byte lines)
     if (const int dirty = ws_layout_switch(workspace, 2 * planes + (l96 ? 1 : 0), p.total)) {
@@ -1084,14 +1121,11 @@ static int trunk_run(const wsi_trunk_weights* wt, const float* in_f32, const uin
         const int nn1 = n - n1 < c1 ? n - n1 : c1;
         for (int n0 = n1; n0 < n1 + nn1; n0 += cs) {
             const int nn = n1 + nn1 - n0 < cs ? n1 + nn1 - n0 : cs;
-            const int pi_ = prof_open(st, 4, 2.0 * nn * (h / 2) * (w / 2) * 64.0 * 147.0);
-            rc = stem_run(in_f32 ? in_f32 + (size_t)n0 * 3 * h * w : nullptr, slide, pitch, slide_h,
-                          slide_w, tile_xy ? tile_xy + 2 * n0 : nullptr, lut, wt->stem_w, wt->stem_b,
-                          wt->stem_w_u8, wt->stem_b_u8, wt->norm,
+            ProfScope ps(st, 4, 2.0 * nn * (h / 2) * (w / 2) * 64.0 * 147.0);
+            rc = stem_run(src.from_image(n0, h, w), wt->stem_w, wt->stem_b, wt->stem_w_u8, wt->stem_b_u8, wt->norm,
                           nn, h, w, (float*)(ws + p.stem_scratch), ws + p.buf[0][0] + img_off(0, n0),
                           planes, st, l96 ? 1 : 0, plane96,
                           x0_out ? x0_out + (size_t)n0 * (h / 2 + 1) * (w / 2 + 1) * 64 * bpc : nullptr);     // (U-Net: the conv map before the pool)
-            prof_close(st, pi_);
             if (rc) return rc;
         }
         if (!do_l1) continue;
@@ -1101,18 +1135,16 @@ static int trunk_run(const wsi_trunk_weights* wt, const float* in_f32, const uin
             char *x = ws + p.buf[0][cur] + img_off(0, n1), *mid = ws + p.buf[0][m] + img_off(0, n1),
                  *out = ws + p.buf[0][o] + img_off(0, n1);
             const int f_in = l96 ? CONV_IN96 : 0, f_res = l96 ? CONV_RESID96 : 0;
-            PROF_CONV(5, nn1, H1, W1, 64, 64, 9, conv_common(x, mid, nullptr, wt->conv_w[2 * b], wt->conv_b[2 * b], nn1,
-                                                              H1, W1, 64, 64, 1, 3, 1, planes, st, -1, 0, 0, nullptr, 0, nullptr, nullptr,
-                                                              f_in | (l96 ? CONV_OUT96 : 0), nullptr, 0, plane96));
+            ConvCall c = conv3(x, mid, nullptr, 2 * b, nn1, H1, W1, 64);
+            c.line_flags = f_in | (l96 ? CONV_OUT96 : 0); c.plane96 = plane96;
+            if ((rc = run(5, c))) return rc;
+            c = conv3(mid, out, x, 2 * b + 1, nn1, H1, W1, 64);
+            c.line_flags = f_in | f_res | (l96 && b == 0 ? CONV_OUT96 : 0); c.plane96 = plane96;
             if (b == 1 && split0) {                    // layer1's output feeds only the stride-2 entry of layer2
-                PROF_CONV(5, nn1, H1, W1, 64, 64, 9, conv_common(mid, ws + p.buf[0][3] + split_off(n1), x, wt->conv_w[3], wt->conv_b[3], nn1, H1, W1, 64,
-                                                                  64, 1, 3, 1, planes, st, -1, 1, pf_alloc_pixels(cap, H1 / 2, W1 / 2), nullptr, 0, nullptr,
-                                                                  nullptr, f_in | f_res, nullptr, 0, plane96));
-            } else {                                   // (the stage's last conv writes 128-byte lines: layer 2, taps and skips read those)
-                PROF_CONV(5, nn1, H1, W1, 64, 64, 9, conv_common(mid, out, x, wt->conv_w[2 * b + 1], wt->conv_b[2 * b + 1],
-                                                                  nn1, H1, W1, 64, 64, 1, 3, 1, planes, st, -1, 0, 0, nullptr, 0, nullptr, nullptr,
-                                                                  f_in | f_res | (l96 && b == 0 ? CONV_OUT96 : 0), nullptr, 0, plane96));
-            }
+                c.out = ws + p.buf[0][3] + split_off(n1);
+                c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H1 / 2, W1 / 2);
+            }                                          // (otherwise the stage's last conv writes 128-byte lines: layer 2, taps and skips read those)
+            if ((rc = run(5, c))) return rc;
             cur = o;
         }
         l1_out = cur;
@@ -1134,25 +1166,25 @@ static int trunk_run(const wsi_trunk_weights* wt, const float* in_f32, const uin
             // r03, mode 3: the 1x1 downsample of a strided block is computed INSIDE the block's second conv as an extra K segment
             // over phase 00 of the block input (ConvArgs.in2): the stride-2 kernel drops its second accumulator set and half its
             // tile epilogues, the downsample tensor is neither written nor read back as a residual
-            const bool fold = b == 0 && x_split && planes == 3 && g_ds_fold && g_s2_slab && C % 128 == 0;
+            const bool fold = b == 0 && x_split && planes == 3 && g_routes.ds_fold && g_routes.s2_slab && C % 128 == 0;
             const void* fold_in2 = fold ? x : nullptr;
             if (b == 0) {                              // strided block with 1x1 downsample branch
                 mid = ws + p.buf[s][1];
                 void* ds = fold ? nullptr : ws + p.buf[s][2];
                 out = ws + p.buf[s][0];
-                if (g_s2_slab) {
-                    const int pi_ = prof_open(st, 2, 2.0 * n * H * W * (double)C * (C / 2) * (fold ? 9 : 10));
+                if (g_routes.s2_slab) {
+                    ProfScope ps(st, 2, conv_flops(n, H, W, C / 2, C, fold ? 9 : 10));
                     rc = x_split ? s2_split_common(x, mid, ds, wt->conv_w[wi], wt->conv_b[wi], wt->down_w[s - 1],
                                                    wt->down_b[s - 1], n, 2 * H, 2 * W, C / 2, C, planes, st, pf_alloc_pixels(cap, H, W))
                                  : wsi_conv3x3s2_ds_fused(x, mid, ds, wt->conv_w[wi], wt->conv_b[wi], wt->down_w[s - 1], wt->down_b[s - 1], n,
                                                           2 * H, 2 * W, C / 2, C, planes, st);
-                    prof_close(st, pi_);
                     if (rc) return rc;
-                } else {
-                    PROF_CONV(2, n, H, W, C / 2, C, 9, wsi_conv3x3_bn_act(x, mid, nullptr, wt->conv_w[wi], wt->conv_b[wi], n, 2 * H,
-                                                                     2 * W, C / 2, C, 2, 1, planes, st));
-    PROF_CONV(3, n, H, W, C / 2, C, 1, wsi_conv1x1_bn(x, ds, wt->down_w[s - 1], wt->down_b[s - 1], n, 2 * H, 2 * W,
-                                                                 C / 2, C, 2, planes, st));
+                } else {                               // gather kernel, then the 1x1 downsample as a launch of its own (no ReLU)
+                    ConvCall c = conv3(x, mid, nullptr, wi, n, 2 * H, 2 * W, C / 2);
+                    c.cout = C; c.stride = 2;
+                    if ((rc = run(2, c))) return rc;
+                    c.out = ds; c.wpk = wt->down_w[s - 1]; c.bias = wt->down_b[s - 1]; c.ksize = 1; c.relu = 0;
+                    if ((rc = run(3, c))) return rc;
                 }
                 resid = ds;
                 cur = 0;
@@ -1161,29 +1193,21 @@ static int trunk_run(const wsi_trunk_weights* wt, const float* in_f32, const uin
                 const int m = (cur + 1) % 3, o = (cur + 2) % 3;
                 mid = ws + p.buf[s][m];
                 out = ws + p.buf[s][o];
-                PROF_CONV(1, n, H, W, C, C, 9, wsi_conv3x3_bn_act(x, mid, nullptr, wt->conv_w[wi], wt->conv_b[wi], n, H, W, C, C,
-                                                                 1, 1, planes, st));
+                if ((rc = run(1, conv3(x, mid, nullptr, wi, n, H, W, C)))) return rc;
                 resid = x;
                 cur = o;
                 last_off = p.buf[s][o];
             }
+            x_split = !fold_in2 && b == 1 && can_split(s);                        // the stage's output feeds only the next stage's stride-2 entry
+            if (x_split) out = ws + p.buf[s][3];
+            ConvCall c = conv3(mid, out, resid, wi + 1, n, H, W, C);
+            if (x_split) { c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H / 2, W / 2); }
             if (fold_in2) {                            // second conv of a strided block with the downsample folded in (never the stage's last conv)
-                const int pi_ = prof_open(st, 1, 2.0 * n * H * W * (double)C * (C * 9 + C / 2));
-                rc = conv_common(mid, out, nullptr, wt->conv_w[wi + 1], wt->conv_b[wi + 1], n, H, W, C, C, 1, 3, 1, planes, st, -1, 0, 0,
-                                 fold_in2, C / 2, wt->down_w[s - 1], wt->down_b[s - 1]);
-                prof_close(st, pi_);
-                if (rc) return rc;
-                x_split = false;
-            } else if (b == 1 && can_split(s)) {       // the stage's output feeds only the next stage's stride-2 entry
-                out = ws + p.buf[s][3];
-                PROF_CONV(1, n, H, W, C, C, 9, conv_common(mid, out, resid, wt->conv_w[wi + 1], wt->conv_b[wi + 1], n, H, W, C, C, 1, 3, 1,
-                                                            planes, st, -1, 1, pf_alloc_pixels(cap, H / 2, W / 2)));
-                x_split = true;
-            } else {
-                PROF_CONV(1, n, H, W, C, C, 9, wsi_conv3x3_bn_act(mid, out, resid, wt->conv_w[wi + 1], wt->conv_b[wi + 1], n, H, W, C,
-                                                                 C, 1, 1, planes, st));
-                x_split = false;
-            }
+                c.in2 = fold_in2; c.in2_c = C / 2; c.wpk2 = wt->down_w[s - 1]; c.bias2 = wt->down_b[s - 1];
+                ProfScope ps(st, 1, 2.0 * n * H * W * (double)C * (C * 9 + C / 2));
+                if ((rc = conv_common(c))) return rc;
+            } else if ((rc = run(1, c)))
+                return rc;
             x = out;
             if (b == 1 && stage_off) stage_off[s] = (size_t)((char*)out - ws);
             ++block;
@@ -1203,7 +1227,7 @@ int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const ui
     if (!wt || !workspace || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
     if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
     size_t off; int stage;
-    int rc = trunk_run(wt, in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut, n, cap, h, w, workspace, 8,
+    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace, 8,
                        (hipStream_t)stream, p, off, stage);
     if (rc) return rc;
     const char* last = (const char*)workspace + off;
@@ -1226,7 +1250,7 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
         trunk_plan(cap, h, w, wt->planes, p))
         return WSI_EINVAL;
     size_t off; int stage;
-    int rc = trunk_run(wt, in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut, n, cap, h, w, workspace,
+    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace,
                        stop_after, (hipStream_t)stream, p, off, stage);
     if (rc) return rc;
     return wsi_pf_unpack((const char*)workspace + off, tap_out_nchw, n, p.sc[stage], p.sh[stage], p.sw[stage], wt->planes,
@@ -1239,9 +1263,6 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
 // at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the split-precision modes, 64 in
 // speed mode; the padding channels carry zero weights), 1x1 head.
 static const int kUnetSkipC[5] = {256, 128, 64, 64, 0};      // encoder maps x3, x2, x1, x0 (and none for the last block)
-int g_unet_fuse_up = 1;                                  // A/B: wsi_conv_set_mode +65536 off
-int g_unet_tail = 1;                                     // A/B: wsi_conv_set_mode +2097152 off
-int g_unet_x0_fused = 1;                                 // A/B: wsi_conv_set_mode +8388608 off
 struct UnetPlan {
     size_t x0, cat[5], mid[5], out[5], total;
     int r_h[5], r_w[5], cx[5];                               // resolution of block L; channels of its upsampled input
@@ -1288,8 +1309,8 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
     // wsi_prof kinds of the decoder (bench.py --workload seg): 6 = decoder 3x3 conv (algorithmic FLOPs over REAL channels are the
     // caller's business: the record carries 2 * N * H * W * cin_stored * cout_stored * 9), 7 = upsample + concat glue, 8 = 1x1 head
     // r05: parity mode runs the last block and the head as ONE kernel (tail.hip) when the caller prepacked its weights
-    // (wsi_unet_tail_prepack -> dw->tail_w) and the map is at most 256 wide; A/B: wsi_conv_set_mode +2097152 off
-    const bool tail = planes == 2 && dw->tail_w && g_unet_tail && u.cx[4] == 32 && kUnetSkipC[4] == 0 && dw->classes <= 4 &&
+    // (wsi_unet_tail_prepack -> dw->tail_w) and the map is at most 256 wide; A/B: WSI_CONV_MODE_UNET_NO_TAIL
+    const bool tail = planes == 2 && dw->tail_w && g_routes.unet_tail && u.cx[4] == 32 && kUnetSkipC[4] == 0 && dw->classes <= 4 &&
                       u.r_w[3] % 32 == 0 && u.r_w[3] <= 128 &&
                       (size_t)pf_alloc_pixels(n, u.r_h[3], u.r_w[3]) * 128 <= (size_t)0x7fffffff;      // (32-bit buffer offsets into x4: ~1000 tiles of 256 x 256)
     for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
@@ -1297,34 +1318,34 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
         // r04: the block's first conv reads the low-resolution tensor and the skip directly (ConvArgs.in_up: nearest x2 upsample +
         // concat as source addresses of its slab DMA) where the shape's kernel is the slab3 kernel; otherwise (EINVAL) the
         // upsample_concat pass writes the concatenated tensor first, as in r02-r03
-        int pi = prof_open(st, 6, 2.0 * n * H * W * (double)cin * cout * 9);
-        rc = g_unet_fuse_up ? wsi_conv3x3_up_concat_bn_act(x, L < 4 ? enc[L + 1] : nullptr, dec + u.mid[L], dw->conv_w[2 * L], dw->conv_b[2 * L], n, H, W,
-                                                           u.cx[L], kUnetSkipC[L], cout, 1, planes, st)
-                            : WSI_EINVAL;
-        prof_close(st, pi);
-        if (rc == WSI_EINVAL) {
-            if (pi >= 0) g_prof.kind[pi] = 9;             // (a refused launch: its empty record is not a decoder conv)
-            pi = prof_open(st, 7, 0.0);
-            rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], kUnetSkipC[L], planes, st);
-            prof_close(st, pi);
-            pi = prof_open(st, 6, 2.0 * n * H * W * (double)cin * cout * 9);
-            if (!rc) rc = conv_common(dec + u.cat[L], dec + u.mid[L], nullptr, dw->conv_w[2 * L], dw->conv_b[2 * L], n, H, W, cin, cout, 1, 3, 1, planes, st);
-            prof_close(st, pi);
+        // conv j of the decoder (3x3, stride 1, ReLU) at this block's resolution
+        auto conv3 = [&](const void* in, void* out, int j, int ci) {
+            return ConvCall{.in = in, .out = out, .wpk = dw->conv_w[j], .bias = dw->conv_b[j], .n = n, .h = H, .w = W, .cin = ci, .cout = cout,
+                            .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
+        };
+        {
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            rc = g_routes.unet_fuse_up ? wsi_conv3x3_up_concat_bn_act(x, L < 4 ? enc[L + 1] : nullptr, dec + u.mid[L], dw->conv_w[2 * L], dw->conv_b[2 * L],
+                                                                      n, H, W, u.cx[L], kUnetSkipC[L], cout, 1, planes, st)
+                                       : WSI_EINVAL;
+            if (rc == WSI_EINVAL) ps.relabel(9);          // (a refused launch: its empty record is not a decoder conv)
         }
-        pi = prof_open(st, 6, 2.0 * n * H * W * (double)cout * cout * 9);
-        if (!rc) rc = conv_common(dec + u.mid[L], dec + u.out[L], nullptr, dw->conv_w[2 * L + 1], dw->conv_b[2 * L + 1], n, H, W, cout, cout, 1, 3, 1, planes, st);
-        prof_close(st, pi);
+        if (rc == WSI_EINVAL) {
+            { ProfScope ps(st, 7, 0.0); rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], kUnetSkipC[L], planes, st); }
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            if (!rc) rc = conv_common(conv3(dec + u.cat[L], dec + u.mid[L], 2 * L, cin));
+        }
+        ProfScope ps(st, 6, conv_flops(n, H, W, cout, cout, 9));
+        if (!rc) rc = conv_common(conv3(dec + u.mid[L], dec + u.out[L], 2 * L + 1, cout));
         x = dec + u.out[L];
     }
     if (tail) {
-        const int pt = prof_open(st, 10, 2.0 * n * u.r_h[4] * u.r_w[4] * (9.0 * (32.0 * 16.0 + 16.0 * 16.0) + 16.0 * dw->classes));    // kind 10: the reference formulation's FLOPs over REAL channels
+        ProfScope ps(st, 10, 2.0 * n * u.r_h[4] * u.r_w[4] * (9.0 * (32.0 * 16.0 + 16.0 * 16.0) + 16.0 * dw->classes));    // kind 10: the reference formulation's FLOPs over REAL channels
         if (!rc) rc = wsi_unet_tail_dispatch(x, dw->tail_w, n, u.r_h[3], u.r_w[3], dw->classes, logits_out, st);
-        prof_close(st, pt);
         return rc;
     }
-    const int pi = prof_open(st, 8, 2.0 * n * u.r_h[4] * u.r_w[4] * (double)dw->head_cin * dw->classes);
+    ProfScope ps(st, 8, 2.0 * n * u.r_h[4] * u.r_w[4] * (double)dw->head_cin * dw->classes);
     if (!rc) rc = wsi_unet_head_dispatch(x, n, u.r_h[4], u.r_w[4], dw->cout[9], dw->head_w, dw->head_b, dw->head_cin, dw->classes, logits_out, planes, st);
-    prof_close(st, pi);
     return rc;
 }
 
@@ -1336,7 +1357,8 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!wt || !dw || !workspace || n <= 0 || cap < n || (!logits_out && !enc_out) || h % 32 || w % 32) return WSI_EINVAL;
     if (trunk_plan(cap, h, w, wt->planes, p) || unet_plan(dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
-    if (!in_f32 && (!slide || !tile_xy || !lut)) return WSI_EINVAL;
+    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
+    if (!src.valid()) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
@@ -1345,29 +1367,26 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     size_t off, stage_off[4];
     int stage;
     // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
-    // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: wsi_conv_set_mode +8388608 off)
-    const bool x0_fused = g_unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && wt->norm && g_stem_u8x && g_stem_fused &&
-                          g_stem_shared_weights;
-    int rc = trunk_run(wt, in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut, n, cap, h, w, workspace, 8, st, p, off, stage,
-                       false, stage_off, x0_fused ? dec + u.x0 : nullptr);
+    // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
+    const ConvRoutes& r = g_routes;
+    const bool x0_fused = r.unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && wt->norm && r.stem_u8x && r.stem_fused &&
+                          r.stem_shared_weights;
+    int rc = trunk_run(wt, src, n, cap, h, w, workspace, 8, st, p, off, stage, false, stage_off, x0_fused ? dec + u.x0 : nullptr);
     if (rc) return rc;
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
     // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines
-    StemArgs a;
-    a.mode = in_f32 ? 0 : 1;
-    a.in_f32 = in_f32; a.slide = slide; a.slide_pitch = slide_pitch_bytes; a.SH = slide_h; a.SW = slide_w;
-    a.origins = tile_xy; a.lut = lut; a.wpk = wt->stem_w; a.bias = wt->stem_b; a.out = (float*)(ws + p.stem_scratch);
-    a.N = n; a.H = h; a.W = w; a.wpk_u8 = nullptr; a.bias_u8 = nullptr;
-    const int pi = prof_open(st, 7, 0.0);                    // (glue: the unfused stem conv for the half-resolution skip x0)
-    if (x0_fused) {
-    } else if (g_unet_fuse_up) {                                    // r04: the conv kernel writes PF lines itself (was: f32 scratch + nhwc_to_pf pass)
-        a.out_pf = dec + u.x0; a.out_planes = planes;
-        rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
-    } else {
-        rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
-        if (!rc) rc = wsi_nhwc_to_pf_dispatch(a.out, dec + u.x0, n, h / 2, w / 2, 64, planes, st);
+    StemArgs a = stem_args(src, wt->stem_w, wt->stem_b, (float*)(ws + p.stem_scratch), n, h, w);
+    {
+        ProfScope ps(st, 7, 0.0);                            // (glue: the unfused stem conv for the half-resolution skip x0)
+        if (x0_fused) {
+        } else if (r.unet_fuse_up) {                         // r04: the conv kernel writes PF lines itself (was: f32 scratch + nhwc_to_pf pass)
+            a.out_pf = dec + u.x0; a.out_planes = planes;
+            rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
+        } else {
+            rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
+            if (!rc) rc = wsi_nhwc_to_pf_dispatch(a.out, dec + u.x0, n, h / 2, w / 2, 64, planes, st);
+        }
     }
-    prof_close(st, pi);
     if (rc) return rc;
     const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], dec + u.x0};
     if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first

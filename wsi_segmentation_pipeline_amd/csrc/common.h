@@ -370,3 +370,38 @@ struct StemArgs {
     void* out_pf = nullptr;
     int out_planes = 0;
 };
+
+// Host-side route switches: which kernel or tensor form the launch code in capi.hip / conv.hip / stem.hip / tail.hip picks where
+// more than one computes the same thing.  Plain data, process-wide, one instance (capi.hip); written only by the setters named
+// below (include/wsi_hip.h gives every mode bit its name), read by the host code that builds launches - never by a kernel.
+struct ConvRoutes {
+    // wsi_stem_set_mode(fused, rows_per_seg)
+    int stem_fused = 1;            // fused stem+maxpool kernel (0: the two-kernel form)
+    int stem_rows = 64;            // pooled rows per workgroup (r05 sweep: 16 / 32 / 64 -> 6.41 / 6.16 / 6.08 ms per 6 162 tiles)
+    int stem_u8x = 1;              // exact-u8 arithmetic when the caller supplies its weights (A/B: fused = 2 disables)
+    int stem_shared_weights = 1;   // A/B: fused = 3 selects the one-strip form (weights in registers)
+    // wsi_trunk_set_chunks(stem_chunk, layer1_chunk)
+    int chunk_stem = 0;            // sub-batch sizes (images); 0 = whole batch (measured r01: no gain)
+    int chunk_l1 = 0;
+    // wsi_conv_set_mode(mode): the base value (mode & 7) ...
+    int s2_slab = 1;               // stride-2 convs: phase-slab kernel (1) or per-tap gather kernel (0)
+    int s2_small_tiles = 1;        // r01: 64-pixel tiles measured ~10 % faster (3 workgroups per CU)
+    // ... and one bit per switch
+    int xcd_order = 0;             // 1: CONV_XCD_ORDER for multi-channel-block launches
+    int wide_min_c = 128;          // channel count from which the wide kernel (cfg 60) is the default (r01: 3-8 % faster than cfg 30 on layers 2-4)
+    int s2_ablate = 0;             // bottleneck study only: stride-2 kernel without weight loads (wrong results)
+    int s2_split = 1;              // trunk: phase-split stage outputs + wide stride-2 kernel
+    int xcd_ranges = 2;            // XCD-contiguous tile ranges: 1 = the 64-channel layer only, 2 = every stride-1 layer (r01: ~-1 % overall)
+    int l1_rows = 1;               // row-stacked layer-1 kernel (cfg 40) instead of slab3 (cfg 38)
+    int ds_fold = 1;               // trunk, mode 3: the strided blocks' 1x1 downsample runs inside their second conv
+    int slab_pair = 1;             // paired-tile LDS addressing of the layer-1 kernel
+    int l1_lines96 = 1;            // trunk, mode 3: stem output and layer-1 tensors in 96-byte lines (capi.hip trunk_run)
+    int s2_nt4 = 1;                // 256-cout workgroups in the wide stride-2 kernel
+    int unet_fuse_up = 1;          // U-Net decoder: upsample + concat inside each block's first conv
+    int wide_d8 = 1;               // 8-pixel slab rows of the wide kernel on 8 x 8 maps (r05)
+    int l1p = 0;                   // the persistent layer-1 kernel (cfg 42) instead of the rows kernel (cfg 40); r05: 45 % slower, off
+    int unet_tail = 1;             // U-Net decoder: last block + head as one kernel (tail.hip)
+    int unet_tail_form = 2;        // 2: unet_tail2_kernel, 1: the first form (unet_tail_kernel)
+    int unet_x0_fused = 1;         // U-Net: the fused stem kernel stores the half-resolution skip x0 itself
+};
+extern ConvRoutes g_routes;

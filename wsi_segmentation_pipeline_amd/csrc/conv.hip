@@ -819,7 +819,6 @@ __global__ __launch_bounds__(320, 1) void conv3x3s1_l1p_kernel(ConvArgs a) {
 }
 
 static int g_l1p_grid = 0;                               // workgroups of the persistent kernel: one per CU (multiple of 8)
-int g_l1p = 0;                                           // A/B (wsi_conv_set_mode +1048576 ON): the persistent layer-1 kernel (cfg 42) instead of the rows kernel (cfg 40); r05: 45 % slower, off
 static int launch_l1p(const ConvArgs& a, hipStream_t st) {
     if (a.go.C != 64 || a.gi.C % 32 || a.gi.C < 64 || a.gi.W != 64 || a.gi.H % 4 || a.in2 || a.in_up || !(a.flags & CONV_IN96) ||
         (a.resid && !(a.flags & CONV_RESID96)))
@@ -1111,13 +1110,12 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
 }
 
 
-int g_wide_d8 = 1;                                       // A/B (wsi_conv_set_mode +131072 off): 8-pixel slab rows on 8 x 8 maps (r05)
 template <int PLANES, int MINW, int ABL = 0, int WM = 2, int WN = 2, int NT = 2, bool D8 = false>
 static int launch_wide(const ConvArgs& a, hipStream_t st) {
     constexpr int BM = WM * 128, NTHREADS = WM * WN * 64, BN = WN * NT * 32;
     if (a.go.C % BN) return WSI_EINVAL;
     if constexpr (!D8 && ABL == 0 && WM == 2 && WN == 2 && NT == 2) {
-        if (g_wide_d8 && a.gi.W == 8 && a.gi.H == 8) return launch_wide<PLANES, MINW, 0, 2, 2, 2, true>(a, st);
+        if (g_routes.wide_d8 && a.gi.W == 8 && a.gi.H == 8) return launch_wide<PLANES, MINW, 0, 2, 2, 2, true>(a, st);
     }
     const int nblocks = a.go.C / BN;
     const long long R = (long long)a.gi.N * a.gi.H * a.gi.W;
@@ -1534,14 +1532,13 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wide_kernel(ConvArgs a) {
     }
 }
 
-int g_s2_nt4 = 1;                                        // A/B (wsi_conv_set_mode +32768 off): 256-cout workgroups in the wide stride-2 kernel
 template <int PLANES>
 static int launch_s2wide(const ConvArgs& a, hipStream_t st) {
     constexpr int BM = 256, XB = 45056;
     const bool ds = a.out2 != nullptr;                                       // fused 1x1 downsample branch, or the 3x3 conv alone
     if (a.go.C % 128 || a.go.P > 34 || !a.in_split_pixels || (ds && (!a.wpk2 || !a.bias2)) || a.out_split_pixels) return WSI_EINVAL;
     const long long R = (long long)a.go.N * a.go.H * a.go.W;
-    const bool nt4 = !ds && PLANES == 3 && g_s2_nt4 && a.go.C % 256 == 0;      // 256 couts per workgroup (r03)
+    const bool nt4 = !ds && PLANES == 3 && g_routes.s2_nt4 && a.go.C % 256 == 0;      // 256 couts per workgroup (r03)
     const int nblocks = a.go.C / (nt4 ? 256 : 128);
     // dense tiles if the span of 256 real pixels (+ the largest phase back-shift) fits one pixel buffer
     ConvArgs g = a;
@@ -1560,18 +1557,12 @@ static int launch_s2wide(const ConvArgs& a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
-int g_s2_ablate = 0;
-int g_l1_rows = 1;                                       // A/B (wsi_conv_set_mode +1024 off): row-stacked layer-1 kernel (cfg 40) instead of slab3 (cfg 38)
-int g_slab_pair = 1;                                     // A/B (wsi_conv_set_mode +4096 off): paired-tile LDS addressing of the layer-1 kernel
-int g_xcd_ranges = 2;                                    // XCD-contiguous tile ranges: 1 = the 64-channel layer only, 2 = every stride-1 layer (r01: ~-1 % overall)
-int g_xcd_order = 0;                                     // 1: CONV_XCD_ORDER for multi-channel-block launches
-int g_s2_small_tiles = 1;                                // r01: 64-pixel tiles measured ~10 % faster (3 workgroups per CU)
 // stride-2 3x3 (+ optional fused downsample) dispatch; cfg 0 = gather kernel (unfused only)
 int wsi_s2_dispatch(const ConvArgs& a_in, int planes, hipStream_t st) {
     ConvArgs a = a_in;
     if (a.in_split_pixels)                                   // phase-split input: the wide kernel is the only reader
         return planes == 3 ? launch_s2wide<3>(a, st) : planes == 2 ? launch_s2wide<2>(a, st) : WSI_EINVAL;
-    if (g_xcd_order && a.go.C > 128) a.flags |= CONV_XCD_ORDER;
+    if (g_routes.xcd_order && a.go.C > 128) a.flags |= CONV_XCD_ORDER;
     if (a.gi.C % 64 || a.go.C % 128 || planes < 1 || planes > 3) return WSI_EINVAL;
     if (a.go.H * 2 != a.gi.H || a.go.W * 2 != a.gi.W || a.gi.N != a.go.N) return WSI_EINVAL;
     const bool fuse = a.out2 != nullptr;
@@ -1582,9 +1573,9 @@ int wsi_s2_dispatch(const ConvArgs& a_in, int planes, hipStream_t st) {
         return WSI_EINVAL;                                   // speed mode: gather kernel
     }
 #ifdef WSI_STUDY
-    if (g_s2_ablate && planes == 3 && fuse) return launch_s2slab<2, 1, 4, 3, 3, true, 34, 16>(a, st);   // weight loads off (wrong results)
+    if (g_routes.s2_ablate && planes == 3 && fuse) return launch_s2slab<2, 1, 4, 3, 3, true, 34, 16>(a, st);   // weight loads off (wrong results)
 #endif
-    if (g_s2_small_tiles) {                                  // 64-pixel tiles: smaller slabs, more workgroups per CU
+    if (g_routes.s2_small_tiles) {                                  // 64-pixel tiles: smaller slabs, more workgroups per CU
         if (planes == 3) return fuse ? launch_s2slab<2, 1, 4, 3, 3, true>(a, st) : launch_s2slab<2, 1, 4, 3, 3, false>(a, st);
         if (planes == 2) return fuse ? launch_s2slab<2, 1, 4, 2, 3, true>(a, st) : launch_s2slab<2, 1, 4, 2, 3, false>(a, st);
     }
@@ -1631,8 +1622,8 @@ int wsi_pp_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st);    
 
 int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t st) {
     ConvArgs a = a_in;
-    if (g_xcd_order && cfg >= 20 && cfg < 40 && !CONV_STUDY(a, ~7)) a.flags |= CONV_XCD_ORDER;     // slab3 family only
-    if (g_xcd_ranges && !CONV_STUDY(a, ~7) && ((cfg >= 20 && cfg < 42) || cfg == 60 || cfg == 90 || cfg == 91 || (cfg >= 70 && cfg < 90)) && (g_xcd_ranges == 2 || a.go.C == 64)) a.flags |= CONV_XCD_RANGES;
+    if (g_routes.xcd_order && cfg >= 20 && cfg < 40 && !CONV_STUDY(a, ~7)) a.flags |= CONV_XCD_ORDER;     // slab3 family only
+    if (g_routes.xcd_ranges && !CONV_STUDY(a, ~7) && ((cfg >= 20 && cfg < 42) || cfg == 60 || cfg == 90 || cfg == 91 || (cfg >= 70 && cfg < 90)) && (g_routes.xcd_ranges == 2 || a.go.C == 64)) a.flags |= CONV_XCD_RANGES;
     if ((a.flags & CONV_IN96) && !((cfg >= 20 && cfg <= 42) || cfg == 90 || cfg == 91)) return WSI_EINVAL;   // 96-byte input lines: slab3 / row-stacked kernels only
     if (a.in_up && !((cfg >= 20 && cfg < 40) || cfg == 90 || cfg == 91)) return WSI_EINVAL;   // fused upsample + concat input: slab3 kernels only
     if (cfg < 20) return WSI_EINVAL;                         // (cfg 0-9 were the first slab kernel, removed)
@@ -1672,7 +1663,7 @@ int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t
     // cfg 38: cfg 31 held to 168 registers = three waves per SIMD, three workgroups per CU (r03 A/B on layer 1)
     if (cfg == 38) {
         if (planes != 3) return WSI_EINVAL;
-        const int rc = g_slab_pair ? launch_slab3<4, 2, 2, 3, 3, true, 0, true>(a, st) : WSI_EINVAL;     // paired-tile addressing where the map allows it
+        const int rc = g_routes.slab_pair ? launch_slab3<4, 2, 2, 3, 3, true, 0, true>(a, st) : WSI_EINVAL;     // paired-tile addressing where the map allows it
         return rc != WSI_EINVAL ? rc : launch_slab3<4, 2, 2, 3, 3, true>(a, st);
     }
     // cfg 39: 512 px x 64 couts (4 x 2 waves) for 64-channel layers on maps wider than 128 (the U-Net decoder's last level): a
@@ -1683,8 +1674,6 @@ int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t
 }
 
 // default config per layer shape (tuned on MI355X, tools/tune_conv.py)
-int g_wide_min_c = 128;                                  // channel count from which the wide kernel (cfg 60) is the default
-                                                         // (r01: 3-8 % faster than cfg 30 on layers 2-4; A/B via wsi_conv_set_mode)
 static int slab_default_cfg(const ConvArgs& a, int planes, bool fallback) {           // r01 / r02 tunes: profiles/r0*_tune_conv*.log
     if (a.go.C % 64) return fallback ? 91 : 90;              // 32 output channels
     // fused upsample + concat input (U-Net decoder, ConvArgs.in_up): the slab3 kernels have the two-source slab DMA; on the
@@ -1705,12 +1694,12 @@ static int slab_default_cfg(const ConvArgs& a, int planes, bool fallback) {     
     // (r04: with its main-loop DMA through inline asm the wide kernel wins in parity mode too - n = 2000, with / without residual:
     // layer 2 1.569 / 1.470 ms against slab3 1.628 / 1.528, layer 3 1.363 / 1.318 against ping-pong 1.434 / 1.363, layer 4 1.257 / 1.237
     // against 1.288 / 1.256, profiles/r04_tune_parity.log - so the two parity rules of r02 are gone and the line below decides)
-    if (a.go.C % 128 == 0 && a.go.C >= g_wide_min_c && !(planes == 1 && a.gi.W > 33)) return 60;
+    if (a.go.C % 128 == 0 && a.go.C >= g_routes.wide_min_c && !(planes == 1 && a.gi.W > 33)) return 60;
     if (a.go.C % 128 != 0 && a.gi.W > 128 && !fallback) return 39;       // r02 tune, C = 64 at 256 x 256: 0.94 vs 1.21 ms (cfg 31); at 128 x 128 cfg 31 wins
-    if (a.go.C == 64 && a.gi.C == 64 && planes == 3 && !fallback && g_l1_rows && g_l1p && a.gi.W == 64 && a.gi.H % 4 == 0 && !a.in2 && (a.flags & CONV_IN96) &&
+    if (a.go.C == 64 && a.gi.C == 64 && planes == 3 && !fallback && g_routes.l1_rows && g_routes.l1p && a.gi.W == 64 && a.gi.H % 4 == 0 && !a.in2 && (a.flags & CONV_IN96) &&
         (!a.resid || (a.flags & CONV_RESID96)))
         return 42;                                           // r05 study route (wsi_conv_set_mode +1048576): persistent producer-fed kernel, measured 45 % SLOWER than cfg 40
-    if (a.go.C % 128 != 0 && planes == 3 && !fallback && g_l1_rows && a.gi.W == 64 && a.gi.H % 4 == 0 && !a.in2) return 40;   // r04: row-stacked tiles (A/B: wsi_conv_set_mode +1024 off)
+    if (a.go.C % 128 != 0 && planes == 3 && !fallback && g_routes.l1_rows && a.gi.W == 64 && a.gi.H % 4 == 0 && !a.in2) return 40;   // r04: row-stacked tiles (A/B: wsi_conv_set_mode +1024 off)
     // r04: with the scheduling fences the two-waves-per-SIMD form (cfg 31) beats the fence-less 168-register form (cfg 38) on
     // 16 x 16 maps (cfg4's layer 1, n = 32000: 1.552 vs 1.693 ms); 64-wide maps whose height is no multiple of four keep cfg 38
     // (1.545 vs 1.590 ms; profiles/r04_tune_slab3_fences.log)

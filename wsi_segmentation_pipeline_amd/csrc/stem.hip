@@ -655,7 +655,6 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
     }
 }
 
-int g_stem_shared_weights = 1;                        // A/B: wsi_stem_set_mode(fused = 3) selects the one-strip form (weights in registers)
 int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows_per_seg, hipStream_t st, int out96, long long plane96, void* x0_pf) {
     if (a.H % 4 || a.W % 4 || a.N <= 0 || planes < 1 || planes > 3 || rows_per_seg <= 0) return WSI_EINVAL;
     StemPoolArgs A;
@@ -668,7 +667,7 @@ int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows
     if (grid > 0x7fffffffLL) return WSI_EINVAL;
     const bool u8x = a.mode == 1 && a.wpk_u8 && a.bias_u8 && planes >= 2;
     const size_t lds = (size_t)(planes == 1 || u8x ? 1 : 2) * SP_PLANE;
-    if (u8x && g_stem_shared_weights) {               // integer stem, two strips per workgroup, digit planes shared in LDS
+    if (u8x && g_routes.stem_shared_weights) {               // integer stem, two strips per workgroup, digit planes shared in LDS
         const size_t lds2 = 2 * SP_RING_I8 + 512 + 2 * 7 * 3 * 1024;
         const int grid2 = (int)((grid + 1) / 2);
         if (x0_pf && planes != 2) return WSI_EINVAL;

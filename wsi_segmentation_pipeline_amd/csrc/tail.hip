@@ -509,7 +509,6 @@ __global__ __launch_bounds__(WT == 4 ? 512 : 256, WT == 4 ? 2 : 1) void unet_tai
     }
 }
 
-int g_unet_tail_form = 2;                                      // A/B: wsi_conv_set_mode +4194304 -> the first form (unet_tail_kernel)
 
 size_t wsi_unet_tail_lds_bytes(int w) { return (size_t)4 * (w + 2) * 128 + (size_t)4 * (2 * w + 2) * 64 + 132 * 4; }
 size_t wsi_unet_tail2_lds_bytes(int w) { return (size_t)4 * (w + 2) * 128 + (size_t)5 * (2 * w + 2) * 64 + 128 + 256; }
@@ -542,7 +541,7 @@ int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w
     }
     const int bands = wsi_unet_tail_bands(n, h, cus);
     a.bands = bands; a.rows_per_band = h / bands;
-    if (g_unet_tail_form == 2 && (w == 32 || w == 64 || w == 128)) {
+    if (g_routes.unet_tail_form == 2 && (w == 32 || w == 64 || w == 128)) {
         const size_t lds2 = wsi_unet_tail2_lds_bytes(w);
 #define TAIL2_LAUNCH(WT)                                                                                                             \
     do {                                                                                                                            \

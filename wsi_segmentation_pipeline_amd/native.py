@@ -3,7 +3,9 @@
 The product path has no CPU fallback: if the library is missing, ``load()`` raises and every caller
 fails loudly.  ``build()`` compiles the library in-tree with hipcc for gfx950 (works without a GPU).
 """
+import contextlib
 import ctypes as C
+import enum
 import os
 import subprocess
 
@@ -160,6 +162,61 @@ def load():
         raise RuntimeError('libwsi_hip.so ABI version mismatch')
     _lib = lib
     return lib
+
+
+class ConvMode(enum.IntFlag):
+    """wsi_conv_set_mode bits: include/wsi_hip.h WSI_CONV_MODE_* (tests/test_capi_symbols.py compares the two)."""
+    S2_GATHER = 0
+    S2_SLAB = 1
+    S2_SLAB_128 = 3
+    XCD_ORDER = 8
+    WIDE_FROM_256 = 16
+    WIDE_NEVER = 32
+    S2_ABLATE = 64
+    NO_S2_SPLIT = 128
+    XCD_RANGES_OFF = 256
+    XCD_RANGES_L1 = 512
+    L1_SLAB3 = 1024
+    NO_DS_FOLD = 2048
+    NO_SLAB_PAIR = 4096
+    L1_LINES128 = 16384
+    S2_NT2 = 32768
+    UNET_CONCAT_PASS = 65536
+    WIDE_NO_D8 = 131072
+    L1_PERSISTENT = 1048576
+    UNET_NO_TAIL = 2097152
+    UNET_TAIL_FORM1 = 4194304
+    UNET_X0_UNFUSED = 8388608
+
+
+class StemMode(enum.IntEnum):
+    """wsi_stem_set_mode `fused` values: include/wsi_hip.h WSI_STEM_MODE_*."""
+    UNFUSED = 0
+    FUSED = 1
+    FUSED_LUT = 2
+    FUSED_ONE_STRIP = 3
+
+
+@contextlib.contextmanager
+def conv_mode(flags=0, base=ConvMode.S2_SLAB):
+    """Run the block under wsi_conv_set_mode(base + flags); the default mode (S2_SLAB alone) is back on exit."""
+    lib = load()
+    check(lib.wsi_conv_set_mode(int(base) | int(flags)), 'wsi_conv_set_mode')
+    try:
+        yield
+    finally:
+        lib.wsi_conv_set_mode(int(ConvMode.S2_SLAB))
+
+
+@contextlib.contextmanager
+def stem_mode(fused, rows=64):
+    """Run the block under wsi_stem_set_mode(fused, rows); the default (FUSED, 64 rows) is back on exit."""
+    lib = load()
+    check(lib.wsi_stem_set_mode(int(fused), rows), 'wsi_stem_set_mode')
+    try:
+        yield
+    finally:
+        lib.wsi_stem_set_mode(int(StemMode.FUSED), 64)
 
 
 def check(rc, what):
