@@ -288,3 +288,90 @@ def test_s2_slab_images_rule(lib):
     assert f(1, 8192, 8192, 64, 3) == 0                          # one image over 4 GiB: no slab launch at all
     assert f(0, 128, 128, 64, 3) == -22 and f(1, 0, 128, 64, 3) == -22 and f(1, 128, 128, 0, 3) == -22
     assert f(1, 128, 128, 64, 0) == -22 and f(1, 128, 128, 64, 4) == -22
+
+
+def _ints(n, seed, lo, hi):
+    """n fp32 values in [lo, hi] from integer arithmetic alone (no random generator: the digests below must not depend on numpy's)"""
+    u = (np.arange(n, dtype=np.uint64) * np.uint64(2654435761) + np.uint64(seed)) % np.uint64(20011)
+    return (lo + (hi - lo) * (u.astype(np.float64) / 20010.0)).astype(np.float32)
+
+
+def _bn(n, seed):
+    """BatchNorm weight, bias, running mean and running variance of n channels"""
+    return [_ints(n, seed + 1, 0.5, 1.5), _ints(n, seed + 2, -1.0, 1.0), _ints(n, seed + 3, -1.0, 1.0), _ints(n, seed + 4, 0.5, 1.5)]
+
+
+def _packed_weight_digests(lib):
+    import hashlib
+    p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    sha = lambda *arrays: hashlib.sha256(b''.join(a.tobytes() for a in arrays)).hexdigest()
+    none4 = [None] * 4
+    got = {}
+    for cout, cin, k in ((64, 128, 3), (128, 64, 1)):
+        w = _ints(cout * cin * k * k, 7 * cout + k, -1.0, 1.0).reshape(cout, cin, k, k)
+        w[3] = 0.0                                                       # an all-zero channel: scale 1
+        w[5] *= np.float32(2.0 ** -100)                                  # the exponent clamp of the planes-2 channel scale
+        w[6] *= np.float32(2.0 ** 20)
+        for planes in (1, 2, 3):
+            for bn in (_bn(cout, cin), none4):
+                pk = np.full(lib.wsi_prepack_conv_bytes(cout, cin, k, planes), 0xa5, np.uint8)
+                bias = np.zeros(cout, np.float32)
+                assert lib.wsi_prepack_conv(p(w), *[p(a) for a in bn], 1e-5, cout, cin, k, planes, p(pk), p(bias)) == 0
+                got['conv %d %d %d planes %d %s' % (cout, cin, k, planes, 'bn' if bn is not none4 else 'no bn')] = sha(pk, bias)
+    w = _ints(64 * 3 * 7 * 7, 11, -0.5, 0.5)
+    bn = _bn(64, 13)
+    mean, std = np.array([0.485, 0.456, 0.406], np.float32), np.array([0.229, 0.224, 0.225], np.float32)
+    for planes in (1, 2, 3):
+        pk = np.full(lib.wsi_prepack_stem_bytes(planes), 0xa5, np.uint8)
+        bias = np.zeros(64, np.float32)
+        assert lib.wsi_prepack_stem(p(w), *[p(a) for a in bn], 1e-5, planes, p(pk), p(bias)) == 0
+        got['stem planes %d' % planes] = sha(pk, bias)
+    pk = np.full(lib.wsi_prepack_stem_bytes(2), 0xa5, np.uint8)
+    bias = np.zeros(64, np.float32)
+    assert lib.wsi_prepack_stem_u8(p(w), *[p(a) for a in bn], 1e-5, p(mean), p(std), 2, p(pk), p(bias)) == 0
+    got['stem u8 planes 2'] = sha(pk, bias)
+    for cmid in (16, 12):
+        w1, w2 = _ints(cmid * 32 * 9, 17, -0.6, 0.6), _ints(cmid * cmid * 9, 19, -0.9, 0.9)
+        hw, hb = _ints(3 * cmid, 23, -2.0, 2.0), _ints(3, 29, -1.0, 1.0)
+        for head_b in (hb, None):
+            blob = np.full(lib.wsi_unet_tail_prepack_bytes(), 0xa5, np.uint8)
+            assert lib.wsi_unet_tail_prepack(p(w1), *[p(a) for a in _bn(cmid, 31)], p(w2), *[p(a) for a in _bn(cmid, 37)], 1e-5, p(hw),
+                                             p(head_b), 32, cmid, 3, p(blob)) == 0
+            got['tail cmid %d %s' % (cmid, 'head_b' if head_b is not None else 'no head_b')] = sha(blob)
+    lut = np.zeros(3 * 256, np.float32)
+    assert lib.wsi_normalize_u8_lut(p(mean), p(std), p(lut)) == 0
+    got['lut'] = sha(lut)
+    return got
+
+
+# recorded from the library as built before the split (the commit that named the conv route switches)
+_PACKED_WEIGHT_DIGESTS = {'conv 64 128 3 planes 1 bn': '7f9f8b331290550917daf0a750667d19aadc9b4ce62d638e3576a8ef62506464',
+ 'conv 64 128 3 planes 1 no bn': '3abc4473eeaf78fb4162ccefb7aeadb1e70a5081a8a61acf0c5f01a70872e5ea',
+ 'conv 64 128 3 planes 2 bn': '145e747e351e27c4781efa2954d97db970107b59198f5dd91ccadcc536179766',
+ 'conv 64 128 3 planes 2 no bn': '2e3c247f046afd760c547edb82cb152b4c6d34aefe735789e7d18fa5bb7a5a87',
+ 'conv 64 128 3 planes 3 bn': 'f694529bca8228f95a1f4bc3f4508a2146a664ad325329c6bc631e0dc458c026',
+ 'conv 64 128 3 planes 3 no bn': 'fd3449a9a7bff0757ac3e100873aa126110b12a1cbb05e948f71722adb0c4479',
+ 'conv 128 64 1 planes 1 bn': '603b86a62ff34590f2f335eccc1b52c389adf842e9ec34497b2f6aa1c54a7779',
+ 'conv 128 64 1 planes 1 no bn': '7bbeecd389ec414a9592ad9ae3bdc126f15a2007fd5c6bdb5d7cb275a3384761',
+ 'conv 128 64 1 planes 2 bn': '6a503aae9622ea660fcb78e584eb3b163c2b7764a26fba9afa88de17ec6565ea',
+ 'conv 128 64 1 planes 2 no bn': '1336745a7aa4a7de7481580c0ff03326bc913fa220b1d35c5f7c70fc1cf61651',
+ 'conv 128 64 1 planes 3 bn': 'b84e1275e17694c0e66aa30860014c76b051207e2e1d8cf88a87b089093338f9',
+ 'conv 128 64 1 planes 3 no bn': '5a6328ecc9fa9f9cc5cbd22ad1a31b63c346a51fe759562f61a94df85fe67bd5',
+ 'stem planes 1': '9b5d8af972e1fc956264ef09f720ed9be8850cece1955160bb8684fc946847c2',
+ 'stem planes 2': '3bc3bf5b348c2ad49b2b05a471c569c00288c38076e91a8698c0595db7a502bc',
+ 'stem planes 3': '3bc3bf5b348c2ad49b2b05a471c569c00288c38076e91a8698c0595db7a502bc',
+ 'stem u8 planes 2': '64426db08384fafb2b055d76cfc00044c4a6dd60ef18d4d6b383af78e1f1d105',
+ 'tail cmid 16 head_b': 'd2db4cd5b15e4b97192246de1783ae42de631537c25e1ae495730aa320a9b737',
+ 'tail cmid 16 no head_b': 'a8555cc24a547e896b6f2ab4e663d9ffa84293c3620a74a1e61e09f659389aab',
+ 'tail cmid 12 head_b': 'be1e2dac5223069610c7956bfcb211fb9102e323f0bc0d9938e8f8d02a84ac71',
+ 'tail cmid 12 no head_b': '708e96f9ec1a60a3313891a220fac0c255d6facd94667f6575322287ce849dc4',
+ 'lut': '1d8b9af12b7b391827f7c801265239e21435c7e29b4d78c6189a35e437633897'}
+
+
+def test_packed_weights_byte_identical(lib):
+    """Every host-side pack (wsi_prepack_conv at planes 1-3 with and without BN, with an all-zero output channel, one at 2^-100 - the
+    exponent clamp of the channel scale - and one at 2^20; wsi_prepack_stem, wsi_prepack_stem_u8, wsi_unet_tail_prepack, wsi_normalize_u8_lut)
+    is byte for byte what the library produced before csrc/prepack.hip was split off and folded each weight once: SHA-256 over the
+    packed bytes and the bias, inputs from integer arithmetic.  The buffers start as 0xa5, so a byte the pack stops writing shows
+    as well."""
+    assert _packed_weight_digests(lib) == _PACKED_WEIGHT_DIGESTS

@@ -394,3 +394,55 @@ def test_persistent_layer1_kernel_is_bit_identical(dev, sd):
             old = eng.forward_tiles(slide, xy, 256, 256, feat=True, logits=True, fmap=True)
             for a, b in zip(new, old):
                 assert torch.equal(a, b), n
+
+
+def _prof_records(lib, run):
+    """(kind, flops) of every launch `run` makes between wsi_prof_begin(64) and wsi_prof_end"""
+    import ctypes as C
+    from wsi_segmentation_pipeline_amd import native
+    native.check(lib.wsi_prof_begin(64), 'wsi_prof_begin')
+    try:
+        run()
+    finally:
+        ms, kind, fl = np.zeros(64, np.float32), np.zeros(64, np.int32), np.zeros(64, np.float64)
+        n = lib.wsi_prof_end(*[a.ctypes.data_as(C.c_void_p) for a in (ms, kind, fl)], 64)
+    assert 0 <= n <= 64
+    return [(int(kind[i]), float(fl[i])) for i in range(n)]
+
+
+# what the host code before the split computes (trunk_run, unet_decoder_run); not yet confirmed by a recording on an MI355X
+_PROF_TRUNK = {
+    'planes 1': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 20971520.0), (1, 37748736.0),
+                 (1, 37748736.0), (1, 37748736.0), (2, 20971520.0), (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (2, 20971520.0),
+                 (1, 37748736.0), (1, 37748736.0), (1, 37748736.0)],
+    'planes 2': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 20971520.0), (1, 37748736.0),
+                 (1, 37748736.0), (1, 37748736.0), (2, 20971520.0), (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (2, 20971520.0),
+                 (1, 37748736.0), (1, 37748736.0), (1, 37748736.0)],
+    'planes 2 gather': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 18874368.0), (3, 2097152.0),
+                        (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (2, 18874368.0), (3, 2097152.0), (1, 37748736.0), (1, 37748736.0),
+                        (1, 37748736.0), (2, 18874368.0), (3, 2097152.0), (1, 37748736.0), (1, 37748736.0), (1, 37748736.0)],
+    'planes 3': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 18874368.0), (1, 39845888.0),
+                 (1, 37748736.0), (1, 37748736.0), (2, 18874368.0), (1, 39845888.0), (1, 37748736.0), (1, 37748736.0), (2, 18874368.0),
+                 (1, 39845888.0), (1, 37748736.0), (1, 37748736.0)],
+}
+
+def test_profiler_records_of_one_forward(dev, sd):
+    """The profiler records (include/wsi_hip.h wsi_prof_begin / _end) of one wsi_trunk_forward on two 64 x 64 tiles: order, kinds and
+    FLOP counts (doubles computed on the host from integers: compared exactly) as the host code computed them before csrc/trunk.hip
+    was split off (_PROF_TRUNK: read from that code, still to be confirmed by a recording of that library on an MI355X).  Default mode at planes 1, 2, 3: the stem (4), four layer-1 convs (5), then per stage the strided entry (2) and three
+    stride-1 convs (1) - at planes 3 the block's second conv carries the folded downsample, C * 9 + C / 2 per output.  Under S2_GATHER a
+    1x1 downsample launch (3) follows each entry."""
+    from wsi_segmentation_pipeline_amd import native
+    from wsi_segmentation_pipeline_amd.engine import TrunkEngine
+    lib = native.load()
+    x = R.normalize_u8(W.make_u8_patches(41, (2, 3, 64, 64))).to(dev)
+    got = {}
+    for planes in (1, 2, 3):
+        eng = TrunkEngine(sd, dev, planes=planes, head=(sd['fc0.weight'], sd['fc0.bias']))
+        got['planes %d' % planes] = _prof_records(lib, lambda: eng.forward_f32(x, logits=True))
+        if planes == 2:
+            with native.conv_mode(base=native.ConvMode.S2_GATHER):
+                got['planes 2 gather'] = _prof_records(lib, lambda: eng.forward_f32(x, logits=True))
+    for name, rec in got.items():
+        print('prof records, %s: %r' % (name, rec))
+    assert got == _PROF_TRUNK

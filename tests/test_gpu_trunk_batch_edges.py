@@ -102,7 +102,7 @@ def _image_at(lib, byte, pixbytes, h, w):
 
 def _crossings(lib, n, cap, h, w, planes):
     """{buffer @ edge: images} of an n-image batch (workspace planned for cap) next to the 2 and 4 GiB byte positions of the trunk's
-    large buffers.  Layout (csrc/capi.hip trunk_plan / trunk_run): the layer-1 tensors are ordinary PF, or, in mx with the phase-split
+    large buffers.  Layout (csrc/trunk.hip trunk_plan / trunk_run): the layer-1 tensors are ordinary PF, or, in mx with the phase-split
     hand-over, two planes of 96-byte lines plane96 = pf_alloc_pixels(cap) * 96 apart; the hand-over to layer 2 (modes 2 and 3, layer-2
     maps at most 33 wide) is four phase images of (cap, h/8, w/8) maps; the layer-2 tensors are ordinary PF."""
     bpc = 2 if planes == 1 else 4

@@ -304,3 +304,37 @@ def test_fused_decoder_tail_with_fewer_classes(dev, classes):
     with torch.no_grad():
         ref = U.unet_forward(sdc, x)
     assert float((fused.cpu() - ref).abs().max()) <= 1e-3 * max(1.0, float(ref.abs().max()) / 16.0)
+
+
+# what the host code before the split computes (trunk_run, unet_decoder_run); not yet confirmed by a recording on an MI355X
+_PROF_UNET = {
+    'f32': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 20971520.0), (1, 37748736.0),
+            (1, 37748736.0), (1, 37748736.0), (2, 20971520.0), (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (2, 20971520.0),
+            (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (7, 0.0), (6, 113246208.0), (6, 37748736.0), (6, 113246208.0),
+            (6, 37748736.0), (6, 113246208.0), (6, 37748736.0), (6, 150994944.0), (6, 37748736.0), (10, 114294784.0)],
+    'u8': [(4, 38535168.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (5, 37748736.0), (2, 20971520.0), (1, 37748736.0),
+           (1, 37748736.0), (1, 37748736.0), (2, 20971520.0), (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (2, 20971520.0),
+           (1, 37748736.0), (1, 37748736.0), (1, 37748736.0), (7, 0.0), (6, 113246208.0), (6, 37748736.0), (6, 113246208.0),
+           (6, 37748736.0), (6, 113246208.0), (6, 37748736.0), (6, 150994944.0), (6, 37748736.0), (10, 114294784.0)],
+}
+
+def test_profiler_records_of_one_unet_forward(dev, sd):
+    """The profiler records of one wsi_unet_forward (planes 2, fused-tail weights prepacked) on two 64 x 64 tiles, from f32 input and
+    from a u8 slide: order, kinds and FLOP counts (host doubles from integers: compared exactly) as the host code computed them before
+    csrc/trunk.hip was split off (_PROF_UNET: read from that code with no decoder launch refused at this size, still to be confirmed by a
+    recording of that library on an MI355X).  The trunk's records, then the x0 glue (7), the decoder blocks (6; a refused fused launch is a 9
+    followed by the concat pass 7 and the conv 6) and the fused tail (10) last."""
+    from wsi_segmentation_pipeline_amd import native
+    from wsi_segmentation_pipeline_amd.unet import UNetEngine
+    from tests.test_gpu_trunk import _prof_records
+    lib = native.load()
+    u8 = W.make_u8_patches(43, (2, 3, 64, 64))
+    strip = np.ascontiguousarray(u8.transpose(0, 2, 3, 1).reshape(-1, 64, 3))
+    slide, xy = torch.from_numpy(strip).to(dev), torch.tensor([[0, 0], [0, 64]], dtype=torch.int32)
+    x = R.normalize_u8(u8).to(dev)
+    eng = UNetEngine(sd, dev, planes=2)
+    assert eng.dw.tail_w
+    got = {'f32': _prof_records(lib, lambda: eng.forward_f32(x)), 'u8': _prof_records(lib, lambda: eng.forward_tiles(slide, xy, 64, 64))}
+    for name, rec in got.items():
+        print('prof records, unet %s: %r' % (name, rec))
+    assert got == _PROF_UNET

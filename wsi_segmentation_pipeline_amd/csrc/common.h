@@ -340,7 +340,7 @@ static inline __device__ void split_f16x4(const float* v, f16x4& hi, f16x4& lo) 
         lo[i] = b;
     }
 }
-// Mode-2 packed weights carry one power-of-two scale per output channel (capi.hip wsi_prepack_conv: every channel's largest
+// Mode-2 packed weights carry one power-of-two scale per output channel (prepack.hip wsi_prepack_conv: every channel's largest
 // |weight| is moved into [2^13, 2^14), so the lo plane of every weight within 2^-16 of it is a NORMAL fp16 and weights of any
 // magnitude fit the format): the inverse scales, Cout floats, follow the fragment blocks of the pack; the epilogue multiplies
 // the accumulator by them (exact) before it adds the bias.
@@ -362,7 +362,7 @@ struct StemArgs {
     float* out;                // [N][H/2][W/2][64] f32 (post ReLU)
     int N, H, W;               // patch size
     // integer path of the fused kernel (mode 1, split precision): pixels as i8 (x - 128) + an inside byte, weights in balanced
-    // base-256 digits with the normalisation and BN folded in (capi.hip wsi_prepack_stem_u8, stem.hip stem_pool_kernel<.., DIG>)
+    // base-256 digits with the normalisation and BN folded in (prepack.hip wsi_prepack_stem_u8, stem.hip stem_pool_kernel<.., DIG>)
     const void* wpk_u8;        // [nt 2][kh 7][digit][lane 64][16] i8 + float scale[64], or null: LUT path
     const float* bias_u8;      // 64
     // unfused conv kernel (stem_conv7x7_kernel): write the post-ReLU map as PF lines of `out_planes` instead of f32 NHWC into `out`
@@ -371,7 +371,7 @@ struct StemArgs {
     int out_planes = 0;
 };
 
-// Host-side route switches: which kernel or tensor form the launch code in capi.hip / conv.hip / stem.hip / tail.hip picks where
+// Host-side route switches: which kernel or tensor form the launch code in capi.hip / trunk.hip / conv.hip / stem.hip / tail.hip picks where
 // more than one computes the same thing.  Plain data, process-wide, one instance (capi.hip); written only by the setters named
 // below (include/wsi_hip.h gives every mode bit its name), read by the host code that builds launches - never by a kernel.
 struct ConvRoutes {
@@ -395,7 +395,7 @@ struct ConvRoutes {
     int l1_rows = 1;               // row-stacked layer-1 kernel (cfg 40) instead of slab3 (cfg 38)
     int ds_fold = 1;               // trunk, mode 3: the strided blocks' 1x1 downsample runs inside their second conv
     int slab_pair = 1;             // paired-tile LDS addressing of the layer-1 kernel
-    int l1_lines96 = 1;            // trunk, mode 3: stem output and layer-1 tensors in 96-byte lines (capi.hip trunk_run)
+    int l1_lines96 = 1;            // trunk, mode 3: stem output and layer-1 tensors in 96-byte lines (trunk.hip trunk_run)
     int s2_nt4 = 1;                // 256-cout workgroups in the wide stride-2 kernel
     int unet_fuse_up = 1;          // U-Net decoder: upsample + concat inside each block's first conv
     int wide_d8 = 1;               // 8-pixel slab rows of the wide kernel on 8 x 8 maps (r05)

@@ -13,6 +13,7 @@
 // (single-pass bf16 is 1.9e-2 off).  PLANES=1 is the single-pass bf16
 // speed mode.
 #include "conv_dev.h"
+#include "internal.h"
 
 // --------------------------------------------------------------------------------------------
 // Generic gather kernel (3x3 stride 2, 1x1 stride 2, also stride 1): per (line, tap) step the BM
@@ -1618,7 +1619,6 @@ static int launch_gather(const ConvArgs& a, hipStream_t st) {
     X(38, 4, 2, 2, 3, true)
 
 
-int wsi_pp_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st);      // conv_pp.hip
 
 int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t st) {
     ConvArgs a = a_in;

@@ -19,6 +19,7 @@
 // (4, 2, 3) = 384 px x 128 couts layer 2: both fit two slabs + two weight stages in the 160 KB LDS.
 // Bit-identical to the wide / slab3 kernels (same per-output accumulation order: lines, taps, K fragments).
 #include "conv_dev.h"
+#include "internal.h"
 
 // raw barriers (LDS-DMA stays in flight across them); the _VM form first drains the wave's own DMA.  No control flow may
 // sit between a multiply phase and its barrier: hipcc then sinks MFMAs past the barrier into the next load phase.
@@ -247,8 +248,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
         for (int nt = 0; nt < NT; ++nt) conv_epilogue_q<MT, PLANES>(a, acc[nt], qs, valid, nb * NTILES + wn * NT + nt, lane, scratch);
     }
 }
-
-long long dense_max_slab_pixels(const ConvArgs& a, int BM);
 
 template <int PLANES, int WM, int WN, int MT, bool STAMP = false, int DMODE = 0, bool PRIO = false>
 static int launch_pp(const ConvArgs& a, hipStream_t st) {

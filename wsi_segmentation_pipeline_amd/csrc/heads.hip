@@ -5,6 +5,7 @@
 //                /root/reference/models/models.py:46-50 Regressor)
 //   pf_pack / pf_unpack : f32 NCHW <-> padded-flat bf16 planes (API boundary + tests)
 #include "pf_lines.h"
+#include "internal.h"
 
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -5,6 +5,7 @@
 //   resample      : Pillow's two-pass BICUBIC resize of u8 tiles, bit-exact (spec: oracle/resize_oracle.py, pinned against the
 //                   installed Pillow): integer taps with 22 fractional bits, horizontal pass then vertical, u8 between passes
 #include "common.h"
+#include "../../include/wsi_hip.h"
 #include <cmath>
 #include <vector>
 
@@ -40,7 +41,7 @@ struct wsi_ring {
     hipEvent_t fence = nullptr;
 };
 
-int wsi_ring_create_impl(wsi_ring** out, int slots, size_t slot_bytes) {
+extern "C" int wsi_ring_create(wsi_ring** out, int slots, size_t slot_bytes) {
     if (!out || slots < 1 || slots > 64 || slot_bytes == 0 || (slot_bytes & 3)) return WSI_EINVAL;
     wsi_ring* r = new wsi_ring();
     r->slots = slots; r->slot_bytes = slot_bytes;
@@ -66,9 +67,9 @@ int wsi_ring_create_impl(wsi_ring** out, int slots, size_t slot_bytes) {
     return WSI_OK;
 }
 
-void* wsi_ring_host_slot_impl(wsi_ring* r, int slot) { return (r && slot >= 0 && slot < r->slots) ? r->host[slot] : nullptr; }
+extern "C" void* wsi_ring_host_slot(wsi_ring* r, int slot) { return (r && slot >= 0 && slot < r->slots) ? r->host[slot] : nullptr; }
 
-int wsi_ring_wait_slot_impl(wsi_ring* r, int slot) {
+extern "C" int wsi_ring_wait_slot(wsi_ring* r, int slot) {
     if (!r || slot < 0 || slot >= r->slots) return WSI_EINVAL;
     if (r->busy[slot]) {
         if (hipEventSynchronize(r->done[slot]) != hipSuccess) return WSI_EFAULT;
@@ -77,7 +78,7 @@ int wsi_ring_wait_slot_impl(wsi_ring* r, int slot) {
     return WSI_OK;
 }
 
-int wsi_ring_submit_impl(wsi_ring* r, int slot, int rows, int width, int channels, long long src_pitch, uint8_t* dst,
+extern "C" int wsi_ring_submit(wsi_ring* r, int slot, int rows, int width, int channels, long long src_pitch, uint8_t* dst,
                          long long dst_pitch) {
     if (!r || slot < 0 || slot >= r->slots || rows <= 0 || width <= 0 || (channels != 3 && channels != 4) || !dst) return WSI_EINVAL;
     if (src_pitch < (long long)width * channels || dst_pitch < (long long)width * 3 || (channels == 4 && (src_pitch & 3))) return WSI_EINVAL;
@@ -91,30 +92,30 @@ int wsi_ring_submit_impl(wsi_ring* r, int slot, int rows, int width, int channel
     return WSI_OK;
 }
 
-int wsi_ring_fence_impl(wsi_ring* r, hipStream_t compute) {
+extern "C" int wsi_ring_fence(wsi_ring* r, void* compute_stream) {
     if (!r) return WSI_EINVAL;
-    if (hipEventRecord(r->fence, r->copy) != hipSuccess || hipStreamWaitEvent(compute, r->fence, 0) != hipSuccess) return WSI_EFAULT;
+    if (hipEventRecord(r->fence, r->copy) != hipSuccess || hipStreamWaitEvent((hipStream_t)compute_stream, r->fence, 0) != hipSuccess) return WSI_EFAULT;
     return WSI_OK;
 }
 
 // The copy stream writes destination memory the caller allocated on its compute stream: a caching allocator may hand out a
 // block whose last readers (kernels of the previous slide) are still queued THERE.  acquire orders the ring's copies after
-// everything enqueued on `compute` so far (an event wait, no host block).
-int wsi_ring_acquire_impl(wsi_ring* r, hipStream_t compute) {
+// everything enqueued on the compute stream so far (an event wait, no host block).
+extern "C" int wsi_ring_acquire(wsi_ring* r, void* compute_stream) {
     if (!r) return WSI_EINVAL;
-    if (hipEventRecord(r->fence, compute) != hipSuccess || hipStreamWaitEvent(r->copy, r->fence, 0) != hipSuccess) return WSI_EFAULT;
+    if (hipEventRecord(r->fence, (hipStream_t)compute_stream) != hipSuccess || hipStreamWaitEvent(r->copy, r->fence, 0) != hipSuccess) return WSI_EFAULT;
     return WSI_OK;
 }
-int wsi_ring_device_impl(const wsi_ring* r) { return r ? r->device : -1; }
+extern "C" int wsi_ring_device(const wsi_ring* r) { return r ? r->device : -1; }
 
-int wsi_ring_drain_impl(wsi_ring* r) {
+extern "C" int wsi_ring_drain(wsi_ring* r) {
     if (!r) return WSI_EINVAL;
     if (hipStreamSynchronize(r->copy) != hipSuccess) return WSI_EFAULT;
     for (auto& b : r->busy) b = 0;
     return WSI_OK;
 }
 
-void wsi_ring_destroy_impl(wsi_ring* r) {
+extern "C" void wsi_ring_destroy(wsi_ring* r) {
     if (!r) return;
     (void)hipStreamSynchronize(r->copy);
     for (void* h : r->host) (void)hipHostFree(h);
@@ -168,15 +169,15 @@ static int rs_axis(RsAxis& ax, int in, int out) {
     return WSI_OK;
 }
 
-void wsi_resample_plan_destroy_impl(wsi_resample_plan* p) {
+extern "C" void wsi_resample_plan_destroy(wsi_resample_plan* p) {
     if (!p) return;
     for (RsAxis* ax : {&p->h, &p->v}) { if (ax->bounds) (void)hipFree(ax->bounds); if (ax->kk) (void)hipFree(ax->kk); }
     delete p;
 }
-int wsi_resample_plan_create_impl(wsi_resample_plan** out, int in_h, int in_w, int out_h, int out_w) {
+extern "C" int wsi_resample_plan_create(wsi_resample_plan** out, int in_h, int in_w, int out_h, int out_w) {
     if (!out || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) return WSI_EINVAL;
     wsi_resample_plan* p = new wsi_resample_plan();
-    if (rs_axis(p->h, in_w, out_w) != WSI_OK || rs_axis(p->v, in_h, out_h) != WSI_OK) { wsi_resample_plan_destroy_impl(p); return WSI_EFAULT; }
+    if (rs_axis(p->h, in_w, out_w) != WSI_OK || rs_axis(p->v, in_h, out_h) != WSI_OK) { wsi_resample_plan_destroy(p); return WSI_EFAULT; }
     *out = p;
     return WSI_OK;
 }
@@ -231,11 +232,12 @@ __global__ __launch_bounds__(256) void resample_v_kernel(const uint8_t* tmp, int
     }
 }
 
-size_t wsi_resample_scratch_bytes_impl(const wsi_resample_plan* p, int n) {
+extern "C" size_t wsi_resample_scratch_bytes(const wsi_resample_plan* p, int n) {
     return (!p || n <= 0) ? 0 : (size_t)n * p->v.in * p->h.out * 3;
 }
-int wsi_resample_tiles_impl(const wsi_resample_plan* p, const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, int N,
-                            uint8_t* out, void* scratch, hipStream_t st) {
+extern "C" int wsi_resample_tiles(const wsi_resample_plan* p, const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, int N,
+                                  uint8_t* out, void* scratch, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
     if (!p || !slide || !origins || !out || N <= 0 || SH <= 0 || SW <= 0) return WSI_EINVAL;
     const int ph = p->v.in, th = p->v.out, tw = p->h.out;
     const bool need_h = p->h.in != p->h.out, need_v = ph != th;

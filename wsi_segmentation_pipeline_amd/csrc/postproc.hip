@@ -12,6 +12,7 @@
 // kernels, no MFMA.  The convex hull runs on per-row extremes only (<= 3 doubled rows per image row), its two monotone
 // chains are built by one lane each out of LDS, and the fill is one interval per row in exact 64-bit integers.
 #include "common.h"
+#include "internal.h"
 #include <limits.h>
 
 // ------------------------------------------------------------------------------------------ resize / argmax / threshold

@@ -7,6 +7,8 @@
 // Thumbnail-sized, irregular, HBM / latency-bound integer work: plain kernels, int64 / float64 arithmetic that NumPy reproduces
 // bit for bit (-ffp-contract=off).
 #include "common.h"
+#include "internal.h"
+#include "../../include/wsi_hip.h"
 
 // ------------------------------------------------------------------------------------------ HSV saturation mask
 __global__ __launch_bounds__(256) void hsv_mask_kernel(const uint8_t* rgb, long long npix, int stride, double thresh, uint8_t* mask) {
@@ -256,8 +258,8 @@ __global__ __launch_bounds__(256) void holes_fill_kernel(const uint8_t* mask, co
     for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
         out[i] = (mask[i] || (labels[i] && !touch[labels[i]])) ? 1 : 0;
 }
-size_t wsi_cc_scratch_bytes(int H, int W);
-size_t wsi_fill_holes_scratch_bytes_impl(int H, int W) {
+extern "C" size_t wsi_fill_holes_scratch_bytes(int H, int W) {
+    if (H <= 0 || W <= 0) return 0;
     const size_t n = (size_t)H * W;
     return wsi_cc_scratch_bytes(H, W) + n /* inverted mask */ + 2 * (n + 2) * sizeof(int) /* labels, touch */ + 512;
 }
@@ -382,7 +384,7 @@ __global__ void slic_update_kernel(const unsigned long long* sums, double* segs,
     for (int c = 0; c < 3; ++c) s[2 + c] = ((double)(long long)sums[k * 6 + 3 + c] / SLIC_FIX) / (double)cnt;
 }
 
-size_t wsi_slic_scratch_bytes_impl(int H, int W, int K) {
+extern "C" size_t wsi_slic_scratch_bytes(int H, int W, int K) {
     if (H <= 0 || W <= 0 || K <= 0 || K > SLIC_MAXK) return 0;
     const size_t npix = (size_t)H * W;
     return 2 * npix * 3 * sizeof(double) + npix * 3 * sizeof(int) + (size_t)K * 6 * sizeof(unsigned long long) + 256;
@@ -391,7 +393,7 @@ size_t wsi_slic_scratch_bytes_impl(int H, int W, int K) {
 // labels (H, W) int32 out
 int wsi_slic_dispatch(const uint8_t* rgb, int H, int W, const double* fw, int radius, double* segs, int K, int step_y, int step_x,
                       double step, double compactness, int iters, int* labels, void* scratch, hipStream_t st) {
-    if (!rgb || !segs || !labels || !scratch || wsi_slic_scratch_bytes_impl(H, W, K) == 0 || iters < 1 || radius < 0 || (radius && !fw) ||
+    if (!rgb || !segs || !labels || !scratch || wsi_slic_scratch_bytes(H, W, K) == 0 || iters < 1 || radius < 0 || (radius && !fw) ||
         step_y < 1 || step_x < 1 || !(step > 0) || !(compactness > 0)) return WSI_EINVAL;
     const long long npix = (long long)H * W;
     double* a = (double*)scratch;
@@ -555,15 +557,15 @@ int wsi_kmeans_dispatch(const int* pts, int n, double* centres, int k, int iters
 }
 
 static int range_len(int lo, int hi, int step) { return hi > lo ? (hi - lo + step - 1) / step : 0; }
-long long wsi_tile_grid_candidates_impl(int iw, int ih, int ph, int pw, int sh, int sw) {
+extern "C" long long wsi_tile_grid_candidates(int iw, int ih, int ph, int pw, int sh, int sw) {
     if (sh <= 0 || sw <= 0) return -1;
     const long long ny = range_len(1, ih - 1 - ph, sh), nx = range_len(1, iw - 1 - pw, sw);
     return ny * nx + ny + nx;
 }
-size_t wsi_tile_grid_scratch_bytes_impl(long long n) { return (size_t)(2 * n + (n + 1023) / 1024 + 4) * sizeof(int); }
+extern "C" size_t wsi_tile_grid_scratch_bytes(long long n) { return n < 0 ? 0 : (size_t)(2 * n + (n + 1023) / 1024 + 4) * sizeof(int); }
 int wsi_tile_grid_dispatch(int iw, int ih, int ph, int pw, int sh, int sw, const uint8_t* mask, int MH, int MW, double m, double thresh,
                            int* out_xy, int* count_out, void* scratch, hipStream_t st) {
-    const long long n = wsi_tile_grid_candidates_impl(iw, ih, ph, pw, sh, sw);
+    const long long n = wsi_tile_grid_candidates(iw, ih, ph, pw, sh, sw);
     if (n < 0 || n > 0x7ffffff0LL || ph <= 0 || pw <= 0 || (mask && (MH <= 0 || MW <= 0 || !(m > 0.0)))) return WSI_EINVAL;
     if (n == 0) return hipMemsetAsync(count_out, 0, sizeof(int), st) == hipSuccess ? WSI_OK : WSI_EFAULT;
     TileGridArgs g;

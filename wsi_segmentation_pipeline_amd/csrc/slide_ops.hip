@@ -6,6 +6,7 @@
 //   softmax_threshold_argmax : /root/reference/utils/preprocessing.py:156-172 (+ heat map of
 //                   /root/reference/utils/eval.py:219-228)
 #include "common.h"
+#include "internal.h"
 
 __global__ __launch_bounds__(256) void tile_gather_kernel(const uint8_t* slide, long long pitch, int SH, int SW,
                                                           const int* origins, const float* lut, float* out, int N,

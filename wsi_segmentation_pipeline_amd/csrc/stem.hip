@@ -8,6 +8,7 @@
 // weights), so K = 224 = 14 k-steps of 16 and a lane's 8 consecutive k are two neighbouring input
 // pixels (4 channels each) = one aligned 16-byte LDS read of the [row][col][4ch] bf16 image.
 #include "common.h"
+#include "internal.h"
 
 constexpr int STEM_TR = 8;                       // conv-output rows per tile
 constexpr int STEM_TC = 32;                      // conv-output cols per tile
@@ -270,7 +271,7 @@ constexpr int SP_PLANE = SP_RING * SP_COLS * 8;
 // the fp16 hi/lo form it replaces (r02: 2.52 -> 2.08 ms per 2000 patches; DIG = 2 measured the same 2.08 ms - the kernel is
 // then bound by its VALU epilogue - and 1.1-1.6x the logit error on the margin families, so it is not used).
 typedef __attribute__((ext_vector_type(16))) int i32x16;
-constexpr int STEM_I8_SCALE_OFFSET = 2 * 7 * 3 * 1024;           // float scale[64] behind the digit planes (capi.hip: wsi_prepack_stem_u8)
+constexpr int STEM_I8_SCALE_OFFSET = 2 * 7 * 3 * 1024;           // float scale[64] behind the digit planes (prepack.hip: wsi_prepack_stem_u8)
 // NSTRIP (integer path only): strips per workgroup.  1 = the form above, weights in registers (236 VGPRs, two waves per SIMD).
 // 2 = a 256-thread workgroup of two strips whose four waves share ONE copy of the digit planes in LDS (42 KB) and read each
 // weight fragment right before its MFMA: ~150 VGPRs, three waves per SIMD.  r02 counters of the 1-strip form: VALU active 68 %

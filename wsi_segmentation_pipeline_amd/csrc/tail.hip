@@ -25,6 +25,7 @@
 // requested at the start of step k.  HBM traffic per tile image: 2.1 MB of x4 in, 1 MB of logits out (the unfused path: ~17 MB).
 #include <hip/hip_runtime.h>
 #include "conv_dev.h"
+#include "internal.h"
 
 struct TailArgs {
     const char* in;            // x4: PF tensor (N, h, w, 32 channels), planes 2

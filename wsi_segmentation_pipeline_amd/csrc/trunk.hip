@@ -1,0 +1,508 @@
+// The model-level entries of libwsi_hip.so (include/wsi_hip.h): the profiler, the trunk workspace and its layout tags, the trunk
+// launch sequence (wsi_trunk_forward, wsi_trunk_forward_tap) and the U-Net host sequence.  No device allocation, no
+// synchronisation, no exceptions.
+#include "internal.h"
+#include "../../include/wsi_hip.h"
+#include <mutex>
+#include <unordered_map>
+
+extern "C" {
+
+// ------------------------------------------------------------------------------------ profiler
+// Optional HIP-event timing of every conv launch made by wsi_trunk_forward, on the stream the
+// kernels run on (bench.py's roofline leg).  Off by default; never active inside graph capture.
+#define WSI_PROF_MAX 16384
+static struct {
+    int enabled, count, cap;
+    hipEvent_t ev[2 * WSI_PROF_MAX];
+    int kind[WSI_PROF_MAX];
+    double flops[WSI_PROF_MAX];
+    int created;
+} g_prof;
+
+int wsi_prof_begin(int max_records) {
+    if (max_records <= 0 || max_records > WSI_PROF_MAX) return WSI_EINVAL;
+    for (; g_prof.created < 2 * max_records; ++g_prof.created)
+        if (hipEventCreate(&g_prof.ev[g_prof.created]) != hipSuccess) return WSI_ENOMEM;
+    g_prof.cap = max_records; g_prof.count = 0; g_prof.enabled = 1;
+    return WSI_OK;
+}
+
+int wsi_prof_end(float* ms_out, int* kind_out, double* flops_out, int cap) {
+    g_prof.enabled = 0;
+    int n = g_prof.count < cap ? g_prof.count : cap;
+    for (int i = 0; i < n; ++i) {
+        if (hipEventSynchronize(g_prof.ev[2 * i + 1]) != hipSuccess) return WSI_EFAULT;
+        float ms = 0.f;
+        if (hipEventElapsedTime(&ms, g_prof.ev[2 * i], g_prof.ev[2 * i + 1]) != hipSuccess) return WSI_EFAULT;
+        ms_out[i] = ms; kind_out[i] = g_prof.kind[i]; flops_out[i] = g_prof.flops[i];
+    }
+    g_prof.count = 0;
+    return n;
+}
+
+// One record: an event on `st` when the scope opens and one when it closes, so a scope holds exactly the launch it times
+// (an early `return rc` inside it closes first).  Kinds and FLOP conventions: trunk_run, unet_decoder_run.
+struct ProfScope {
+    const hipStream_t st;
+    int i = -1;                                        // record index, -1 = not recording
+    ProfScope(hipStream_t st, int kind, double flops) : st(st) {
+        if (!g_prof.enabled || g_prof.count >= g_prof.cap) return;
+        i = g_prof.count++;
+        g_prof.kind[i] = kind; g_prof.flops[i] = flops;
+        (void)hipEventRecord(g_prof.ev[2 * i], st);
+    }
+    ~ProfScope() { if (i >= 0) (void)hipEventRecord(g_prof.ev[2 * i + 1], st); }
+    void relabel(int kind) { if (i >= 0) g_prof.kind[i] = kind; }
+};
+// 2*M*N*K of a conv over real output pixels (padding taps counted)
+static inline double conv_flops(int n, int ho, int wo, int ci, int co, int taps) { return 2.0 * n * ho * wo * (double)co * ci * taps; }
+
+// ------------------------------------------------------------------------------------ trunk
+// Layer-1 tensors of a full mode-3 trunk run live in 96-byte lines (common.h CONV_IN96): the pad positions of a PF buffer sit at
+// other BYTES than in the 128-byte layout, and pads are only ever zero because nobody writes them - so a workspace remembers
+// which layout its three stage-0 buffers last held, and a run in the other layout zero-fills them first (taps and the U-Net
+// encoder keep the 128-byte layout; a workspace that only ever runs one kind of call never pays).  -1 = all zero (after
+// wsi_trunk_workspace_init), otherwise 2 * planes + (1 if stage 0 holds 96-byte lines); an unknown workspace counts as dirty.
+static std::mutex g_ws_mutex;
+struct WsTag { int layout; size_t bytes; };                  // bytes: what wsi_trunk_workspace_init planned (0 = never initialised here)
+static std::unordered_map<const void*, WsTag> g_ws_layout;
+// returns 1 if the stage-0 buffers must be zero-filled first, 2 if everything must, -1 if the current plan (`need` bytes) exceeds
+// what the workspace was initialised for (r04 advisor finding: a workspace sized for one planes value - 2 bytes per channel at
+// planes 1 - and then run with another would be zero-filled and written past its end; the API carries no size, the tag does)
+static int ws_layout_switch(const void* ws, int want, size_t need) {
+    std::lock_guard<std::mutex> lk(g_ws_mutex);
+    auto it = g_ws_layout.find(ws);
+    const int have = it == g_ws_layout.end() ? -2 : it->second.layout;
+    const size_t bytes = it == g_ws_layout.end() ? 0 : it->second.bytes;
+    if (bytes && need > bytes) return -1;
+    g_ws_layout[ws] = WsTag{want, bytes};
+    if (have == want || have == -1) return 0;
+    return (have >= 0 && have / 2 != want / 2) ? 2 : 1;      // 2: the workspace last ran another planes value - every pad may be dirty
+}
+// A workspace that is freed must be forgotten: a later allocation at the same address would inherit its layout tag (r03 advisor
+// finding) and the map would grow without bound.  Unknown pointers are fine (nothing to forget).
+int wsi_trunk_workspace_release(void* workspace) {
+    std::lock_guard<std::mutex> lk(g_ws_mutex);
+    g_ws_layout.erase(workspace);
+    return WSI_OK;
+}
+
+int wsi_trunk_set_chunks(int stem_chunk, int layer1_chunk) {
+    if (stem_chunk < 0 || layer1_chunk < 0) return WSI_EINVAL;
+    if (stem_chunk && layer1_chunk && layer1_chunk % stem_chunk) return WSI_EINVAL;
+    g_routes.chunk_stem = stem_chunk; g_routes.chunk_l1 = layer1_chunk;
+    return WSI_OK;
+}
+struct TrunkPlan {
+    size_t stem_scratch;          // byte offsets into the workspace
+    size_t buf[4][4];             // [stage][0..2]: rotating PF buffers; [stage][3]: phase-split output of the stage (stages 0-2)
+    size_t total;
+    int sh[4], sw[4], sc[4];
+};
+
+static int trunk_plan(int n, int h, int w, int planes, TrunkPlan& p) {
+    if (n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 3) return WSI_EINVAL;
+    size_t off = 0;
+    p.stem_scratch = off;
+    off += align_up((size_t)n * (h / 2) * (w / 2) * 64 * sizeof(float), 256);
+    for (int s = 0; s < 4; ++s) {
+        p.sh[s] = h >> (2 + s); p.sw[s] = w >> (2 + s); p.sc[s] = 64 << s;
+        for (int b = 0; b < 3; ++b) {
+            p.buf[s][b] = off;
+            off += align_up(wsi_pf_bytes(n, p.sh[s], p.sw[s], p.sc[s], planes), 256);
+        }
+        p.buf[s][3] = off;                             // never holds anything but the phase-split form: its pads stay zero
+        if (s < 3 && planes >= 2) off += align_up(wsi_pf_split_bytes(n, p.sh[s], p.sw[s], p.sc[s], planes), 256);
+    }
+    p.total = off;
+    return WSI_OK;
+}
+
+size_t wsi_trunk_workspace_bytes(int n, int h, int w, int planes) {
+    TrunkPlan p;
+    return trunk_plan(n, h, w, planes, p) ? 0 : p.total;
+}
+
+int wsi_trunk_workspace_init(void* workspace, int n, int h, int w, int planes, void* stream) {
+    TrunkPlan p;
+    if (!workspace || trunk_plan(n, h, w, planes, p)) return WSI_EINVAL;
+    {
+        std::lock_guard<std::mutex> lk(g_ws_mutex);
+        g_ws_layout[workspace] = WsTag{-1, p.total};
+    }
+    return hipMemsetAsync((char*)workspace + p.buf[0][0], 0, p.total - p.buf[0][0], (hipStream_t)stream) == hipSuccess
+               ? WSI_OK
+               : WSI_EFAULT;
+}
+
+// What a trunk run leaves in the workspace: byte offset and stage of the last tensor produced, and the offset of every stage's
+// output (ordinary PF only when allow_split was off).
+struct TrunkResult { size_t last_off; int last_stage; size_t stage_off[4]; };
+// What the U-Net asks of the trunk beyond a plain run.
+struct TrunkOpts {
+    bool allow_split = true;      // stage outputs may be handed over phase-split (off: every stage output stays an ordinary PF tensor)
+    char* x0_out = nullptr;       // the fused stem kernel also stores the conv map before the pool here (PF, h / 2 x w / 2 x 64)
+};
+// Runs stem + residual stages; stops after stage `stop_after` (0 = pool, 1..8 = blocks, >= 8 all).
+// `p` is the plan of the workspace, made for `cap` >= n images: buffer offsets and the distance between phase images
+// come from the plan, so one workspace serves every batch size up to cap (image i sits at the same place whatever n is;
+// what images >= n still hold from an earlier, larger batch is never read: the zero row / column that close image
+// n-1 belong to its own block).
+static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, int cap, int h, int w, void* workspace,
+                     int stop_after, hipStream_t st, const TrunkPlan& p, TrunkResult& res, const TrunkOpts& opt = {}) {
+    char* ws = (char*)workspace;
+    const int planes = wt->planes;
+    int rc = WSI_OK;
+    // ProfScope kinds: 1 = 3x3 stride-1 of layers 2-4 (wide kernel), 5 = 3x3 stride-1 of the 64-channel layer 1 (slab3 kernel),
+    // 2 = 3x3 stride-2 (+ fused downsample), 3 = 1x1 downsample, 4 = stem+maxpool
+    // conv wi of the trunk (3x3, stride 1, ReLU) on n0 images of an H x W map with C channels in and out; call sites name what differs
+    auto conv3 = [&](const void* in, void* out, const void* resid, int wi, int n0, int H, int W, int C) {
+        return ConvCall{.in = in, .out = out, .resid = resid, .wpk = wt->conv_w[wi], .bias = wt->conv_b[wi], .n = n0, .h = H, .w = W, .cin = C,
+                        .cout = C, .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
+    };
+    auto run = [&](int kind, const ConvCall& c) {      // one conv launch = one profiler record
+        ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
+        return conv_common(c);
+    };
+    const size_t bpc = planes == 1 ? PFmt<1>::BPC : PFmt<2>::BPC;     // bytes per channel: 2 (speed) or 4 (parity, mx)
+    // ---- stem + maxpool + layer1 run in sub-batches so that the 4 MB/patch fp32 stem scratch and
+    //      the 1 MB/patch layer-1 tensors stay resident in the 256 MiB Infinity Cache; the deeper
+    //      (small-map) stages run on the whole batch to fill the chip.
+    const int cs = g_routes.chunk_stem > 0 ? g_routes.chunk_stem : n, c1 = g_routes.chunk_l1 > 0 ? g_routes.chunk_l1 : n;
+    const int H1 = p.sh[0], W1 = p.sw[0];
+    const int do_l1 = stop_after != 0;
+    // stage s writes its output phase-split when the next stage's entry can read it with the wide stride-2 kernel:
+    // full runs only (taps unpack ordinary PF), split precision, next output maps <= 33 wide, whole-batch stages
+    auto can_split = [&](int s) { return opt.allow_split && g_routes.s2_split && g_routes.s2_slab && stop_after >= 8 && planes >= 2 && s < 3 && p.sw[s + 1] <= 33; };
+    const bool split0 = can_split(0);                  // (a layer-1 sub-batch writes its images' slice of each phase image)
+    // r03: a full mode-3 run keeps stem output and layer-1 tensors in 96-byte lines (layer 1 is HBM-bound: 25 % fewer bytes);
+    // the last layer-1 conv writes the ordinary (or phase-split) 128-byte form every other kernel reads
+    // (only with the phase-split hand-over to layer 2: an ordinary 128-byte output would land in a buffer that held 96-byte lines)
+    const bool l96 = g_routes.l1_lines96 && planes == 3 && split0;
+    // the tag is recorded for EVERY planes value (r03 advisor finding: a planes 1 / 2 run used to leave a stale '96-byte lines' tag,
+    // and a later mx run on the same workspace then skipped the zero-fill): tag = 2 * planes + (96-byte lines)
+    if (const int dirty = ws_layout_switch(workspace, 2 * planes + (l96 ? 1 : 0), p.total)) {
+        if (dirty < 0) return WSI_EINVAL;              // planned for a smaller batch / another planes value than this call needs
+        const size_t nbytes = dirty == 2 ? p.total - p.buf[0][0] : p.buf[0][3] - p.buf[0][0];   // the three rotating stage-0 buffers (or everything)
+        if (hipMemsetAsync(ws + p.buf[0][0], 0, nbytes, st) != hipSuccess) return WSI_EFAULT;
+    }
+    // byte offset of image n0 inside a PF buffer of stage s
+    // (96-byte lines are line-planar: an image's offset inside every line plane; the planes lie plane96 bytes apart, a distance fixed by
+    //  the plan's capacity, so sub-batches and smaller batches address the same places)
+    auto img_off = [&](int s, int n0) { return (size_t)n0 * (p.sh[s] + 1) * (p.sw[s] + 1) * (s == 0 && l96 ? (size_t)96 : (size_t)p.sc[s] * bpc); };
+    const long long plane96 = l96 ? (long long)pf_alloc_pixels(cap, p.sh[0], p.sw[0]) * 96 : 0;
+    // ... and inside one phase image of stage 0's phase-split output (a PF tensor of stage 1's map size, 64 channels)
+    auto split_off = [&](int n0) { return (size_t)n0 * (p.sh[1] + 1) * (p.sw[1] + 1) * p.sc[0] * bpc; };
+
+    int l1_out = 0;                                    // buffer index holding layer1's output
+    for (int n1 = 0; n1 < n; n1 += c1) {
+        const int nn1 = n - n1 < c1 ? n - n1 : c1;
+        for (int n0 = n1; n0 < n1 + nn1; n0 += cs) {
+            const int nn = n1 + nn1 - n0 < cs ? n1 + nn1 - n0 : cs;
+            ProfScope ps(st, 4, 2.0 * nn * (h / 2) * (w / 2) * 64.0 * 147.0);
+            rc = stem_run(src.from_image(n0, h, w), wt->stem_w, wt->stem_b, wt->stem_w_u8, wt->stem_b_u8, wt->norm,
+                          nn, h, w, (float*)(ws + p.stem_scratch), ws + p.buf[0][0] + img_off(0, n0),
+                          planes, st, l96 ? 1 : 0, plane96,
+                          opt.x0_out ? opt.x0_out + (size_t)n0 * (h / 2 + 1) * (w / 2 + 1) * 64 * bpc : nullptr);     // (U-Net: the conv map before the pool)
+            if (rc) return rc;
+        }
+        if (!do_l1) continue;
+        int cur = 0;
+        for (int b = 0; b < 2 && (stop_after >= 8 || b < stop_after); ++b) {
+            const int m = (cur + 1) % 3, o = (cur + 2) % 3;
+            char *x = ws + p.buf[0][cur] + img_off(0, n1), *mid = ws + p.buf[0][m] + img_off(0, n1),
+                 *out = ws + p.buf[0][o] + img_off(0, n1);
+            const int f_in = l96 ? CONV_IN96 : 0, f_res = l96 ? CONV_RESID96 : 0;
+            ConvCall c = conv3(x, mid, nullptr, 2 * b, nn1, H1, W1, 64);
+            c.line_flags = f_in | (l96 ? CONV_OUT96 : 0); c.plane96 = plane96;
+            if ((rc = run(5, c))) return rc;
+            c = conv3(mid, out, x, 2 * b + 1, nn1, H1, W1, 64);
+            c.line_flags = f_in | f_res | (l96 && b == 0 ? CONV_OUT96 : 0); c.plane96 = plane96;
+            if (b == 1 && split0) {                    // layer1's output feeds only the stride-2 entry of layer2
+                c.out = ws + p.buf[0][3] + split_off(n1);
+                c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H1 / 2, W1 / 2);
+            }                                          // (otherwise the stage's last conv writes 128-byte lines: layer 2, taps and skips read those)
+            if ((rc = run(5, c))) return rc;
+            cur = o;
+        }
+        l1_out = cur;
+    }
+    res.last_off = res.stage_off[0] = p.buf[0][l1_out]; res.last_stage = 0;
+    if (stop_after >= 0 && stop_after <= 2) return WSI_OK;
+
+    int cur = l1_out;
+    const void* x = split0 ? ws + p.buf[0][3] : ws + p.buf[0][cur];
+    bool x_split = split0;
+    int block = 2;
+    for (int s = 1; s < 4; ++s) {
+        const int H = p.sh[s], W = p.sw[s], C = p.sc[s];
+        for (int b = 0; b < 2; ++b) {
+            const int wi = s * 4 + b * 2;
+            void *mid, *out;
+            const void* resid;
+            // r03, mode 3: the 1x1 downsample of a strided block is computed INSIDE the block's second conv as an extra K segment
+            // over phase 00 of the block input (ConvArgs.in2): the stride-2 kernel drops its second accumulator set and half its
+            // tile epilogues, the downsample tensor is neither written nor read back as a residual
+            const bool fold = b == 0 && x_split && planes == 3 && g_routes.ds_fold && g_routes.s2_slab && C % 128 == 0;
+            const void* fold_in2 = fold ? x : nullptr;
+            if (b == 0) {                              // strided block with 1x1 downsample branch
+                mid = ws + p.buf[s][1];
+                void* ds = fold ? nullptr : ws + p.buf[s][2];
+                out = ws + p.buf[s][0];
+                if (g_routes.s2_slab) {
+                    ProfScope ps(st, 2, conv_flops(n, H, W, C / 2, C, fold ? 9 : 10));
+                    rc = x_split ? s2_split_common(x, mid, ds, wt->conv_w[wi], wt->conv_b[wi], wt->down_w[s - 1],
+                                                   wt->down_b[s - 1], n, 2 * H, 2 * W, C / 2, C, planes, st, pf_alloc_pixels(cap, H, W))
+                                 : wsi_conv3x3s2_ds_fused(x, mid, ds, wt->conv_w[wi], wt->conv_b[wi], wt->down_w[s - 1], wt->down_b[s - 1], n,
+                                                          2 * H, 2 * W, C / 2, C, planes, st);
+                    if (rc) return rc;
+                } else {                               // gather kernel, then the 1x1 downsample as a launch of its own (no ReLU)
+                    ConvCall c = conv3(x, mid, nullptr, wi, n, 2 * H, 2 * W, C / 2);
+                    c.cout = C; c.stride = 2;
+                    if ((rc = run(2, c))) return rc;
+                    c.out = ds; c.wpk = wt->down_w[s - 1]; c.bias = wt->down_b[s - 1]; c.ksize = 1; c.relu = 0;
+                    if ((rc = run(3, c))) return rc;
+                }
+                resid = ds;
+                cur = 0;
+                res.last_off = p.buf[s][0];
+            } else {
+                const int m = (cur + 1) % 3, o = (cur + 2) % 3;
+                mid = ws + p.buf[s][m];
+                out = ws + p.buf[s][o];
+                if ((rc = run(1, conv3(x, mid, nullptr, wi, n, H, W, C)))) return rc;
+                resid = x;
+                cur = o;
+                res.last_off = p.buf[s][o];
+            }
+            x_split = !fold_in2 && b == 1 && can_split(s);                        // the stage's output feeds only the next stage's stride-2 entry
+            if (x_split) out = ws + p.buf[s][3];
+            ConvCall c = conv3(mid, out, resid, wi + 1, n, H, W, C);
+            if (x_split) { c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H / 2, W / 2); }
+            if (fold_in2) {                            // second conv of a strided block with the downsample folded in (never the stage's last conv)
+                c.in2 = fold_in2; c.in2_c = C / 2; c.wpk2 = wt->down_w[s - 1]; c.bias2 = wt->down_b[s - 1];
+                ProfScope ps(st, 1, 2.0 * n * H * W * (double)C * (C * 9 + C / 2));
+                if ((rc = conv_common(c))) return rc;
+            } else if ((rc = run(1, c)))
+                return rc;
+            x = out;
+            if (b == 1) res.stage_off[s] = (size_t)((char*)out - ws);
+            ++block;
+            res.last_stage = s;
+            if (block == stop_after) return WSI_OK;
+        }
+    }
+    return WSI_OK;
+}
+
+int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide,
+                      long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                      int n, int h, int w, void* workspace, int workspace_n, float* feat_out, float* logits_out,
+                      float* fmap_out, void* stream) {
+    TrunkPlan p;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !workspace || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
+    if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
+    TrunkResult res;
+    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace, 8,
+                       (hipStream_t)stream, p, res);
+    if (rc) return rc;
+    const char* last = (const char*)workspace + res.last_off;
+    if (feat_out || logits_out) {
+        rc = wsi_avgpool_fc(last, n, p.sh[3], p.sw[3], 512, wt->head_w, wt->head_b, wt->head_k, feat_out, logits_out,
+                            wt->planes, stream);
+        if (rc) return rc;
+    }
+    if (fmap_out) rc = wsi_pf_unpack(last, fmap_out, n, 512, p.sh[3], p.sw[3], wt->planes, stream);
+    return rc;
+}
+
+int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide,
+                          long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                          int n, int h, int w, void* workspace, int workspace_n, int stop_after, float* tap_out_nchw,
+                          void* stream) {
+    TrunkPlan p;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || stop_after > 8 || n <= 0 || cap < n ||
+        trunk_plan(cap, h, w, wt->planes, p))
+        return WSI_EINVAL;
+    TrunkResult res;
+    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace,
+                       stop_after, (hipStream_t)stream, p, res);
+    if (rc) return rc;
+    const int stage = res.last_stage;
+    return wsi_pf_unpack((const char*)workspace + res.last_off, tap_out_nchw, n, p.sc[stage], p.sh[stage], p.sw[stage], wt->planes,
+                         stream);
+}
+
+// ------------------------------------------------------------------------------------ U-Net (dense 'seg' path)
+// smp-style decoder on the ResNet-18 trunk: five blocks of [nearest x2 upsample, concat skip, 2 x (3x3 conv + BN + ReLU)]
+// at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the split-precision modes, 64 in
+// speed mode; the padding channels carry zero weights), 1x1 head.
+static const int kUnetSkipC[5] = {256, 128, 64, 64, 0};      // encoder maps x3, x2, x1, x0 (and none for the last block)
+// encoder map i of an h x w input, deepest first: x4 (512 channels, / 32), x3, x2, x1 (64, / 4), x0 (64, / 2: the stem conv before the pool)
+struct EncMap { int c, h, w; };
+static EncMap enc_map(int i, int h, int w) {
+    static const int ec[5] = {512, 256, 128, 64, 64};
+    return {ec[i], i < 4 ? h >> (5 - i) : h / 2, i < 4 ? w >> (5 - i) : w / 2};
+}
+struct UnetPlan {
+    size_t x0, cat[5], mid[5], out[5], total;
+    int r_h[5], r_w[5], cx[5];                               // resolution of block L; channels of its upsampled input
+};
+static int unet_plan(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes, UnetPlan& u) {
+    if (!dw || n <= 0 || h % 32 || w % 32 || planes < 1 || planes > 3) return WSI_EINVAL;
+    size_t off = 0;
+    u.x0 = off; off += align_up(wsi_pf_bytes(n, h / 2, w / 2, 64, planes), 256);
+    int cprev = 512;
+    for (int L = 0; L < 5; ++L) {
+        u.r_h[L] = (h / 16) << L; u.r_w[L] = (w / 16) << L; u.cx[L] = cprev;
+        const int cin = cprev + kUnetSkipC[L], cout = dw->cout[2 * L];
+        if (dw->cin[2 * L] != cin || dw->cin[2 * L + 1] != cout || dw->cout[2 * L + 1] != cout || cout % (planes == 1 ? 64 : 32) || cout <= 0) return WSI_EINVAL;
+        u.cat[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cin, planes), 256);
+        u.mid[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cout, planes), 256);
+        u.out[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cout, planes), 256);
+        cprev = cout;
+    }
+    if (dw->head_cin <= 0 || dw->head_cin > cprev || dw->classes <= 0) return WSI_EINVAL;
+    u.total = off;
+    return WSI_OK;
+}
+
+size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
+    UnetPlan u;
+    const size_t t = wsi_trunk_workspace_bytes(n, h, w, planes);
+    return (!t || unet_plan(dw, n, h, w, planes, u)) ? 0 : align_up(t, 256) + u.total;
+}
+
+int wsi_unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    UnetPlan u;
+    if (!workspace || unet_plan(dw, n, h, w, planes, u)) return WSI_EINVAL;
+    int rc = wsi_trunk_workspace_init(workspace, n, h, w, planes, stream);
+    if (rc) return rc;
+    char* base = (char*)workspace + align_up(wsi_trunk_workspace_bytes(n, h, w, planes), 256);
+    return hipMemsetAsync(base, 0, u.total, (hipStream_t)stream) == hipSuccess ? WSI_OK : WSI_EFAULT;
+}
+
+// the decoder on five PF encoder maps (x4 deepest ... x0 = stem output at half resolution), `dec` = decoder part of the workspace
+static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                            float* logits_out, hipStream_t st) {
+    const void* x = enc[0];
+    int rc = WSI_OK;
+    // wsi_prof kinds of the decoder (bench.py --workload seg): 6 = decoder 3x3 conv (algorithmic FLOPs over REAL channels are the
+    // caller's business: the record carries 2 * N * H * W * cin_stored * cout_stored * 9), 7 = upsample + concat glue, 8 = 1x1 head
+    // r05: parity mode runs the last block and the head as ONE kernel (tail.hip) when the caller prepacked its weights
+    // (wsi_unet_tail_prepack -> dw->tail_w) and the map is at most 256 wide; A/B: WSI_CONV_MODE_UNET_NO_TAIL
+    const bool tail = planes == 2 && dw->tail_w && g_routes.unet_tail && u.cx[4] == 32 && kUnetSkipC[4] == 0 && dw->classes <= 4 &&
+                      u.r_w[3] % 32 == 0 && u.r_w[3] <= 128 &&
+                      (size_t)pf_alloc_pixels(n, u.r_h[3], u.r_w[3]) * 128 <= (size_t)0x7fffffff;      // (32-bit buffer offsets into x4: ~1000 tiles of 256 x 256)
+    for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
+        const int H = u.r_h[L], W = u.r_w[L], cin = dw->cin[2 * L], cout = dw->cout[2 * L];
+        // r04: the block's first conv reads the low-resolution tensor and the skip directly (ConvArgs.in_up: nearest x2 upsample +
+        // concat as source addresses of its slab DMA) where the shape's kernel is the slab3 kernel; otherwise (EINVAL) the
+        // upsample_concat pass writes the concatenated tensor first, as in r02-r03
+        // conv j of the decoder (3x3, stride 1, ReLU) at this block's resolution
+        auto conv3 = [&](const void* in, void* out, int j, int ci) {
+            return ConvCall{.in = in, .out = out, .wpk = dw->conv_w[j], .bias = dw->conv_b[j], .n = n, .h = H, .w = W, .cin = ci, .cout = cout,
+                            .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
+        };
+        {
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            rc = g_routes.unet_fuse_up ? wsi_conv3x3_up_concat_bn_act(x, L < 4 ? enc[L + 1] : nullptr, dec + u.mid[L], dw->conv_w[2 * L], dw->conv_b[2 * L],
+                                                                      n, H, W, u.cx[L], kUnetSkipC[L], cout, 1, planes, st)
+                                       : WSI_EINVAL;
+            if (rc == WSI_EINVAL) ps.relabel(9);          // (a refused launch: its empty record is not a decoder conv)
+        }
+        if (rc == WSI_EINVAL) {
+            { ProfScope ps(st, 7, 0.0); rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], kUnetSkipC[L], planes, st); }
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            if (!rc) rc = conv_common(conv3(dec + u.cat[L], dec + u.mid[L], 2 * L, cin));
+        }
+        ProfScope ps(st, 6, conv_flops(n, H, W, cout, cout, 9));
+        if (!rc) rc = conv_common(conv3(dec + u.mid[L], dec + u.out[L], 2 * L + 1, cout));
+        x = dec + u.out[L];
+    }
+    if (tail) {
+        ProfScope ps(st, 10, 2.0 * n * u.r_h[4] * u.r_w[4] * (9.0 * (32.0 * 16.0 + 16.0 * 16.0) + 16.0 * dw->classes));    // kind 10: the reference formulation's FLOPs over REAL channels
+        if (!rc) rc = wsi_unet_tail_dispatch(x, dw->tail_w, n, u.r_h[3], u.r_w[3], dw->classes, logits_out, st);
+        return rc;
+    }
+    ProfScope ps(st, 8, 2.0 * n * u.r_h[4] * u.r_w[4] * (double)dw->head_cin * dw->classes);
+    if (!rc) rc = wsi_unet_head_dispatch(x, n, u.r_h[4], u.r_w[4], dw->cout[9], dw->head_w, dw->head_b, dw->head_cin, dw->classes, logits_out, planes, st);
+    return rc;
+}
+
+int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                     long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                     int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    TrunkPlan p;
+    UnetPlan u;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !dw || !workspace || n <= 0 || cap < n || (!logits_out && !enc_out) || h % 32 || w % 32) return WSI_EINVAL;
+    if (trunk_plan(cap, h, w, wt->planes, p) || unet_plan(dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
+    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
+    if (!src.valid()) return WSI_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    char* dec = ws + align_up(p.total, 256);
+    const int planes = wt->planes;
+    // encoder: the trunk with every stage output kept as an ordinary PF tensor (no phase-split hand-over) ...
+    TrunkResult res;
+    // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
+    // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
+    const ConvRoutes& r = g_routes;
+    const bool x0_fused = r.unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
+                          r.stem_shared_weights;
+    int rc = trunk_run(wt, src, n, cap, h, w, workspace, 8, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr});
+    if (rc) return rc;
+    // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
+    // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines
+    StemArgs a = stem_args(src, wt->stem_w, wt->stem_b, (float*)(ws + p.stem_scratch), n, h, w);
+    {
+        ProfScope ps(st, 7, 0.0);                            // (glue: the unfused stem conv for the half-resolution skip x0)
+        if (x0_fused) {
+        } else if (r.unet_fuse_up) {                         // r04: the conv kernel writes PF lines itself (was: f32 scratch + nhwc_to_pf pass)
+            a.out_pf = dec + u.x0; a.out_planes = planes;
+            rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
+        } else {
+            rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
+            if (!rc) rc = wsi_nhwc_to_pf_dispatch(a.out, dec + u.x0, n, h / 2, w / 2, 64, planes, st);
+        }
+    }
+    if (rc) return rc;
+    const void* enc[5] = {ws + res.stage_off[3], ws + res.stage_off[2], ws + res.stage_off[1], ws + res.stage_off[0], dec + u.x0};
+    if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first
+        for (int i = 0; i < 5 && !rc; ++i) {
+            const EncMap m = enc_map(i, h, w);
+            if (enc_out[i]) rc = wsi_pf_unpack(enc[i], enc_out[i], n, m.c, m.h, m.w, planes, stream);
+        }
+        if (rc) return rc;
+    }
+    return logits_out ? unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, st) : WSI_OK;
+}
+
+// `model.decoder(encoding)` with caller-held fp32 NCHW maps (deepest first): pack, then the same decoder launches
+int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                     int workspace_n, float* logits_out, void* stream) {
+    TrunkPlan p;
+    UnetPlan u;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!dw || !enc_nchw || !workspace || !logits_out || n <= 0 || cap < n) return WSI_EINVAL;
+    if (trunk_plan(cap, h, w, planes, p) || unet_plan(dw, cap, h, w, planes, u)) return WSI_EINVAL;
+    char* ws = (char*)workspace;
+    char* dec = ws + align_up(p.total, 256);
+    // encoder maps are packed into the trunk part of the workspace (stage buffers 0 of stages 3..0) and x0
+    const void* enc[5];
+    int rc = WSI_OK;
+    for (int i = 0; i < 5 && !rc; ++i) {
+        if (!enc_nchw[i]) return WSI_EINVAL;
+        char* dst = i < 4 ? ws + p.buf[3 - i][0] : dec + u.x0;
+        const EncMap m = enc_map(i, h, w);
+        rc = wsi_pf_pack(enc_nchw[i], dst, n, m.c, m.h, m.w, planes, stream);
+        enc[i] = dst;
+    }
+    return rc ? rc : unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, (hipStream_t)stream);
+}
+
+}  // extern "C"

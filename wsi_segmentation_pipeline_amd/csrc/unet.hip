@@ -9,6 +9,7 @@
 //   unet_head       : final_conv (1x1, <= 64 input channels, K classes) from PF lines straight to fp32 NCHW logits
 // All three are plain HBM-bound copies / dot products.
 #include "pf_lines.h"
+#include "internal.h"
 
 // out (N, 2h, 2w, Cx + Cs) <- x (N, h, w, Cx) upsampled x2 | skip (N, 2h, 2w, Cs); one 16-byte piece per thread
 __global__ __launch_bounds__(256) void upsample_concat_kernel(const char* x, const char* skip, char* out, PFGeom gx, PFGeom go,

@@ -143,7 +143,7 @@ class UNetEngine:
         return ent
 
     def release_workspaces(self):
-        """Free every planned workspace and make the library forget its layout tag (capi.hip g_ws_layout)."""
+        """Free every planned workspace and make the library forget its layout tag (trunk.hip g_ws_layout)."""
         for ws, _ in self._ws.values():
             self.lib.wsi_trunk_workspace_release(_ptr(ws))
         self._ws.clear()
