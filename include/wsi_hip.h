@@ -96,7 +96,8 @@ int wsi_stem_set_mode(int fused, int rows_per_seg);
 
 /* ---- conv + folded BN (+ residual) (+ ReLU) (resnets_shift.py:49-65, 19-27) -------------------
  * in_pf: PF (h_in, w_in, cin); out_pf / resid_pf: PF (h_in/stride, w_in/stride, cout).
- * resid_pf may be NULL.  in_pf must not alias out_pf. */
+ * resid_pf may be NULL (planes 3 with stride 2: must be, the stride-2 kernels of that mode add no residual: -22).
+ * in_pf must not alias out_pf.  wsi_conv1x1_bn: planes 1 and 2 (-22 for planes 3, whose 1x1 downsample runs inside other kernels). */
 int wsi_conv3x3_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,
                        int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes,
                        void* stream);
@@ -169,7 +170,8 @@ int wsi_conv3x3_bn_act_cfg(const void* in_pf, void* out_pf, const void* resid_pf
 
 /* ---- heads -----------------------------------------------------------------------------------
  * avgpool_fc: AdaptiveAvgPool2d(1) + flatten (+ Linear(c -> k)) (resnets_shift.py:206-208,
- *   models/models.py:32-38).  feat_out [n][c] and logits_out [n][k] may each be NULL.
+ *   models/models.py:32-38).  feat_out [n][c] and logits_out [n][k] may each be NULL.  c: whole 128-byte lines, as for
+ *   wsi_pf_pack (a multiple of 64 for planes 1, of 32 for planes 2 and 3; planes 3: at most 2048), -22 otherwise.
  * linear: y[b][j] = act(x[b] . w[j] + bias[j]) in fp32 (resnets_shift.py:135-139, models.py:46-50) */
 int wsi_avgpool_fc(const void* in_pf, int n, int h, int w, int c, const float* fc_w, const float* fc_b, int k,
                    float* feat_out, float* logits_out, int planes, void* stream);

@@ -58,6 +58,7 @@ int conv_common(const ConvCall& c) {
                          (c.line_flags & ~(CONV_IN96 | CONV_OUT96 | CONV_RESID96)) || ((c.line_flags & CONV_RESID96) && !c.resid)))
         return WSI_EINVAL;
     if ((c.stride != 1 && c.stride != 2) || c.h % c.stride || c.w % c.stride) return WSI_EINVAL;
+    if (c.planes == 3 && c.stride == 2 && c.resid) return WSI_EINVAL;   // the mode-3 stride-2 kernels have no residual tail (conv_tail_mx): refuse, never drop it
     ConvArgs a = conv_args(c);
     a.plane96 = c.line_flags ? (c.plane96 > 0 ? c.plane96 : (long long)pf_alloc_pixels(c.n, c.h, c.w) * 96) : 0;   // line-planar 96-byte tensors (common.h)
 #ifdef WSI_STUDY

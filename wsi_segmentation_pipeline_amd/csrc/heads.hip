@@ -309,7 +309,8 @@ static int grid_for(long long total) {
 
 int wsi_avgpool_fc_dispatch(const void* in, const PFGeom& g, const float* w, const float* b, int K, float* feat,
                             float* logits, int planes, hipStream_t st) {
-    if (g.C % 4 || g.N <= 0 || planes < 1 || planes > 3 || (planes == 3 && g.C % 32)) return WSI_EINVAL;
+    // whole 128-byte lines only: the same channel counts wsi_pf_pack accepts (the kernels address channels by line)
+    if (g.N <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || planes < 1 || planes > 3 || g.C % (planes == 1 ? PFmt<1>::CPL : PFmt<2>::CPL)) return WSI_EINVAL;
     size_t lds = (size_t)g.C * 4;
     if (planes == 3) {                                      // + partial sums of the 256 / (4 C/32) pixel groups
         if (g.C > 2048) return WSI_EINVAL;
