@@ -7,13 +7,16 @@
 #include "pf_lines.h"
 #include "internal.h"
 
+typedef __attribute__((ext_vector_type(3))) unsigned u32x3;
+
 static __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
     return v;
 }
 
-// One workgroup per image. feat[n][c] = mean over H*W of (hi+lo); logits[n][k] = feat . w[k] + b[k].
+// One workgroup per image. feat[n][c] = mean over H*W of (hi+lo); logits[n][k] = feat . w[k] + b[k].  (PLANES 1, 2; mode 3:
+// avgpool_fc_mx_kernel below)
 template <int PLANES>
 __global__ __launch_bounds__(256) void avgpool_fc_kernel(const void* in, PFGeom g, const float* w, const float* b, int K,
                                                          float* feat, float* logits) {
@@ -22,42 +25,6 @@ __global__ __launch_bounds__(256) void avgpool_fc_kernel(const void* in, PFGeom 
     const int n = blockIdx.x, tid = threadIdx.x;
     const size_t pixstride = (size_t)g.C * PFmt<PLANES>::BPC;
     const float inv = 1.0f / (float)(g.H * g.W);
-    if constexpr (PLANES == 3) {
-        // Thread t owns one 16-byte slice (8 line positions) of 32-channel line (t >> 2) mod NL, for pixels t / (4 NL),
-        // + 256 / (4 NL), ...: whole lines are read by 4 neighbouring lanes (coalesced 64 B of fp16 + the lo6 plane / scale),
-        // partial sums meet in LDS.  (The per-channel form read 2 bytes per access: 0.125 ms per 1000 patches.)
-        const int NL = g.C / 32, HW = g.H * g.W;
-        float* part = f + g.C;                                  // [256 / (4 NL) pixel groups][C] partial sums (launcher sizes it)
-        const int slice = tid & 3, line = (tid >> 2) % NL, pg = tid / (4 * NL), npg = 256 / (4 * NL);
-        float sm[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (pg < npg) {
-            for (int p = pg; p < HW; p += npg) {
-                const int y = p / g.W, x = p - y * g.W;
-                const char* L = (const char*)in + (size_t)(g.G + n * g.S + y * g.P + x) * pixstride + (size_t)line * 128;
-                const f16x8 hi = *(const f16x8*)(L + 16 * slice);
-                const u32x4 p0 = *(const u32x4*)(L + MX6_PLANE_LO(0)), p1 = *(const u32x4*)(L + MX6_PLANE_HI(0));   // lo6 plane + {rest, scale_lo}
-                const unsigned sl = p1[2] & 255u;
-                const f32x32 dd = mx6_unpack32(u32x6{p0[0], p0[1], p0[2], p0[3], p1[0], p1[1]}, sl ? mx_scale_value((int)sl) : 0.f);
-                float d[8];                                                           // position 8 slice + i = field 16 (slice & 1) + 2 i + (slice >> 1)
-#pragma unroll
-                for (int i = 0; i < 8; ++i) {
-                    const float e0 = (slice >> 1) ? dd[2 * i + 1] : dd[2 * i], e1 = (slice >> 1) ? dd[16 + 2 * i + 1] : dd[16 + 2 * i];
-                    d[i] = (slice & 1) ? e1 : e0;
-                }
-#pragma unroll
-                for (int i = 0; i < 8; ++i) sm[i] += (float)hi[i] + d[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 8; ++i) part[pg * g.C + line * 32 + mx_line_chan(8 * slice + i)] = sm[i];
-        }
-        __syncthreads();
-        for (int c = tid; c < g.C; c += 256) {
-            float t = 0.f;
-            for (int k = 0; k < npg; ++k) t += part[k * g.C + c];
-            f[c] = t * inv;
-            if (feat) feat[(size_t)n * g.C + c] = t * inv;
-        }
-    } else
     for (int c4 = tid; c4 < g.C / 4; c4 += 256) {
         const int c = c4 * 4;
         const size_t coff = PLANES == 2 ? (size_t)(c >> 5) * 128 + (c & 31) * 2 : (size_t)c * 2;
@@ -85,6 +52,84 @@ __global__ __launch_bounds__(256) void avgpool_fc_kernel(const void* in, PFGeom 
     if (!logits) return;
     const int lane = tid & 63, wave = tid >> 6;
     for (int k = wave; k < K; k += 4) {
+        float acc = 0.f;
+        for (int c = lane; c < g.C; c += 64) acc += f[c] * w[(size_t)k * g.C + c];
+        acc = wave_sum(acc);
+        if (lane == 0) logits[(size_t)n * K + k] = acc + b[k];
+    }
+}
+
+// Mode 3 (fp16 + MX-fp6 lines): one WAVE per image, four images per workgroup.  Lane l owns the whole 32-channel line l % NL
+// (NL = C / 32) of the pixels p = k, k + npg, ... of chain k = l / NL, npg = 64 / NL chains: per pixel it loads the line's 64 bytes of
+// fp16 and its lo6 plane + scale once, decodes the plane with ONE v_cvt_scalef32_pk32_f32_fp6 and adds all 32 channels; the loads of
+// POOL_U pixels are issued before the first add.  (The r01 form gave a line to four lanes: each of them loaded the same lo6 plane and
+// decoded 32 values to use 8, and walked its pixels as a serial load -> decode -> add chain: 0.599 ms per 6 162 images against
+// 0.173 ms now, NOTEBOOK r06.)  The summation order is the r01 one, bit for bit: per channel, chain k adds its pixels in
+// ascending order onto +0.0f, each term (float)hi + lo6 * scale; the chains are combined as ((0 + part[0]) + part[1]) + ...,
+// then * 1/(H W); the fc dot product walks c = lane, lane + 64, ... and meets in wave_sum.
+constexpr int POOL_U = 4;
+__global__ __launch_bounds__(256, 3) void avgpool_fc_mx_kernel(const void* in, PFGeom g, const float* w, const float* b, int K,
+                                                            float* feat, float* logits) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int n = blockIdx.x * 4 + wave;                    // (a workgroup's last images may be missing: their waves only keep the barriers)
+    const int NL = g.C / 32, HW = g.H * g.W, npg = 64 / NL;
+    float* f = (float*)smem + (size_t)wave * (size_t)(g.C + npg * g.C);     // this image's C features ...
+    float* part = f + g.C;                                  // ... and [npg chains][C] partial sums (launcher sizes both)
+    const size_t pixstride = (size_t)g.C * 4;
+    const float inv = 1.0f / (float)HW;
+    const int line = lane % NL, pg = lane / NL;
+    if (n < g.N && pg < npg) {
+        float sm[32];
+#pragma unroll
+        for (int i = 0; i < 32; ++i) sm[i] = 0.f;
+        const char* base = (const char*)in + (size_t)(g.G + n * g.S) * pixstride + (size_t)line * 128;
+        const int dy = npg / g.W, dx = npg - dy * g.W;      // one chain step in map coordinates ...
+        const int dpos = dy * g.P + dx;                     // ... and in padded-flat positions (+ the pad column when x wraps)
+        int x = pg % g.W, pos = (pg / g.W) * g.P + x;
+        for (int p0 = pg; p0 < HW; p0 += POOL_U * npg) {
+            uint4 q[POOL_U][5];                             // fp16 plane (4 x 16 B), lo6 plane ...
+            u32x3 qs[POOL_U];                               // ... {its last 64 bits, scale}
+#pragma unroll
+            for (int u = 0; u < POOL_U; ++u) {
+                if (p0 + u * npg < HW) {
+                    const uint4* L = (const uint4*)(base + (size_t)pos * pixstride);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) q[u][k] = L[k];
+                    q[u][4] = L[MX6_PLANE_LO(0) / 16];
+                    qs[u] = *(const u32x3*)(L + MX6_PLANE_HI(0) / 16);
+                }
+                x += dx; pos += dpos;
+                if (x >= g.W) { x -= g.W; pos += g.P - g.W; }
+            }
+#pragma unroll
+            for (int u = 0; u < POOL_U; ++u) {
+                if (p0 + u * npg < HW) {
+                    const unsigned sl = qs[u][2] & 255u;
+                    const f32x32 d = mx6_unpack32(u32x6{q[u][4].x, q[u][4].y, q[u][4].z, q[u][4].w, qs[u][0], qs[u][1]}, sl ? mx_scale_value((int)sl) : 0.f);
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const f16x8 hi = __builtin_bit_cast(f16x8, q[u][k]);
+#pragma unroll
+                        for (int i = 0; i < 8; ++i) sm[8 * k + i] += (float)hi[i] + d[mx6_field_of_pos(8 * k + i)];
+                    }
+                }
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 32; ++i) part[pg * g.C + line * 32 + mx_line_chan(i)] = sm[i];
+    }
+    __syncthreads();
+    if (n < g.N)
+        for (int c = lane; c < g.C; c += 64) {
+            float t = 0.f;
+            for (int k = 0; k < npg; ++k) t += part[k * g.C + c];
+            f[c] = t * inv;
+            if (feat) feat[(size_t)n * g.C + c] = t * inv;
+        }
+    __syncthreads();
+    if (!logits || n >= g.N) return;
+    for (int k = 0; k < K; ++k) {
         float acc = 0.f;
         for (int c = lane; c < g.C; c += 64) acc += f[c] * w[(size_t)k * g.C + c];
         acc = wave_sum(acc);
@@ -312,12 +357,12 @@ int wsi_avgpool_fc_dispatch(const void* in, const PFGeom& g, const float* w, con
     // whole 128-byte lines only: the same channel counts wsi_pf_pack accepts (the kernels address channels by line)
     if (g.N <= 0 || g.H <= 0 || g.W <= 0 || g.C <= 0 || planes < 1 || planes > 3 || g.C % (planes == 1 ? PFmt<1>::CPL : PFmt<2>::CPL)) return WSI_EINVAL;
     size_t lds = (size_t)g.C * 4;
-    if (planes == 3) {                                      // + partial sums of the 256 / (4 C/32) pixel groups
+    if (planes == 3) {                                      // four images per workgroup, each + the partial sums of its 64 / (C/32) chains
         if (g.C > 2048) return WSI_EINVAL;
-        lds += (size_t)(256 / (4 * (g.C / 32))) * g.C * 4;
+        lds = 4 * (lds + (size_t)(64 / (g.C / 32)) * g.C * 4);             // <= 64 KB
     }
     if (planes == 3)
-        hipLaunchKernelGGL(avgpool_fc_kernel<3>, dim3(g.N), dim3(256), lds, st, in, g, w, b, K, feat, logits);
+        hipLaunchKernelGGL(avgpool_fc_mx_kernel, dim3((g.N + 3) / 4), dim3(256), lds, st, in, g, w, b, K, feat, logits);
     else if (planes == 2)
         hipLaunchKernelGGL(avgpool_fc_kernel<2>, dim3(g.N), dim3(256), lds, st, in, g, w, b, K, feat, logits);
     else
