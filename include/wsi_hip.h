@@ -83,14 +83,25 @@ int wsi_stem_conv7x7_bn_relu_maxpool(const float* in_f32, const uint8_t* slide, 
                                      const float* stem_bias_u8, const float* norm_mean_std /* HOST: mean[3], std[3] */,
                                      int n, int h, int w, float* scratch, void* out_pf, int planes, void* stream);
 
+/* The same op in mx mode (planes 3) writing what the trunk's layer 1 reads: 96-byte lines, line-planar - the 32-channel line
+ * planes of the two channel halves lie plane96 bytes apart (> 0; the trunk uses 96 bytes times the pixel slots of the tensor, wsi_pf_bytes(n, h/4, w/4, 64, 3) / 256), pixel stride 96 bytes
+ * inside a plane.  out_pf96: 2 * plane96 bytes. */
+int wsi_stem_conv7x7_bn_relu_maxpool_lines96(const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes,
+                                             int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                                             const void* stem_wpk, const float* stem_bias, const void* stem_wpk_u8,
+                                             const float* stem_bias_u8, const float* norm_mean_std, int n, int h, int w,
+                                             float* scratch, void* out_pf96, long long plane96, void* stream);
+
 /* tuning / A-B hook, process-wide: which stem launch form runs (`fused`, one of the values below) and how many pooled
- * rows one workgroup of the fused kernel takes (`rows_per_seg` > 0, default 64).  All four forms agree to the precision
- * mode's rounding; FUSED and FUSED_ONE_STRIP are bit-identical. */
+ * rows one workgroup of the fused kernel takes (`rows_per_seg` > 0, default 64).  All forms agree to the precision
+ * mode's rounding; FUSED, FUSED_ONE_STRIP and FUSED_STRIPS are bit-identical. */
 enum {
     WSI_STEM_MODE_UNFUSED = 0,          /* two kernels: stem conv into the fp32 scratch, then the max pool */
     WSI_STEM_MODE_FUSED = 1,            /* default: one fused stem+maxpool kernel (no fp32 intermediate; scratch unused) */
     WSI_STEM_MODE_FUSED_LUT = 2,        /* the fused kernel with the table look-up arithmetic even when u8 weights are supplied */
-    WSI_STEM_MODE_FUSED_ONE_STRIP = 3   /* the integer stem, one strip per workgroup: digit planes in registers, not shared in LDS */
+    WSI_STEM_MODE_FUSED_ONE_STRIP = 3,  /* the integer stem, one strip per workgroup: digit planes in registers, not shared in LDS */
+    WSI_STEM_MODE_FUSED_STRIPS = 4      /* FUSED without the dense column mapping that mx output takes on pooled maps 64 or 128 wide
+                                           (stem.hip stem_pool_dense_kernel): the two-strip form on every shape */
 };
 int wsi_stem_set_mode(int fused, int rows_per_seg);
 

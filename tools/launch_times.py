@@ -24,14 +24,15 @@ def main():
     ap.add_argument('--tile', type=int, default=256, help='patch size (multiple of 32)')
     ap.add_argument('--slide-tiles-per-row', type=int, default=0, help='tiles per slide row (default: square slide); 156 = the 40k-wide cfg3 slide, 1 = tiles stacked in one column (pitch 768 B)')
     ap.add_argument('--stem-rows', type=int, default=0, help='pooled rows per stem workgroup (default: library default)')
+    ap.add_argument('--stem-mode', type=int, default=int(native.StemMode.FUSED), help='wsi_stem_set_mode form (native.StemMode; 4 = the strip form on every shape)')
     ap.add_argument('--s2', type=int, default=-1, help='wsi_conv_set_mode value (native.ConvMode: 0 S2_GATHER, 1 S2_SLAB with 64-pixel tiles, 3 S2_SLAB_128; plus switch bits)')
     args = ap.parse_args()
     dev = torch.device('cuda:0')
     lib = native.load()
     if args.s2 >= 0:
         native.check(lib.wsi_conv_set_mode(args.s2), 'wsi_conv_set_mode')
-    if args.stem_rows:
-        native.check(lib.wsi_stem_set_mode(native.StemMode.FUSED, args.stem_rows), 'wsi_stem_set_mode')
+    if args.stem_rows or args.stem_mode != int(native.StemMode.FUSED):
+        native.check(lib.wsi_stem_set_mode(args.stem_mode, args.stem_rows or 64), 'wsi_stem_set_mode')
     sd = W.make_resnet18_state_dict(11, with_fc=False)
     cls = W.make_head_state_dict(22, 'classifier')
     eng = TrunkEngine(sd, dev, planes=args.planes, head=(cls['fc.0.weight'], cls['fc.0.bias']), max_batch=args.n)

@@ -142,6 +142,7 @@ int wsi_stem_set_mode(int fused, int rows_per_seg) {
     g_routes.stem_fused = fused != WSI_STEM_MODE_UNFUSED; g_routes.stem_rows = rows_per_seg;
     g_routes.stem_u8x = fused != WSI_STEM_MODE_FUSED_LUT;
     g_routes.stem_shared_weights = fused != WSI_STEM_MODE_FUSED_ONE_STRIP;
+    g_routes.stem_dense = fused == WSI_STEM_MODE_FUSED;
     return WSI_OK;
 }
 
@@ -152,6 +153,16 @@ int wsi_stem_conv7x7_bn_relu_maxpool(const float* in_f32, const uint8_t* slide, 
                                      float* scratch, void* out_pf, int planes, void* stream) {
     return stem_run({in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, stem_wpk, stem_bias, stem_wpk_u8, stem_bias_u8,
                     norm_mean_std, n, h, w, scratch, out_pf, planes, stream, 0);
+}
+
+int wsi_stem_conv7x7_bn_relu_maxpool_lines96(const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes,
+                                             int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                                             const void* stem_wpk, const float* stem_bias, const void* stem_wpk_u8,
+                                             const float* stem_bias_u8, const float* norm_mean_std, int n, int h, int w,
+                                             float* scratch, void* out_pf96, long long plane96, void* stream) {
+    if (plane96 <= 0) return WSI_EINVAL;
+    return stem_run({in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, stem_wpk, stem_bias, stem_wpk_u8, stem_bias_u8,
+                    norm_mean_std, n, h, w, scratch, out_pf96, 3, stream, 1, plane96);
 }
 
 int wsi_conv3x3_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,

@@ -380,6 +380,7 @@ struct ConvRoutes {
     int stem_rows = 64;            // pooled rows per workgroup (r05 sweep: 16 / 32 / 64 -> 6.41 / 6.16 / 6.08 ms per 6 162 tiles)
     int stem_u8x = 1;              // exact-u8 arithmetic when the caller supplies its weights (A/B: fused = 2 disables)
     int stem_shared_weights = 1;   // A/B: fused = 3 selects the one-strip form (weights in registers)
+    int stem_dense = 1;            // mx lines, pooled maps 64 / 128 wide: the dense column mapping (A/B: fused = 4 keeps the two-strip form)
     // wsi_trunk_set_chunks(stem_chunk, layer1_chunk)
     int chunk_stem = 0;            // sub-batch sizes (images); 0 = whole batch (measured r01: no gain)
     int chunk_l1 = 0;

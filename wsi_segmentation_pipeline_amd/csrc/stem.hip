@@ -656,6 +656,229 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
     }
 }
 
+// --------------------------------------------------------------------------------------------
+// Dense form of the integer, mx-output stem (U8X, OUT == 3, digit planes shared in LDS) for pooled maps 64 or 128 wide.
+// The strip form above puts conv columns on consecutive lanes, so a strip of 31 conv columns yields 15 pooled ones on every
+// other lane: a 64-wide map costs five strips (160 column-lanes for 128 conv columns) and ten half-empty line encodes per row.
+// Here a UNIT is 32 pooled columns p0 .. p0 + 31 = conv columns 2 p0 .. 2 p0 + 63, as TWO MFMA pixel tiles per conv row:
+//   tile E, lane p = conv column 2 (p0 + p)       (ring column 4 p + 4 h: one aligned 16-byte fragment read)
+//   tile O, lane p = conv column 2 (p0 + p) + 1   (ring column 4 p + 2 + 4 h: two 8-byte reads)
+// so pooled[p] = max(E[p], O[p], O[p - 1]) lands on ALL 32 lanes of each half: no conv column is computed twice, O[p - 1] is one
+// DPP shift, and one line encode + one pair of 16-byte stores per lane serve 32 pooled columns x 32 channels.
+// A wave pair serves a unit (wave = 32-channel output tile, as above); a workgroup holds the NU = Wp / 32 units of one band of
+// pooled rows (image, segment).  Lane 0 of unit u > 0 needs conv column 2 p0 - 1: its left neighbour's O lane 31.  The neighbour
+// publishes that lane's 16 values (per half) in LDS AFTER the med3 - the value is then final, the reader only takes a maximum,
+// and it is the same rounded value the strip form computes for that column, so the bits agree; the raw-domain value would need
+// the reader to repeat the scale / shift / clamp.  No second barrier: unit u runs u steps BEHIND unit u - 1 (it handles pooled
+// row py0 - 1 + it - u on trip it), so what it reads was written before the previous trip's barrier; two buffers per boundary
+// (trip parity) keep the writer's next trip off the reader's values.  Lane 0 of unit 0 takes the pool's padding, 0 (neutral:
+// every value is >= 0 after the ReLU).
+// Registers: the two conv rows' digit accumulators of ONE tile are live at a time (96, both rows share each weight fragment read),
+// E's pooled row is held across tile O, and each tile has its own carried row: 256 VGPRs, no scratch, two waves per SIMD - which
+// is also what the LDS allows (two 136-column rings + the digit planes = 60 KB, two workgroups per CU).  The forms that keep three
+// waves per SIMD (a 9-row ring behind a second barrier, one conv row's accumulators at a time) measured slower than the strip
+// form: NOTEBOOK "dense stem".  The vertical max and the carry stay in the raw domain exactly as in the strip form.
+constexpr int SD_PITCH = 136;                // ring columns per row: 134 read (4 * 31 + 2 + 4 + 3 is the last), pitch 544 B = 34 x 16
+constexpr int SD_COLS = 134;
+constexpr int SD_RING_BYTES = SP_RING * SD_PITCH * 4;
+constexpr size_t stem_dense_lds(int nu) { return (size_t)nu * SD_RING_BYTES + 512 + nu * 512 + 2 * 7 * 3 * 1024; }
+template <int NU>
+__global__ __launch_bounds__(128 * NU, 2) void stem_pool_dense_kernel(StemPoolArgs A) {
+    constexpr int DIG = 3, RING_BYTES = SD_RING_BYTES;
+    extern __shared__ __attribute__((aligned(16))) char smem_all[];
+    const StemArgs& a = A.s;
+    const int tid = threadIdx.x & 127, lane = tid & 63;                 // tid: thread within the unit's wave pair
+    const int wave_g = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+    const int wave = wave_g & 1;                                        // = output-channel tile
+    const int u = wave_g >> 1;                                          // unit within the band
+    char* const smem = smem_all + u * RING_BYTES;                       // this unit's ring
+    float* const sb_lds = (float*)(smem_all + NU * RING_BYTES);         // [scale 64][shift 64]
+    float* const xbuf = sb_lds + 128;                                   // [boundary][trip parity][wave][h][16]: the shared columns
+    char* const wl = smem_all + NU * RING_BYTES + 512 + NU * 512;       // the digit planes [nt 2][kh 7][digit][lane][16 B]
+    const int l31 = lane & 31, h = lane >> 5;
+    const int Hp = a.H / 4, Wp = a.W / 4;
+    const int nsegs = (Hp + A.rows_per_seg - 1) / A.rows_per_seg;
+    const int seg = blockIdx.x % nsegs, n = blockIdx.x / nsegs;
+    const int p0 = 32 * u;
+    const int py0 = seg * A.rows_per_seg;
+    const int py1 = min(py0 + A.rows_per_seg, Hp);
+    const int ix0 = 4 * p0 - 3;                                         // input column of ring column 0
+    const int tx = a.origins[2 * n], ty = a.origins[2 * n + 1];
+    for (int i = threadIdx.x; i < 2 * 7 * DIG * 64; i += 128 * NU) ((uint4*)wl)[i] = ((const uint4*)a.wpk_u8)[i];
+    if (threadIdx.x < 64) {
+        sb_lds[threadIdx.x] = ((const float*)((const char*)a.wpk_u8 + STEM_I8_SCALE_OFFSET))[threadIdx.x];
+        sb_lds[64 + threadIdx.x] = a.bias_u8[threadIdx.x];
+    }
+    const size_t slide_bytes = (size_t)a.SH * (size_t)a.slide_pitch;
+    auto slot_of = [&](int iy) { return (iy + 64) & (SP_RING - 1); };
+    auto load_px = [&](int iy, int ix) {                                // R, G, B (+ a stray byte) of input pixel (iy, ix); black outside the slide
+        unsigned rgb = 0u;
+        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+            const int sx = tx + ix, sy = ty + iy;
+            if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
+                const size_t off = (size_t)sy * a.slide_pitch + (size_t)sx * 3;
+                const uint8_t* pp = a.slide + off;
+                if (off + 4 <= slide_bytes) __builtin_memcpy(&rgb, pp, 4);
+                else rgb = pp[0] | (pp[1] << 8) | (pp[2] << 16);             // last pixel of the buffer
+            }
+        }
+        return rgb;
+    };
+    auto put_px = [&](int iy, int cc, unsigned rgb) {                   // (R, G, B) - 128 as i8 + inside = 127; zero padding outside the patch
+        const int ix = ix0 + cc;
+        unsigned q = 0u;
+        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) q = ((rgb & 0xffffffu) ^ 0x808080u) | 0x7f000000u;
+        *(unsigned*)(smem + (size_t)(slot_of(iy) * SD_PITCH + cc) * 4) = q;
+    };
+    // a step's 4 new rows x 134 columns: thread t takes column t of each row, threads 0..23 the 4 x 6 columns 128..133
+    const int ex_r = tid / 6, ex_c = 128 + tid - 6 * ex_r;
+    unsigned pf_rgb[5];
+    auto fetch_rows = [&](int row_lo) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pf_rgb[k] = load_px(row_lo + k, ix0 + tid);
+        pf_rgb[4] = tid < 24 ? load_px(row_lo + ex_r, ix0 + ex_c) : 0u;
+    };
+    auto commit_rows = [&](int row_lo) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) put_px(row_lo + k, tid, pf_rgb[k]);
+        if (tid < 24) put_px(row_lo + ex_r, ex_c, pf_rgb[4]);
+    };
+    // the first step of a unit is py0 - 1: it only produces the carried conv row 2 py0 - 1
+    for (int i = tid; i < 9 * SD_COLS; i += 128) {
+        const int r = i / SD_COLS, cc = i - r * SD_COLS, iy = 4 * (py0 - 1) - 3 + r;
+        put_px(iy, cc, load_px(iy, ix0 + cc));
+    }
+    __syncthreads();
+    float carry[2][16];
+#pragma unroll
+    for (int r = 0; r < 16; ++r) carry[0][r] = carry[1][r] = 0.f;
+    const bool o96 = A.out96;
+    const size_t pixstride = o96 ? (size_t)96 : (size_t)256;
+    const PFGeom go = pf_geom(a.N, Hp, Wp, 64);
+    const int ntrips = A.rows_per_seg + NU;                             // every unit makes the same trips; unit u idles u trips first
+    for (int it = 0; it < ntrips; ++it) {
+        const int py = py0 - 1 + it - u;
+        if (it < u || py >= py1) { __syncthreads(); continue; }
+        if (py + 1 < py1) fetch_rows(4 * (py + 1) + 2);                 // rows the NEXT step adds: loads in flight behind the MFMAs
+        float vE[16], vO[16];
+#pragma unroll
+        for (int tile = 0; tile < 2; ++tile) {
+            float m[16];
+#pragma unroll
+            for (int r = 0; r < 16; ++r) m[r] = carry[tile][r];
+            {
+                // (compiler fence: without it tile O's weight fragment reads are merged into tile E's and all 21 fragments, 84 registers,
+                //  stay live across the step; the scheduling barrier keeps tile E's recombination in front of tile O's MFMAs)
+                asm volatile("" ::: "memory");
+                __builtin_amdgcn_sched_barrier(0);
+                i32x16 aq[2][DIG];                                      // [conv row 2py + j][digit]
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int d = 0; d < DIG; ++d)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) aq[j][d][r] = 0;
+#pragma unroll
+                for (int ks = 0; ks < 7; ++ks) {                        // one kernel row per step: 4 pixels x 4 bytes per lane half = K 32
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int slot = slot_of(4 * py + 2 * j - 3 + ks);
+                        const char* xp = smem + (size_t)(slot * SD_PITCH + 4 * l31 + 4 * h + 2 * tile) * 4;
+                        i32x4 x;
+                        if (tile == 0) x = *(const i32x4*)xp;           // 16-byte aligned
+                        else {
+                            const uint2 x01 = *(const uint2*)xp, x23 = *(const uint2*)(xp + 8);
+                            x = i32x4{(int)x01.x, (int)x01.y, (int)x23.x, (int)x23.y};
+                        }
+#pragma unroll
+                        for (int d = 0; d < DIG; ++d) {
+                            const i32x4 wv = *(const i32x4*)(wl + ((wave * 7 + ks) * DIG + d) * 1024 + lane * 16);
+                            aq[j][d] = __builtin_amdgcn_mfma_i32_32x32x32_i8(wv, x, aq[j][d], 0, 0, 0);
+                        }
+                    }
+                }
+                // exact recombination of the digit planes, vertical max in the raw domain (see the strip form), row 2py+1 is the next carry
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        float c = (float)(aq[j][1][r] * 256 + aq[j][0][r]);
+                        c = __builtin_fmaf((float)aq[j][2][r], 65536.0f, c);
+                        m[r] = fmaxf(m[r], c);
+                        if (j == 1) carry[tile][r] = c;
+                        asm volatile("" : "+v"(m[r]));          // the maximum is taken HERE: left free, the compiler defers the maxima, keeps the values and spills
+                    }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int ch = wave * 32 + 8 * (r >> 2) + 4 * h + (r & 3);
+                // ReLU and the fp16-range clamp of the line encode in one v_med3_f32 (every column of a unit is inside the map)
+                const float v = __builtin_amdgcn_fmed3f(__builtin_fmaf(m[r], sb_lds[ch], sb_lds[64 + ch]), 0.f, 65504.f);
+                if (tile == 0) vE[r] = v; else vO[r] = v;
+            }
+        }
+        if (py < 0) {                                                   // above the image: the carry is the pool's padding
+#pragma unroll
+            for (int r = 0; r < 16; ++r) carry[0][r] = carry[1][r] = -3.4028234e38f;
+        }
+        if (py + 1 < py1) commit_rows(4 * (py + 1) + 2);               // not read by this step: safe before the barrier
+        if (py >= py0) {
+            if (u + 1 < NU && l31 == 31) {                              // the right neighbour's column 2 p0' - 1
+                float* xw = xbuf + (((u * 2 + (it & 1)) * 2 + wave) * 2 + h) * 16;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) *(f32x4*)(xw + 4 * g) = f32x4{vO[4 * g], vO[4 * g + 1], vO[4 * g + 2], vO[4 * g + 3]};
+            }
+            float v[16];
+            const float* xr = xbuf + ((((u > 0 ? u - 1 : 0) * 2 + ((it - 1) & 1)) * 2 + wave) * 2 + h) * 16;   // written on the previous trip
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 xin = *(const f32x4*)(xr + 4 * g);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int r = 4 * g + i;
+                    // O[p - 1]: DPP wave shift (lane i <- i - 1); lanes 0 and 32 take the shared column, or the padding 0 in unit 0
+                    float up = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, vO[r]), 0x138, 0xf, 0xf, true));
+                    if (l31 == 0) up = u > 0 ? xin[i] : 0.f;
+                    v[r] = fmaxf(vE[r], fmaxf(vO[r], up));
+                }
+            }
+            char* o = (char*)A.out_pf + (size_t)(go.G + n * go.S + py * go.P + p0 + l31) * pixstride;
+            // fp16 hi + MX-fp6 (lo6, hi6): the strip form's encode, on 32 real pixels per half
+            f32x16 hi, lo;
+            f16x8 hv[2];
+            float mh = 0.f, ml = 0.f;
+#pragma unroll
+            for (int r = 0; r < 16; r += 2) {
+                const f16x2 hh = __builtin_convertvector(f32x2{v[r], v[r + 1]}, f16x2);
+                hv[r >> 3][r & 7] = hh[0];
+                hv[r >> 3][(r & 7) + 1] = hh[1];
+                hi[r] = (float)hh[0];
+                hi[r + 1] = (float)hh[1];
+                lo[r] = v[r] - hi[r];
+                lo[r + 1] = v[r + 1] - hi[r + 1];
+                mh = fmaxf(mh, fmaxf(hi[r], hi[r + 1]));
+                ml = fmaxf(ml, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
+            }
+            pair_max2(mh, ml);
+            const int sh = mx6_scale_byte(mh), sl = mx6_scale_byte(ml);
+            const int sb = h ? sh : sl;
+            swap32_halves(lo, hi);
+            const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
+            char* ol = o + (o96 ? (size_t)wave * (size_t)A.plane96 : (size_t)wave * 128);
+            *(f16x8*)(ol + 32 * h) = hv[0];
+            *(f16x8*)(ol + 32 * h + 16) = hv[1];
+            if (!o96) {
+                *(u32x4*)(ol + MX6_PLANE_LO(0) + 16 * h) = u32x4{q[0], q[1], q[2], q[3]};
+                *(u32x4*)(ol + MX6_PLANE_HI(0) + 16 * h) = u32x4{q[4], q[5], (unsigned)sb, 0u};
+            } else if (h == 0) {
+                *(u32x4*)(ol + 64) = u32x4{q[0], q[1], q[2], q[3]};
+                *(u32x4*)(ol + 80) = u32x4{q[4], q[5], (unsigned)sl, (unsigned)sh};
+            }
+        }
+        __syncthreads();                                                // next rows staged, this step's reads done, shared column published
+    }
+}
+
 int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows_per_seg, hipStream_t st, int out96, long long plane96, void* x0_pf) {
     if (a.H % 4 || a.W % 4 || a.N <= 0 || planes < 1 || planes > 3 || rows_per_seg <= 0) return WSI_EINVAL;
     StemPoolArgs A;
@@ -668,6 +891,18 @@ int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows
     if (grid > 0x7fffffffLL) return WSI_EINVAL;
     const bool u8x = a.mode == 1 && a.wpk_u8 && a.bias_u8 && planes >= 2;
     const size_t lds = (size_t)(planes == 1 || u8x ? 1 : 2) * SP_PLANE;
+    // integer stem, mx lines, pooled maps 64 or 128 wide (256 and 512 pixel patches): the dense column mapping, one workgroup per band of rows
+    if (u8x && planes == 3 && !x0_pf && g_routes.stem_shared_weights && g_routes.stem_dense && (Wp == 64 || Wp == 128)) {
+        const long long gd = (long long)a.N * ((Hp + rows_per_seg - 1) / rows_per_seg);
+        if (gd > 0x7fffffffLL) return WSI_EINVAL;
+        if (Wp == 128) {                              // (78.5 KB of LDS: above the 64 KB a kernel gets without asking)
+            auto k = stem_pool_dense_kernel<4>;
+            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_dense_lds(4)) != hipSuccess) return WSI_EINVAL;
+            hipLaunchKernelGGL(k, dim3((int)gd), dim3(512), stem_dense_lds(4), st, A);
+        } else
+            hipLaunchKernelGGL(stem_pool_dense_kernel<2>, dim3((int)gd), dim3(256), stem_dense_lds(2), st, A);
+        return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    }
     if (u8x && g_routes.stem_shared_weights) {               // integer stem, two strips per workgroup, digit planes shared in LDS
         const size_t lds2 = 2 * SP_RING_I8 + 512 + 2 * 7 * 3 * 1024;
         const int grid2 = (int)((grid + 1) / 2);

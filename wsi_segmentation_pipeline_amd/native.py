@@ -55,6 +55,7 @@ SIGNATURES = {
     'wsi_prepack_stem_u8': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i, _vp, _vp]),
     'wsi_normalize_u8_lut': (_i, [_vp, _vp, _vp]),
     'wsi_stem_conv7x7_bn_relu_maxpool': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'wsi_stem_conv7x7_bn_relu_maxpool_lines96': (_i, [_vp, _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _ll, _vp]),
     'wsi_stem_set_mode': (_i, [_i, _i]),
     'wsi_conv3x3_bn_act': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'wsi_conv3x3_bn_act_cfg': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
@@ -195,6 +196,7 @@ class StemMode(enum.IntEnum):
     FUSED = 1
     FUSED_LUT = 2
     FUSED_ONE_STRIP = 3
+    FUSED_STRIPS = 4
 
 
 @contextlib.contextmanager
