@@ -7,8 +7,11 @@ concat conv - write the model's bytes, all 128 of every real line (fp16 plane, b
 dwords) and nothing else, on inputs built so that the expected line needs no tolerance, (d) wsi_avgpool_fc reads every line
 format at every channel count and pixel-group split, to a bound derived from fp32 summation alone.
 
-Out of scope: the 96-byte-line form of layer 1 and the stem's pooled output are not reachable as single operations through the
-C ABI; tests/test_gpu_trunk.py ties them bit for bit to the 128-byte route that (c) pins here."""
+(d') the stem - wsi_stem_conv7x7_bn_relu_maxpool and ..._lines96, 128- and 96-byte lines - is held to the model in
+tests/test_gpu_stem_lines.py, which reuses the helpers here.
+
+Out of scope: the 96-byte-line form of layer 1 is not reachable as a single operation through the C ABI; tests/test_gpu_trunk.py
+ties it bit for bit to the 128-byte route that (c) pins here."""
 import ctypes as C
 import functools
 

@@ -348,6 +348,10 @@ static inline __device__ const float* conv_wscale_inv(const void* wpk, int cout,
     return (const float*)((const char*)wpk + (size_t)(cout / 32) * (cin / 32) * ksize * ksize * 4096);
 }
 
+// The integer stem's weight pack (prepack.hip wsi_prepack_stem_u8 writes it, stem.hip reads it): digit planes
+// [nt 2][kh 7][digit STEM_I8_DIGITS][lane 64][16] i8, then float scale[64] at byte STEM_I8_SCALE_OFFSET.
+constexpr int STEM_I8_DIGITS = 3;
+constexpr int STEM_I8_SCALE_OFFSET = 2 * 7 * STEM_I8_DIGITS * 1024;
 struct StemArgs {
     // mode 0: f32 NCHW input; mode 1: u8 HWC slide + per-tile origins + LUT
     int mode;

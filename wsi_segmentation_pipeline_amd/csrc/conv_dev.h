@@ -272,6 +272,7 @@ static __device__ __forceinline__ void acc_init_bias(f32x16 (&acc)[MT], const fl
 // bytes) and, after one exchange with lane ^ 32 (v_permlane32_swap per register), ALL 32 values of one fp6 plane (h = 0:
 // lo6, h = 1: hi6), which one v_cvt_scalef32_2xpk16_fp6_f32 converts.  Four 16-byte stores per 32x32 tile; the whole
 // 128-byte line is written.  (`a.resid` is not read here: conv_tail_mx adds the residual.)
+// stem.hip stem_store_line_mx is the stem kernels' copy of this encode (values already clamped, >= 0): a change to the format is made in both.
 template <int MT, int MTN = MT>
 static __device__ __forceinline__ void conv_epilogue_mx(const ConvArgs& a, f32x16 (&acc)[MT], const int (&qs)[MT],
                                                         const bool (&valid)[MT], int ntile, int lane, int mt0 = 0) {

@@ -296,15 +296,15 @@ int wsi_prepack_stem(const float* w, const float* bn_weight, const float* bn_bia
 // written as fixed-point numbers q * scale[co] with q in DIG balanced base-256 digits (each an i8 in [-128, 127];
 // |q| <= 127 * 256^(DIG-1)), DIG = 3 (24 bits) in both split-precision modes.
 // Layout: [nt 2][kh 7][digit DIG][lane 64][16 B: k = 16 h + j -> kw = 4 h + (j >> 2), byte j & 3], then float scale[64]
-// at byte 2 * 7 * 3 * 1024 (inside the wsi_prepack_stem_bytes(2) buffer the callers allocate); bias_out = bn_shift.
+// at byte STEM_I8_SCALE_OFFSET (common.h; inside the wsi_prepack_stem_bytes(2) buffer the callers allocate); bias_out = bn_shift.
 int wsi_prepack_stem_u8(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean,
                         const float* bn_var, float eps, const float mean[3], const float std_[3], int planes,
                         void* wpk_out, float* bias_out) {
     if (!w || !wpk_out || !bias_out || !mean || !std_ || planes < 2 || planes > 3) return WSI_EINVAL;
-    constexpr int DIG = 3;                                                    // stem.hip launches stem_pool_kernel<.., 3> in both modes
+    constexpr int DIG = STEM_I8_DIGITS;                                       // stem.hip launches stem_pool_kernel<.., 3> in both modes
     int8_t* o = (int8_t*)wpk_out;
-    float* scale_out = (float*)((char*)wpk_out + 2 * 7 * 3 * 1024);
-    memset(wpk_out, 0, (size_t)2 * 7 * 3 * 1024 + 64 * sizeof(float));
+    float* scale_out = (float*)((char*)wpk_out + STEM_I8_SCALE_OFFSET);
+    memset(wpk_out, 0, (size_t)STEM_I8_SCALE_OFFSET + 64 * sizeof(float));
     const double qmax = 127.0 * 65536.0;                                      // 127 * 256^(DIG - 1)
     for (int co = 0; co < 64; ++co) {
         double sc, sh;

@@ -16,11 +16,160 @@ constexpr int STEM_LR = 2 * STEM_TR + 5;         // 21 input rows
 constexpr int STEM_LC = 70;                      // 2*32 + 6 input cols
 constexpr int STEM_PLANE_BYTES = STEM_LR * STEM_LC * 8;
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Pieces every stem kernel below shares.  Each exists once: the forms are compared bit for bit (tests/test_gpu_stem_dense.py,
+// test_integer_stem_forms_bit_identical) and their lines byte for byte against the host model (tests/test_gpu_stem_lines.py).
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
+typedef __attribute__((ext_vector_type(16))) int i32x16;
+
+// R, G, B (+ a stray byte) of input pixel (iy, ix) of the patch whose corner is slide pixel (tx, ty): 0 outside the patch, black
+// outside the slide (OpenSlide's padding).  One unaligned dword per pixel; the buffer's last pixel is read byte by byte.  `wanted`
+// false (a prefetch slot past the step's rows): no pixel, 0 without a load.
+static __device__ __forceinline__ unsigned stem_fetch_px(const StemArgs& a, int tx, int ty, int iy, int ix, bool wanted = true) {
+    unsigned rgb = 0u;
+    if (wanted && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+        const int sx = tx + ix, sy = ty + iy;
+        if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
+            const size_t off = (size_t)sy * a.slide_pitch + (size_t)sx * 3;
+            const uint8_t* pp = a.slide + off;
+            if (off + 4 <= (size_t)a.SH * (size_t)a.slide_pitch) __builtin_memcpy(&rgb, pp, 4);   // R, G, B, next R
+            else rgb = pp[0] | (pp[1] << 8) | (pp[2] << 16);
+        }
+    }
+    return rgb;
+}
+// The integer path's pixel operand: (R, G, B) - 128 as i8 and inside = 127; outside the patch the zero padding, all four bytes 0,
+// which contributes exactly nothing (see stem_pool_kernel).
+static __device__ __forceinline__ unsigned stem_px_i8(const StemArgs& a, int iy, int ix, unsigned rgb) {
+    return (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) ? ((rgb & 0xffffffu) ^ 0x808080u) | 0x7f000000u : 0u;
+}
+// The float paths' staging: input rows [row_lo, row_lo + nrows) x columns [ix0, ix0 + ncols) of image n - f32 NCHW, or slide + LUT -
+// normalised and split into (hi, lo) of PLANES' element type (2: fp16 pair, common.h PairElem; 1: bf16, hi only), four channels
+// per pixel (the fourth 0), zero outside the patch.  LDS image [row][ncols][4] at img, the lo plane plane_bytes behind it; RING:
+// input row iy lives in ring row (iy + 64) & (RING - 1), otherwise row_lo is image row 0.  NT threads, this one is tid.
+template <int PLANES, int NT, int RING>
+static __device__ __forceinline__ void stem_stage_rows(const StemArgs& a, int n, int tx, int ty, int tid, int row_lo, int nrows, int ix0, int ncols,
+                                                       char* img, int plane_bytes) {
+    for (int i = tid; i < nrows * ncols; i += NT) {
+        const int r = i / ncols, cc = i - r * ncols;
+        const int iy = row_lo + r, ix = ix0 + cc;
+        float v[3] = {0.f, 0.f, 0.f};
+        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
+            if (a.mode == 0) {
+                const size_t base = ((size_t)n * 3 * a.H + iy) * a.W + ix;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = a.in_f32[base + (size_t)c * a.H * a.W];
+            } else {
+                const int sx = tx + ix, sy = ty + iy;
+                int px[3] = {0, 0, 0};                  // outside the slide OpenSlide pads with black (int: a byte type costs stem_conv7x7_kernel a register)
+                if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
+                    const uint8_t* p = a.slide + (size_t)sy * a.slide_pitch + (size_t)sx * 3;
+                    px[0] = p[0]; px[1] = p[1]; px[2] = p[2];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c] = a.lut[c * 256 + px[c]];
+            }
+        }
+        typedef typename PairElem<PLANES>::T E;
+        typedef __attribute__((ext_vector_type(4))) E Ex4;
+        Ex4 hi, lo;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { hi[c] = (E)v[c]; lo[c] = (E)(v[c] - (float)hi[c]); }
+        hi[3] = (E)0.f; lo[3] = (E)0.f;
+        char* dst = img + (size_t)(RING ? ((iy + 64) & (RING - 1)) * ncols + cc : i) * 8;
+        *(Ex4*)dst = hi;
+        if constexpr (PLANES == 2) *(Ex4*)(dst + plane_bytes) = lo;
+    }
+}
+
+// Output lines of planes 2 (fp16 pair, common.h split_f16) and 1 (bf16): the four channels c .. c + 3 (c a multiple of 4) of the
+// 64-channel pixel record at o.
+template <int PLANES>
+static __device__ __forceinline__ void stem_store4(char* o, int c, const float* v) {
+    if constexpr (PLANES == 2) {
+        f16x4 hi, lo;
+        split_f16x4(v, hi, lo);
+        *(f16x4*)(o + (c >> 5) * 128 + (c & 31) * 2) = hi;
+        *(f16x4*)(o + (c >> 5) * 128 + 64 + (c & 31) * 2) = lo;
+    } else {
+        bf16x4 hi;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) hi[i] = (__bf16)v[i];
+        *(bf16x4*)(o + c * 2) = hi;
+    }
+}
+
+// Output line of planes 3 (fp16 hi + MX-fp6 lo6 / hi6, one scale per plane and 32-channel line; line order: common.h mx_line_pos /
+// mx6_field_of_pos).  Lane (pixel, h) passes the 16 channels 8g + 4h + i of the 32x32 MFMA accumulator layout, already clamped to
+// [0, 65504]; the line's other 16 sit in lane ^ 32.  Every lane of the wave takes part in the exchanges; only the stores are
+// predicated.  ol = the line: 128 bytes, or with o96 the 96-byte form [fp16 plane][lo6][lo6 rest, scale_lo, scale_hi] that lane
+// h = 0 completes alone.  conv_dev.h conv_epilogue_mx is the conv kernels' copy of this encode (it clamps inside and takes |hi|,
+// values there can be negative): a change to the format is made in both.
+static __device__ __forceinline__ void stem_store_line_mx(const float (&v)[16], int h, char* ol, bool store, bool o96) {
+    f32x16 hi, lo;
+    f16x8 hv[2];
+    float mh = 0.f, ml = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; r += 2) {
+        const f16x2 hh = __builtin_convertvector(f32x2{v[r], v[r + 1]}, f16x2);
+        hv[r >> 3][r & 7] = hh[0];
+        hv[r >> 3][(r & 7) + 1] = hh[1];
+        hi[r] = (float)hh[0];
+        hi[r + 1] = (float)hh[1];
+        lo[r] = v[r] - hi[r];
+        lo[r + 1] = v[r + 1] - hi[r + 1];
+        mh = fmaxf(mh, fmaxf(hi[r], hi[r + 1]));                                // (v >= 0 after the ReLU)
+        ml = fmaxf(ml, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
+    }
+    pair_max2(mh, ml);                                                          // block maxima over the pixel's two lanes
+    const int sh = mx6_scale_byte(mh), sl = mx6_scale_byte(ml);
+    const int sb = h ? sh : sl;                                                 // this lane's plane: h = 0 lo6, h = 1 hi6
+    swap32_halves(lo, hi);
+    const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
+    if (store) {
+        *(f16x8*)(ol + 32 * h) = hv[0];
+        *(f16x8*)(ol + 32 * h + 16) = hv[1];
+        if (!o96) {
+            *(u32x4*)(ol + MX6_PLANE_LO(0) + 16 * h) = u32x4{q[0], q[1], q[2], q[3]};
+            *(u32x4*)(ol + MX6_PLANE_HI(0) + 16 * h) = u32x4{q[4], q[5], (unsigned)sb, 0u};
+        } else if (h == 0) {
+            *(u32x4*)(ol + 64) = u32x4{q[0], q[1], q[2], q[3]};
+            *(u32x4*)(ol + 80) = u32x4{q[4], q[5], (unsigned)sl, (unsigned)sh};
+        }
+    }
+}
+
+// Integer path: exact value of accumulator register r of the DIG balanced base-256 digit passes, (a2 2^16 + a1 2^8 + a0).  The two low
+// digits combine in i32, the third by one FMA: this order is part of the result's bits.
+template <int DIG>
+static __device__ __forceinline__ float stem_digits_value(const i32x16 (&aq)[DIG], int r) {
+    float c = (float)(DIG >= 2 ? aq[DIG >= 2 ? 1 : 0][r] * 256 + aq[0][r] : aq[0][r]);
+    if constexpr (DIG == 3) c = __builtin_fmaf((float)aq[DIG - 1][r], 65536.0f, c);
+    return c;
+}
+// Integer path: the pack's per-channel [scale 64][shift 64] into LDS at sb_lds and, for the forms whose waves share one copy of the
+// digit planes (WLDS), those at wl; nthreads = workgroup size.
+template <bool WLDS>
+static __device__ __forceinline__ void stem_preload_i8(const StemArgs& a, char* wl, float* sb_lds, int nthreads) {
+    if constexpr (WLDS)
+        for (int i = threadIdx.x; i < STEM_I8_SCALE_OFFSET / 16; i += nthreads) ((uint4*)wl)[i] = ((const uint4*)a.wpk_u8)[i];
+    if (threadIdx.x < 64) {
+        sb_lds[threadIdx.x] = ((const float*)((const char*)a.wpk_u8 + STEM_I8_SCALE_OFFSET))[threadIdx.x];
+        sb_lds[64 + threadIdx.x] = a.bias_u8[threadIdx.x];
+    }
+}
+
+// Dynamic LDS of the two-kernel form: the packed weights, then the input image planes [row][col][4]
+template <int PLANES> struct StemConvLds {
+    static constexpr int W = 0, X = 28 * PLANES * 1024, TOTAL = X + PLANES * STEM_PLANE_BYTES;
+};
+
 template <int PLANES>
 __global__ __launch_bounds__(256, 2) void stem_conv7x7_kernel(StemArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* wl = smem;                                  // weights: 28*PLANES KiB
-    char* xl = smem + 28 * PLANES * 1024;             // input image planes
+    typedef StemConvLds<PLANES> Lds;
+    char* wl = smem + Lds::W;                         // weights: 28*PLANES KiB
+    char* xl = smem + Lds::X;                         // input image planes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l31 = lane & 31, h = lane >> 5;
     const int Hc = a.H / 2, Wc = a.W / 2;
@@ -43,35 +192,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv7x7_kernel(StemArgs a) {
         // ---- stage the normalised input patch as bf16 (hi, lo) [row][col][4] ------------------
         int tx = 0, ty = 0;
         if (a.mode == 1) { tx = a.origins[2 * n]; ty = a.origins[2 * n + 1]; }
-        for (int i = tid; i < STEM_LR * STEM_LC; i += 256) {
-            const int r = i / STEM_LC, cc = i - r * STEM_LC;
-            const int iy = 2 * oy0 - 3 + r, ix = 2 * ox0 - 3 + cc;
-            float v[3] = {0.f, 0.f, 0.f};
-            if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
-                if (a.mode == 0) {
-                    const size_t base = ((size_t)n * 3 * a.H + iy) * a.W + ix;
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c] = a.in_f32[base + (size_t)c * a.H * a.W];
-                } else {
-                    const int sx = tx + ix, sy = ty + iy;
-                    uint8_t px[3] = {0, 0, 0};       // outside the slide OpenSlide pads with black
-                    if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
-                        const uint8_t* p = a.slide + (size_t)sy * a.slide_pitch + (size_t)sx * 3;
-                        px[0] = p[0]; px[1] = p[1]; px[2] = p[2];
-                    }
-#pragma unroll
-                    for (int c = 0; c < 3; ++c) v[c] = a.lut[c * 256 + px[c]];
-                }
-            }
-            typedef typename PairElem<PLANES>::T E;       // PLANES 2: fp16 pair (common.h), 1: bf16
-            typedef __attribute__((ext_vector_type(4))) E Ex4;
-            Ex4 hi, lo;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { hi[c] = (E)v[c]; lo[c] = (E)(v[c] - (float)hi[c]); }
-            hi[3] = (E)0.f; lo[3] = (E)0.f;
-            *(Ex4*)(xl + (size_t)i * 8) = hi;
-            if constexpr (PLANES == 2) *(Ex4*)(xl + STEM_PLANE_BYTES + (size_t)i * 8) = lo;
-        }
+        stem_stage_rows<PLANES, 256, 0>(a, n, tx, ty, tid, 2 * oy0 - 3, STEM_LR, 2 * ox0 - 3, STEM_LC, xl, STEM_PLANE_BYTES);
         __syncthreads();
 
         f32x16 acc[2][2];                             // [nt][mt]
@@ -112,8 +233,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv7x7_kernel(StemArgs a) {
         // ---- epilogue: bias + ReLU -> PF lines (a.out_pf) or f32 NHWC --------------------------
         const int ox = ox0 + l31;
         if (a.out_pf) {
-            // Lane (column, h) holds channels nt * 32 + 8g + 4h + i of its pixel: the conv kernels' accumulator layout, so the line
-            // encodes are theirs (conv_dev.h conv_epilogue_q / conv_epilogue_mx; pf_lines.h is the scalar reference form)
+            // Lane (column, h) holds channels nt * 32 + 8g + 4h + i of its pixel: the conv kernels' accumulator layout
             const PFGeom go = pf_geom(a.N, Hc, Wc, 64);
             const int bpc = a.out_planes == 1 ? 2 : 4;
 #pragma unroll
@@ -126,48 +246,14 @@ __global__ __launch_bounds__(256, 2) void stem_conv7x7_kernel(StemArgs a) {
 #pragma unroll
                     for (int r = 0; r < 16; ++r) v[r] = fmaxf(acc[nt][mt][r] + bias[nt][r], 0.f);
                     if (a.out_planes == 3) {
-                        f32x16 hi, lo;
-                        f16x8 hv[2];
-                        float mh = 0.f, ml = 0.f;
 #pragma unroll
-                        for (int r = 0; r < 16; r += 2) {
-                            const float v0 = fminf(v[r], 65504.f), v1 = fminf(v[r + 1], 65504.f);
-                            const f16x2 hh = __builtin_convertvector(f32x2{v0, v1}, f16x2);
-                            hv[r >> 3][r & 7] = hh[0];
-                            hv[r >> 3][(r & 7) + 1] = hh[1];
-                            hi[r] = (float)hh[0];
-                            hi[r + 1] = (float)hh[1];
-                            lo[r] = v0 - hi[r];
-                            lo[r + 1] = v1 - hi[r + 1];
-                            mh = fmaxf(mh, fmaxf(hi[r], hi[r + 1]));
-                            ml = fmaxf(ml, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
-                        }
-                        pair_max2(mh, ml);                                      // (every lane takes part: the stores below are masked, not these)
-                        const int sh = mx6_scale_byte(mh), sl = mx6_scale_byte(ml);
-                        const int sb = h ? sh : sl;
-                        swap32_halves(lo, hi);
-                        const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
-                        if (ox < Wc) {
-                            char* ol = o + nt * 128;
-                            *(f16x8*)(ol + 32 * h) = hv[0];
-                            *(f16x8*)(ol + 32 * h + 16) = hv[1];
-                            *(u32x4*)(ol + MX6_PLANE_LO(0) + 16 * h) = u32x4{q[0], q[1], q[2], q[3]};
-                            *(u32x4*)(ol + MX6_PLANE_HI(0) + 16 * h) = u32x4{q[4], q[5], (unsigned)sb, 0u};
-                        }
+                        for (int r = 0; r < 16; ++r) v[r] = fminf(v[r], 65504.f);
+                        stem_store_line_mx(v, h, o + nt * 128, ox < Wc, false);
                     } else if (ox < Wc) {
 #pragma unroll
                         for (int g = 0; g < 4; ++g) {
-                            if (a.out_planes == 2) {                             // fp16 pair (common.h split_f16)
-                                f16x4 hi, lo;
-                                split_f16x4(v + 4 * g, hi, lo);
-                                *(f16x4*)(o + nt * 128 + (8 * g + 4 * h) * 2) = hi;
-                                *(f16x4*)(o + nt * 128 + 64 + (8 * g + 4 * h) * 2) = lo;
-                            } else {
-                                bf16x4 hi;
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) hi[i] = (__bf16)v[4 * g + i];
-                                *(bf16x4*)(o + (nt * 32 + 8 * g + 4 * h) * 2) = hi;
-                            }
+                            if (a.out_planes == 2) stem_store4<2>(o, nt * 32 + 8 * g + 4 * h, v + 4 * g);
+                            else stem_store4<1>(o, nt * 32 + 8 * g + 4 * h, v + 4 * g);
                         }
                     }
                 }
@@ -217,20 +303,8 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float* in, void
             }
         }
         const int q = go.G + n * go.S + py * go.P + px;
-        const int c = c4 * 4;
-        char* o = (char*)out + (size_t)q * (64 * PLANES * 2);
-        if constexpr (PLANES == 2) {                                              // fp16 pair (common.h split_f16)
-            f16x4 hi, lo;
-            const float mv[4] = {m[0], m[1], m[2], m[3]};
-            split_f16x4(mv, hi, lo);
-            *(f16x4*)(o + (c >> 5) * 128 + (c & 31) * 2) = hi;
-            *(f16x4*)(o + (c >> 5) * 128 + 64 + (c & 31) * 2) = lo;
-        } else {
-            bf16x4 hi;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) hi[k] = (__bf16)m[k];
-            *(bf16x4*)(o + c * 2) = hi;
-        }
+        const float mv[4] = {m[0], m[1], m[2], m[3]};
+        stem_store4<PLANES>((char*)out + (size_t)q * (64 * PLANES * 2), c4 * 4, mv);
     }
 }
 
@@ -244,7 +318,6 @@ __global__ __launch_bounds__(256) void maxpool3x3s2_kernel(const float* in, void
 //   carried row 2py-1 is register-local, the horizontal 3-max is two lane shuffles, results sit on
 //   odd lanes.  The normalised input lives in a 16-row LDS ring: 4 new rows are staged per step,
 //   one barrier per step.
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 struct StemPoolArgs {
     StemArgs s;              // s.out unused
     void* out_pf;            // PF (H/4, W/4, 64)
@@ -270,8 +343,6 @@ constexpr int SP_PLANE = SP_RING * SP_COLS * 8;
 // (a2 2^16 + a1 2^8 + a0) scale[cout] + bn_shift[cout].  42 MFMAs of 32 cycles per pooled row and wave instead of the 56 of
 // the fp16 hi/lo form it replaces (r02: 2.52 -> 2.08 ms per 2000 patches; DIG = 2 measured the same 2.08 ms - the kernel is
 // then bound by its VALU epilogue - and 1.1-1.6x the logit error on the margin families, so it is not used).
-typedef __attribute__((ext_vector_type(16))) int i32x16;
-constexpr int STEM_I8_SCALE_OFFSET = 2 * 7 * 3 * 1024;           // float scale[64] behind the digit planes (prepack.hip: wsi_prepack_stem_u8)
 // NSTRIP (integer path only): strips per workgroup.  1 = the form above, weights in registers (236 VGPRs, two waves per SIMD).
 // 2 = a 256-thread workgroup of two strips whose four waves share ONE copy of the digit planes in LDS (42 KB) and read each
 // weight fragment right before its MFMA: ~150 VGPRs, three waves per SIMD.  r02 counters of the 1-strip form: VALU active 68 %
@@ -282,6 +353,16 @@ constexpr int SP_RING_I8 = SP_RING * SP_COLS * 4;                       // ring 
 // x0 = relu(bn1(conv1(x))), which the pool consumes and r02-r04 recomputed with the unfused fp16-pair stem kernel (325 us per 128 tiles
 // of 256 x 256 beside this kernel's 227).  A strip's lanes 1..30 (odd layout) own conv columns 2 px0 .. 2 px0 + 29 - lane 0 is the
 // left neighbour's last column - and the carry-only first step of a segment owns nothing, so every conv pixel is stored exactly once.
+//
+// Dynamic LDS of the strip kernel.  Float paths: one strip's ring, plane p of [slot][col][4 x 16 bit] at p * SP_PLANE.  Integer path:
+// NSTRIP rings of 4-byte pixels, then [scale 64][shift 64], then - NSTRIP > 1 - the digit planes [nt 2][kh 7][digit][lane][16 B].  (The
+// one-strip integer form is launched with the one-plane float ring's byte count, which holds its ring and scales.)
+template <int PLANES, bool U8X, int NSTRIP> struct StemStripLds {
+    static constexpr int RING = U8X ? SP_RING_I8 : SP_PLANE;            // bytes from one strip's ring to the next / from plane hi to lo
+    static constexpr int SB = NSTRIP * SP_RING_I8, WL = SB + 512;
+    static constexpr int TOTAL = NSTRIP > 1 ? WL + STEM_I8_SCALE_OFFSET : (PLANES == 1 || U8X ? 1 : 2) * SP_PLANE;
+    static_assert(!U8X || WL <= TOTAL, "ring + scales fit");
+};
 template <int PLANES, int OUT, int DIG = 0, int NSTRIP = 1, bool X0 = false>
 __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_kernel(StemPoolArgs A) {
     constexpr bool U8X = DIG > 0, WLDS = NSTRIP > 1;
@@ -289,11 +370,12 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
     static_assert(!X0 || (U8X && OUT == 2), "x0 output: integer path, fp16-pair lines");
     extern __shared__ __attribute__((aligned(16))) char smem_all[];
     const StemArgs& a = A.s;
+    typedef StemStripLds<PLANES, U8X, NSTRIP> Lds;
     const int tid = threadIdx.x & 127, lane = tid & 63;                 // tid: thread within the strip's wave pair
     const int wave_g = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int wave = wave_g & 1;                                        // = output-channel tile
     const int sl = wave_g >> 1;                                         // strip within the workgroup
-    char* const smem = smem_all + (WLDS ? sl * SP_RING_I8 : 0);         // this strip's ring
+    char* const smem = smem_all + (WLDS ? sl * Lds::RING : 0);          // this strip's ring
     const int l31 = lane & 31, h = lane >> 5;
     const int Hc = a.H / 2, Wc = a.W / 2, Hp = a.H / 4, Wp = a.W / 4;
     // Strips: normally 15 pooled columns on the ODD lanes 1..29 (lane = conv column 2*px0 - 1 + lane: the column left of
@@ -321,21 +403,16 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
     float bias[U8X ? 1 : 16];
     // integer path: per-channel scale and shift live in LDS behind the (4-byte) ring and are read four at a time in the
     // epilogue - 32 fewer live registers across the MFMA loop
-    float* const sb_lds = (float*)(smem_all + NSTRIP * SP_RING_I8);     // [scale 64][shift 64]
-    char* const wl = smem_all + NSTRIP * SP_RING_I8 + 512;        // WLDS: the digit planes [nt 2][kh 7][digit][lane][16 B]
+    float* const sb_lds = (float*)(smem_all + Lds::SB);                 // [scale 64][shift 64]
+    char* const wl = smem_all + Lds::WL;                                // WLDS: the digit planes [nt 2][kh 7][digit][lane][16 B]
     if constexpr (U8X) {
-        if constexpr (WLDS) {
-            for (int i = threadIdx.x; i < 2 * 7 * DIG * 64; i += 128 * NSTRIP) ((uint4*)wl)[i] = ((const uint4*)a.wpk_u8)[i];
-        } else {
+        if constexpr (!WLDS) {
 #pragma unroll
             for (int ks = 0; ks < 7; ++ks)
 #pragma unroll
                 for (int d = 0; d < DIG; ++d) wq[ks][d] = *((const i32x4*)a.wpk_u8 + ((size_t)(wave * 7 + ks) * DIG + d) * 64 + lane);
         }
-        if (threadIdx.x < 64) {
-            sb_lds[threadIdx.x] = ((const float*)((const char*)a.wpk_u8 + STEM_I8_SCALE_OFFSET))[threadIdx.x];
-            sb_lds[64 + threadIdx.x] = a.bias_u8[threadIdx.x];
-        }
+        stem_preload_i8<WLDS>(a, wl, sb_lds, 128 * NSTRIP);
     } else {
 #pragma unroll
         for (int ks = 0; ks < 14; ++ks)
@@ -345,56 +422,17 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
 #pragma unroll
         for (int r = 0; r < 16; ++r) bias[r] = a.bias[wave * 32 + 8 * (r >> 2) + 4 * h + (r & 3)];
     }
-    const size_t slide_bytes = (size_t)a.SH * (size_t)a.slide_pitch;
 
     auto stage_rows = [&](int row_lo, int nrows) {                      // input rows [row_lo, row_lo+nrows) -> ring
-        for (int i = tid; i < nrows * SP_COLS; i += 128) {
-            const int r = i / SP_COLS, cc = i - r * SP_COLS;
-            const int iy = row_lo + r, ix = ix0 + cc;
-            const int slot = (iy + 64) & (SP_RING - 1);
-            const bool inside = iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-            if constexpr (U8X) {
-                unsigned q = 0u;                                        // zero padding: contributes exactly nothing
-                if (inside) {
-                    const int sx = tx + ix, sy = ty + iy;
-                    unsigned rgb = 0u;                                  // outside the slide OpenSlide pads with black
-                    if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
-                        const size_t off = (size_t)sy * a.slide_pitch + (size_t)sx * 3;
-                        const uint8_t* pp = a.slide + off;
-                        if (off + 4 <= slide_bytes) __builtin_memcpy(&rgb, pp, 4);   // one (unaligned) dword: R, G, B, next R
-                        else rgb = pp[0] | (pp[1] << 8) | (pp[2] << 16);             // last pixel of the buffer
-                    }
-                    q = ((rgb & 0xffffffu) ^ 0x808080u) | 0x7f000000u;  // (R, G, B) - 128 as i8, inside = 127
-                }
-                *(unsigned*)(smem + (size_t)(slot * SP_COLS + cc) * 4) = q;
-            } else {
-                float v[3] = {0.f, 0.f, 0.f};
-                if (inside) {
-                    if (a.mode == 0) {
-                        const size_t base = ((size_t)n * 3 * a.H + iy) * a.W + ix;
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) v[c] = a.in_f32[base + (size_t)c * a.H * a.W];
-                    } else {
-                        const int sx = tx + ix, sy = ty + iy;
-                        uint8_t px[3] = {0, 0, 0};
-                        if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
-                            const uint8_t* pp = a.slide + (size_t)sy * a.slide_pitch + (size_t)sx * 3;
-                            px[0] = pp[0]; px[1] = pp[1]; px[2] = pp[2];
-                        }
-#pragma unroll
-                        for (int c = 0; c < 3; ++c) v[c] = a.lut[c * 256 + px[c]];
-                    }
-                }
-                typedef typename PairElem<PLANES>::T E;   // PLANES 2: fp16 pair (common.h), 1: bf16
-                typedef __attribute__((ext_vector_type(4))) E Ex4;
-                Ex4 hi, lo;
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { hi[c] = (E)v[c]; lo[c] = (E)(v[c] - (float)hi[c]); }
-                hi[3] = (E)0.f; lo[3] = (E)0.f;
-                *(Ex4*)(smem + (size_t)(slot * SP_COLS + cc) * 8) = hi;
-                if constexpr (PLANES == 2) *(Ex4*)(smem + SP_PLANE + (size_t)(slot * SP_COLS + cc) * 8) = lo;
+        if constexpr (U8X) {
+            for (int i = tid; i < nrows * SP_COLS; i += 128) {
+                const int r = i / SP_COLS, cc = i - r * SP_COLS;
+                const int iy = row_lo + r, ix = ix0 + cc;
+                const int slot = (iy + 64) & (SP_RING - 1);
+                *(unsigned*)(smem + (size_t)(slot * SP_COLS + cc) * 4) = stem_px_i8(a, iy, ix, stem_fetch_px(a, tx, ty, iy, ix));
             }
-        }
+        } else
+            stem_stage_rows<PLANES, 128, SP_RING>(a, n, tx, ty, tid, row_lo, nrows, ix0, SP_COLS, smem, Lds::RING);
     };
 
     // U8X: the 4 rows of the NEXT step are fetched into registers before this step's MFMAs (their latency hides
@@ -406,18 +444,7 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
         for (int k = 0; k < NPF; ++k) {
             const int i = tid + k * 128;
             const int r = i / SP_COLS, cc = i - r * SP_COLS;
-            const int iy = row_lo + r, ix = ix0 + cc;
-            unsigned rgb = 0u;
-            if (i < 4 * SP_COLS && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
-                const int sx = tx + ix, sy = ty + iy;
-                if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
-                    const size_t off = (size_t)sy * a.slide_pitch + (size_t)sx * 3;
-                    const uint8_t* pp = a.slide + off;
-                    if (off + 4 <= slide_bytes) __builtin_memcpy(&rgb, pp, 4);
-                    else rgb = pp[0] | (pp[1] << 8) | (pp[2] << 16);
-                }
-            }
-            pf_rgb[k] = rgb;
+            pf_rgb[k] = stem_fetch_px(a, tx, ty, row_lo + r, ix0 + cc, i < 4 * SP_COLS);
         }
     };
     auto commit_rows = [&](int row_lo) {
@@ -426,11 +453,9 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
             const int i = tid + k * 128;
             if (i >= 4 * SP_COLS) continue;
             const int r = i / SP_COLS, cc = i - r * SP_COLS;
-            const int iy = row_lo + r, ix = ix0 + cc;
+            const int iy = row_lo + r;
             const int slot = (iy + 64) & (SP_RING - 1);
-            unsigned q = 0u;
-            if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) q = ((pf_rgb[k] & 0xffffffu) ^ 0x808080u) | 0x7f000000u;
-            *(unsigned*)(smem + (size_t)(slot * SP_COLS + cc) * 4) = q;
+            *(unsigned*)(smem + (size_t)(slot * SP_COLS + cc) * 4) = stem_px_i8(a, iy, ix0 + cc, pf_rgb[k]);
         }
     };
 
@@ -496,7 +521,7 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
                 const char* xp = smem + (size_t)(slot * SP_COLS + 2 * lc + kw0) * 8;
                 const bf16x8 x0 = *(const bf16x8*)xp;
                 if constexpr (PLANES == 2) {
-                    const bf16x8 x1 = *(const bf16x8*)(xp + SP_PLANE);
+                    const bf16x8 x1 = *(const bf16x8*)(xp + Lds::RING);
                     acc[mt] = mfma16<PLANES>(wreg[ks][1], x0, acc[mt]);
                     acc[mt] = mfma16<PLANES>(wreg[ks][0], x1, acc[mt]);
                 }
@@ -515,17 +540,12 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
             // rounding included, and commutes with the maximum: one FMA + ReLU per pooled value instead of one per conv value,
             // bit-identical.  Conv rows 2py, 2py+1 are inside the map for every py >= 0; above the image (py = -1, the carry-only
             // step of the first segment) the carry is the pool's padding, -FLT_MAX here.
-            auto raw = [&](int mt, int r) {                             // exact recombination of the digit planes
-                float c = (float)(DIG >= 2 ? aq[mt][DIG >= 2 ? 1 : 0][r] * 256 + aq[mt][0][r] : aq[mt][0][r]);
-                if constexpr (DIG == 3) c = __builtin_fmaf((float)aq[mt][DIG - 1][r], 65536.0f, c);
-                return c;
-            };
             const bool x0_store = X0 && py >= py0 && col_ok && (even || (l31 >= 1 && l31 <= 30));
             const PFGeom gx = pf_geom(a.N, Hc, Wc, 64);
             char* const x0p = X0 ? (char*)A.x0_pf + ((size_t)(gx.G + n * gx.S + 2 * py * gx.P + (x0_store ? c0 + l31 : 0)) * 256 + wave * 128 + 16 * h) : nullptr;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float c0 = raw(0, r), c1 = raw(1, r);
+                const float c0 = stem_digits_value(aq[0], r), c1 = stem_digits_value(aq[1], r);
                 if constexpr (X0) {                                     // conv rows 2py, 2py + 1 themselves: scale, shift, ReLU, fp16 pair
                     xv[0][r & 3] = __builtin_amdgcn_fmed3f(__builtin_fmaf(c0, sb_lds[wave * 32 + 8 * (r >> 2) + 4 * h + (r & 3)],
                                                                           sb_lds[64 + wave * 32 + 8 * (r >> 2) + 4 * h + (r & 3)]), 0.f, 65504.f);
@@ -596,57 +616,14 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
             const bool store = (even ? !(l31 & 1) : ((l31 & 1) && l31 <= 29)) && px < Wp;
             char* o = (char*)A.out_pf + (size_t)(go.G + n * go.S + py * go.P + (store ? px : 0)) * pixstride;
             if constexpr (OUT == 3) {
-                // fp16 hi + MX-fp6 (lo6, hi6) with one scale per plane and 32-channel line; the line's channels sit in lanes l, l^32
-                // (same encode as conv_epilogue_mx: conv_dev.h)
-                f32x16 hi, lo;
-                f16x8 hv[2];
-                float mh = 0.f, ml = 0.f;
+                if constexpr (!U8X) {                                               // (integer path: clamped in the v_med3 above)
 #pragma unroll
-                for (int r = 0; r < 16; r += 2) {
-                    const float v0 = U8X ? v[r] : fminf(v[r], 65504.f), v1 = U8X ? v[r + 1] : fminf(v[r + 1], 65504.f);   // (integer path: clamped above)
-                    const f16x2 hh = __builtin_convertvector(f32x2{v0, v1}, f16x2);
-                    hv[r >> 3][r & 7] = hh[0];
-                    hv[r >> 3][(r & 7) + 1] = hh[1];
-                    hi[r] = (float)hh[0];
-                    hi[r + 1] = (float)hh[1];
-                    lo[r] = v0 - hi[r];
-                    lo[r + 1] = v1 - hi[r + 1];
-                    mh = fmaxf(mh, fmaxf(hi[r], hi[r + 1]));                                // (v >= 0 after the ReLU)
-                    ml = fmaxf(ml, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
+                    for (int r = 0; r < 16; ++r) v[r] = fminf(v[r], 65504.f);
                 }
-                pair_max2(mh, ml);
-                const int sh = mx6_scale_byte(mh), sl = mx6_scale_byte(ml);
-                const int sb = h ? sh : sl;
-                swap32_halves(lo, hi);
-                const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
-                if (store) {                                                        // line order: common.h mx_line_pos / mx6_field_of_pos
-                    char* ol = o + (o96 ? (size_t)wave * (size_t)A.plane96 : (size_t)wave * 128);
-                    *(f16x8*)(ol + 32 * h) = hv[0];
-                    *(f16x8*)(ol + 32 * h + 16) = hv[1];
-                    if (!o96) {
-                        *(u32x4*)(ol + MX6_PLANE_LO(0) + 16 * h) = u32x4{q[0], q[1], q[2], q[3]};
-                        *(u32x4*)(ol + MX6_PLANE_HI(0) + 16 * h) = u32x4{q[4], q[5], (unsigned)sb, 0u};
-                    } else if (h == 0) {                                            // lo6 plane + both scales (conv_dev.h conv_epilogue_mx)
-                        *(u32x4*)(ol + 64) = u32x4{q[0], q[1], q[2], q[3]};
-                        *(u32x4*)(ol + 80) = u32x4{q[4], q[5], (unsigned)sl, (unsigned)sh};
-                    }
-                }
+                stem_store_line_mx(v, h, o + (o96 ? (size_t)wave * (size_t)A.plane96 : (size_t)wave * 128), store, o96);
             } else if (store) {
 #pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int c = wave * 32 + 8 * g + 4 * h;
-                    if constexpr (OUT == 2) {                                        // fp16 pair (common.h split_f16)
-                        f16x4 hi, lo;
-                        split_f16x4(v + 4 * g, hi, lo);
-                        *(f16x4*)(o + wave * 128 + (8 * g + 4 * h) * 2) = hi;
-                        *(f16x4*)(o + wave * 128 + 64 + (8 * g + 4 * h) * 2) = lo;
-                    } else {
-                        bf16x4 hi;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) hi[i] = (__bf16)v[4 * g + i];
-                        *(bf16x4*)(o + c * 2) = hi;
-                    }
-                }
+                for (int g = 0; g < 4; ++g) stem_store4<OUT>(o, wave * 32 + 8 * g + 4 * h, v + 4 * g);
             }
         }
         if constexpr (U8X) {
@@ -681,20 +658,24 @@ __global__ __launch_bounds__(128 * NSTRIP, NSTRIP == 1 ? 2 : 3) void stem_pool_k
 constexpr int SD_PITCH = 136;                // ring columns per row: 134 read (4 * 31 + 2 + 4 + 3 is the last), pitch 544 B = 34 x 16
 constexpr int SD_COLS = 134;
 constexpr int SD_RING_BYTES = SP_RING * SD_PITCH * 4;
-constexpr size_t stem_dense_lds(int nu) { return (size_t)nu * SD_RING_BYTES + 512 + nu * 512 + 2 * 7 * 3 * 1024; }
+// Dynamic LDS of the dense kernel: NU rings, [scale 64][shift 64], the shared columns, the digit planes
+template <int NU> struct StemDenseLds {
+    static constexpr int RING = SD_RING_BYTES, SB = NU * RING, XBUF = SB + 512, WL = XBUF + NU * 512, TOTAL = WL + STEM_I8_SCALE_OFFSET;
+};
 template <int NU>
 __global__ __launch_bounds__(128 * NU, 2) void stem_pool_dense_kernel(StemPoolArgs A) {
-    constexpr int DIG = 3, RING_BYTES = SD_RING_BYTES;
+    constexpr int DIG = STEM_I8_DIGITS;
+    typedef StemDenseLds<NU> Lds;
     extern __shared__ __attribute__((aligned(16))) char smem_all[];
     const StemArgs& a = A.s;
     const int tid = threadIdx.x & 127, lane = tid & 63;                 // tid: thread within the unit's wave pair
     const int wave_g = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
     const int wave = wave_g & 1;                                        // = output-channel tile
     const int u = wave_g >> 1;                                          // unit within the band
-    char* const smem = smem_all + u * RING_BYTES;                       // this unit's ring
-    float* const sb_lds = (float*)(smem_all + NU * RING_BYTES);         // [scale 64][shift 64]
-    float* const xbuf = sb_lds + 128;                                   // [boundary][trip parity][wave][h][16]: the shared columns
-    char* const wl = smem_all + NU * RING_BYTES + 512 + NU * 512;       // the digit planes [nt 2][kh 7][digit][lane][16 B]
+    char* const smem = smem_all + u * Lds::RING;                        // this unit's ring
+    float* const sb_lds = (float*)(smem_all + Lds::SB);                 // [scale 64][shift 64]
+    float* const xbuf = (float*)(smem_all + Lds::XBUF);                 // [boundary][trip parity][wave][h][16]: the shared columns
+    char* const wl = smem_all + Lds::WL;                                // the digit planes [nt 2][kh 7][digit][lane][16 B]
     const int l31 = lane & 31, h = lane >> 5;
     const int Hp = a.H / 4, Wp = a.W / 4;
     const int nsegs = (Hp + A.rows_per_seg - 1) / A.rows_per_seg;
@@ -704,31 +685,11 @@ __global__ __launch_bounds__(128 * NU, 2) void stem_pool_dense_kernel(StemPoolAr
     const int py1 = min(py0 + A.rows_per_seg, Hp);
     const int ix0 = 4 * p0 - 3;                                         // input column of ring column 0
     const int tx = a.origins[2 * n], ty = a.origins[2 * n + 1];
-    for (int i = threadIdx.x; i < 2 * 7 * DIG * 64; i += 128 * NU) ((uint4*)wl)[i] = ((const uint4*)a.wpk_u8)[i];
-    if (threadIdx.x < 64) {
-        sb_lds[threadIdx.x] = ((const float*)((const char*)a.wpk_u8 + STEM_I8_SCALE_OFFSET))[threadIdx.x];
-        sb_lds[64 + threadIdx.x] = a.bias_u8[threadIdx.x];
-    }
-    const size_t slide_bytes = (size_t)a.SH * (size_t)a.slide_pitch;
+    stem_preload_i8<true>(a, wl, sb_lds, 128 * NU);
     auto slot_of = [&](int iy) { return (iy + 64) & (SP_RING - 1); };
-    auto load_px = [&](int iy, int ix) {                                // R, G, B (+ a stray byte) of input pixel (iy, ix); black outside the slide
-        unsigned rgb = 0u;
-        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
-            const int sx = tx + ix, sy = ty + iy;
-            if (sx >= 0 && sx < a.SW && sy >= 0 && sy < a.SH) {
-                const size_t off = (size_t)sy * a.slide_pitch + (size_t)sx * 3;
-                const uint8_t* pp = a.slide + off;
-                if (off + 4 <= slide_bytes) __builtin_memcpy(&rgb, pp, 4);
-                else rgb = pp[0] | (pp[1] << 8) | (pp[2] << 16);             // last pixel of the buffer
-            }
-        }
-        return rgb;
-    };
-    auto put_px = [&](int iy, int cc, unsigned rgb) {                   // (R, G, B) - 128 as i8 + inside = 127; zero padding outside the patch
-        const int ix = ix0 + cc;
-        unsigned q = 0u;
-        if (iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) q = ((rgb & 0xffffffu) ^ 0x808080u) | 0x7f000000u;
-        *(unsigned*)(smem + (size_t)(slot_of(iy) * SD_PITCH + cc) * 4) = q;
+    auto load_px = [&](int iy, int ix) { return stem_fetch_px(a, tx, ty, iy, ix); };             // black outside the slide
+    auto put_px = [&](int iy, int cc, unsigned rgb) {
+        *(unsigned*)(smem + (size_t)(slot_of(iy) * SD_PITCH + cc) * 4) = stem_px_i8(a, iy, ix0 + cc, rgb);
     };
     // a step's 4 new rows x 134 columns: thread t takes column t of each row, threads 0..23 the 4 x 6 columns 128..133
     const int ex_r = tid / 6, ex_c = 128 + tid - 6 * ex_r;
@@ -802,8 +763,7 @@ __global__ __launch_bounds__(128 * NU, 2) void stem_pool_dense_kernel(StemPoolAr
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        float c = (float)(aq[j][1][r] * 256 + aq[j][0][r]);
-                        c = __builtin_fmaf((float)aq[j][2][r], 65536.0f, c);
+                        const float c = stem_digits_value(aq[j], r);
                         m[r] = fmaxf(m[r], c);
                         if (j == 1) carry[tile][r] = c;
                         asm volatile("" : "+v"(m[r]));          // the maximum is taken HERE: left free, the compiler defers the maxima, keeps the values and spills
@@ -843,40 +803,27 @@ __global__ __launch_bounds__(128 * NU, 2) void stem_pool_dense_kernel(StemPoolAr
                 }
             }
             char* o = (char*)A.out_pf + (size_t)(go.G + n * go.S + py * go.P + p0 + l31) * pixstride;
-            // fp16 hi + MX-fp6 (lo6, hi6): the strip form's encode, on 32 real pixels per half
-            f32x16 hi, lo;
-            f16x8 hv[2];
-            float mh = 0.f, ml = 0.f;
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-                const f16x2 hh = __builtin_convertvector(f32x2{v[r], v[r + 1]}, f16x2);
-                hv[r >> 3][r & 7] = hh[0];
-                hv[r >> 3][(r & 7) + 1] = hh[1];
-                hi[r] = (float)hh[0];
-                hi[r + 1] = (float)hh[1];
-                lo[r] = v[r] - hi[r];
-                lo[r + 1] = v[r + 1] - hi[r + 1];
-                mh = fmaxf(mh, fmaxf(hi[r], hi[r + 1]));
-                ml = fmaxf(ml, fmaxf(fabsf(lo[r]), fabsf(lo[r + 1])));
-            }
-            pair_max2(mh, ml);
-            const int sh = mx6_scale_byte(mh), sl = mx6_scale_byte(ml);
-            const int sb = h ? sh : sl;
-            swap32_halves(lo, hi);
-            const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
-            char* ol = o + (o96 ? (size_t)wave * (size_t)A.plane96 : (size_t)wave * 128);
-            *(f16x8*)(ol + 32 * h) = hv[0];
-            *(f16x8*)(ol + 32 * h + 16) = hv[1];
-            if (!o96) {
-                *(u32x4*)(ol + MX6_PLANE_LO(0) + 16 * h) = u32x4{q[0], q[1], q[2], q[3]};
-                *(u32x4*)(ol + MX6_PLANE_HI(0) + 16 * h) = u32x4{q[4], q[5], (unsigned)sb, 0u};
-            } else if (h == 0) {
-                *(u32x4*)(ol + 64) = u32x4{q[0], q[1], q[2], q[3]};
-                *(u32x4*)(ol + 80) = u32x4{q[4], q[5], (unsigned)sl, (unsigned)sh};
-            }
+            // the strip form's line encode, on 32 real pixels per half
+            stem_store_line_mx(v, h, o + (o96 ? (size_t)wave * (size_t)A.plane96 : (size_t)wave * 128), true, o96);
         }
         __syncthreads();                                                // next rows staged, this step's reads done, shared column published
     }
+}
+
+// one launch of the strip kernel: `strips` strips, NSTRIP per workgroup of 128 * NSTRIP threads, the layout's LDS
+template <int PLANES, int OUT, int DIG = 0, int NSTRIP = 1, bool X0 = false>
+static void stem_pool_launch(long long strips, const StemPoolArgs& A, hipStream_t st) {
+    hipLaunchKernelGGL((stem_pool_kernel<PLANES, OUT, DIG, NSTRIP, X0>), dim3((int)((strips + NSTRIP - 1) / NSTRIP)), dim3(128 * NSTRIP),
+                       (StemStripLds<PLANES, (DIG > 0), NSTRIP>::TOTAL), st, A);
+}
+// one launch of the dense kernel: a workgroup of NU units per band (above 64 KB of LDS a kernel has to ask: NU = 4 takes 78.5 KB)
+template <int NU>
+static int stem_dense_launch(int bands, const StemPoolArgs& A, hipStream_t st) {
+    constexpr int lds = StemDenseLds<NU>::TOTAL;
+    if (lds > 65536 && hipFuncSetAttribute((const void*)stem_pool_dense_kernel<NU>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return WSI_EINVAL;
+    hipLaunchKernelGGL(stem_pool_dense_kernel<NU>, dim3(bands), dim3(128 * NU), lds, st, A);
+    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
 int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows_per_seg, hipStream_t st, int out96, long long plane96, void* x0_pf) {
@@ -890,56 +837,46 @@ int wsi_stem_pool_dispatch(const StemArgs& a, void* out_pf, int planes, int rows
     const long long grid = (long long)a.N * (Wp <= 16 ? 1 : (Wp + 14) / 15) * ((Hp + rows_per_seg - 1) / rows_per_seg);   // strips, see kernel
     if (grid > 0x7fffffffLL) return WSI_EINVAL;
     const bool u8x = a.mode == 1 && a.wpk_u8 && a.bias_u8 && planes >= 2;
-    const size_t lds = (size_t)(planes == 1 || u8x ? 1 : 2) * SP_PLANE;
     // integer stem, mx lines, pooled maps 64 or 128 wide (256 and 512 pixel patches): the dense column mapping, one workgroup per band of rows
     if (u8x && planes == 3 && !x0_pf && g_routes.stem_shared_weights && g_routes.stem_dense && (Wp == 64 || Wp == 128)) {
         const long long gd = (long long)a.N * ((Hp + rows_per_seg - 1) / rows_per_seg);
         if (gd > 0x7fffffffLL) return WSI_EINVAL;
-        if (Wp == 128) {                              // (78.5 KB of LDS: above the 64 KB a kernel gets without asking)
-            auto k = stem_pool_dense_kernel<4>;
-            if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)stem_dense_lds(4)) != hipSuccess) return WSI_EINVAL;
-            hipLaunchKernelGGL(k, dim3((int)gd), dim3(512), stem_dense_lds(4), st, A);
-        } else
-            hipLaunchKernelGGL(stem_pool_dense_kernel<2>, dim3((int)gd), dim3(256), stem_dense_lds(2), st, A);
-        return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+        return Wp == 128 ? stem_dense_launch<4>((int)gd, A, st) : stem_dense_launch<2>((int)gd, A, st);
     }
     if (u8x && g_routes.stem_shared_weights) {               // integer stem, two strips per workgroup, digit planes shared in LDS
-        const size_t lds2 = 2 * SP_RING_I8 + 512 + 2 * 7 * 3 * 1024;
-        const int grid2 = (int)((grid + 1) / 2);
         if (x0_pf && planes != 2) return WSI_EINVAL;
-        if (planes == 3) hipLaunchKernelGGL((stem_pool_kernel<2, 3, 3, 2>), dim3(grid2), dim3(256), lds2, st, A);
-        else if (x0_pf) hipLaunchKernelGGL((stem_pool_kernel<2, 2, 3, 2, true>), dim3(grid2), dim3(256), lds2, st, A);
-        else hipLaunchKernelGGL((stem_pool_kernel<2, 2, 3, 2>), dim3(grid2), dim3(256), lds2, st, A);
+        if (planes == 3) stem_pool_launch<2, 3, 3, 2>(grid, A, st);
+        else if (x0_pf) stem_pool_launch<2, 2, 3, 2, true>(grid, A, st);
+        else stem_pool_launch<2, 2, 3, 2>(grid, A, st);
     } else if (x0_pf)
         return WSI_EINVAL;                            // the x0 output exists in the shared-weights integer form only
     else if (u8x && planes == 3)                      // integer stem, 24-bit weights in both modes (r02: the 16-bit form, DIG 2, costs mx margin)
-        hipLaunchKernelGGL((stem_pool_kernel<2, 3, 3>), dim3((int)grid), dim3(128), lds, st, A);
+        stem_pool_launch<2, 3, 3>(grid, A, st);
     else if (u8x)
-        hipLaunchKernelGGL((stem_pool_kernel<2, 2, 3>), dim3((int)grid), dim3(128), lds, st, A);
+        stem_pool_launch<2, 2, 3>(grid, A, st);
     else if (planes == 3)                             // f32 input: fp16 hi/lo arithmetic, mode-3 output lines
-        hipLaunchKernelGGL((stem_pool_kernel<2, 3>), dim3((int)grid), dim3(128), lds, st, A);
+        stem_pool_launch<2, 3>(grid, A, st);
     else if (planes == 2)
-        hipLaunchKernelGGL((stem_pool_kernel<2, 2>), dim3((int)grid), dim3(128), lds, st, A);
+        stem_pool_launch<2, 2>(grid, A, st);
     else
-        hipLaunchKernelGGL((stem_pool_kernel<1, 1>), dim3((int)grid), dim3(128), lds, st, A);
+        stem_pool_launch<1, 1>(grid, A, st);
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
+template <int PLANES>
+static int stem_conv_launch(int grid, const StemArgs& a, hipStream_t st) {
+    constexpr int lds = StemConvLds<PLANES>::TOTAL;
+    if (lds > 65536 && hipFuncSetAttribute((const void*)stem_conv7x7_kernel<PLANES>, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
+        return WSI_EINVAL;
+    hipLaunchKernelGGL(stem_conv7x7_kernel<PLANES>, dim3(grid), dim3(256), lds, st, a);
+    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+}
 int wsi_stem_dispatch(const StemArgs& a, int planes, hipStream_t st) {
     if (a.H % 16 || a.W % 2 || a.N <= 0 || (planes != 1 && planes != 2)) return WSI_EINVAL;
     const int Hc = a.H / 2, Wc = a.W / 2;
     const int total = a.N * ((Wc + STEM_TC - 1) / STEM_TC) * (Hc / STEM_TR);
     const int grid = total < 2048 ? total : 2048;
-    const size_t lds = (size_t)28 * planes * 1024 + (size_t)planes * STEM_PLANE_BYTES;
-    if (planes == 2) {
-        auto k = stem_conv7x7_kernel<2>;
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return WSI_EINVAL;
-        hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, st, a);
-    } else {
-        hipLaunchKernelGGL(stem_conv7x7_kernel<1>, dim3(grid), dim3(256), lds, st, a);
-    }
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return planes == 2 ? stem_conv_launch<2>(grid, a, st) : stem_conv_launch<1>(grid, a, st);
 }
 
 int wsi_maxpool_dispatch(const float* in, void* out, int N, int Hc, int Wc, int planes, hipStream_t st) {
