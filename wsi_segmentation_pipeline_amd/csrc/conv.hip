@@ -59,10 +59,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gather_kernel(ConvArgs a) {
     }
 
     f32x16 acc[MT];
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    conv_acc_start<PLANES, MT>(acc, a.bias, ntile, lane);     // (modes 1 / 2 only: zero)
     int xbase[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) xbase[mt] = lds_xbase(wm * MT * 32 + mt * 32 + l31, h);
@@ -105,6 +102,21 @@ extern "C" int wsi_study_wide_stamps(unsigned long long* out8, int reset) {
     }
     return WSI_OK;
 }
+// one workgroup in 64 reports: 10^5 waves adding to seven words distort the launch (the stores before it count as tail)
+static __device__ __forceinline__ void wide_stamps_report(int lane, unsigned long long st_begin, unsigned long long st_setup, unsigned long long st_pro,
+                                                          unsigned long long st_line, unsigned long long st_tap, unsigned long long st_loop_end) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0 && (blockIdx.x & 63) == 0) {
+        const unsigned long long st_end = __builtin_readcyclecounter();
+        atomicAdd(&g_wide_stamps[0], 1ull);
+        atomicAdd(&g_wide_stamps[1], st_end - st_begin);
+        atomicAdd(&g_wide_stamps[2], st_setup - st_begin);
+        atomicAdd(&g_wide_stamps[3], st_pro);
+        atomicAdd(&g_wide_stamps[4], st_line);
+        atomicAdd(&g_wide_stamps[5], st_tap);
+        atomicAdd(&g_wide_stamps[6], st_end - st_loop_end);
+    }
+}
 #else
 #define WSTAMP(...)
 #endif
@@ -141,25 +153,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (WN * 32);
-    // Workgroup id -> (pixel tile, channel block).  Ids are dealt round-robin to the 8 XCDs (own L2 each): with
-    // bit 512 the channel blocks of one pixel tile get ids 8 apart, i.e. the SAME XCD, so the slab they share is
-    // fetched from HBM once instead of once per channel block.
-    int nb = blockIdx.x % nblocks, mtile = blockIdx.x / nblocks;
-    if (a.flags & CONV_XCD_ORDER) {
-        const int per = 8 * nblocks, r = blockIdx.x % per;
-        nb = r >> 3;
-        mtile = (blockIdx.x / per) * 8 + (r & 7);
-        const int mtiles = DENSE ? (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM : (a.gi.NS + BM - 1) / BM;
-        if (mtile >= mtiles) return;
-    } else if (a.flags & CONV_XCD_RANGES) {
-        // XCD-contiguous ranges: XCD x (= id & 7) walks tiles [x*chunk, (x+1)*chunk) in dispatch order, so the halo rows
-        // two neighbouring pixel tiles share are still in THAT XCD's L2 when the second one asks for them
-        const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-        nb = lin % nblocks;
-        mtile = lin / nblocks;
-        const int mtiles = DENSE ? (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM : (a.gi.NS + BM - 1) / BM;
-        if (mtile >= mtiles) return;
-    }
+    int nb, mtile;
+    if (!conv_tile_of_block(a.flags, nblocks, DENSE ? (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM : (a.gi.NS + BM - 1) / BM, nb, mtile)) return;
     const int P = a.gi.P;
     const int ntile = nb * WN + wn;
     const int NC = CONV_STUDY(a, CONV_ABL_NO_MAINLOOP) ? 0 : a.gi.C / PFmt<PLANES>::CPL;  // study builds: epilogue only
@@ -167,23 +162,13 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
     const int ncup = a.in_up ? a.up_c / PFmt<PLANES>::CPL : 0;    // leading lines that come from the half-size tensor (U-Net decoder)
     const size_t in_pixstride = in96 ? (size_t)96 : (size_t)(a.gi.C - (a.in_up ? a.up_c : 0)) * PFmt<PLANES>::BPC;
     const int in_line = in96 ? 0 : 128;                       // (96-byte lines: the line's plane is part of the resource base)
-    int xoff[MT], qs[MT];                                     // slab-local pixel / PF position of each tile row
-    bool valid[MT];
-    int slab0, npieces;
+    DenseTile<MT> tl;                                         // slab-local pixel / PF position of each tile row
+    int (&xoff)[MT] = tl.xoff, (&qs)[MT] = tl.qs;
+    bool (&valid)[MT] = tl.valid;
+    int &slab0 = tl.slab0, &npieces = tl.npieces;
     if constexpr (DENSE) {
-        const int HW = a.gi.H * a.gi.W, R = a.gi.N * HW;
-        auto pos = [&](int i) { return pf_pos_of_index(a.gi, i); };
-        const int i0 = mtile * BM, i1 = min(i0 + BM, R) - 1;
-        slab0 = pos(i0) - P - 1;
-        npieces = (pos(i1) + P + 1 - slab0 + 1) * 8;
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int i = i0 + wm * MT * 32 + mt * 32 + (a.gi.W < 32 ? dense_lane_pixel(l31) : l31);   // (conv_dev.h: LDS bank conflicts)
-            valid[mt] = i < R;
-            qs[mt] = pos(valid[mt] ? i : i1);
-            xoff[mt] = qs[mt] - slab0 - (P + 1);             // tap (0,0) adds toff relative to q - P - 1
-        }
-    } else {
+        dense_tile(tl, a.gi, mtile, BM, wm * MT * 32, a.gi.W < 32 ? dense_lane_pixel(l31) : l31);   // (conv_dev.h: LDS bank conflicts)
+    } else {                                                  // BM consecutive PF positions, pads included
         const int q0 = a.gi.G + mtile * BM;
         slab0 = q0 - P - 1;
         npieces = (BM + 2 * P + 2) * 8;
@@ -194,19 +179,11 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
             valid[mt] = pf_is_pixel(a.go, qs[mt]);
         }
     }
-    static_assert((NTHREADS / 8) % 16 == 0, "whole swizzle periods per DMA round");
-    const size_t slab_byte0 = (size_t)slab0 * in_pixstride;
-    const size_t in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.in + slab_byte0), 0, a.in ? (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff) : 0, 0x00020000);
-    int xvoff, upl, usl;
-    bool xact = true;                                         // 96-byte lines: the lanes of the two hi6 slots fetch nothing
-    {
-        const int i = wave * 64 + lane, Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-        xvoff = Pl * (int)in_pixstride + (in96 ? mx96_piece(sl) : sl) * 16;
-        if (in96) xact = mx96_stored(sl);
-        upl = Pl; usl = sl;
-    }
+    const size_t slab_byte0 = (size_t)slab0 * in_pixstride, in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
+    const __amdgpu_buffer_rsrc_t xrs = slab_rsrc(a.in, slab_byte0, in_bytes, 0, a.in != nullptr);   // (a.in is null where in_up has every channel)
+    bool xact;
+    const int xvoff = slab_lane_voff96(wave * 64 + lane, (int)in_pixstride, in96, xact);
+    const int upl = (wave * 64 + lane) >> 3, usl = slab_lane_slot(wave * 64 + lane);      // in_up: this lane's slab pixel and slot of round 0
     const int up_pixstride = a.up_c * PFmt<PLANES>::BPC;
     const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)a.in_up, 0, a.in_up ? (int)((size_t)pf_alloc_pixels(a.gup.N, a.gup.H, a.gup.W) * up_pixstride) : 0, 0x00020000);
@@ -217,14 +194,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
         (void*)((const char*)a.wpk + wcopy + (size_t)ntile * NC * 9 * 4096), 0, NC * 9 * 4096, 0x00020000);
     const int wvoff = lane * 16;
 
-    f32x16 acc[1][MT];                                        // [1]: the shape conv_residual_mx takes
-    if constexpr (PLANES == 3) acc_init_bias<MT>(acc[0], a.bias, ntile, lane);
-    else {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[0][mt][r] = 0.f;
-    }
+    f32x16 acc[1][MT];                                        // [1]: the shape conv_tail_mx takes
+    conv_acc_start<PLANES, MT>(acc[0], a.bias, ntile, lane);
     auto wload = [&](bf16x8(&w)[4], int soff) {
 #pragma unroll
         for (int f = 0; f < 4; ++f)
@@ -254,9 +225,6 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
         bf16x8 wbuf[3][4], xf[2][4];
         wload(wbuf[0], sline);                                // W(c,0) flies during the slab DMA
         if (c) __syncthreads();
-        // slab pieces by buffer addressing: a round of NTHREADS pieces is NTHREADS / 8 pixels, a multiple of 16, so the swizzle
-        // term ((Pl >> 1) & 7) of a lane does not depend on the round - one per-lane byte offset (computed once per tile),
-        // everything else scalar (r02: the 64-bit per-piece address arithmetic was ~10 % of this kernel's vector instructions)
         if (c < ncup) {
             // line of the up-sampled tensor (ConvArgs.in_up): the piece of slab pixel Pl comes from pixel (y >> 1, x >> 1) of the
             // half-size tensor; pad / guard positions of the slab read pixel 0 of it (a zero guard).  One magic division pair per piece
@@ -271,11 +239,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
                 dma16_buf(urs, smem + (size_t)i0 * 16, src * up_pixstride + usl * 16, c * 128);
             }
         } else {
-            const __amdgpu_buffer_rsrc_t xr = in96 ? __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.in + (size_t)c * (size_t)a.plane96 + slab_byte0), 0,
-                                                                                        (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff), 0x00020000)
-                                                   : xrs;
-            for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += NTHREADS, ++r)
-                if (xact) dma16_buf(xr, smem + (size_t)i0 * 16, xvoff, (c - ncup) * in_line + r * (NTHREADS / 8) * (int)in_pixstride);
+            const __amdgpu_buffer_rsrc_t xr = in96 ? slab_rsrc(a.in, slab_byte0, in_bytes, (size_t)c * (size_t)a.plane96) : xrs;
+            slab_dma_rounds<NTHREADS, false>(xr, smem, wave, npieces, xvoff, (c - ncup) * in_line, (NTHREADS / 8) * (int)in_pixstride, xact);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -322,6 +287,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
         }
     }
     WSTAMP(const unsigned long long st_loop_end = __builtin_readcyclecounter();)
+    // (the choice of epilogue is written in the wide and ping-pong kernels too: see the note at the end of conv_dev.h)
     if constexpr (PLANES == 3) {
         if (a.resid) __syncthreads();                         // every wave is done reading pixel fragments: slab memory becomes
         conv_tail_mx<1, MT, RESID_NBUF>(a, acc, qs, valid, ntile, lane, smem + wave * (RESID_NBUF * 4096), slab0);   // the waves' residual staging
@@ -333,19 +299,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_slab3_kernel(Conv
         }
         conv_epilogue_q<MT, PLANES>(a, acc[0], qs, valid, ntile, lane, scratch);
     }
-#ifdef WSI_STUDY
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && (blockIdx.x & 63) == 0) {                // one workgroup in 64 reports (same slots as the wide kernel; [5] = the hi6 rebuild passes here)
-        const unsigned long long st_end = __builtin_readcyclecounter();
-        atomicAdd(&g_wide_stamps[0], 1ull);
-        atomicAdd(&g_wide_stamps[1], st_end - st_begin);
-        atomicAdd(&g_wide_stamps[2], st_setup - st_begin);
-        atomicAdd(&g_wide_stamps[3], st_pro);
-        atomicAdd(&g_wide_stamps[4], st_line);
-        atomicAdd(&g_wide_stamps[5], st_tap);
-        atomicAdd(&g_wide_stamps[6], st_end - st_loop_end);
-    }
-#endif
+    WSTAMP(wide_stamps_report(lane, st_begin, st_setup, st_pro, st_line, st_tap, st_loop_end);)   // (same slots as the wide kernel; [5] = the hi6 rebuild passes here)
 }
 
 // exact largest slab (pixels) over the dense tiles of BM real pixels
@@ -364,6 +318,19 @@ long long dense_max_slab_pixels(const ConvArgs& a, int BM) {
     return maxpix;
 }
 
+// ---- what every launcher shares (internal.h: conv_launch, by_planes) ----
+// LDS bytes of a slab of maxpix pixels fetched in whole DMA rounds of nthreads pieces; at least the 8 KB per wave in which the
+// epilogues stage residual tiles (waves = 0: a kernel that stages none)
+size_t conv_slab_lds(long long maxpix, int nthreads, int waves) {
+    const size_t lds = (size_t)((maxpix * 8 + nthreads - 1) / nthreads * nthreads) * 16;
+    return lds < (size_t)waves * 8192 ? (size_t)waves * 8192 : lds;
+}
+// workgroups of mtiles x nblocks tiles under the tile order `flags` names (conv_dev.h conv_tile_of_block: the XCD orders deal
+// whole rounds of 8 ids; the workgroups past the last tile leave at once)
+int conv_grid(int mtiles, int nblocks, int flags) {
+    return (flags & CONV_XCD_ORDER) ? (mtiles + 7) / 8 * 8 * nblocks : (flags & CONV_XCD_RANGES) ? (mtiles * nblocks + 7) / 8 * 8 : mtiles * nblocks;
+}
+
 template <int MT, int WM, int WN, int PLANES, int MINW, bool DENSE, int ABL = 0, bool PAIR = false>
 static int launch_slab3(const ConvArgs& a, hipStream_t st) {
     constexpr int BM = WM * MT * 32, NTHREADS = WM * WN * 64;
@@ -378,8 +345,7 @@ static int launch_slab3(const ConvArgs& a, hipStream_t st) {
         mtiles = (a.gi.NS + BM - 1) / BM;
         maxpix = BM + 2 * a.gi.P + 2;
     }
-    size_t lds = (size_t)((maxpix * 8 + NTHREADS - 1) / NTHREADS * NTHREADS) * 16;
-    if (lds < (size_t)WM * WN * 8192) lds = (size_t)WM * WN * 8192;          // the epilogue stages residual tiles there (8 KB per wave)
+    const size_t lds = conv_slab_lds(maxpix, NTHREADS, WM * WN);
     if (lds > 160 * 1024) return WSI_EINVAL;
     if (PAIR && (!DENSE || MT % 2 || a.gi.W % 64 || ((long long)a.gi.N * a.gi.H * a.gi.W) % BM)) return WSI_EINVAL;
     if (a.in_up) {                                           // fused upsample + concat input (common.h): 32-bit offsets into the half-size tensor
@@ -389,14 +355,7 @@ static int launch_slab3(const ConvArgs& a, hipStream_t st) {
             (size_t)pf_alloc_pixels(a.gup.N, a.gup.H, a.gup.W) * a.up_c * PFmt<PLANES>::BPC > (size_t)0x7fffffff)
             return WSI_EINVAL;
     }
-    auto k = conv3x3s1_slab3_kernel<MT, WM, WN, PLANES, MINW, DENSE, ABL, PAIR>;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return WSI_EINVAL;
-    }
-    const int grid = (a.flags & CONV_XCD_ORDER) ? (mtiles + 7) / 8 * 8 * nblocks : (a.flags & CONV_XCD_RANGES) ? (mtiles * nblocks + 7) / 8 * 8 : mtiles * nblocks;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(conv3x3s1_slab3_kernel<MT, WM, WN, PLANES, MINW, DENSE, ABL, PAIR>, conv_grid(mtiles, nblocks, a.flags), NTHREADS, lds, st, a);
 }
 
 
@@ -430,13 +389,8 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
     const int wm = wave / WN, wn = wave % WN;                 // wm: column half of the 64-wide map, wn: channel tile
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (WN * 32);
-    int nb = blockIdx.x % nblocks, mtile = blockIdx.x / nblocks;
-    if (a.flags & CONV_XCD_RANGES) {                          // XCD-contiguous tile ranges (see conv3x3s1_slab3_kernel)
-        const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-        nb = lin % nblocks;
-        mtile = lin / nblocks;
-        if (mtile >= (a.gi.N * a.gi.H * a.gi.W) / BM) return;
-    }
+    int nb, mtile;
+    if (!conv_tile_of_block(a.flags & CONV_XCD_RANGES, nblocks, (a.gi.N * a.gi.H * a.gi.W) / BM, nb, mtile)) return;
     const int P = a.gi.P;                                     // 65
     const int ntile = nb * WN + wn;
     const int NC = NCT ? NCT : a.gi.C / 32;
@@ -448,17 +402,10 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
     const int slab0 = p0 - P - 1;
     const int npieces = (5 * P + 66) * 8;                     // rows -1 .. 4 of the tile: p0 + 3P + 63 + P + 1 - slab0 + 1 pixels
     const int xoff0 = wm * 32 + l31;                          // slab-local pixel of tap (0, 0) of tile row 0
-    const size_t slab_byte0 = (size_t)slab0 * in_pixstride;
-    const size_t in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.in + slab_byte0), 0, (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff), 0x00020000);
-    int xvoff;
-    bool xact = true;                                         // 96-byte lines: the lanes of the two hi6 slots fetch nothing
-    {
-        const int i = wave * 64 + lane, Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-        xvoff = Pl * (int)in_pixstride + (in96 ? mx96_piece(sl) : sl) * 16;
-        if (in96) xact = mx96_stored(sl);
-    }
+    const size_t slab_byte0 = (size_t)slab0 * in_pixstride, in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
+    const __amdgpu_buffer_rsrc_t xrs = slab_rsrc(a.in, slab_byte0, in_bytes);
+    bool xact;
+    const int xvoff = slab_lane_voff96(wave * 64 + lane, (int)in_pixstride, in96, xact);
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)((const char*)a.wpk + (size_t)ntile * NC * 9 * 4096), 0, NC * 9 * 4096, 0x00020000);
     const int wvoff = lane * 16;
@@ -466,7 +413,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
     f32x16 acc[1][MT];
     auto wload = [&](bf16x8(&w)[4], int soff) {
 #pragma unroll
-        for (int f = 0; f < 4; ++f)                           // fragment offset in the SCALAR operand: one address VGPR instead of four
+        for (int f = 0; f < 4; ++f)                           // fragment offset in the SCALAR operand: one address VGPR instead of four (slab3's wload keeps it in the vector operand, as its r02-r04 measurements were taken)
             w[f] = __builtin_bit_cast(bf16x8, __builtin_amdgcn_raw_buffer_load_b128(wrs, wvoff, soff + f * 1024, 0));
     };
     auto xload = [&](bf16x8(&x)[4], int Pl) {
@@ -489,11 +436,8 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
         WSTAMP(st_a = __builtin_readcyclecounter();)
         if (c) __syncthreads();
         {
-            const __amdgpu_buffer_rsrc_t xr = in96 ? __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)a.in + (size_t)c * (size_t)a.plane96 + slab_byte0), 0,
-                                                                                        (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff), 0x00020000)
-                                                   : xrs;
-            for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += NTHREADS, ++r)
-                if (xact) dma16_buf(xr, smem + (size_t)i0 * 16, xvoff, c * in_line + r * (NTHREADS / 8) * (int)in_pixstride);
+            const __amdgpu_buffer_rsrc_t xr = in96 ? slab_rsrc(a.in, slab_byte0, in_bytes, (size_t)c * (size_t)a.plane96) : xrs;
+            slab_dma_rounds<NTHREADS, false>(xr, smem, wave, npieces, xvoff, c * in_line, (NTHREADS / 8) * (int)in_pixstride, xact);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -503,7 +447,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
             __syncthreads();
         }
         WSTAMP(st_tap += __builtin_readcyclecounter() - st_a;)
-        int Pc = P;                                           // opaque per line (see conv3x3s1_slab3_kernel)
+        int Pc = P;                                           // opaque per line: stops LICM from keeping every set's LDS address live
         asm volatile("" : "+s"(Pc));
         const int sline = c * 9 * 4096;
         // the line's first column of weights is requested HERE, after the hi6 rebuild pass: fetched across the slab wait it would
@@ -549,19 +493,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
     }
     if (a.resid) __syncthreads();                             // every wave is done reading pixel fragments: slab memory becomes
     conv_tail_mx<1, MT, RESID_NBUF>(a, acc, qs, valid, ntile, lane, smem + wave * (RESID_NBUF * 4096), slab0);   // the waves' residual staging
-#ifdef WSI_STUDY
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (lane == 0 && (blockIdx.x & 63) == 0) {
-        const unsigned long long st_end = __builtin_readcyclecounter();
-        atomicAdd(&g_wide_stamps[0], 1ull);
-        atomicAdd(&g_wide_stamps[1], st_end - st_begin);
-        atomicAdd(&g_wide_stamps[2], st_setup - st_begin);
-        atomicAdd(&g_wide_stamps[3], st_pro);
-        atomicAdd(&g_wide_stamps[4], st_line);
-        atomicAdd(&g_wide_stamps[5], st_tap);
-        atomicAdd(&g_wide_stamps[6], st_end - st_loop_end);
-    }
-#endif
+    WSTAMP(wide_stamps_report(lane, st_begin, st_setup, st_pro, st_line, st_tap, st_loop_end);)
 }
 
 template <int MINW>
@@ -572,17 +504,11 @@ static int launch_rows(const ConvArgs& a, hipStream_t st) {
     const int nblocks = a.go.C / 64;
     const long long R = (long long)a.gi.N * a.gi.H * a.gi.W;
     const int mtiles = (int)(R / BM);                        // whole tiles: H % 4 == 0
-    const int npix = 5 * a.gi.P + 66;
-    size_t lds = (size_t)((npix * 8 + NTHREADS - 1) / NTHREADS * NTHREADS) * 16;
-    if (lds < (size_t)4 * 8192) lds = (size_t)4 * 8192;      // residual staging of the tail (8 KB per wave)
+    const size_t lds = conv_slab_lds(5 * a.gi.P + 66, NTHREADS, 4);
     const bool i96 = a.flags & CONV_IN96;
     auto k = nc2 ? (i96 ? conv3x3s1_rows_kernel<MINW, 2, true> : conv3x3s1_rows_kernel<MINW, 2, false>)
                  : (i96 ? conv3x3s1_rows_kernel<MINW, 0, true> : conv3x3s1_rows_kernel<MINW, 0, false>);
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return WSI_EINVAL;
-    const int grid = (a.flags & CONV_XCD_RANGES) ? (mtiles * nblocks + 7) / 8 * 8 : mtiles * nblocks;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(k, conv_grid(mtiles, nblocks, a.flags & CONV_XCD_RANGES), NTHREADS, lds, st, a);
 }
 
 
@@ -622,7 +548,8 @@ __global__ __launch_bounds__(320, 1) void conv3x3s1_l1p_kernel(ConvArgs a) {
     constexpr int NC = NCT;                                   // input lines (the line loop is unrolled: accumulators live inside one tile iteration)
     const int in_pixstride = 96;                              // 96-byte lines, line-planar (ConvArgs.plane96)
     // this workgroup's tiles: XCD x (= id & 7) owns a contiguous range of tiles, its workgroups take them round-robin, so the tiles in
-    // flight on one XCD are neighbours (they share halo rows in that XCD's L2)
+    // flight on one XCD are neighbours (they share halo rows in that XCD's L2).  A persistent workgroup WALKS its range: its own
+    // statement of the range split that conv_tile_of_block (conv_dev.h, CONV_XCD_RANGES) makes for one-tile workgroups
     const int mtiles = (a.gi.N * a.gi.H * a.gi.W) >> 8;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = gridDim.x >> 3;
     const int chunk = (mtiles + 7) >> 3;
@@ -834,10 +761,7 @@ static int launch_l1p(const ConvArgs& a, hipStream_t st) {
     int grid = g_l1p_grid;
     if (mtiles < grid) grid = (int)((mtiles + 7) / 8 * 8);
     if (a.gi.C != 64) return WSI_EINVAL;                      // (two input lines: the only instantiation)
-    auto k = conv3x3s1_l1p_kernel<2>;
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, L1P_LDS) != hipSuccess) return WSI_EINVAL;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(320), L1P_LDS, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(conv3x3s1_l1p_kernel<2>, grid, 320, L1P_LDS, st, a);      // (its grid: one workgroup per CU, above)
 }
 
 
@@ -877,13 +801,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (NTILES * 32);
-    int nb = blockIdx.x % nblocks, mtile = blockIdx.x / nblocks;
-    if (a.flags & CONV_XCD_RANGES) {                           // XCD-contiguous tile ranges (see conv3x3s1_slab3_kernel)
-        const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-        nb = lin % nblocks;
-        mtile = lin / nblocks;
-        if (mtile >= (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM) return;
-    }
+    int nb, mtile;
+    if (!conv_tile_of_block(a.flags & CONV_XCD_RANGES, nblocks, (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM, nb, mtile)) return;
     const int P = a.gi.P;
     const int NC = a.gi.C / PFmt<PLANES>::CPL;
     const size_t in_pixstride = (size_t)a.gi.C * PFmt<PLANES>::BPC;
@@ -906,6 +825,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
             xoff[mt] = 8 * (9 * ((ii >> 6) - n0) + ((ii >> 3) & 7)) + (ii & 7) - 1;
         }
     } else {
+        // conv_dev.h dense_tile's geometry in this kernel's own text (no qs): filled by the helper - through references into the
+        // struct or through copies - the mode-1 form takes 227 registers instead of 223 and the mode-3 form spills 4 bytes more
         auto pos = [&](int i) { return pf_pos_of_index(a.gi, i); };
         const int i0 = mtile * BM, i1 = min(i0 + BM, Rtot) - 1;
         slab0 = pos(i0) - P - 1;
@@ -921,17 +842,14 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
     // the column is the same for every tile of the lane)
     const bool d8_left = D8 && (lpix & 7) == 0, d8_right = D8 && (lpix & 7) == 7;
     constexpr int RPIX = D8 ? 36 : NTHREADS / 8;              // memory pixels one DMA round advances
-    // slab DMA by buffer addressing (see conv3x3s1_slab3_kernel): one per-lane byte offset, scalar offsets per line / round
-    static_assert((NTHREADS / 8) % 16 == 0, "whole swizzle periods per DMA round");
-    const size_t slab_byte0 = (size_t)slab0 * in_pixstride;
-    const size_t in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.in + slab_byte0), 0, (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff), 0x00020000);
-    int xvoff;
-    {
-        const int i = wave * 64 + lane, Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-        xvoff = (D8 ? (Pl >> 3) * 9 + (Pl & 7) : Pl) * (int)in_pixstride + sl * 16;
-    }
+    // D8: slab pixel Pl of a round's 32 = memory pixel 9 (Pl >> 3) + (Pl & 7) (the pad column is not copied)
+    auto lane_voff = [&](int pixstride) {
+        const int i = wave * 64 + lane, Pl = i >> 3;
+        return D8 ? ((Pl >> 3) * 9 + (Pl & 7)) * pixstride + slab_lane_slot(i) * 16 : slab_lane_voff(i, pixstride);
+    };
+    const size_t slab_byte0 = (size_t)slab0 * in_pixstride, in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
+    const __amdgpu_buffer_rsrc_t xrs = slab_rsrc(a.in, slab_byte0, in_bytes);
+    const int xvoff = lane_voff((int)in_pixstride);
     if constexpr (D8) {                                       // the 16 zero pixels (2 KB; the first line's barrier publishes them)
         if (tid < 128) *(u32x4*)(xl + D8_ZB * 128 + tid * 16) = u32x4{0u, 0u, 0u, 0u};
     }
@@ -941,7 +859,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         (void*)((const char*)a.wpk + (size_t)(nb * NTILES) * NC * 9 * 4096), 0, NTILES * NC * 9 * 4096, 0x00020000);
     const int wvoff = (tid & 255) * 16;
-    const unsigned wl_addr = lds_addr_of(wl), xl_addr = lds_addr_of(xl);
+    const unsigned wl_addr = lds_addr_of(wl);
     auto wdma = [&](int c, int t, int wboff) {
 #pragma unroll
         for (int p0 = 0; p0 < NTILES * 256; p0 += NTHREADS) {
@@ -953,15 +871,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
 
     f32x16 acc[NT][MT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        if constexpr (PLANES == 3) acc_init_bias<MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);
-        else {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[nt][mt][r] = 0.f;
-        }
-    }
+    for (int nt = 0; nt < NT; ++nt) conv_acc_start<PLANES, MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);
 
     auto xload = [&](bf16x8(&x)[4], int Pl, int tx = 1) {     // tx: the tap's column (D8: 0 / 2 leave the row on the edge lanes)
         asm volatile("" : "+v"(Pl));                          // opaque: each step's address arithmetic stays at the step (no hoisting, no spills)
@@ -984,8 +894,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
     for (int c = 0; c < NC; ++c) {
         WSTAMP(st_a = __builtin_readcyclecounter();)
         if (c) __syncthreads();                               // slab and weight buffers are free again
-        for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += NTHREADS, ++r)
-            dma16_buf_asm(xrs, xl_addr + i0 * 16, xvoff, c * 128 + r * RPIX * (int)in_pixstride);
+        slab_dma_rounds<NTHREADS, true>(xrs, xl, wave, npieces, xvoff, c * 128, RPIX * (int)in_pixstride);
         wdma(c, 0, kpar * WB);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
@@ -1042,15 +951,9 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
             // 32-channel line of `in2` (same pixel geometry as the output: the same slab shape and offsets), accumulated on top
             // of the 3x3 conv; its BN bias joins the accumulators here.
             const int NC2 = a.in2_c / 32;
-            const size_t ps2 = (size_t)a.in2_c * 4, sb2 = (size_t)slab0 * ps2;
-            const size_t bytes2 = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * ps2;
-            const __amdgpu_buffer_rsrc_t xrs2 = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)((const char*)a.in2 + sb2), 0, (int)min(bytes2 - sb2, (size_t)0x7fffffff), 0x00020000);
-            int xvoff2;
-            {
-                const int i = wave * 64 + lane, Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-                xvoff2 = (D8 ? (Pl >> 3) * 9 + (Pl & 7) : Pl) * (int)ps2 + sl * 16;
-            }
+            const size_t ps2 = (size_t)a.in2_c * 4;
+            const __amdgpu_buffer_rsrc_t xrs2 = slab_rsrc(a.in2, (size_t)slab0 * ps2, (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * ps2);
+            const int xvoff2 = lane_voff((int)ps2);
             const char* wsrc2 = (const char*)a.wpk2 + (size_t)(nb * NTILES) * NC2 * 4096 + (size_t)(tid & 255) * 16;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
@@ -1063,8 +966,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
             }
             for (int c = 0; c < NC2; ++c) {
                 __syncthreads();                              // slab and weight buffers are free again
-                for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += NTHREADS, ++r)
-                    dma16_buf(xrs2, xl + (size_t)i0 * 16, xvoff2, c * 128 + r * RPIX * (int)ps2);
+                slab_dma_rounds<NTHREADS, false>(xrs2, xl, wave, npieces, xvoff2, c * 128, RPIX * (int)ps2);   // (builtin DMA: nothing else is read meanwhile)
 #pragma unroll
                 for (int p0 = 0; p0 < NTILES * 256; p0 += NTHREADS) {
                     const int pw = p0 + wave * 64;
@@ -1087,6 +989,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
         if (a.resid) __syncthreads();                         // weight stages + slab become the waves' residual staging (NBUF tiles each)
         conv_tail_mx<NT, MT, RESID_NBUF>(a, acc, qs, valid, nb * NTILES + wn * NT, lane, smem + wave * (RESID_NBUF * 4096), slab0);
     } else {
+        // (the same choice as in the slab3 and ping-pong kernels: see the note at the end of conv_dev.h)
         char* scratch = nullptr;
         if (PLANES == 2 && a.resid && !(a.flags & CONV_RESID_DIRECT)) {    // slab memory becomes the waves' residual staging (epilogues)
             __syncthreads();
@@ -1095,19 +998,7 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s1_wide_kernel(ConvA
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) conv_epilogue_q<MT, PLANES>(a, acc[nt], qs, valid, nb * NTILES + wn * NT + nt, lane, scratch);
     }
-#ifdef WSI_STUDY
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the stores count as tail)
-    if (lane == 0 && (blockIdx.x & 63) == 0) {                // one workgroup in 64 reports: 10^5 waves adding to seven words distort the launch
-        const unsigned long long st_end = __builtin_readcyclecounter();
-        atomicAdd(&g_wide_stamps[0], 1ull);
-        atomicAdd(&g_wide_stamps[1], st_end - st_begin);
-        atomicAdd(&g_wide_stamps[2], st_setup - st_begin);
-        atomicAdd(&g_wide_stamps[3], st_pro);
-        atomicAdd(&g_wide_stamps[4], st_line);
-        atomicAdd(&g_wide_stamps[5], st_tap);
-        atomicAdd(&g_wide_stamps[6], st_end - st_loop_end);
-    }
-#endif
+    WSTAMP(wide_stamps_report(lane, st_begin, st_setup, st_pro, st_line, st_tap, st_loop_end);)
 }
 
 
@@ -1121,18 +1012,12 @@ static int launch_wide(const ConvArgs& a, hipStream_t st) {
     const int nblocks = a.go.C / BN;
     const long long R = (long long)a.gi.N * a.gi.H * a.gi.W;
     const int mtiles = (int)((R + BM - 1) / BM);
-    size_t xbytes = D8 ? (size_t)(304 + 16) * 128       // 37 rows of 8 pixels (rounded to 16) + the 16 zero pixels
-                       : (size_t)((dense_max_slab_pixels(a, BM) * 8 + NTHREADS - 1) / NTHREADS * NTHREADS) * 16;
-    if (xbytes < (size_t)WM * WN * 8192) xbytes = (size_t)WM * WN * 8192;    // residual staging of the epilogue (mode 2: in the slab)
+    const size_t xbytes = D8 ? (size_t)(304 + 16) * 128       // 37 rows of 8 pixels (rounded to 16) + the 16 zero pixels (> the 32 KB of residual staging)
+                             : conv_slab_lds(dense_max_slab_pixels(a, BM), NTHREADS, WM * WN);   // (mode 2 stages residual tiles in the slab)
     size_t lds = 2 * (BN / 32) * 4096 + xbytes;
     if (PLANES == 3 && lds < (size_t)WM * WN * 4 * 4096) lds = (size_t)WM * WN * 4 * 4096;   // mode 3: four residual tiles per wave, from smem + 0
     if (lds > 160 * 1024) return WSI_EINVAL;
-    auto k = conv3x3s1_wide_kernel<PLANES, MINW, ABL, WM, WN, NT, D8>;
-    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return WSI_EINVAL;
-    const int grid = (a.flags & CONV_XCD_RANGES) ? (mtiles * nblocks + 7) / 8 * 8 : mtiles * nblocks;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(conv3x3s1_wide_kernel<PLANES, MINW, ABL, WM, WN, NT, D8>, conv_grid(mtiles, nblocks, a.flags & CONV_XCD_RANGES), NTHREADS, lds, st, a);
 }
 
 
@@ -1159,13 +1044,8 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s2_slab_kernel(ConvA
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (WN * 32);
-    int nb = blockIdx.x % nblocks, mtile = blockIdx.x / nblocks;
-    if (a.flags & CONV_XCD_ORDER) {                            // XCD-aware order, see conv3x3s1_slab3_kernel
-        const int per = 8 * nblocks, r = blockIdx.x % per;
-        nb = r >> 3;
-        mtile = (blockIdx.x / per) * 8 + (r & 7);
-        if (mtile >= (a.go.NS + BM - 1) / BM) return;
-    }
+    int nb, mtile;
+    if (!conv_tile_of_block(a.flags & CONV_XCD_ORDER, nblocks, (a.go.NS + BM - 1) / BM, nb, mtile)) return;
     const int P = a.go.P;
     const int q0 = a.go.G + mtile * BM;
     const int R01 = BM, R10 = 2 * BM + 1, R11 = 3 * BM + 1 + P;                      // region bases (pixels)
@@ -1200,27 +1080,14 @@ __global__ __launch_bounds__(WM* WN * 64, MINW) void conv3x3s2_slab_kernel(ConvA
             const int y = r / P, x = r - y * P;
             if (x != a.go.W && y != a.go.H) src = a.gi.G + n * a.gi.S + (2 * y + py) * a.gi.P + 2 * x + px;
         }
-        const int sl = (i & 7) ^ ((Pl >> 1) & 7);                                    // swizzled 16-byte slot
-        srcpix[k] = (int)((unsigned)src * (unsigned)in_pixstride + (unsigned)sl * 16u);   // byte offset (< 4 GiB, host-checked)
+        // per-piece source pixels (a gather over four phase regions), not slab_lane_voff's one offset per lane; the same swizzled slot
+        srcpix[k] = (int)((unsigned)src * (unsigned)in_pixstride + (unsigned)slab_lane_slot(i) * 16u);   // byte offset (< 4 GiB, host-checked)
     }
     const __amdgpu_buffer_rsrc_t irs = __builtin_amdgcn_make_buffer_rsrc((void*)a.in, 0, 0xffffffff, 0x00020000);
 
     f32x16 acc[MT], accd[FUSE ? MT : 1];
-    if constexpr (PLANES == 3) {                               // mode 3: accumulators start from the folded BN bias
-        acc_init_bias<MT>(acc, a.bias, ntile, lane);
-        if constexpr (FUSE) acc_init_bias<MT>(accd, a.bias2, ntile, lane);
-    } else {
-#pragma unroll
-        for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
-        if constexpr (FUSE) {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) accd[mt][r] = 0.f;
-        }
-    }
+    conv_acc_start<PLANES, MT>(acc, a.bias, ntile, lane);
+    if constexpr (FUSE) conv_acc_start<PLANES, MT>(accd, a.bias2, ntile, lane);
     int xoff[MT];
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) xoff[mt] = wm * MT * 32 + mt * 32 + l31;
@@ -1308,17 +1175,9 @@ static int launch_s2slab(const ConvArgs& a, hipStream_t st) {
     if ((unsigned long long)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * a.gi.C * PFmt<PLANES>::BPC >= 0xffffffffull) return WSI_EINVAL;
     const int mtiles = (a.go.NS + BM - 1) / BM;
     const int nblocks = a.go.C / (WN * 32);
-    const int npieces = (4 * BM + 2 * a.go.P + 2) * 8;
-    const size_t lds = (size_t)((npieces + NTHREADS - 1) / NTHREADS * NTHREADS) * 16;
+    const size_t lds = conv_slab_lds(4 * BM + 2 * a.go.P + 2, NTHREADS, 0);          // the four phase regions; no residual
     if (lds > 160 * 1024) return WSI_EINVAL;
-    auto k = conv3x3s2_slab_kernel<MT, WM, WN, PLANES, MINW, FUSE, PMAX, ABL>;
-    if (lds > 64 * 1024) {
-        if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return WSI_EINVAL;
-    }
-    const int grid = (a.flags & CONV_XCD_ORDER) ? (mtiles + 7) / 8 * 8 * nblocks : mtiles * nblocks;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(NTHREADS), lds, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(conv3x3s2_slab_kernel<MT, WM, WN, PLANES, MINW, FUSE, PMAX, ABL>, conv_grid(mtiles, nblocks, a.flags & CONV_XCD_ORDER), NTHREADS, lds, st, a);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1349,15 +1208,14 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wide_kernel(ConvArgs a) {
     const int wm = wave >> 1, wn = wave & 1;
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (NTILES * 32);
-    // XCD-contiguous ranges (ids are dealt round-robin to the 8 XCDs): XCD x walks workgroups [x*chunk, (x+1)*chunk) in
-    // dispatch order, so the channel blocks of one pixel tile - which read the same input pixels - and neighbouring tiles'
-    // halo rows meet in ONE L2 instead of being fetched by up to four (r01 PMC: 1.53x the algorithmic bytes)
-    const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-    const int nb = lin % nblocks, mtile = lin / nblocks;
-    if (mtile >= a.mtiles) return;                    // grid is rounded up to a multiple of 8 (whole workgroup leaves)
+    // always XCD-contiguous ranges: the channel blocks of one pixel tile - which read the same input pixels - and neighbouring
+    // tiles' halo rows meet in ONE L2 instead of being fetched by up to four (r01 PMC: 1.53x the algorithmic bytes)
+    int nb, mtile;
+    if (!conv_tile_of_block(CONV_XCD_RANGES, nblocks, a.mtiles, nb, mtile)) return;
     const int P = a.go.P;
     // dense tile: 256 REAL output pixels (raster order); the pixels a phase needs are still one contiguous PF range,
-    // from the first pixel (minus the phase's back-shift) to the last; no MFMA work on pad positions
+    // from the first pixel (minus the phase's back-shift) to the last; no MFMA work on pad positions.  (Not DenseTile: the tile is
+    // in the OUTPUT geometry and every phase has its own range - there is no one slab0 / xoff.)
     int q0, qlast, qs[MT];
     bool valid[MT];
     if constexpr (!DENSE) {                                   // tiny maps (a dense tile would span too many pad rows): 256 consecutive positions
@@ -1404,8 +1262,7 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wide_kernel(ConvArgs a) {
         const int npieces = (qlast - q0 + 1 + back) * 8;
         for (int i0 = wave * 64; i0 < npieces; i0 += 256) {
             const int i = i0 + lane;
-            const int Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-            dma16_asm(src + (size_t)Pl * in_pixstride + sl * 16, lds_addr_of(xb) + i0 * 16);
+            dma16_asm(src + (size_t)(i >> 3) * in_pixstride + slab_lane_slot(i) * 16, lds_addr_of(xb) + i0 * 16);   // (64-bit per-lane addresses: the phase images may lie > 2 GiB apart)
         }
     };
     auto wread = [&](bf16x8(&w)[NT][4], const char* wb) {
@@ -1420,18 +1277,8 @@ __global__ __launch_bounds__(512, 1) void conv3x3s2_wide_kernel(ConvArgs a) {
     f32x16 acc[NT][MT], accd[DS ? NT : 1][DS ? MT : 1];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        if constexpr (PLANES == 3) {                           // mode 3: accumulators start from the folded BN bias
-            acc_init_bias<MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);
-            if constexpr (DS) acc_init_bias<MT>(accd[nt], a.bias2, nb * NTILES + wn * NT + nt, lane);
-        } else {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) {
-                    acc[nt][mt][r] = 0.f;
-                    if constexpr (DS) accd[nt][mt][r] = 0.f;
-                }
-        }
+        conv_acc_start<PLANES, MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);
+        if constexpr (DS) conv_acc_start<PLANES, MT>(accd[nt], a.bias2, nb * NTILES + wn * NT + nt, lane);
     }
 
     // Steps of one 32-channel line in execution order: (phase, 3x3 tap; tap 9 = the fused 1x1 downsample, which reads the
@@ -1551,38 +1398,29 @@ static int launch_s2wide(const ConvArgs& a, hipStream_t st) {
     auto k = nt4 ? (dense ? conv3x3s2_wide_kernel<PLANES, true, false, 4> : conv3x3s2_wide_kernel<PLANES, false, false, 4>)
            : dense ? (ds ? conv3x3s2_wide_kernel<PLANES, true, true> : conv3x3s2_wide_kernel<PLANES, true, false>)
                    : (ds ? conv3x3s2_wide_kernel<PLANES, false, true> : conv3x3s2_wide_kernel<PLANES, false, false>);
-    if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return WSI_EINVAL;
     ConvArgs b = a;
     b.mtiles = mtiles;
-    hipLaunchKernelGGL(k, dim3((mtiles * nblocks + 7) / 8 * 8), dim3(512), lds, st, b);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(k, conv_grid(mtiles, nblocks, CONV_XCD_RANGES), 512, lds, st, b);
 }
 
 // stride-2 3x3 (+ optional fused downsample) dispatch; cfg 0 = gather kernel (unfused only)
 int wsi_s2_dispatch(const ConvArgs& a_in, int planes, hipStream_t st) {
     ConvArgs a = a_in;
     if (a.in_split_pixels)                                   // phase-split input: the wide kernel is the only reader
-        return planes == 3 ? launch_s2wide<3>(a, st) : planes == 2 ? launch_s2wide<2>(a, st) : WSI_EINVAL;
+        return by_planes<P23>(planes, [&](auto p) { return launch_s2wide<p()>(a, st); });
     if (g_routes.xcd_order && a.go.C > 128) a.flags |= CONV_XCD_ORDER;
     if (a.gi.C % 64 || a.go.C % 128 || planes < 1 || planes > 3) return WSI_EINVAL;
     if (a.go.H * 2 != a.gi.H || a.go.W * 2 != a.gi.W || a.gi.N != a.go.N) return WSI_EINVAL;
     const bool fuse = a.out2 != nullptr;
     if (fuse && (!a.wpk2 || !a.bias2)) return WSI_EINVAL;
-    if (a.go.P > 34) {                                       // output maps wider than 33 (patches > 256): 64-pixel tiles, MINW 2
-        if (planes == 3) return fuse ? launch_s2slab<2, 1, 4, 3, 2, true, 130>(a, st) : launch_s2slab<2, 1, 4, 3, 2, false, 130>(a, st);
-        if (planes == 2) return fuse ? launch_s2slab<2, 1, 4, 2, 2, true, 130>(a, st) : launch_s2slab<2, 1, 4, 2, 2, false, 130>(a, st);
-        return WSI_EINVAL;                                   // speed mode: gather kernel
-    }
+    if (a.go.P > 34)                                         // output maps wider than 33 (patches > 256): 64-pixel tiles, MINW 2 (speed mode: gather kernel)
+        return by_planes<P23>(planes, [&](auto p) { return fuse ? launch_s2slab<2, 1, 4, p(), 2, true, 130>(a, st) : launch_s2slab<2, 1, 4, p(), 2, false, 130>(a, st); });
 #ifdef WSI_STUDY
     if (g_routes.s2_ablate && planes == 3 && fuse) return launch_s2slab<2, 1, 4, 3, 3, true, 34, 16>(a, st);   // weight loads off (wrong results)
 #endif
-    if (g_routes.s2_small_tiles) {                                  // 64-pixel tiles: smaller slabs, more workgroups per CU
-        if (planes == 3) return fuse ? launch_s2slab<2, 1, 4, 3, 3, true>(a, st) : launch_s2slab<2, 1, 4, 3, 3, false>(a, st);
-        if (planes == 2) return fuse ? launch_s2slab<2, 1, 4, 2, 3, true>(a, st) : launch_s2slab<2, 1, 4, 2, 3, false>(a, st);
-    }
-    if (planes == 3) return fuse ? launch_s2slab<4, 1, 4, 3, 2, true>(a, st) : launch_s2slab<4, 1, 4, 3, 2, false>(a, st);
-    if (planes == 2) return fuse ? launch_s2slab<4, 1, 4, 2, 2, true>(a, st) : launch_s2slab<4, 1, 4, 2, 2, false>(a, st);
-    return fuse ? launch_s2slab<4, 1, 4, 1, 2, true>(a, st) : launch_s2slab<4, 1, 4, 1, 2, false>(a, st);
+    if (g_routes.s2_small_tiles && planes >= 2)                     // 64-pixel tiles: smaller slabs, more workgroups per CU
+        return by_planes<P23>(planes, [&](auto p) { return fuse ? launch_s2slab<2, 1, 4, p(), 3, true>(a, st) : launch_s2slab<2, 1, 4, p(), 3, false>(a, st); });
+    return by_planes<P123>(planes, [&](auto p) { return fuse ? launch_s2slab<4, 1, 4, p(), 2, true>(a, st) : launch_s2slab<4, 1, 4, p(), 2, false>(a, st); });
 }
 
 template <int MT, int WM, int WN, int PLANES>
@@ -1591,9 +1429,7 @@ static int launch_gather(const ConvArgs& a, hipStream_t st) {
     if (a.go.C % (WN * 32)) return WSI_EINVAL;
     const int mtiles = (a.go.NS + BM - 1) / BM;
     const int nblocks = a.go.C / (WN * 32);
-    const size_t lds = (size_t)BM * 128;
-    hipLaunchKernelGGL((conv_gather_kernel<MT, WM, WN, PLANES>), dim3(mtiles * nblocks), dim3(WM * WN * 64), lds, st, a);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch(conv_gather_kernel<MT, WM, WN, PLANES>, conv_grid(mtiles, nblocks, 0), WM * WN * 64, (size_t)BM * 128, st, a);
 }
 
 // Slab tile configurations (cfg index -> MT, WM, WN, min waves/SIMD, dense).  Every wave owns 32 output channels and
@@ -1628,19 +1464,22 @@ int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t
     if (a.in_up && !((cfg >= 20 && cfg < 40) || cfg == 90 || cfg == 91)) return WSI_EINVAL;   // fused upsample + concat input: slab3 kernels only
     if (cfg < 20) return WSI_EINVAL;                         // (cfg 0-9 were the first slab kernel, removed)
     if (cfg >= 70 && cfg < 90) return wsi_pp_dispatch(a, planes, cfg, st);           // ping-pong kernels (conv_pp.hip)
+    // one line per cfg: the precision modes it takes, and its kernel with the mode p() among the template arguments
+#define SLAB3(MT, WM, WN, MINW, DENSE) [&](auto p) { return launch_slab3<MT, WM, WN, p(), MINW, DENSE>(a, st); }
     // cfg 90: 512 px x 32 couts (8 x 1 waves, two pixel tiles each) for 32-channel outputs (U-Net decoder levels 4-5)
-    if (cfg == 90) return planes == 3 ? launch_slab3<2, 8, 1, 3, 1, true>(a, st) : planes == 2 ? launch_slab3<2, 8, 1, 2, 1, true>(a, st) : WSI_EINVAL;
+    if (cfg == 90) return by_planes<P23>(planes, SLAB3(2, 8, 1, 1, true));
     // cfg 91: 256 px x 32 couts, the fallback where a 512-pixel tile's slab exceeds the LDS (tiles straddling two images of a wide map)
-    if (cfg == 91) return planes == 3 ? launch_slab3<2, 4, 1, 3, 2, true>(a, st) : planes == 2 ? launch_slab3<2, 4, 1, 2, 2, true>(a, st) : WSI_EINVAL;
+    if (cfg == 91) return by_planes<P23>(planes, SLAB3(2, 4, 1, 2, true));
+    // cfg 42 (r05): persistent, producer-fed form of the row-stacked layer-1 kernel (mode 3, 96-byte lines only)
+    if (cfg == 42) return planes == 3 ? launch_l1p(a, st) : WSI_EINVAL;
     // cfg 40 / 41: row-stacked layer-1 kernel (mode 3, 64-wide maps), three / two workgroups per CU
-    if (cfg == 42) return planes == 3 ? launch_l1p(a, st) : WSI_EINVAL;         // r05: persistent, producer-fed form (96-byte lines only)
     if (cfg == 40) return planes == 3 ? launch_rows<3>(a, st) : WSI_EINVAL;
     if (cfg == 41) return planes == 3 ? launch_rows<2>(a, st) : WSI_EINVAL;
-    if (cfg == 60) return planes == 3 ? launch_wide<3, 2>(a, st) : planes == 2 ? launch_wide<2, 2>(a, st) : launch_wide<1, 2>(a, st);
+    if (cfg == 60) return by_planes<P123>(planes, [&](auto p) { return launch_wide<p(), 2>(a, st); });
 #ifdef WSI_STUDY
-    if (cfg == 61 && planes == 3) return launch_wide<3, 2, 32>(a, st);               // ablation: no pixel-fragment reads
-    if (cfg == 67) return planes == 3 ? launch_wide<3, 1, 0, 4, 2, 1>(a, st) : planes == 2 ? launch_wide<2, 1, 0, 4, 2, 1>(a, st) : WSI_EINVAL;   // 512 px x 64 couts
-    if (cfg == 68) return planes == 3 ? launch_wide<3, 2, 0, 2, 2, 1>(a, st) : planes == 2 ? launch_wide<2, 2, 0, 2, 2, 1>(a, st) : WSI_EINVAL;   // 256 px x 64 couts
+    if (cfg == 61) return by_planes<P3>(planes, [&](auto p) { return launch_wide<p(), 2, 32>(a, st); });            // ablation: no pixel-fragment reads
+    if (cfg == 67) return by_planes<P23>(planes, [&](auto p) { return launch_wide<p(), 1, 0, 4, 2, 1>(a, st); });   // 512 px x 64 couts
+    if (cfg == 68) return by_planes<P23>(planes, [&](auto p) { return launch_wide<p(), 2, 0, 2, 2, 1>(a, st); });   // 256 px x 64 couts
     if (cfg >= 50 && cfg <= 53 && planes == 3) {             // ablation builds of cfg 30 (bottleneck studies only)
         switch (cfg) {
         case 50: return launch_slab3<4, 1, 4, 3, 2, true, 16>(a, st);
@@ -1650,16 +1489,14 @@ int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t
         }
     }
     switch (cfg) {
-#define X(id, MT, WM, WN, MINW, DENSE) \
-    case id: return planes == 3 ? launch_slab3<MT, WM, WN, 3, MINW, DENSE>(a, st) \
-                  : planes == 2 ? launch_slab3<MT, WM, WN, 2, MINW, DENSE>(a, st) : launch_slab3<MT, WM, WN, 1, MINW, DENSE>(a, st);
+#define X(id, MT, WM, WN, MINW, DENSE) case id: return by_planes<P123>(planes, SLAB3(MT, WM, WN, MINW, DENSE));
         SLAB3_CFGS(X)
 #undef X
     }
 #else
     // product build: only the tuned configurations are instantiated (cfg 30 / 31: slab3 for 128-multiple / 64-channel outputs)
-    if (cfg == 30) return planes == 3 ? launch_slab3<4, 1, 4, 3, 2, true>(a, st) : planes == 2 ? launch_slab3<4, 1, 4, 2, 2, true>(a, st) : launch_slab3<4, 1, 4, 1, 2, true>(a, st);
-    if (cfg == 31) return planes == 3 ? launch_slab3<4, 2, 2, 3, 2, true>(a, st) : planes == 2 ? launch_slab3<4, 2, 2, 2, 2, true>(a, st) : launch_slab3<4, 2, 2, 1, 2, true>(a, st);
+    if (cfg == 30) return by_planes<P123>(planes, SLAB3(4, 1, 4, 2, true));
+    if (cfg == 31) return by_planes<P123>(planes, SLAB3(4, 2, 2, 2, true));
     // cfg 38: cfg 31 held to 168 registers = three waves per SIMD, three workgroups per CU (r03 A/B on layer 1)
     if (cfg == 38) {
         if (planes != 3) return WSI_EINVAL;
@@ -1668,8 +1505,9 @@ int wsi_slab_dispatch_cfg(const ConvArgs& a_in, int planes, int cfg, hipStream_t
     }
     // cfg 39: 512 px x 64 couts (4 x 2 waves) for 64-channel layers on maps wider than 128 (the U-Net decoder's last level): a
     // 256-pixel tile of a 256-wide map is ONE row under a three-row slab; two rows per tile cut the halo from 3x to 2x
-    if (cfg == 39) return planes == 3 ? launch_slab3<4, 4, 2, 3, 1, true>(a, st) : planes == 2 ? launch_slab3<4, 4, 2, 2, 1, true>(a, st) : launch_slab3<4, 4, 2, 1, 1, true>(a, st);
+    if (cfg == 39) return by_planes<P123>(planes, SLAB3(4, 4, 2, 1, true));
 #endif
+#undef SLAB3
     return WSI_EINVAL;
 }
 

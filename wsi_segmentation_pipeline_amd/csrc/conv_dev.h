@@ -504,3 +504,123 @@ static __device__ __forceinline__ void mfma_step(f32x16& d, const bf16x8 (&w)[4]
     }
 }
 
+// --------------------------------------------------------------------------------------------
+// What the slab kernels share (conv.hip: slab3, row-stacked, wide, stride-2; conv_pp.hip: ping-pong): the workgroup -> tile map,
+// the dense tile geometry, the slab fetch, the accumulator start and the choice of epilogue.  One statement each: a divergence
+// between copies of these is a wrong-pixel bug that only shows on ragged tiles.
+// --------------------------------------------------------------------------------------------
+
+// Workgroup id -> (channel block nb, pixel tile mtile); false where the workgroup has no tile (the grid is rounded up to a multiple
+// of 8, host conv_grid: the whole workgroup leaves).  Ids are dealt round-robin to the 8 XCDs (own L2 each).
+//   CONV_XCD_ORDER: the channel blocks of one pixel tile get ids 8 apart, i.e. the SAME XCD, so the slab they share is fetched
+//     from HBM once instead of once per channel block.
+//   CONV_XCD_RANGES: XCD x (= id & 7) walks tiles [x*chunk, (x+1)*chunk) in dispatch order, so the halo rows two neighbouring
+//     pixel tiles share are still in THAT XCD's L2 when the second one asks for them.
+// `flags`: the kernel passes a.flags masked by the orders its launcher can give it (a constant where the order is fixed), so the
+// other order's arithmetic is not compiled into it.
+static __device__ __forceinline__ bool conv_tile_of_block(int flags, int nblocks, int mtiles, int& nb, int& mtile) {
+    nb = blockIdx.x % nblocks;
+    mtile = blockIdx.x / nblocks;
+    if (flags & CONV_XCD_ORDER) {
+        const int per = 8 * nblocks, r = blockIdx.x % per;
+        nb = r >> 3;
+        mtile = (blockIdx.x / per) * 8 + (r & 7);
+        return mtile < mtiles;
+    }
+    if (flags & CONV_XCD_RANGES) {
+        const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
+        nb = lin % nblocks;
+        mtile = lin / nblocks;
+        return mtile < mtiles;
+    }
+    return true;
+}
+
+// Dense tile: BM REAL pixels in (n, y, x) raster order from index mtile * BM on; the slab is the contiguous PF range from the first
+// to the last pixel's neighbourhood.  Per tile row mt of the lane (its pixel: row0 + mt * 32 + lpix, lpix = the lane's column of
+// the 32-pixel MFMA tile, dense_lane_pixel on narrow maps): qs = PF position, xoff = slab-local pixel of tap (0, 0) (a tap adds
+// its offset relative to q - P - 1), valid = inside the tensor; rows past the end repeat the tile's last pixel.
+// (The wide kernel's D8 slab image and the row-stacked kernels' p0 form have other geometries: they stay beside their kernels.)
+template <int MT>
+struct DenseTile {
+    int slab0, npieces;                                       // first PF pixel of the slab; its 16-byte pieces
+    int xoff[MT], qs[MT];
+    bool valid[MT];
+};
+template <int MT>
+static __device__ __forceinline__ void dense_tile(DenseTile<MT>& t, const PFGeom& g, int mtile, int BM, int row0, int lpix) {
+    const int P = g.P, R = g.N * g.H * g.W;
+    const int i0 = mtile * BM, i1 = min(i0 + BM, R) - 1;
+    t.slab0 = pf_pos_of_index(g, i0) - P - 1;
+    t.npieces = (pf_pos_of_index(g, i1) + P + 1 - t.slab0 + 1) * 8;
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+        const int i = i0 + row0 + mt * 32 + lpix;
+        t.valid[mt] = i < R;
+        t.qs[mt] = pf_pos_of_index(g, t.valid[mt] ? i : i1);
+        t.xoff[mt] = t.qs[mt] - t.slab0 - (P + 1);
+    }
+}
+
+// Slab fetch.  Piece i of a slab = 16-byte slot (i & 7) of slab pixel i >> 3, stored swizzled (source-side XOR): the lane that
+// writes LDS piece i reads source slot slab_lane_slot(i).  A DMA round of NTHREADS pieces is NTHREADS / 8 pixels, a multiple of 16,
+// so the swizzle term of a lane does not depend on the round - one per-lane byte offset (computed once per tile), everything else
+// scalar (r02: the 64-bit per-piece address arithmetic was ~10 % of the slab3 kernel's vector instructions).
+static __device__ __forceinline__ int slab_lane_slot(int i) { return (i & 7) ^ (((i >> 3) >> 1) & 7); }
+static __device__ __forceinline__ int slab_lane_voff(int i, int pixstride) { return (i >> 3) * pixstride + slab_lane_slot(i) * 16; }
+// ... of a source that may have 96-byte lines (in96): the lanes of the two hi6 slots fetch nothing (xact false)
+static __device__ __forceinline__ int slab_lane_voff96(int i, int pixstride, bool in96, bool& xact) {
+    const int sl = slab_lane_slot(i);
+    xact = !in96 || mx96_stored(sl);
+    return (i >> 3) * pixstride + (in96 ? mx96_piece(sl) : sl) * 16;
+}
+// Buffer resource of a tile's slab: from byte0 (= slab0 x the pixel stride) of the tensor at base (+ plane_off: the line's plane
+// of a 96-byte-line tensor) to the end of its `bytes` (= pf_alloc_pixels x the pixel stride), so a ragged last tile's rounds read
+// zeros instead of the neighbouring allocation.  live = false: an empty resource (a kernel whose tensor may be absent).
+// (Two products as arguments, not slab0 / stride / pixels: multiplied in here, the slab3 kernel's per-line resource of 96-byte
+// lines cost it 17 instructions.)
+static __device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(const void* base, size_t byte0, size_t bytes,
+                                                                   size_t plane_off = 0, bool live = true) {
+    return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)base + plane_off + byte0), 0,
+                                             live ? (int)min(bytes - byte0, (size_t)0x7fffffff) : 0, 0x00020000);
+}
+// Round r of a slab's DMA for the wave whose first piece of round 0 is 64 * wave, and all rounds.  ASM: dma16_buf_asm (DMA that
+// stays in flight while the wave reads other parts of the LDS, see there); act: this lane fetches (slab_lane_voff96).
+template <int NTHREADS, bool ASM>
+static __device__ __forceinline__ void slab_dma_round(__amdgpu_buffer_rsrc_t rs, char* dst, int wave, int npieces, int voff, int soff0,
+                                                      int round_bytes, int r, bool act = true) {
+    static_assert((NTHREADS / 8) % 16 == 0, "whole swizzle periods per DMA round");
+    const int i0 = r * NTHREADS + wave * 64;
+    if (i0 < npieces && act) {
+        if constexpr (ASM) dma16_buf_asm(rs, lds_addr_of(dst) + i0 * 16, voff, soff0 + r * round_bytes);
+        else dma16_buf(rs, dst + (size_t)i0 * 16, voff, soff0 + r * round_bytes);
+    }
+}
+template <int NTHREADS, bool ASM>
+static __device__ __forceinline__ void slab_dma_rounds(__amdgpu_buffer_rsrc_t rs, char* dst, int wave, int npieces, int voff, int soff0,
+                                                       int round_bytes, bool act = true) {
+    static_assert((NTHREADS / 8) % 16 == 0, "whole swizzle periods per DMA round");
+    for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += NTHREADS, ++r) {
+        if (!act) continue;
+        if constexpr (ASM) dma16_buf_asm(rs, lds_addr_of(dst) + i0 * 16, voff, soff0 + r * round_bytes);
+        else dma16_buf(rs, dst + (size_t)i0 * 16, voff, soff0 + r * round_bytes);
+    }
+}
+
+// Accumulator start: the folded BN bias in mode 3 (the epilogue then adds nothing), zero in the other modes (theirs adds it)
+template <int PLANES, int MT>
+static __device__ __forceinline__ void conv_acc_start(f32x16 (&acc)[MT], const float* bias, int ntile, int lane) {
+    if constexpr (PLANES == 3) acc_init_bias<MT>(acc, bias, ntile, lane);
+    else {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[mt][r] = 0.f;
+    }
+}
+
+// Not shared, on purpose: the choice of epilogue after the main loop (mode 3: conv_tail_mx; modes 1 / 2: conv_epilogue_q per channel
+// tile, the residual staged in 8 KB of the wave's own unless the call asks for direct loads).  It stays written out in the slab3, wide
+// and ping-pong kernels: gathered into one helper (conv_finish<PLANES, NT, MT, NBUF>) the wide and ping-pong kernels' mode-1 / mode-2
+// forms came out 1.0 - 3.6 % longer, and ten mode-2 slab3 forms of the study build took a register or 12 bytes of scratch more
+// (profiles/conv_refactor_regs.txt).  A change to the rule is made in all three.

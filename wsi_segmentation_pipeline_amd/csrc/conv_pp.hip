@@ -49,34 +49,18 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
     const int wm = wave / WN, wn = wave % WN;
     const int l31 = lane & 31, h = lane >> 5;
     const int nblocks = a.go.C / (NTILES * 32);
-    int nb = blockIdx.x % nblocks, mtile = blockIdx.x / nblocks;
-    if (a.flags & CONV_XCD_RANGES) {                          // XCD-contiguous tile ranges (see conv3x3s1_slab3_kernel)
-        const int chunk = gridDim.x >> 3, lin = (blockIdx.x & 7) * chunk + (blockIdx.x >> 3);
-        nb = lin % nblocks;
-        mtile = lin / nblocks;
-        if (mtile >= (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM) return;
-    }
+    int nb, mtile;
+    if (!conv_tile_of_block(a.flags & CONV_XCD_RANGES, nblocks, (a.gi.N * a.gi.H * a.gi.W + BM - 1) / BM, nb, mtile)) return;
     const int P = a.gi.P;
     const int NC = a.gi.C / PFmt<PLANES>::CPL;
     const size_t in_pixstride = (size_t)a.gi.C * PFmt<PLANES>::BPC;
-    int xoff[MT], qs[MT];
-    bool valid[MT];
-    int slab0, npieces;
-    const int lpix = dense_lane_pixel(l31);                   // lane -> pixel of a 32-pixel tile: conv_dev.h (LDS bank conflicts)
-    {
-        const int HW = a.gi.H * a.gi.W, R = a.gi.N * HW;
-        auto pos = [&](int i) { return pf_pos_of_index(a.gi, i); };
-        const int i0 = mtile * BM, i1 = min(i0 + BM, R) - 1;
-        slab0 = pos(i0) - P - 1;
-        npieces = (pos(i1) + P + 1 - slab0 + 1) * 8;
+    DenseTile<MT> tl;
+    dense_tile(tl, a.gi, mtile, BM, wm * MT * 32, dense_lane_pixel(l31));   // (this lane order on maps of every width: the kernel serves W <= 33)
+    const int slab0 = tl.slab0, npieces = tl.npieces;
+    int xoff[MT], qs[MT];                                     // copies: read through references into `tl`, the mode-3 forms of this kernel
+    bool valid[MT];                                           // spill 28 bytes more per lane and take one more register (256 px x 256 couts / 384 px)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            const int i = i0 + wm * MT * 32 + mt * 32 + lpix;
-            valid[mt] = i < R;
-            qs[mt] = pos(valid[mt] ? i : i1);
-            xoff[mt] = qs[mt] - slab0 - (P + 1);
-        }
-    }
+    for (int mt = 0; mt < MT; ++mt) { xoff[mt] = tl.xoff[mt]; qs[mt] = tl.qs[mt]; valid[mt] = tl.valid[mt]; }
     // Both DMA streams use buffer addressing: one per-lane byte offset each (computed once), everything that changes with
     // the line / tap / round is a scalar offset - no 64-bit per-lane address arithmetic inside the loop.
     // group A: weights of (line c, tap t) for the workgroup's NTILES channel tiles -> stage wb; 256 pieces of 16 B per tile
@@ -89,33 +73,15 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
             if (half == 2 || (j >= NTILES / 2) == (half == 1))
                 dma16_buf(wrs, wb + j * 4096 + (wave & 3) * 1024, wvoff, ((j * NC + c) * 9 + t) * 4096);
     };
-    // slab pieces: piece i = 16-byte slot (i & 7) of slab pixel i >> 3, stored swizzled (source-side XOR, like every slab
-    // kernel).  A round of 256 pieces is 32 pixels, so the swizzle term ((Pl >> 1) & 7) does not depend on the round:
-    // per-lane offset of round 0 + scalar 32 * round * pixstride.
-    const size_t slab_byte0 = (size_t)slab0 * in_pixstride;
-    const size_t in_bytes = (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)((const char*)a.in + slab_byte0), 0, (int)min(in_bytes - slab_byte0, (size_t)0x7fffffff), 0x00020000);
-    int xvoff, xvoff8;                                        // group B rounds (4 waves) / prologue rounds (8 waves, 64 pixels)
-    {
-        const int i = (wave & 3) * 64 + lane, Pl = i >> 3, sl = (i & 7) ^ ((Pl >> 1) & 7);
-        xvoff = Pl * (int)in_pixstride + sl * 16;
-        const int i8 = wave * 64 + lane, Pl8 = i8 >> 3, sl8 = (i8 & 7) ^ ((Pl8 >> 1) & 7);
-        xvoff8 = Pl8 * (int)in_pixstride + sl8 * 16;
-    }
+    // slab pieces (conv_dev.h slab fetch): rounds of 256 pieces = 32 pixels by the four waves of a group, of 512 in the prologue
+    const __amdgpu_buffer_rsrc_t xrs = slab_rsrc(a.in, (size_t)slab0 * in_pixstride, (size_t)pf_alloc_pixels(a.gi.N, a.gi.H, a.gi.W) * in_pixstride);
+    const int xvoff = slab_lane_voff((wave & 3) * 64 + lane, (int)in_pixstride);     // group rounds (4 waves)
+    const int xvoff8 = slab_lane_voff(wave * 64 + lane, (int)in_pixstride);          // prologue rounds (8 waves, 64 pixels)
     const int round_bytes = 32 * (int)in_pixstride;           // source bytes between two 256-piece rounds
 
     f32x16 acc[NT][MT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) {
-        if constexpr (PLANES == 3) acc_init_bias<MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);   // mode 3: start from the folded BN bias
-        else {
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[nt][mt][r] = 0.f;
-        }
-    }
+    for (int nt = 0; nt < NT; ++nt) conv_acc_start<PLANES, MT>(acc[nt], a.bias, nb * NTILES + wn * NT + nt, lane);
 
     // LDS byte addresses of one tap's pixel fragments (and scale dwords), relative to smem: computed one step ahead,
     // inside the previous multiply phase (VALU beside MFMA is nearly free; in the load phase these ~12 instructions per
@@ -137,7 +103,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
     const int wlane = (wn * NT) * 4096 + lane * 16;           // this lane's slot inside a weight stage
 
     // prologue: slab of line 0 (all waves) + weight stage of step 0 (both groups, half the channel tiles each)
-    for (int i0 = wave * 64, r = 0; i0 < npieces; i0 += 512, ++r) dma16_buf(xrs, xl + (size_t)i0 * 16, xvoff8, 2 * r * round_bytes);
+    slab_dma_rounds<512, false>(xrs, xl, wave, npieces, xvoff8, 0, 2 * round_bytes);
     wdma(0, 0, wl, grp);
     if constexpr (DMODE == 1) wdma(0, 1, wl + WB, grp);       // (all later stages: group B's multiply phases, two steps ahead)
     if constexpr (DMODE == 2) { if (grp == 1) wdma(0, 1, wl + WB, 1); }   // B's half of step 1 (A requests its half in load phase 0)
@@ -161,9 +127,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
             // next line's slab), then every fragment of this tap into registers
             auto slab_slices = [&]() {                        // rounds t and t + 8 of the next line's slab (<= 16 rounds: 64 KB)
                 if (c + 1 < NC && t < 8) {
-                    const int i0 = t * 256 + (wave & 3) * 64;
-                    if (i0 < npieces) dma16_buf(xrs, xnext + (size_t)i0 * 16, xvoff, t * round_bytes + (c + 1) * 128);
-                    if (i0 + 2048 < npieces) dma16_buf(xrs, xnext + (size_t)(i0 + 2048) * 16, xvoff, (t + 8) * round_bytes + (c + 1) * 128);
+                    slab_dma_round<256, false>(xrs, xnext, wave & 3, npieces, xvoff, (c + 1) * 128, round_bytes, t);
+                    slab_dma_round<256, false>(xrs, xnext, wave & 3, npieces, xvoff, (c + 1) * 128, round_bytes, t + 8);
                 }
             };
             auto next_weights = [&](int half) {               // this wave's share of the NEXT step's stage (half 2 = all tiles)
@@ -238,6 +203,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3s1_pp_kernel(ConvArgs a, int xb
     }
 #endif
     if (grp == 0) PP_BARRIER();                               // group A's matching extra barrier
+    // The same choice of epilogue as in the slab3 and wide kernels (see the note at the end of conv_dev.h); the barriers above have
+    // already said that every wave is done with the slabs: no __syncthreads here.
     if constexpr (PLANES == 3) {                              // weight stages and slabs are dead: residual staging, NBUF tiles per wave
         constexpr int NBUF = RESID_NBUF % MT ? MT : (RESID_NBUF < NT * MT ? RESID_NBUF : NT * MT);
         conv_tail_mx<NT, MT, NBUF>(a, acc, qs, valid, nb * NTILES + wn * NT, lane, smem + wave * (RESID_NBUF * 4096), slab0);
@@ -256,41 +223,43 @@ static int launch_pp(const ConvArgs& a, hipStream_t st) {
     const int nblocks = a.go.C / BN;
     const long long R = (long long)a.gi.N * a.gi.H * a.gi.W;
     const int mtiles = (int)((R + BM - 1) / BM);
-    size_t xbytes = (size_t)((dense_max_slab_pixels(a, BM) * 8 + 63) / 64 * 64) * 16;         // whole 1 KB DMA instructions
-    if (2 * xbytes < 8 * 8192) xbytes = 8 * 8192 / 2;                                          // residual staging of the epilogue (mode 2: in the slabs)
+    // each of the two slabs in whole 1 KB DMA instructions; together at least the eight waves' residual staging (mode 2: in the slabs)
+    const size_t xbytes = conv_slab_lds(dense_max_slab_pixels(a, BM), 64, 4);
     size_t lds = 2 * (size_t)(BN / 32) * 4096 + 2 * xbytes;
     if (PLANES == 3 && lds < 8 * 4 * 4096) lds = 8 * 4 * 4096;                                // mode 3: four residual tiles per wave, from smem + 0
     if (lds > 160 * 1024 || xbytes > 65536) return WSI_EINVAL;                                 // (group B moves a slab in <= 16 rounds)
     auto k = conv3x3s1_pp_kernel<PLANES, WM, WN, MT, STAMP, DMODE, PRIO>;
-    static bool lds_ok = false;                              // once per instantiation: up to the whole 160 KB
+    // the dominant kernel of the trunk keeps the attribute call out of its launches: set once per instantiation, to the whole
+    // 160 KB, instead of conv_launch's per-launch call above 64 KB
+    static bool lds_ok = false;
     if (!lds_ok) {
         if (hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return WSI_EINVAL;
         lds_ok = true;
     }
-    const int grid = (a.flags & CONV_XCD_RANGES) ? (mtiles * nblocks + 7) / 8 * 8 : mtiles * nblocks;
-    hipLaunchKernelGGL(k, dim3(grid), dim3(512), lds, st, a, (int)xbytes);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return conv_launch_only(k, conv_grid(mtiles, nblocks, a.flags & CONV_XCD_RANGES), 512, lds, st, a, (int)xbytes);
 }
 
 // cfg 70: 256 px x 256 couts (2 x 4 waves, MT 4); cfg 71: 384 px x 128 couts (4 x 2 waves, MT 3); cfg 72: 512 px x 128 couts
 // (4 x 2 waves, MT 4; small maps only: two 512-pixel slabs must fit)
 int wsi_pp_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st) {
     switch (cfg) {
-    case 70: return planes == 3 ? launch_pp<3, 2, 4, 4>(a, st) : planes == 2 ? launch_pp<2, 2, 4, 4>(a, st) : launch_pp<1, 2, 4, 4>(a, st);
-    case 71: return planes == 3 ? launch_pp<3, 4, 2, 3>(a, st) : planes == 2 ? launch_pp<2, 4, 2, 3>(a, st) : launch_pp<1, 4, 2, 3>(a, st);
-    case 73: return planes == 3 ? launch_pp<3, 2, 4, 4, false, 1>(a, st) : planes == 1 ? launch_pp<1, 2, 4, 4, false, 1>(a, st) : WSI_EINVAL;
-    case 74: return planes == 3 ? launch_pp<3, 2, 4, 4, false, 2>(a, st) : planes == 1 ? launch_pp<1, 2, 4, 4, false, 2>(a, st) : WSI_EINVAL;
-    case 77: return planes == 3 ? launch_pp<3, 4, 2, 3, false, 1>(a, st) : planes == 1 ? launch_pp<1, 4, 2, 3, false, 1>(a, st) : WSI_EINVAL;
-    case 78: return planes == 3 ? launch_pp<3, 4, 2, 3, false, 2>(a, st) : planes == 1 ? launch_pp<1, 4, 2, 3, false, 2>(a, st) : WSI_EINVAL;
+#define PP(...) [&](auto p) { return launch_pp<p(), __VA_ARGS__>(a, st); }   // launch_pp<PLANES, WM, WN, MT, STAMP, DMODE, PRIO>
+    case 70: return by_planes<P123>(planes, PP(2, 4, 4));
+    case 71: return by_planes<P123>(planes, PP(4, 2, 3));
+    case 73: return by_planes<P13>(planes, PP(2, 4, 4, false, 1));
+    case 74: return by_planes<P13>(planes, PP(2, 4, 4, false, 2));
+    case 77: return by_planes<P13>(planes, PP(4, 2, 3, false, 1));
+    case 78: return by_planes<P13>(planes, PP(4, 2, 3, false, 2));
 #ifdef WSI_STUDY
-    case 75: return planes == 3 ? launch_pp<3, 2, 4, 4, true>(a, st) : WSI_EINVAL;       // cfg 70 with phase stamps (a.out2 = 512-byte debug buffer)
-    case 76: return planes == 3 ? launch_pp<3, 4, 2, 3, true>(a, st) : WSI_EINVAL;       // cfg 71 with phase stamps
-    case 79: return planes == 3 ? launch_pp<3, 8, 1, 1>(a, st) : WSI_EINVAL;             // 256 px x 64 couts (layer 1 study)
-    case 82: return planes == 2 ? launch_pp<2, 2, 4, 3>(a, st) : WSI_EINVAL;             // parity mode: 192 px x 256 couts (MT 4 spills)
-    case 84: return planes == 2 ? launch_pp<2, 2, 4, 2>(a, st) : WSI_EINVAL;             // parity mode: 128 px x 256 couts
+    case 75: return by_planes<P3>(planes, PP(2, 4, 4, true));            // cfg 70 with phase stamps (a.out2 = 512-byte debug buffer)
+    case 76: return by_planes<P3>(planes, PP(4, 2, 3, true));            // cfg 71 with phase stamps
+    case 79: return by_planes<P3>(planes, PP(8, 1, 1));                  // 256 px x 64 couts (layer 1 study)
+    case 82: return by_planes<P2>(planes, PP(2, 4, 3));                  // parity mode: 192 px x 256 couts (MT 4 spills)
+    case 84: return by_planes<P2>(planes, PP(2, 4, 2));                  // parity mode: 128 px x 256 couts
 #endif
-    case 83: return planes == 2 ? launch_pp<2, 4, 2, 2>(a, st) : WSI_EINVAL;             // parity mode: 256 px x 128 couts (MT 4 spills there)
-    case 72: return planes == 3 ? launch_pp<3, 2, 4, 4, false, 0, true>(a, st) : planes == 1 ? launch_pp<1, 2, 4, 4, false, 0, true>(a, st) : WSI_EINVAL;   // A/B: raised priority in the multiply phase
+    case 83: return by_planes<P2>(planes, PP(4, 2, 2));                  // parity mode: 256 px x 128 couts (MT 4 spills there)
+    case 72: return by_planes<P13>(planes, PP(2, 4, 4, false, 0, true)); // A/B: raised priority in the multiply phase
+#undef PP
     }
     return WSI_EINVAL;
 }

@@ -1,6 +1,7 @@
 // Internal to libwsi_hip.so: every function one translation unit defines and another calls, declared once (default arguments
 // live here only), and what the host layer's files (capi.hip, trunk.hip) share.  Definer and callers include it.
 #pragma once
+#include <type_traits>
 #include "common.h"
 
 // ------------------------------------------------------------------------------------ kernel launchers, by defining file
@@ -9,6 +10,29 @@ int wsi_conv_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st);
 int wsi_s2_dispatch(const ConvArgs& a, int planes, hipStream_t st);
 int wsi_pp_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st);
 long long dense_max_slab_pixels(const ConvArgs& a, int BM);        // the largest slab (pixels) over the dense tiles of BM real pixels
+size_t conv_slab_lds(long long maxpix, int nthreads, int waves);   // LDS bytes of a slab in whole DMA rounds, >= 8 KB of residual staging per wave
+int conv_grid(int mtiles, int nblocks, int flags);                 // workgroups under the tile order of `flags` (CONV_XCD_ORDER / _RANGES)
+// launch + error mapping of every conv kernel; conv_launch first raises the kernel's dynamic LDS limit where lds exceeds the 64 KB default
+template <class K, class... Args>
+static inline int conv_launch_only(K kernel, int grid, int threads, size_t lds, hipStream_t st, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, args...);
+    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+}
+template <class K, class... Args>
+static inline int conv_launch(K kernel, int grid, int threads, size_t lds, hipStream_t st, const Args&... args) {
+    if (lds > 64 * 1024 && hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return WSI_EINVAL;
+    return conv_launch_only(kernel, grid, threads, lds, st, args...);
+}
+// f(std::integral_constant<int, planes>) for the precision modes `MASK` allows (bit p = planes p), WSI_EINVAL for the others: the
+// dispatch tables name a kernel's template arguments once
+constexpr int P1 = 2, P2 = 4, P3 = 8, P23 = P2 | P3, P13 = P1 | P3, P123 = P1 | P2 | P3;
+template <int MASK, class F>
+static inline int by_planes(int planes, F&& f) {
+    if constexpr (MASK & P3) { if (planes == 3) return f(std::integral_constant<int, 3>{}); }
+    if constexpr (MASK & P2) { if (planes == 2) return f(std::integral_constant<int, 2>{}); }
+    if constexpr (MASK & P1) { if (planes == 1) return f(std::integral_constant<int, 1>{}); }
+    return WSI_EINVAL;
+}
 // stem.hip
 int wsi_stem_dispatch(const StemArgs& a, int planes, hipStream_t st);
 int wsi_maxpool_dispatch(const float* in, void* out, int N, int Hc, int Wc, int planes, hipStream_t st);
