@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 8            /* wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w)) */
+#define WSI_HIP_ABI_VERSION 9            /* wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -195,12 +195,20 @@ int wsi_pf_unpack(const void* in_pf, float* out_nchw, int n, int c, int h, int w
 
 /* ---- whole trunk: stem + layer1..4 (+ avgpool + Linear) for n patches -------------------------
  * The per-batch compute of ResNet.forward (resnets_shift.py:194-212) and of
- * predict_tumorbed(mode='cls') (utils/eval.py:196-198).  All pointers device memory. */
+ * predict_tumorbed(mode='cls') (utils/eval.py:196-198).  All pointers device memory.
+ * The trunk is a BasicBlock ResNet of any depth (resnets_shift.py:111-187 `ResNet(BasicBlock, layers)`): blocks[L-1] residual
+ * blocks in layerL, each entry 1 ... WSI_TRUNK_MAX_BLOCKS and at most WSI_TRUNK_MAX_BLOCKS blocks in all ([2,2,2,2] = ResNet-18,
+ * [3,4,6,3] = ResNet-34); anything else is -22 before any launch.  Convs are indexed block-major: layerL.B.convK sits at
+ *   2 * (blocks[0] + ... + blocks[L-2] + B) + (K-1)
+ * which for [2,2,2,2] is (L-1)*4 + B*2 + (K-1).  Channel counts (64/128/256/512) and map sizes do not depend on the depth, and
+ * neither does the workspace: three rotating buffers per stage carry any number of blocks. */
+#define WSI_TRUNK_MAX_BLOCKS 36
 typedef struct {
     const void* stem_w;   const float* stem_b;
     const void* stem_w_u8; const float* stem_b_u8;     /* wsi_prepack_stem_u8 (u8 slide input) or NULL */
     float norm[6];                                     /* mean[3], std[3] of the transform folded into stem_w_u8 */
-    const void* conv_w[16]; const float* conv_b[16];   /* layerL.B.convK at index (L-1)*4 + B*2 + (K-1) */
+    int blocks[4];                                     /* residual blocks of layer1..4 */
+    const void* conv_w[2 * WSI_TRUNK_MAX_BLOCKS]; const float* conv_b[2 * WSI_TRUNK_MAX_BLOCKS];   /* block-major, see above */
     const void* down_w[3];  const float* down_b[3];    /* layer2..4 .0.downsample */
     const float* head_w;  const float* head_b;  int head_k;  /* Linear(512 -> head_k) or NULL */
     int planes;
@@ -225,8 +233,8 @@ int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const ui
  * 0 = whole batch (default; measured on MI355X, r03: every chunk size from 32 to 768 is slower than the whole batch at
  * 6 162 tiles - DESIGN.md section 4).  Results are bit-identical to the unchunked run for every setting.  Process-wide. */
 int wsi_trunk_set_chunks(int stem_chunk, int layer1_chunk);
-/* debug / parity taps: run the trunk up to stage `stop_after` (0 = stem+maxpool output, 1..8 =
- * layer1.0, layer1.1, ..., layer4.1) and unpack that tensor to f32 NCHW. */
+/* debug / parity taps: run the trunk up to stage `stop_after` (0 = stem+maxpool output, 1 ... total blocks = the residual blocks in
+ * network order: layer1.0, layer1.1, ..., the last block of layer4; [2,2,2,2]: 1..8) and unpack that tensor to f32 NCHW. */
 int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide,
                           long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
                           int n, int h, int w, void* workspace, int workspace_n, int stop_after, float* tap_out_nchw,
@@ -237,7 +245,8 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
  * wsi_trunk_forward; wsi_prof_end disarms, waits for the events and returns the number of records
  * copied: ms, kind (1 = 3x3 stride 1 of layers 2-4, 5 = 3x3 stride 1 of layer 1, 2 = 3x3 stride 2, 3 = 1x1 downsample,
  * 4 = stem+maxpool)
- * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch. */
+ * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch.  The records follow the depth table: per stage one entry
+ * (kind 2, plus 3 on the gather route) and 2 * blocks - 1 stride-1 convs, layer 1 2 * blocks[0] of kind 5. */
 int wsi_prof_begin(int max_records);
 int wsi_prof_end(float* ms_out, int* kind_out, double* flops_out, int cap);
 
@@ -380,7 +389,8 @@ int wsi_score_counts(const uint8_t* p, const uint8_t* gt, const uint8_t* mask, l
 int wsi_esp(const double* pts_xy, int n, int num_pts, double* out_xy, double* scratch, void* stream);
 
 /* ---- U-Net decoder: the dense 'seg' path (utils/eval.py:51 `model(batch_image)`, :196-200 `model.decoder(model.encoder(x))`) ----
- * The reference drives segmentation_models_pytorch's Unet('resnet18') here (eval_tumorbed.py:21-28): third-party, absent and
+ * The reference drives segmentation_models_pytorch's Unet(args.arch_encoder) here (eval_tumorbed.py:21-28; 'resnet18' by default - the
+ * encoder is the trunk at whatever depth wsi_trunk_weights.blocks states, its five maps keep their channels): third-party, absent and
  * un-pinned, so the architecture is restated from the published 0.0.x source (parity unpinned):
  * encoder maps [x4 512 ch /32, x3 256 /16, x2 128 /8, x1 64 /4, x0 64 /2 (conv1+bn1+relu before the max pool)]; five decoder
  * blocks L = 1..5: nearest x2 upsample, concat the next skip, 2 x (conv3x3 + BN + ReLU) to 256/128/64/32/16 channels;

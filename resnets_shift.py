@@ -1,8 +1,10 @@
-"""Drop-in for the reference's ``resnets_shift`` module: the bag-of-patches ResNet-18.
+"""Drop-in for the reference's ``resnets_shift`` module: the bag-of-patches BasicBlock ResNet (ResNet-18, ResNet-34, ...).
 
-Same public names, constructor arguments, 130 state-dict keys and output convention as
-/root/reference/resnets_shift.py (ResNet :111-217, resnet18 :219-242), so existing checkpoints
-load and ``train_hr.py`` / ``scannet.py`` / ``slic.py``-style callers import it unchanged.
+Same public names, constructor arguments, state-dict keys (130 for ``resnet18()``, 226 for ``resnet34()``) and output convention
+as /root/reference/resnets_shift.py (ResNet :111-217, resnet18 :219-242), so existing checkpoints
+load and ``train_hr.py`` / ``scannet.py`` / ``slic.py``-style callers import it unchanged.  ``ResNet(BasicBlock, layers)`` takes
+any four positive block counts (the reference's ``__all__`` names ``resnet34`` but never defines it; its loader mirrors
+``resnet18``'s here); Bottleneck nets (ResNet-50 and deeper) are not implemented.
 In eval mode ``forward`` runs entirely on the gfx950 HIP kernels (libwsi_hip.so) and refuses CPU
 tensors - there is no CPU fallback.  In training mode (autograd needed, out of the inference hot
 path) the same parameters are evaluated with torch ops so the training scripts keep working.
@@ -11,12 +13,14 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ['ResNet', 'BasicBlock', 'resnet18', 'conv3x3', 'conv1x1']
+__all__ = ['ResNet', 'BasicBlock', 'resnet18', 'resnet34', 'model_urls', 'conv3x3', 'conv1x1']
 
 HR_NUM_CNT_SAMPLES = 8       # reference utils/dataset_hr.py:14-15 (kept here to avoid a circular import)
 HR_NUM_PERIM_SAMPLES = 8
 
-model_urls = {'resnet18': 'https://download.pytorch.org/models/resnet18-5c106cde.pth'}
+model_urls = {'resnet18': 'https://download.pytorch.org/models/resnet18-5c106cde.pth',
+              'resnet34': 'https://download.pytorch.org/models/resnet34-333f7ec4.pth'}
+MAX_BLOCKS = 36              # include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS (wsi_segmentation_pipeline_amd.native.TRUNK_MAX_BLOCKS)
 
 
 def conv3x3(in_planes, out_planes, stride=1, groups=1):
@@ -54,8 +58,18 @@ class ResNet(nn.Module):
     def __init__(self, block, layers, num_classes=1000, zero_init_residual=False, groups=1, width_per_group=64,
                  norm_layer=None, precision='auto'):
         super().__init__()
-        if block is not BasicBlock or list(layers) != [2, 2, 2, 2]:
-            raise NotImplementedError('the HIP path implements the ResNet-18 configuration used by resnet18()')
+        supported = ('the HIP path implements BasicBlock ResNets: ResNet(BasicBlock, [n1, n2, n3, n4]) with four positive block counts '
+                     'and at most %d blocks in all, e.g. resnet18() = [2, 2, 2, 2], resnet34() = [3, 4, 6, 3]' % MAX_BLOCKS)
+        if block is not BasicBlock:
+            raise NotImplementedError('%s; Bottleneck nets (ResNet-50 and deeper) are not implemented' % supported)
+        try:
+            layers = [int(nb) for nb in layers]
+            ok = len(layers) == 4 and all(nb >= 1 for nb in layers) and sum(layers) <= MAX_BLOCKS
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise NotImplementedError('%s; got layers = %r' % (supported, layers))
+        self.layers = layers
         norm_layer = norm_layer or nn.BatchNorm2d
         self.inplanes, self.groups, self.base_width = 64, groups, width_per_group
         self.conv1 = nn.Conv2d(3, 64, 7, 2, 3, bias=False)
@@ -145,12 +159,21 @@ class ResNet(nn.Module):
         return singles, eng.linear(hidden, self.fc[2].weight, self.fc[2].bias)
 
 
-def resnet18(pretrained=False, **kwargs):
-    """ResNet-18 bag model; ``pretrained`` overlays the ImageNet trunk weights (needs network access)."""
-    model = ResNet(BasicBlock, [2, 2, 2, 2], **kwargs)
+def _bag_resnet(name, layers, pretrained, kwargs):
+    model = ResNet(BasicBlock, layers, **kwargs)
     if pretrained:
         import torch.utils.model_zoo as model_zoo
         own = model.state_dict()
-        own.update({k: v for k, v in model_zoo.load_url(model_urls['resnet18']).items() if k in own})
+        own.update({k: v for k, v in model_zoo.load_url(model_urls[name]).items() if k in own})
         model.load_state_dict(own)
     return model
+
+
+def resnet18(pretrained=False, **kwargs):
+    """ResNet-18 bag model; ``pretrained`` overlays the ImageNet trunk weights (needs network access)."""
+    return _bag_resnet('resnet18', [2, 2, 2, 2], pretrained, kwargs)
+
+
+def resnet34(pretrained=False, **kwargs):
+    """ResNet-34 bag model ([3, 4, 6, 3] BasicBlocks); ``pretrained`` as in resnet18."""
+    return _bag_resnet('resnet34', [3, 4, 6, 3], pretrained, kwargs)

@@ -24,7 +24,7 @@ from wsi_segmentation_pipeline_amd import slide as S
 
 
 class TrunkEncoder(torch.nn.Module):
-    """``model.encoder`` surface over a resnets_shift.ResNet: encoder(x) -> [deepest feature map]
+    """``model.encoder`` surface over a resnets_shift.ResNet of any BasicBlock depth: encoder(x) -> [deepest feature map]
     (the reference indexes ``encoding[0]`` for the 512-channel map, utils/eval.py:196-198).  The full five-map encoder of
     the dense 'seg' model is wsi_segmentation_pipeline_amd.unet.UNetEncoder."""
 
@@ -38,8 +38,8 @@ class TrunkEncoder(torch.nn.Module):
 
 
 class SlideClassifierModel(torch.nn.Module):
-    """First-party composition that predict_tumorbed(mode='cls') drives: ResNet-18 trunk as
-    ``encoder`` + models.models.Classifier / Regressor heads."""
+    """First-party composition that predict_tumorbed(mode='cls') drives: BasicBlock ResNet trunk (resnets_shift.resnet18(),
+    resnet34() or any other depth) as ``encoder`` + models.models.Classifier / Regressor heads."""
 
     def __init__(self, resnet, classifier, regressor=None):
         super().__init__()

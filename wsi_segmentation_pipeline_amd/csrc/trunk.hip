@@ -139,21 +139,42 @@ int wsi_trunk_workspace_init(void* workspace, int n, int h, int w, int planes, v
 // What a trunk run leaves in the workspace: byte offset and stage of the last tensor produced, and the offset of every stage's
 // output (ordinary PF only when allow_split was off).
 struct TrunkResult { size_t last_off; int last_stage; size_t stage_off[4]; };
+// The depth table of a trunk (wsi_trunk_weights.blocks): blocks per stage, the index of each stage's first conv in the block-major conv
+// tables, and the block count of the whole net.  valid() is what every entry checks before its first launch.
+struct TrunkDepth {
+    int nb[4], conv0[4], total;
+    explicit TrunkDepth(const wsi_trunk_weights* wt) : total(0) {
+        for (int s = 0; s < 4; ++s) {
+            nb[s] = wt->blocks[s];
+            conv0[s] = 2 * total;
+            total = nb[s] >= 1 && nb[s] <= WSI_TRUNK_MAX_BLOCKS && total >= 0 ? total + nb[s] : -1;
+        }
+    }
+    bool valid() const { return total >= 1 && total <= WSI_TRUNK_MAX_BLOCKS; }
+};
 // What the U-Net asks of the trunk beyond a plain run.
 struct TrunkOpts {
     bool allow_split = true;      // stage outputs may be handed over phase-split (off: every stage output stays an ordinary PF tensor)
     char* x0_out = nullptr;       // the fused stem kernel also stores the conv map before the pool here (PF, h / 2 x w / 2 x 64)
 };
-// Runs stem + residual stages; stops after stage `stop_after` (0 = pool, 1..8 = blocks, >= 8 all).
+// Runs stem + residual stages; stops after stage `stop_after` (0 = pool, 1..total = blocks in network order, >= total all); `d` is the
+// (valid) depth table of `wt`.
+// Hand-overs between kernels follow a block's place in its stage - first, middle or last - never its number:
+//   stage 0 on 96-byte lines: every conv reads 96-byte input and residual lines and writes 96-byte lines, except the stage's last
+//     conv, which writes the phase-split (or ordinary 128-byte) form the next stage reads;
+//   stages 1-3: block 0 is the strided block (split entry / fused downsample / gather fallback / downsample fold), blocks 1..nb-1
+//     are plain stride-1 blocks; only the second conv of the stage's LAST block may write the phase-split output, and a conv that
+//     carries the folded downsample (in2) never does - which matters once a stage has a single block.
 // `p` is the plan of the workspace, made for `cap` >= n images: buffer offsets and the distance between phase images
 // come from the plan, so one workspace serves every batch size up to cap (image i sits at the same place whatever n is;
 // what images >= n still hold from an earlier, larger batch is never read: the zero row / column that close image
 // n-1 belong to its own block).
-static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, int cap, int h, int w, void* workspace,
+static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const TileSource& src, int n, int cap, int h, int w, void* workspace,
                      int stop_after, hipStream_t st, const TrunkPlan& p, TrunkResult& res, const TrunkOpts& opt = {}) {
     char* ws = (char*)workspace;
     const int planes = wt->planes;
     int rc = WSI_OK;
+    const bool full = stop_after >= d.total;           // a run through every block (taps stop earlier)
     // ProfScope kinds: 1 = 3x3 stride-1 of layers 2-4 (wide kernel), 5 = 3x3 stride-1 of the 64-channel layer 1 (slab3 kernel),
     // 2 = 3x3 stride-2 (+ fused downsample), 3 = 1x1 downsample, 4 = stem+maxpool
     // conv wi of the trunk (3x3, stride 1, ReLU) on n0 images of an H x W map with C channels in and out; call sites name what differs
@@ -174,7 +195,7 @@ static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, 
     const int do_l1 = stop_after != 0;
     // stage s writes its output phase-split when the next stage's entry can read it with the wide stride-2 kernel:
     // full runs only (taps unpack ordinary PF), split precision, next output maps <= 33 wide, whole-batch stages
-    auto can_split = [&](int s) { return opt.allow_split && g_routes.s2_split && g_routes.s2_slab && stop_after >= 8 && planes >= 2 && s < 3 && p.sw[s + 1] <= 33; };
+    auto can_split = [&](int s) { return opt.allow_split && g_routes.s2_split && g_routes.s2_slab && full && planes >= 2 && s < 3 && p.sw[s + 1] <= 33; };
     const bool split0 = can_split(0);                  // (a layer-1 sub-batch writes its images' slice of each phase image)
     // r03: a full mode-3 run keeps stem output and layer-1 tensors in 96-byte lines (layer 1 is HBM-bound: 25 % fewer bytes);
     // the last layer-1 conv writes the ordinary (or phase-split) 128-byte form every other kernel reads
@@ -209,8 +230,9 @@ static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, 
         }
         if (!do_l1) continue;
         int cur = 0;
-        for (int b = 0; b < 2 && (stop_after >= 8 || b < stop_after); ++b) {
+        for (int b = 0; b < d.nb[0] && (full || b < stop_after); ++b) {
             const int m = (cur + 1) % 3, o = (cur + 2) % 3;
+            const bool last = b == d.nb[0] - 1;
             char *x = ws + p.buf[0][cur] + img_off(0, n1), *mid = ws + p.buf[0][m] + img_off(0, n1),
                  *out = ws + p.buf[0][o] + img_off(0, n1);
             const int f_in = l96 ? CONV_IN96 : 0, f_res = l96 ? CONV_RESID96 : 0;
@@ -218,8 +240,8 @@ static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, 
             c.line_flags = f_in | (l96 ? CONV_OUT96 : 0); c.plane96 = plane96;
             if ((rc = run(5, c))) return rc;
             c = conv3(mid, out, x, 2 * b + 1, nn1, H1, W1, 64);
-            c.line_flags = f_in | f_res | (l96 && b == 0 ? CONV_OUT96 : 0); c.plane96 = plane96;
-            if (b == 1 && split0) {                    // layer1's output feeds only the stride-2 entry of layer2
+            c.line_flags = f_in | f_res | (l96 && !last ? CONV_OUT96 : 0); c.plane96 = plane96;
+            if (last && split0) {                      // layer1's output feeds only the stride-2 entry of layer2
                 c.out = ws + p.buf[0][3] + split_off(n1);
                 c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H1 / 2, W1 / 2);
             }                                          // (otherwise the stage's last conv writes 128-byte lines: layer 2, taps and skips read those)
@@ -229,16 +251,17 @@ static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, 
         l1_out = cur;
     }
     res.last_off = res.stage_off[0] = p.buf[0][l1_out]; res.last_stage = 0;
-    if (stop_after >= 0 && stop_after <= 2) return WSI_OK;
+    if (stop_after >= 0 && stop_after <= d.nb[0]) return WSI_OK;
 
     int cur = l1_out;
     const void* x = split0 ? ws + p.buf[0][3] : ws + p.buf[0][cur];
     bool x_split = split0;
-    int block = 2;
+    int block = d.nb[0];
     for (int s = 1; s < 4; ++s) {
         const int H = p.sh[s], W = p.sw[s], C = p.sc[s];
-        for (int b = 0; b < 2; ++b) {
-            const int wi = s * 4 + b * 2;
+        for (int b = 0; b < d.nb[s]; ++b) {
+            const int wi = d.conv0[s] + b * 2;
+            const bool last = b == d.nb[s] - 1;
             void *mid, *out;
             const void* resid;
             // r03, mode 3: the 1x1 downsample of a strided block is computed INSIDE the block's second conv as an extra K segment
@@ -276,18 +299,18 @@ static int trunk_run(const wsi_trunk_weights* wt, const TileSource& src, int n, 
                 cur = o;
                 res.last_off = p.buf[s][o];
             }
-            x_split = !fold_in2 && b == 1 && can_split(s);                        // the stage's output feeds only the next stage's stride-2 entry
+            x_split = !fold_in2 && last && can_split(s);                          // the stage's output feeds only the next stage's stride-2 entry
             if (x_split) out = ws + p.buf[s][3];
             ConvCall c = conv3(mid, out, resid, wi + 1, n, H, W, C);
             if (x_split) { c.split_out = 1; c.split_pixels = pf_alloc_pixels(cap, H / 2, W / 2); }
-            if (fold_in2) {                            // second conv of a strided block with the downsample folded in (never the stage's last conv)
+            if (fold_in2) {                            // second conv of a strided block with the downsample folded in (never writes the phase-split form)
                 c.in2 = fold_in2; c.in2_c = C / 2; c.wpk2 = wt->down_w[s - 1]; c.bias2 = wt->down_b[s - 1];
                 ProfScope ps(st, 1, 2.0 * n * H * W * (double)C * (C * 9 + C / 2));
                 if ((rc = conv_common(c))) return rc;
             } else if ((rc = run(1, c)))
                 return rc;
             x = out;
-            if (b == 1) res.stage_off[s] = (size_t)((char*)out - ws);
+            if (last) res.stage_off[s] = (size_t)((char*)out - ws);
             ++block;
             res.last_stage = s;
             if (block == stop_after) return WSI_OK;
@@ -303,9 +326,11 @@ int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const ui
     TrunkPlan p;
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!wt || !workspace || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
+    const TrunkDepth d(wt);
+    if (!d.valid()) return WSI_EINVAL;
     if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
     TrunkResult res;
-    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace, 8,
+    int rc = trunk_run(wt, d, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace, d.total,
                        (hipStream_t)stream, p, res);
     if (rc) return rc;
     const char* last = (const char*)workspace + res.last_off;
@@ -324,11 +349,12 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
                           void* stream) {
     TrunkPlan p;
     const int cap = workspace_n > 0 ? workspace_n : n;
-    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || stop_after > 8 || n <= 0 || cap < n ||
-        trunk_plan(cap, h, w, wt->planes, p))
+    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p))
         return WSI_EINVAL;
+    const TrunkDepth d(wt);
+    if (!d.valid() || stop_after > d.total) return WSI_EINVAL;
     TrunkResult res;
-    int rc = trunk_run(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace,
+    int rc = trunk_run(wt, d, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace,
                        stop_after, (hipStream_t)stream, p, res);
     if (rc) return rc;
     const int stage = res.last_stage;
@@ -337,7 +363,7 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
 }
 
 // ------------------------------------------------------------------------------------ U-Net (dense 'seg' path)
-// smp-style decoder on the ResNet-18 trunk: five blocks of [nearest x2 upsample, concat skip, 2 x (3x3 conv + BN + ReLU)]
+// smp-style decoder on the BasicBlock trunk (any depth: the five encoder maps keep their channels): five blocks of [nearest x2 upsample, concat skip, 2 x (3x3 conv + BN + ReLU)]
 // at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the split-precision modes, 64 in
 // speed mode; the padding channels carry zero weights), 1x1 head.
 static const int kUnetSkipC[5] = {256, 128, 64, 64, 0};      // encoder maps x3, x2, x1, x0 (and none for the last block)
@@ -443,6 +469,8 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     if (trunk_plan(cap, h, w, wt->planes, p) || unet_plan(dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
     const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
     if (!src.valid()) return WSI_EINVAL;
+    const TrunkDepth d(wt);
+    if (!d.valid()) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
@@ -454,7 +482,7 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     const ConvRoutes& r = g_routes;
     const bool x0_fused = r.unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
                           r.stem_shared_weights;
-    int rc = trunk_run(wt, src, n, cap, h, w, workspace, 8, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr});
+    int rc = trunk_run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr});
     if (rc) return rc;
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
     // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines

@@ -67,11 +67,42 @@ def batch_sizes(n, cap, h=256, w=256):
     return [min(mb, n - i) for i in range(0, n, mb)]
 
 
-class TrunkEngine:
-    """ResNet-18 trunk (stem + layer1..4) of the reference ``resnets_shift.ResNet`` on HIP kernels,
-    with an optional Linear(512->K) head fused after the average pool (``fc0`` or ``Classifier``).
+def trunk_layers(state_dict):
+    """Blocks per stage of a BasicBlock ResNet state dict (reference key names): the count of ``layerL.B.conv1.weight`` keys, e.g.
+    [2, 2, 2, 2] for ResNet-18 and [3, 4, 6, 3] for ResNet-34.  ValueError for Bottleneck checkpoints (a ``conv3`` key), for block
+    numbers with gaps, for a stage without blocks and for more blocks than the C ABI carries (native.TRUNK_MAX_BLOCKS)."""
+    found = [set(), set(), set(), set()]
+    for key in state_dict:
+        parts = key.split('.')
+        if len(parts) < 4 or not parts[0].startswith('layer') or not parts[0][5:].isdigit() or not parts[1].isdigit():
+            continue
+        L = int(parts[0][5:])
+        if not 1 <= L <= 4:
+            raise ValueError('state dict key %r: a ResNet trunk has layer1 ... layer4' % key)
+        if parts[2] == 'conv3':
+            raise ValueError('state dict key %r belongs to a Bottleneck block (ResNet-50 and deeper): the HIP trunk runs BasicBlock '
+                             'ResNets (resnet18, resnet34, any [n1, n2, n3, n4] of two-conv blocks) only' % key)
+        if parts[2:] == ['conv1', 'weight']:
+            found[L - 1].add(int(parts[1]))
+    layers = []
+    for L, blocks in enumerate(found, start=1):
+        if not blocks:
+            raise ValueError('state dict has no layer%d.0.conv1.weight: not a ResNet trunk' % L)
+        if blocks != set(range(len(blocks))):
+            raise ValueError('state dict has gaps in the blocks of layer%d: found %s' % (L, sorted(blocks)))
+        layers.append(len(blocks))
+    if sum(layers) > native.TRUNK_MAX_BLOCKS:
+        raise ValueError('%s = %d residual blocks: the C ABI carries at most %d (include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS)'
+                         % (layers, sum(layers), native.TRUNK_MAX_BLOCKS))
+    return layers
 
-    state_dict: reference key names (conv1.weight, bn1.*, layerL.B.convK.weight, ...).
+
+class TrunkEngine:
+    """BasicBlock ResNet trunk (stem + layer1..4; ResNet-18, ResNet-34 or any other depth: `trunk_layers`) of the reference
+    ``resnets_shift.ResNet`` on HIP kernels, with an optional Linear(512->K) head fused after the average pool (``fc0`` or
+    ``Classifier``).
+
+    state_dict: reference key names (conv1.weight, bn1.*, layerL.B.convK.weight, ...); the depth is read from it (`.layers`).
     """
 
     def __init__(self, state_dict, device, planes=MX, head=None, max_batch=None,
@@ -95,6 +126,9 @@ class TrunkEngine:
         self.wt = native.WsiTrunkWeights()
         self.wt.planes = planes
         sd = state_dict
+        self.layers = trunk_layers(sd)
+        for L in range(4):
+            self.wt.blocks[L] = self.layers[L]
 
         def bn(prefix):
             return [_f32(sd, prefix + s) for s in ('.weight', '.bias', '.running_mean', '.running_var')]
@@ -136,10 +170,10 @@ class TrunkEngine:
             return dev(pk).data_ptr(), dev(bias).data_ptr()
 
         for L in range(1, 5):
-            for B in range(2):
+            for B in range(self.layers[L - 1]):
                 for K in (1, 2):
                     p = 'layer%d.%d' % (L, B)
-                    i = (L - 1) * 4 + B * 2 + (K - 1)
+                    i = 2 * (sum(self.layers[:L - 1]) + B) + (K - 1)      # block-major (include/wsi_hip.h wsi_trunk_weights)
                     self.wt.conv_w[i], self.wt.conv_b[i] = conv('%s.conv%d.weight' % (p, K), '%s.bn%d' % (p, K), 3)
             if L > 1:
                 p = 'layer%d.0.downsample' % L
@@ -210,7 +244,9 @@ class TrunkEngine:
         else:
             sp, pitch, sh, sw = None, 0, 0, 0
         if tap is not None:
-            stage = (0, 1, 1, 2, 2, 3, 3, 4, 4)[tap]
+            if not 0 <= tap <= sum(self.layers):
+                raise ValueError('tap must be 0 (pool) ... %d (the last block), got %r' % (sum(self.layers), tap))
+            stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 0 = pool, 1..4 = layer of block `tap`
             c = 64 << max(stage - 1, 0)
             hh = h >> (2 + max(stage - 1, 0))
             ww = w >> (2 + max(stage - 1, 0))

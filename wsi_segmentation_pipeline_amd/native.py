@@ -20,11 +20,16 @@ class NativeLibraryMissing(RuntimeError):
     pass
 
 
+TRUNK_MAX_BLOCKS = 36                    # include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS: residual blocks of one trunk, all stages together
+
+
 class WsiTrunkWeights(C.Structure):
+    """wsi_trunk_weights: `blocks` residual blocks per stage; layerL.B.convK at 2 * (sum(blocks[:L-1]) + B) + (K-1)."""
     _fields_ = [
         ('stem_w', C.c_void_p), ('stem_b', C.c_void_p),
         ('stem_w_u8', C.c_void_p), ('stem_b_u8', C.c_void_p), ('norm', C.c_float * 6),
-        ('conv_w', C.c_void_p * 16), ('conv_b', C.c_void_p * 16),
+        ('blocks', C.c_int * 4),
+        ('conv_w', C.c_void_p * (2 * TRUNK_MAX_BLOCKS)), ('conv_b', C.c_void_p * (2 * TRUNK_MAX_BLOCKS)),
         ('down_w', C.c_void_p * 3), ('down_b', C.c_void_p * 3),
         ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_k', C.c_int),
         ('planes', C.c_int),
@@ -143,7 +148,7 @@ def build(verbose=False):
     return LIB_PATH
 
 
-ABI_VERSION = 8                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
+ABI_VERSION = 9                          # include/wsi_hip.h WSI_HIP_ABI_VERSION (tests/test_capi_symbols.py compares the two)
 
 
 def load():

@@ -7,16 +7,26 @@ fetch), so the parity fixtures use seeded random weights with *randomised BatchN
 outputs need to be committed, not 179 MB of weights.
 
 Key names / shapes follow the reference ``resnets_shift.ResNet`` state dict
-(/root/reference/resnets_shift.py:122-150, 169-187): 130 keys.
+(/root/reference/resnets_shift.py:122-150, 169-187): 130 keys for ResNet-18 ([2, 2, 2, 2]), 226 for ResNet-34
+([3, 4, 6, 3]); ``resnet_key_shapes`` / ``make_resnet_state_dict`` take the block counts of any BasicBlock depth.
 """
 import numpy as np
 import torch
 
-_STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))   # (planes, stride of first block); 2 BasicBlocks each
+_STAGES = ((64, 1), (128, 2), (256, 2), (512, 2))   # (planes, stride of first block)
+RESNET18_LAYERS = (2, 2, 2, 2)                      # BasicBlocks per stage
+RESNET34_LAYERS = (3, 4, 6, 3)
 
 
 def resnet18_key_shapes(n_bag=16, include_aux_heads=True):
     """[(key, shape, kind)] in the reference's state-dict order."""
+    return resnet_key_shapes(RESNET18_LAYERS, n_bag, include_aux_heads)
+
+
+def resnet_key_shapes(layers, n_bag=16, include_aux_heads=True):
+    """[(key, shape, kind)] of ``ResNet(BasicBlock, layers)`` in the reference's state-dict order."""
+    if len(layers) != 4 or any(int(nb) < 1 for nb in layers):
+        raise ValueError('layers must be four positive block counts, got %r' % (layers,))
     out = []
 
     def bn(prefix, c):
@@ -30,7 +40,7 @@ def resnet18_key_shapes(n_bag=16, include_aux_heads=True):
     bn('bn1', 64)
     inpl = 64
     for li, (planes, stride) in enumerate(_STAGES, start=1):
-        for bi in range(2):
+        for bi in range(int(layers[li - 1])):
             p = 'layer%d.%d' % (li, bi)
             out.append((p + '.conv1.weight', (planes, inpl if bi == 0 else planes, 3, 3), 'conv'))
             bn(p + '.bn1', planes)
@@ -77,9 +87,15 @@ def _fill(rng, shape, kind):
 
 def make_resnet18_state_dict(seed, with_fc=True):
     """Seeded state dict; ``with_fc=False`` skips the 33.5M-parameter ``fc.0`` draw (keys absent)."""
+    return make_resnet_state_dict(seed, RESNET18_LAYERS, with_fc)
+
+
+def make_resnet_state_dict(seed, layers, with_fc=True):
+    """Seeded state dict of ``ResNet(BasicBlock, layers)``: one generator, drawn in state-dict order, so [2, 2, 2, 2] gives
+    make_resnet18_state_dict(seed) tensor for tensor; ``with_fc`` as there."""
     rng = np.random.Generator(np.random.PCG64(seed))
     sd = {}
-    for key, shape, kind in resnet18_key_shapes():
+    for key, shape, kind in resnet_key_shapes(layers):
         if not with_fc and key.startswith('fc.'):
             continue
         sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
@@ -161,8 +177,14 @@ def make_he_patches(seed, n, size=256):
 def make_unet_state_dict(seed, classes=4):
     """Seeded state dict of the U-Net 'seg' model (encoder.* = the ResNet-18 trunk keys of make_resnet18_state_dict(seed),
     decoder.* per wsi_segmentation_pipeline_amd.unet.decoder_key_shapes), randomised BN statistics as everywhere."""
+    return make_unet_resnet_state_dict(seed, RESNET18_LAYERS, classes)
+
+
+def make_unet_resnet_state_dict(seed, layers, classes=4):
+    """make_unet_state_dict with a BasicBlock encoder of any depth (encoder.* = make_resnet_state_dict(seed, layers) without its
+    heads); the decoder draw does not depend on the depth: the five encoder maps keep their channels."""
     from .unet import decoder_key_shapes
-    sd = {'encoder.' + k: v for k, v in make_resnet18_state_dict(seed, with_fc=False).items()
+    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
           if not k.startswith('fc')}
     rng = np.random.Generator(np.random.PCG64(seed + 5000))
     for key, shape, kind in decoder_key_shapes(classes):

@@ -6,8 +6,9 @@
 segmentation_models_pytorch is third-party, absent here and un-pinned in the reference, so the architecture
 and the state-dict key names are restated from its published 0.0.x source - **parity unpinned**; the numerical spec is
 oracle/unet_oracle.py (torch fp32 CPU) and the HIP path is held to it:
-  encoder  ResNet-18 (torchvision key names under ``encoder.``); forward returns [x4, x3, x2, x1, x0] (deepest first),
-           x0 = relu(bn1(conv1(x))) at half resolution
+  encoder  ResNet-18 or ResNet-34 (``encoder='resnet18' | 'resnet34'``; torchvision key names ``encoder.layerL.B.*``); forward
+           returns [x4, x3, x2, x1, x0] (deepest first): x1..x4 = the LAST block of layer1..4, x0 = relu(bn1(conv1(x))) at half
+           resolution.  Both depths give the same channels (512, 256, 128, 64, 64), so the decoder does not depend on the choice
   decoder  ``decoder.layer{1..5}.block.{0,1}.block.0.weight`` (3x3 conv, no bias) + ``.block.1.*`` (BatchNorm) + ReLU, each block
            preceded by nearest x2 upsampling and (blocks 1-4) concatenation of the next skip; channels 256/128/64/32/16;
            ``decoder.final_conv.{weight,bias}`` (1x1 to `classes`)
@@ -26,6 +27,13 @@ from .engine import BN_EPS, MX, PARITY, SPEED, TrunkEngine, _np_ptr, _ptr, _requ
 
 DEC_CH = (256, 128, 64, 32, 16)
 SKIP_CH = (256, 128, 64, 64, 0)
+ENCODER_LAYERS = {'resnet18': [2, 2, 2, 2], 'resnet34': [3, 4, 6, 3]}      # smp encoder names -> BasicBlocks per stage
+
+
+def encoder_layers(encoder):
+    if encoder not in ENCODER_LAYERS:
+        raise ValueError('encoder must be one of %s (BasicBlock ResNets), got %r' % (sorted(ENCODER_LAYERS), encoder))
+    return ENCODER_LAYERS[encoder]
 
 
 def _pad64(c):
@@ -60,14 +68,17 @@ def decoder_key_shapes(classes):
 
 
 class UNetEngine:
-    """ResNet-18 encoder (TrunkEngine) + smp-style decoder on HIP kernels.  state_dict: ``encoder.*`` + ``decoder.*`` keys."""
+    """BasicBlock ResNet encoder (TrunkEngine) + smp-style decoder on HIP kernels.  state_dict: ``encoder.*`` + ``decoder.*`` keys.
+    The encoder's depth is read from the state dict; `encoder` ('resnet18' | 'resnet34'), when given, must agree with it."""
 
-    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None):
+    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
         self._ws = {}
         self.lib = native.load()
         self.device = torch.device(device)
         enc_sd = {k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')}
         self.trunk = TrunkEngine(enc_sd, device, planes=planes)
+        if encoder is not None and self.trunk.layers != encoder_layers(encoder):
+            raise ValueError('state dict holds a %s encoder, not %s' % (self.trunk.layers, encoder))
         self.planes = planes
         self.classes = int(classes if classes is not None else state_dict['decoder.final_conv.weight'].shape[0])
         self.max_batch = max_batch
@@ -269,12 +280,12 @@ class UNetDecoder(nn.Module):
 
 
 class UNetEncoder(nn.Module):
-    """ResNet-18 trunk with the smp encoder surface: forward(x) -> [x4, x3, x2, x1, x0]; ``out_shapes``."""
+    """ResNet-18 / ResNet-34 trunk with the smp encoder surface: forward(x) -> [x4, x3, x2, x1, x0]; ``out_shapes``."""
 
-    def __init__(self, owner=None):
+    def __init__(self, owner=None, encoder='resnet18'):
         super().__init__()
         import resnets_shift
-        net = resnets_shift.resnet18(False)
+        net = resnets_shift.ResNet(resnets_shift.BasicBlock, encoder_layers(encoder))
         for name in ('conv1', 'bn1', 'relu', 'maxpool', 'layer1', 'layer2', 'layer3', 'layer4'):
             setattr(self, name, getattr(net, name))
         self.out_shapes = (512, 256, 128, 64, 64)
@@ -292,14 +303,15 @@ class UNetEncoder(nn.Module):
 
 
 class UNetSeg(nn.Module):
-    """Drop-in for ``smp.Unet('resnet18', classes=C, activation=None)`` as the reference uses it: ``model(x)`` -> (B,C,H,W)
-    logits; ``model.encoder`` / ``model.decoder`` callable separately; ``classifier`` / ``regressor`` heads attachable."""
+    """Drop-in for ``smp.Unet(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34' as the reference
+    uses it: ``model(x)`` -> (B,C,H,W) logits; ``model.encoder`` / ``model.decoder`` callable separately; ``classifier`` /
+    ``regressor`` heads attachable."""
 
-    def __init__(self, classes=4, precision='parity'):
+    def __init__(self, classes=4, precision='parity', encoder='resnet18'):
         super().__init__()
-        self.encoder = UNetEncoder(self)
+        self.encoder = UNetEncoder(self, encoder)
         self.decoder = UNetDecoder(classes, self)
-        self.classes, self.precision = classes, precision
+        self.classes, self.precision, self.encoder_name = classes, precision, encoder
         self._engine, self._engine_sig = None, None
 
     def hip_engine(self, device=None):
@@ -308,7 +320,7 @@ class UNetSeg(nn.Module):
             + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._engine is None or sig != self._engine_sig:
             self._engine = UNetEngine(self.state_dict(), device, planes={'parity': PARITY, 'mx': MX, 'speed': SPEED}[self.precision],
-                                      classes=self.classes)
+                                      classes=self.classes, encoder=self.encoder_name)
             self._engine_sig = sig
         return self._engine
 
