@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 9            /* wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
+#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -114,6 +114,13 @@ int wsi_conv3x3_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, co
                        void* stream);
 int wsi_conv1x1_bn(const void* in_pf, void* out_pf, const void* wpk, const float* bias, int n, int h_in, int w_in,
                    int cin, int cout, int stride, int planes, void* stream);
+/* The 1x1 convs of a Bottleneck block (resnets_shift.py:68-108: conv1 + bn1 + relu, conv3 + bn3 + residual + relu; :169-187 the
+ * downsample branch): out = act(bn(conv1x1(in)) (+ resid)).  Stride 1 in planes 1 / 2 with cin a multiple of 64 and cout a multiple of
+ * 128, both up to 2048, runs on the pointwise kernel (csrc/conv_pw.hip: LDS-DMA line ring, every input byte read once); every other
+ * call - stride 2, 64-channel outputs (measured faster there), WSI_CONV_MODE_PW_GATHER - takes the route of wsi_conv1x1_bn (the
+ * gather kernel; cin, cout multiples of 64; planes 3: -22).  wpk: wsi_prepack_conv with k = 1. */
+int wsi_conv1x1_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,
+                       int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes, void* stream);
 /* The two stride-2 convs of a downsampling BasicBlock in one pass over the input
  * (resnets_shift.py:41 conv1 with stride 2 + ReLU, and :173-177 the 1x1 stride-2 downsample, no ReLU):
  * out_conv_pf = relu(bn1(conv3x3_s2(x))), out_ds_pf = bn_d(conv1x1_s2(x)).  cout % 128 == 0. */
@@ -167,6 +174,7 @@ enum {
     WSI_CONV_MODE_S2_NT2 = 32768,           /* wide stride-2 kernel with 128, not 256, output channels per workgroup (mode 3; bit-identical) */
     WSI_CONV_MODE_UNET_CONCAT_PASS = 65536, /* U-Net decoder blocks write the upsampled + concatenated tensor before their first conv (bit-identical) */
     WSI_CONV_MODE_WIDE_NO_D8 = 131072,      /* wide stride-1 kernel keeps the 9-pixel slab pitch on 8 x 8 maps (r05 default: 8-pixel rows; bit-identical) */
+    WSI_CONV_MODE_PW_GATHER = 262144,       /* wsi_conv1x1_bn_act and the Bottleneck trunk run stride-1 1x1 convs on the gather kernel, not the pointwise kernel (bit-identical: both add the K lines in the same order) */
     WSI_CONV_MODE_L1_PERSISTENT = 1048576,  /* 64-channel layer 1 on the persistent producer-fed kernel (r05 study route: bit-identical, 30-45 % slower) */
     WSI_CONV_MODE_UNET_NO_TAIL = 2097152,   /* U-Net decoder's last block and head as three launches even with fused-tail weights (planes 2; equal to fp32 rounding) */
     WSI_CONV_MODE_UNET_TAIL_FORM1 = 4194304,/* the fused U-Net tail in its first form (every wave does both convs), not the specialised one */
@@ -240,11 +248,49 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
                           int n, int h, int w, void* workspace, int workspace_n, int stop_after, float* tap_out_nchw,
                           void* stream);
 
+/* ---- Bottleneck trunk: stem + layer1..4 of `ResNet(Bottleneck, layers)` (+ avgpool + Linear) ---------------------
+ * resnets_shift.py:68-108 (Bottleneck: conv1 1x1 inplanes -> planes + ReLU, conv2 3x3 planes -> planes at the block's stride + ReLU,
+ * conv3 1x1 planes -> 4 * planes, + residual, ReLU; the stride sits on conv2) and :169-187 (_make_layer: block 0 of every stage,
+ * layer 1 included, has a 1x1 downsample branch at the stage's stride).  Stage widths 256 / 512 / 1024 / 2048, mid widths 64 / 128 /
+ * 256 / 512, maps h/4 ... h/32.  blocks as in wsi_trunk_weights: 1 ... WSI_TRUNK_MAX_BLOCKS each and in all ([3,4,6,3] = ResNet-50,
+ * [3,4,23,3] = ResNet-101; ResNet-152 has 50: -22).  layerL.B.convK sits at 3 * (blocks[0] + ... + blocks[L-2] + B) + (K-1).
+ * planes 1 or 2 (3: -22, there is no pointwise kernel in that mode).  Every tensor between convs is an ordinary PF tensor. */
+typedef struct {
+    const void* stem_w;   const float* stem_b;
+    const void* stem_w_u8; const float* stem_b_u8;     /* wsi_prepack_stem_u8 (u8 slide input) or NULL */
+    float norm[6];                                     /* mean[3], std[3] of the transform folded into stem_w_u8 */
+    int blocks[4];                                     /* Bottleneck blocks of layer1..4 (resnets_shift.py:169-187) */
+    const void* conv_w[3 * WSI_TRUNK_MAX_BLOCKS]; const float* conv_b[3 * WSI_TRUNK_MAX_BLOCKS];   /* block-major: 3 * block + (K-1) */
+    const void* down_w[4];  const float* down_b[4];    /* layer1..4 .0.downsample (layer1's is stride 1, 64 -> 256) */
+    const float* head_w;  const float* head_b;  int head_k;  /* Linear(2048 -> head_k) or NULL */
+    int planes;                                        /* 1 or 2; 3 is -22 */
+} wsi_bneck_weights;
+/* resnets_shift.py:68-108, 169-187: bytes of the workspace of an (n, h, w) batch (0 for h or w no multiple of 32 or planes outside 1-2):
+ * the stem scratch, the pooled stem output, per stage two rotating buffers at the stage width and two at the mid width, and for
+ * stages 2-4 one more mid-width buffer at the previous stage's map size (conv1 of the strided block): 30.8 MB per 256 x 256 patch
+ * at planes 2. */
+size_t wsi_bneck_workspace_bytes(int n, int h, int w, int planes);
+/* resnets_shift.py:68-108, 169-187: zero-fills the workspace once before the first forward.  No layout tags are kept (every
+ * tensor is an ordinary 128-byte-line PF tensor), so there is nothing to release: wsi_trunk_workspace_release is not needed. */
+int wsi_bneck_workspace_init(void* workspace, int n, int h, int w, int planes, void* stream);
+/* resnets_shift.py:68-108, 169-187, 194-212: arguments as wsi_trunk_forward; feat_out [n][2048], fmap_out [n][2048][h/32][w/32]. */
+int wsi_bneck_forward(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide,
+                      long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                      int n, int h, int w, void* workspace, int workspace_n, float* feat_out, float* logits_out,
+                      float* fmap_out, void* stream);
+/* resnets_shift.py:68-108, 169-187: parity taps as wsi_trunk_forward_tap: stop_after 0 = stem + maxpool output, 1 ... total = the
+ * blocks in network order ([3,4,6,3]: 1..16). */
+int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide,
+                          long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
+                          int n, int h, int w, void* workspace, int workspace_n, int stop_after, float* tap_out_nchw,
+                          void* stream);
+
 /* ---- measurement hook -------------------------------------------------------------------------
  * wsi_prof_begin arms HIP-event timing (on the launch stream) of every conv / stem launch made by
  * wsi_trunk_forward; wsi_prof_end disarms, waits for the events and returns the number of records
  * copied: ms, kind (1 = 3x3 stride 1 of layers 2-4, 5 = 3x3 stride 1 of layer 1, 2 = 3x3 stride 2, 3 = 1x1 downsample,
- * 4 = stem+maxpool)
+ * 4 = stem+maxpool; the U-Net decoder adds 6-10; 11 = stride-1 1x1 conv of the Bottleneck trunk, whose 3x3 convs are kind 1
+ * and 2 and whose strided 1x1 downsamples are kind 3)
  * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch.  The records follow the depth table: per stage one entry
  * (kind 2, plus 3 on the gather route) and 2 * blocks - 1 stride-1 convs, layer 1 2 * blocks[0] of kind 5. */
 int wsi_prof_begin(int max_records);

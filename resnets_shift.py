@@ -1,10 +1,14 @@
-"""Drop-in for the reference's ``resnets_shift`` module: the bag-of-patches BasicBlock ResNet (ResNet-18, ResNet-34, ...).
+"""Drop-in for the reference's ``resnets_shift`` module: the bag-of-patches ResNet, BasicBlock (ResNet-18, ResNet-34, ...) and
+Bottleneck (ResNet-50, ResNet-101).
 
-Same public names, constructor arguments, state-dict keys (130 for ``resnet18()``, 226 for ``resnet34()``) and output convention
-as /root/reference/resnets_shift.py (ResNet :111-217, resnet18 :219-242), so existing checkpoints
-load and ``train_hr.py`` / ``scannet.py`` / ``slic.py``-style callers import it unchanged.  ``ResNet(BasicBlock, layers)`` takes
-any four positive block counts (the reference's ``__all__`` names ``resnet34`` but never defines it; its loader mirrors
-``resnet18``'s here); Bottleneck nets (ResNet-50 and deeper) are not implemented.
+Same public names, constructor arguments, state-dict keys (130 for ``resnet18()``, 226 for ``resnet34()``, 328 for ``resnet50()``,
+634 for ``resnet101()``) and output convention as /root/reference/resnets_shift.py (Bottleneck :68-108, ResNet :111-217,
+resnet18 :219-242), so existing checkpoints
+load and ``train_hr.py`` / ``scannet.py`` / ``slic.py``-style callers import it unchanged.  ``ResNet(BasicBlock, layers)`` and
+``ResNet(Bottleneck, layers)`` take any four positive block counts up to 36 in all (the reference's ``__all__`` names ``resnet34``,
+``resnet50`` and ``resnet101`` but defines none of them and keeps the Bottleneck constructors as comments; the loaders here mirror
+``resnet18``'s).  Bottleneck nets run in 'parity' or 'speed' precision ('auto' resolves to parity; there is no mx pointwise kernel),
+their features and heads are 2048 wide.  ResNeXt (groups, width_per_group), ResNet-152 and block classes of other modules are refused.
 In eval mode ``forward`` runs entirely on the gfx950 HIP kernels (libwsi_hip.so) and refuses CPU
 tensors - there is no CPU fallback.  In training mode (autograd needed, out of the inference hot
 path) the same parameters are evaluated with torch ops so the training scripts keep working.
@@ -13,13 +17,15 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-__all__ = ['ResNet', 'BasicBlock', 'resnet18', 'resnet34', 'model_urls', 'conv3x3', 'conv1x1']
+__all__ = ['ResNet', 'BasicBlock', 'Bottleneck', 'resnet18', 'resnet34', 'resnet50', 'resnet101', 'model_urls', 'conv3x3', 'conv1x1']
 
 HR_NUM_CNT_SAMPLES = 8       # reference utils/dataset_hr.py:14-15 (kept here to avoid a circular import)
 HR_NUM_PERIM_SAMPLES = 8
 
 model_urls = {'resnet18': 'https://download.pytorch.org/models/resnet18-5c106cde.pth',
-              'resnet34': 'https://download.pytorch.org/models/resnet34-333f7ec4.pth'}
+              'resnet34': 'https://download.pytorch.org/models/resnet34-333f7ec4.pth',
+              'resnet50': 'https://download.pytorch.org/models/resnet50-19c8e357.pth',
+              'resnet101': 'https://download.pytorch.org/models/resnet101-5d3b4d8f.pth'}
 MAX_BLOCKS = 36              # include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS (wsi_segmentation_pipeline_amd.native.TRUNK_MAX_BLOCKS)
 
 
@@ -52,6 +58,31 @@ class BasicBlock(nn.Module):
         return self.relu(y + (x if self.downsample is None else self.downsample(x)))
 
 
+class Bottleneck(nn.Module):
+    """Parameter container for one three-conv block (keys conv1/bn1/conv2/bn2/conv3/bn3/downsample.{0,1}; reference :68-108):
+    1x1 inplanes -> planes, 3x3 planes -> planes at the block's stride, 1x1 planes -> 4 * planes."""
+    expansion = 4
+
+    def __init__(self, inplanes, planes, stride=1, downsample=None, groups=1, base_width=64, norm_layer=None):
+        super().__init__()
+        if groups != 1 or base_width != 64:
+            raise NotImplementedError('Bottleneck with groups=%r, base_width=%r is a ResNeXt / wide block: the HIP path runs plain '
+                                      'Bottleneck nets (groups=1, width_per_group=64) only - ResNeXt is not supported' % (groups, base_width))
+        norm_layer = norm_layer or nn.BatchNorm2d
+        self.conv1, self.bn1 = conv1x1(inplanes, planes), norm_layer(planes)
+        self.conv2, self.bn2 = conv3x3(planes, planes, stride), norm_layer(planes)
+        self.conv3, self.bn3 = conv1x1(planes, planes * self.expansion), norm_layer(planes * self.expansion)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):          # torch-op path: training / autograd only
+        y = self.relu(self.bn1(self.conv1(x)))
+        y = self.relu(self.bn2(self.conv2(y)))
+        y = self.bn3(self.conv3(y))
+        return self.relu(y + (x if self.downsample is None else self.downsample(x)))
+
+
 class ResNet(nn.Module):
     """forward(xs: (B,P,3,H,W)) -> (per-patch logits (P*B,4) patch-major, ensemble logits (B,4))."""
 
@@ -60,15 +91,27 @@ class ResNet(nn.Module):
         super().__init__()
         supported = ('the HIP path implements BasicBlock ResNets: ResNet(BasicBlock, [n1, n2, n3, n4]) with four positive block counts '
                      'and at most %d blocks in all, e.g. resnet18() = [2, 2, 2, 2], resnet34() = [3, 4, 6, 3]' % MAX_BLOCKS)
-        if block is not BasicBlock:
-            raise NotImplementedError('%s; Bottleneck nets (ResNet-50 and deeper) are not implemented' % supported)
+        if block is not BasicBlock and block is not Bottleneck:
+            raise NotImplementedError("%s, and the Bottleneck class of this module (resnet50(), resnet101()); other modules' Bottleneck nets "
+                                      "(ResNet-50 and deeper) are not implemented" % supported)
         try:
             layers = [int(nb) for nb in layers]
             ok = len(layers) == 4 and all(nb >= 1 for nb in layers) and sum(layers) <= MAX_BLOCKS
         except (TypeError, ValueError):
             ok = False
+        if not ok and block is Bottleneck:
+            raise NotImplementedError('the HIP path implements Bottleneck ResNets of four positive block counts and at most %d blocks in '
+                                      'all, e.g. resnet50() = [3, 4, 6, 3], resnet101() = [3, 4, 23, 3] (ResNet-152 = [3, 8, 36, 3] has '
+                                      '50); got layers = %r' % (MAX_BLOCKS, layers))
         if not ok:
             raise NotImplementedError('%s; got layers = %r' % (supported, layers))
+        if block is Bottleneck:
+            if groups != 1 or width_per_group != 64:
+                raise NotImplementedError('groups=%r, width_per_group=%r is a ResNeXt / wide ResNet: not supported (plain Bottleneck nets only)'
+                                          % (groups, width_per_group))
+            if precision == 'mx':
+                raise NotImplementedError("precision='mx' is not implemented for Bottleneck nets: the pointwise-conv kernel has no mx "
+                                          "(planes 3) form; use 'parity', 'speed' or 'auto' (which resolves to parity)")
         self.layers = layers
         norm_layer = norm_layer or nn.BatchNorm2d
         self.inplanes, self.groups, self.base_width = 64, groups, width_per_group
@@ -95,11 +138,15 @@ class ResNet(nn.Module):
             for mod in self.modules():
                 if isinstance(mod, BasicBlock):
                     nn.init.zeros_(mod.bn2.weight)
+                elif isinstance(mod, Bottleneck):
+                    nn.init.zeros_(mod.bn3.weight)
         # 'auto' (default: mx unless a stratified two-mode probe of the batch / slide shows its logits more than 5e-4 from parity
         # mode: engine.AutoTrunkEngine), 'parity' (bf16x2 split, 3 MFMA passes, logit error ~3e-5), 'mx' (fp16 + MX-fp6 cross
         # terms, <= 5.4e-4 up to |logit| = 16, grows with the logit scale, ~1.5x faster) or 'speed' (single bf16, ~2e-2, outside
-        # the 1e-3 contract)
+        # the 1e-3 contract).  Bottleneck nets: 'parity' or 'speed'; 'auto' resolves to parity (no mx pointwise kernel; at 16 BasicBlocks mx
+        # already measured 1.13e-3)
         self.precision = precision
+        self.bottleneck = block is Bottleneck
         self._engine = None
         self._engine_sig = None
 
@@ -116,12 +163,20 @@ class ResNet(nn.Module):
     # ------------------------------------------------------------------ HIP engine plumbing
     def hip_engine(self, device=None):
         """TrunkEngine over the current parameters (rebuilt when they change or move)."""
-        from wsi_segmentation_pipeline_amd.engine import AutoTrunkEngine, TrunkEngine
+        from wsi_segmentation_pipeline_amd.engine import AutoTrunkEngine, BottleneckEngine, TrunkEngine
         device = torch.device(device) if device is not None else self.conv1.weight.device
         sig = (str(device), self.precision) + tuple((p.data_ptr(), p._version) for p in self.parameters()) \
             + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._engine is None or sig != self._engine_sig:
-            if self.precision == 'auto':
+            if self.bottleneck:
+                if self.precision not in ('auto', 'parity', 'speed'):
+                    raise NotImplementedError("Bottleneck nets run in 'parity', 'speed' or 'auto' precision, not %r" % (self.precision,))
+                self._engine = BottleneckEngine(self.state_dict(), device, planes=1 if self.precision == 'speed' else 2,
+                                                head=(self.fc0.weight, self.fc0.bias))
+                if self.precision == 'auto':
+                    self._engine.report = {'mode': 'parity', 'probe_error': None,
+                                           'reason': 'Bottleneck nets have no mx mode (no pointwise-conv kernel in planes 3): auto resolves to parity'}
+            elif self.precision == 'auto':
                 self._engine = AutoTrunkEngine(self.state_dict(), device, head=(self.fc0.weight, self.fc0.bias))
             else:
                 self._engine = TrunkEngine(self.state_dict(), device, planes={'parity': 2, 'mx': 3, 'speed': 1}[self.precision],
@@ -130,7 +185,7 @@ class ResNet(nn.Module):
         return self._engine
 
     def features(self, x):
-        """(N,3,H,W) normalised fp32 on the GPU -> (N,512,H/32,W/32) via the HIP trunk."""
+        """(N,3,H,W) normalised fp32 on the GPU -> (N,512,H/32,W/32) via the HIP trunk (Bottleneck nets: 2048 channels)."""
         return self.hip_engine(x.device).forward_f32(x, fmap=True)[2]
 
     def _forward_autograd(self, xs):
@@ -159,8 +214,8 @@ class ResNet(nn.Module):
         return singles, eng.linear(hidden, self.fc[2].weight, self.fc[2].bias)
 
 
-def _bag_resnet(name, layers, pretrained, kwargs):
-    model = ResNet(BasicBlock, layers, **kwargs)
+def _bag_resnet(name, layers, pretrained, kwargs, block=BasicBlock):
+    model = ResNet(block, layers, **kwargs)
     if pretrained:
         import torch.utils.model_zoo as model_zoo
         own = model.state_dict()
@@ -177,3 +232,13 @@ def resnet18(pretrained=False, **kwargs):
 def resnet34(pretrained=False, **kwargs):
     """ResNet-34 bag model ([3, 4, 6, 3] BasicBlocks); ``pretrained`` as in resnet18."""
     return _bag_resnet('resnet34', [3, 4, 6, 3], pretrained, kwargs)
+
+
+def resnet50(pretrained=False, **kwargs):
+    """ResNet-50 bag model ([3, 4, 6, 3] Bottleneck blocks, 2048 features; reference :227 as a commented alternative); ``pretrained`` as in resnet18."""
+    return _bag_resnet('resnet50', [3, 4, 6, 3], pretrained, kwargs, Bottleneck)
+
+
+def resnet101(pretrained=False, **kwargs):
+    """ResNet-101 bag model ([3, 4, 23, 3] Bottleneck blocks; reference :228); ``pretrained`` as in resnet18."""
+    return _bag_resnet('resnet101', [3, 4, 23, 3], pretrained, kwargs, Bottleneck)

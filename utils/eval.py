@@ -24,22 +24,25 @@ from wsi_segmentation_pipeline_amd import slide as S
 
 
 class TrunkEncoder(torch.nn.Module):
-    """``model.encoder`` surface over a resnets_shift.ResNet of any BasicBlock depth: encoder(x) -> [deepest feature map]
-    (the reference indexes ``encoding[0]`` for the 512-channel map, utils/eval.py:196-198).  The full five-map encoder of
-    the dense 'seg' model is wsi_segmentation_pipeline_amd.unet.UNetEncoder."""
+    """``model.encoder`` surface over a resnets_shift.ResNet of any BasicBlock depth or a Bottleneck net (resnet50(), resnet101()):
+    encoder(x) -> [deepest feature map] (the reference indexes ``encoding[0]`` for the 512-channel map, utils/eval.py:196-198;
+    2048 channels for a Bottleneck net).  ``out_shapes`` lists the channels of the net's five maps, deepest first, as smp's encoders
+    do; only the deepest is produced here.  The full five-map encoder of the dense 'seg' model is
+    wsi_segmentation_pipeline_amd.unet.UNetEncoder (BasicBlock nets only)."""
 
     def __init__(self, resnet):
         super().__init__()
         self.net = resnet
-        self.out_shapes = (512, 256, 128, 64, 64)
+        self.out_shapes = (2048, 1024, 512, 256, 64) if getattr(resnet, 'bottleneck', False) else (512, 256, 128, 64, 64)
 
     def forward(self, x):
         return [self.net.features(x)]
 
 
 class SlideClassifierModel(torch.nn.Module):
-    """First-party composition that predict_tumorbed(mode='cls') drives: BasicBlock ResNet trunk (resnets_shift.resnet18(),
-    resnet34() or any other depth) as ``encoder`` + models.models.Classifier / Regressor heads."""
+    """First-party composition that predict_tumorbed(mode='cls') drives: ResNet trunk (resnets_shift.resnet18(), resnet34() or any
+    other BasicBlock depth with 512-wide heads; resnet50() / resnet101() with 2048-wide heads) as ``encoder`` +
+    models.models.Classifier / Regressor heads."""
 
     def __init__(self, resnet, classifier, regressor=None):
         super().__init__()

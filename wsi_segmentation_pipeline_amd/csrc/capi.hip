@@ -98,6 +98,17 @@ int conv_common(const ConvCall& c) {
     return wsi_conv_dispatch(a, c.planes, cfg, st);
 }
 
+int conv1x1_common(const ConvCall& c) {
+    if (c.ksize != 1) return WSI_EINVAL;
+    if (!g_routes.pw_gather && c.stride == 1 && (c.planes == 1 || c.planes == 2) && c.cin > 0 && c.cout > 0 && c.h > 0 && c.w > 0) {
+        if (!c.in || !c.out || !c.wpk || !c.bias || c.in == c.out || c.resid == c.out || c.n <= 0 || (c.relu & ~1)) return WSI_EINVAL;
+        if (c.split_out || c.in2 || c.in_up || c.line_flags) return WSI_EINVAL;
+        const ConvArgs a = conv_args(c);               // a channel count outside the pointwise kernel's range -> gather kernel; a launch
+        if (wsi_pw_takes(a, c.planes)) return wsi_pw_dispatch(a, c.planes, (hipStream_t)c.stream);   // error is returned, not routed around
+    }
+    return conv_common(c);
+}
+
 // the ConvArgs of a stride-2 3x3 conv + ReLU with the 1x1 downsample branch as second output (out_ds_pf null: the 3x3 conv alone)
 static ConvArgs s2_ds_args(const void* in, void* out_conv_pf, void* out_ds_pf, const void* wpk3, const float* bias3, const void* wpk1,
                            const float* bias1, int n, int h_in, int w_in, int cin, int cout) {
@@ -270,6 +281,7 @@ int wsi_conv_set_mode(int mode) {
     r.unet_tail = (mode & WSI_CONV_MODE_UNET_NO_TAIL) ? 0 : 1;
     r.unet_tail_form = (mode & WSI_CONV_MODE_UNET_TAIL_FORM1) ? 1 : 2;
     r.unet_x0_fused = (mode & WSI_CONV_MODE_UNET_X0_UNFUSED) ? 0 : 1;
+    r.pw_gather = (mode & WSI_CONV_MODE_PW_GATHER) ? 1 : 0;
     return WSI_OK;
 }
 
@@ -277,6 +289,12 @@ int wsi_conv1x1_bn(const void* in_pf, void* out_pf, const void* wpk, const float
                    int cin, int cout, int stride, int planes, void* stream) {
     return conv_common({.in = in_pf, .out = out_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin, .cout = cout,
                         .stride = stride, .ksize = 1, .relu = 0, .planes = planes, .stream = stream});
+}
+
+int wsi_conv1x1_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, const void* wpk, const float* bias,
+                       int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes, void* stream) {
+    return conv1x1_common({.in = in_pf, .out = out_pf, .resid = resid_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin,
+                           .cout = cout, .stride = stride, .ksize = 1, .relu = relu, .planes = planes, .stream = stream});
 }
 
 int wsi_avgpool_fc(const void* in_pf, int n, int h, int w, int c, const float* fc_w, const float* fc_b, int k,

@@ -408,5 +408,6 @@ struct ConvRoutes {
     int unet_tail = 1;             // U-Net decoder: last block + head as one kernel (tail.hip)
     int unet_tail_form = 2;        // 2: unet_tail2_kernel, 1: the first form (unet_tail_kernel)
     int unet_x0_fused = 1;         // U-Net: the fused stem kernel stores the half-resolution skip x0 itself
+    int pw_gather = 0;             // stride-1 1x1 convs (wsi_conv1x1_bn_act, Bottleneck trunk) on the gather kernel, not conv_pw.hip
 };
 extern ConvRoutes g_routes;

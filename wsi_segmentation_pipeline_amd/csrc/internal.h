@@ -33,6 +33,9 @@ static inline int by_planes(int planes, F&& f) {
     if constexpr (MASK & P1) { if (planes == 1) return f(std::integral_constant<int, 1>{}); }
     return WSI_EINVAL;
 }
+// conv_pw.hip: stride-1 1x1 conv, planes 1 / 2; wsi_pw_takes: the shape is in the kernel's range (otherwise: the caller's other route)
+bool wsi_pw_takes(const ConvArgs& a, int planes);
+int wsi_pw_dispatch(const ConvArgs& a, int planes, hipStream_t st);
 // stem.hip
 int wsi_stem_dispatch(const StemArgs& a, int planes, hipStream_t st);
 int wsi_maxpool_dispatch(const float* in, void* out, int N, int Hc, int Wc, int planes, hipStream_t st);
@@ -133,6 +136,8 @@ struct ConvCall {
     long long plane96 = 0;           // bytes between the line planes of 96-byte-line tensors (0 = the tight distance for n images)
 };
 int conv_common(const ConvCall& c);
+// a 1x1 conv call (ksize 1): stride 1 in planes 1 / 2 on the pointwise kernel unless g_routes.pw_gather, everything else conv_common
+int conv1x1_common(const ConvCall& c);
 // the stride-2 block entry on a phase-split input (wsi_conv3x3s2_ds_fused_split), the phase images split_pixels apart (0 = the tight
 // distance for n images); out_ds_pf null: the 3x3 conv alone
 int s2_split_common(const void* in_split, void* out_conv_pf, void* out_ds_pf, const void* wpk3, const float* bias3, const void* wpk1,

@@ -362,6 +362,163 @@ int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, cons
                          stream);
 }
 
+// ------------------------------------------------------------------------------------ Bottleneck trunk (ResNet-50 / -101)
+// resnets_shift.py:68-108 (Bottleneck.forward) and :169-187 (_make_layer): per block conv1 1x1 + ReLU, conv2 3x3 at the block's
+// stride + ReLU, conv3 1x1 + residual + ReLU; block 0 of every stage (layer 1 too) takes downsample(x) as its residual.  Table-driven
+// like trunk_run; every tensor is an ordinary 128-byte-line PF tensor (no phase-split hand-over, no downsample fold, no 96-byte lines),
+// so a workspace needs no layout tag.  Stride-1 1x1 convs: conv1x1_common (the pointwise kernel, conv_pw.hip); the three stride-2 1x1
+// downsamples stay on the gather kernel; the stride-2 conv2 (cin == cout) takes conv_common's stride-2 slab route.
+struct BneckPlan {
+    size_t stem_scratch, pool;    // byte offsets: the stem's fp32 scratch; its pooled output (64 channels at h / 4)
+    size_t wide[4][2];            // [stage]: two rotating buffers at the stage width
+    size_t mid[4][2];             // [stage]: conv1 / conv2 outputs at the mid width and the stage's map size
+    size_t mid_in[4];             // stages 1-3: conv1 output of the strided block (mid width at the PREVIOUS stage's map size)
+    size_t total;
+    int sh[4], sw[4], sc[4], mc[4];
+};
+static int bneck_plan(int n, int h, int w, int planes, BneckPlan& p) {
+    if (n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    p.stem_scratch = take((size_t)n * (h / 2) * (w / 2) * 64 * sizeof(float));
+    p.pool = take(wsi_pf_bytes(n, h / 4, w / 4, 64, planes));
+    for (int s = 0; s < 4; ++s) {
+        p.sh[s] = h >> (2 + s); p.sw[s] = w >> (2 + s); p.sc[s] = 256 << s; p.mc[s] = 64 << s;
+        for (int b = 0; b < 2; ++b) p.wide[s][b] = take(wsi_pf_bytes(n, p.sh[s], p.sw[s], p.sc[s], planes));
+        for (int b = 0; b < 2; ++b) p.mid[s][b] = take(wsi_pf_bytes(n, p.sh[s], p.sw[s], p.mc[s], planes));
+        p.mid_in[s] = s ? take(wsi_pf_bytes(n, p.sh[s - 1], p.sw[s - 1], p.mc[s], planes)) : 0;
+    }
+    p.total = off;
+    return WSI_OK;
+}
+size_t wsi_bneck_workspace_bytes(int n, int h, int w, int planes) {
+    BneckPlan p;
+    return bneck_plan(n, h, w, planes, p) ? 0 : p.total;
+}
+int wsi_bneck_workspace_init(void* workspace, int n, int h, int w, int planes, void* stream) {
+    BneckPlan p;
+    if (!workspace || bneck_plan(n, h, w, planes, p)) return WSI_EINVAL;
+    return hipMemsetAsync((char*)workspace + p.pool, 0, p.total - p.pool, (hipStream_t)stream) == hipSuccess ? WSI_OK : WSI_EFAULT;
+}
+// the depth table of a Bottleneck trunk: as TrunkDepth, three convs per block
+struct BneckDepth {
+    int nb[4], blk0[4], total;
+    explicit BneckDepth(const wsi_bneck_weights* wt) : total(0) {
+        for (int s = 0; s < 4; ++s) {
+            nb[s] = wt->blocks[s];
+            blk0[s] = total;
+            total = nb[s] >= 1 && nb[s] <= WSI_TRUNK_MAX_BLOCKS && total >= 0 ? total + nb[s] : -1;
+        }
+    }
+    bool valid() const { return total >= 1 && total <= WSI_TRUNK_MAX_BLOCKS; }
+};
+// every pointer a run of `d` reads is there (checked before the first launch)
+static bool bneck_weights_ok(const wsi_bneck_weights* wt, const BneckDepth& d) {
+    if (!wt->stem_w || !wt->stem_b) return false;
+    for (int i = 0; i < 3 * d.total; ++i) if (!wt->conv_w[i] || !wt->conv_b[i]) return false;
+    for (int s = 0; s < 4; ++s) if (!wt->down_w[s] || !wt->down_b[s]) return false;
+    return true;
+}
+struct BneckResult { size_t last_off; int last_c, last_h, last_w; };
+// stem + blocks; stops after `stop_after` (0 = pool, 1..total = blocks in network order, >= total all).  `p`: the plan for cap >= n images.
+// ProfScope kinds: 4 = stem+maxpool, 11 = stride-1 1x1 (conv1, conv3, layer 1's downsample), 1 = 3x3 stride 1, 2 = 3x3 stride 2,
+// 3 = 1x1 stride-2 downsample
+static int bneck_run(const wsi_bneck_weights* wt, const BneckDepth& d, const TileSource& src, int n, int h, int w, void* workspace,
+                     int stop_after, hipStream_t st, const BneckPlan& p, BneckResult& res) {
+    char* ws = (char*)workspace;
+    const int planes = wt->planes;
+    int rc;
+    {
+        ProfScope ps(st, 4, 2.0 * n * (h / 2) * (w / 2) * 64.0 * 147.0);
+        rc = stem_run(src, wt->stem_w, wt->stem_b, wt->stem_w_u8, wt->stem_b_u8, wt->norm, n, h, w, (float*)(ws + p.stem_scratch), ws + p.pool,
+                      planes, st, 0);
+        if (rc) return rc;
+    }
+    res = {p.pool, 64, p.sh[0], p.sw[0]};
+    if (stop_after == 0) return WSI_OK;
+    auto run = [&](int kind, const ConvCall& c) {      // one conv launch = one profiler record
+        ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
+        return c.ksize == 1 ? conv1x1_common(c) : conv_common(c);
+    };
+    const void* x = ws + p.pool;
+    int xc = 64, block = 0;
+    for (int s = 0; s < 4; ++s) {
+        const int H = p.sh[s], W = p.sw[s], C = p.sc[s], M = p.mc[s];
+        int cur = 0;
+        for (int b = 0; b < d.nb[s]; ++b) {
+            const int wi = 3 * (d.blk0[s] + b);
+            const int stride = (b == 0 && s > 0) ? 2 : 1;                          // (the stride sits on conv2: resnets_shift.py:86)
+            const int Hi = H * stride, Wi = W * stride;                            // the block input's map
+            auto conv = [&](const void* in, void* out, const void* resid, int k, int hh, int ww, int ci, int co, int str, int ks, int relu) {
+                return ConvCall{.in = in, .out = out, .resid = resid, .wpk = wt->conv_w[wi + k], .bias = wt->conv_b[wi + k], .n = n, .h = hh, .w = ww,
+                                .cin = ci, .cout = co, .stride = str, .ksize = ks, .relu = relu, .planes = planes, .stream = st};
+            };
+            char* m1 = ws + (stride == 2 ? p.mid_in[s] : p.mid[s][0]);
+            char* m2 = ws + p.mid[s][1];
+            const void* resid = x;
+            char* out;
+            if (b == 0) {                                                          // downsample branch: 1x1 at the stage's stride, no ReLU
+                char* ds = ws + p.wide[s][1];
+                out = ws + p.wide[s][0];
+                ConvCall c = conv(x, ds, nullptr, 0, Hi, Wi, xc, C, stride, 1, 0);
+                c.wpk = wt->down_w[s]; c.bias = wt->down_b[s];
+                if ((rc = run(stride == 2 ? 3 : 11, c))) return rc;
+                resid = ds;
+                cur = 0;
+            } else {
+                out = ws + p.wide[s][cur ^ 1];
+                cur ^= 1;
+            }
+            if ((rc = run(11, conv(x, m1, nullptr, 0, Hi, Wi, xc, M, 1, 1, 1)))) return rc;
+            if ((rc = run(stride == 2 ? 2 : 1, conv(m1, m2, nullptr, 1, Hi, Wi, M, M, stride, 3, 1)))) return rc;
+            if ((rc = run(11, conv(m2, out, resid, 2, H, W, M, C, 1, 1, 1)))) return rc;
+            x = out; xc = C;
+            res = {(size_t)(out - ws), C, H, W};
+            if (++block == stop_after) return WSI_OK;
+        }
+    }
+    return WSI_OK;
+}
+
+int wsi_bneck_forward(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
+                      int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
+                      float* feat_out, float* logits_out, float* fmap_out, void* stream) {
+    BneckPlan p;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !workspace || n <= 0 || cap < n || bneck_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
+    const BneckDepth d(wt);
+    if (!d.valid() || !bneck_weights_ok(wt, d)) return WSI_EINVAL;
+    if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
+    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
+    if (!src.valid()) return WSI_EINVAL;
+    BneckResult res;
+    int rc = bneck_run(wt, d, src, n, h, w, workspace, d.total, (hipStream_t)stream, p, res);
+    if (rc) return rc;
+    const char* last = (const char*)workspace + res.last_off;
+    if (feat_out || logits_out) {
+        rc = wsi_avgpool_fc(last, n, p.sh[3], p.sw[3], 2048, wt->head_w, wt->head_b, wt->head_k, feat_out, logits_out, wt->planes, stream);
+        if (rc) return rc;
+    }
+    if (fmap_out) rc = wsi_pf_unpack(last, fmap_out, n, 2048, p.sh[3], p.sw[3], wt->planes, stream);
+    return rc;
+}
+
+int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
+                          int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
+                          int stop_after, float* tap_out_nchw, void* stream) {
+    BneckPlan p;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || n <= 0 || cap < n || bneck_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
+    const BneckDepth d(wt);
+    if (!d.valid() || stop_after > d.total || !bneck_weights_ok(wt, d)) return WSI_EINVAL;
+    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
+    if (!src.valid()) return WSI_EINVAL;
+    BneckResult res;
+    int rc = bneck_run(wt, d, src, n, h, w, workspace, stop_after, (hipStream_t)stream, p, res);
+    if (rc) return rc;
+    return wsi_pf_unpack((const char*)workspace + res.last_off, tap_out_nchw, n, res.last_c, res.last_h, res.last_w, wt->planes, stream);
+}
+
 // ------------------------------------------------------------------------------------ U-Net (dense 'seg' path)
 // smp-style decoder on the BasicBlock trunk (any depth: the five encoder maps keep their channels): five blocks of [nearest x2 upsample, concat skip, 2 x (3x3 conv + BN + ReLU)]
 // at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the split-precision modes, 64 in

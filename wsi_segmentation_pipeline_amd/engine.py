@@ -97,6 +97,42 @@ def trunk_layers(state_dict):
     return layers
 
 
+def trunk_arch(state_dict):
+    """('basic' | 'bottleneck', blocks per stage) of a ResNet state dict with the reference's key names.  A trunk whose every block has a
+    ``conv3`` key is a Bottleneck net (ResNet-50: [3, 4, 6, 3], ResNet-101: [3, 4, 23, 3]), one without any is a BasicBlock net
+    (`trunk_layers`); ValueError for a mixture, for gaps in the block numbers, for a stage without blocks and for more than
+    native.TRUNK_MAX_BLOCKS blocks (ResNet-152 has 50)."""
+    found = [set(), set(), set(), set()]
+    third = [set(), set(), set(), set()]
+    for key in state_dict:
+        parts = key.split('.')
+        if len(parts) < 4 or not parts[0].startswith('layer') or not parts[0][5:].isdigit() or not parts[1].isdigit():
+            continue
+        L = int(parts[0][5:])
+        if not 1 <= L <= 4:
+            raise ValueError('state dict key %r: a ResNet trunk has layer1 ... layer4' % key)
+        if parts[2:] == ['conv1', 'weight']:
+            found[L - 1].add(int(parts[1]))
+        if parts[2:] == ['conv3', 'weight']:
+            third[L - 1].add(int(parts[1]))
+    if not any(third):
+        return 'basic', trunk_layers(state_dict)
+    if third != found:
+        raise ValueError('state dict mixes blocks with and without conv3 (blocks with conv1: %s, with conv3: %s): neither a BasicBlock '
+                         'nor a Bottleneck ResNet' % ([sorted(b) for b in found], [sorted(b) for b in third]))
+    layers = []
+    for L, blocks in enumerate(found, start=1):
+        if not blocks:
+            raise ValueError('state dict has no layer%d.0.conv1.weight: not a ResNet trunk' % L)
+        if blocks != set(range(len(blocks))):
+            raise ValueError('state dict has gaps in the blocks of layer%d: found %s' % (L, sorted(blocks)))
+        layers.append(len(blocks))
+    if sum(layers) > native.TRUNK_MAX_BLOCKS:
+        raise ValueError('%s = %d Bottleneck blocks: the C ABI carries at most %d (include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS; ResNet-152 '
+                         'is not supported)' % (layers, sum(layers), native.TRUNK_MAX_BLOCKS))
+    return 'bottleneck', layers
+
+
 class TrunkEngine:
     """BasicBlock ResNet trunk (stem + layer1..4; ResNet-18, ResNet-34 or any other depth: `trunk_layers`) of the reference
     ``resnets_shift.ResNet`` on HIP kernels, with an optional Linear(512->K) head fused after the average pool (``fc0`` or
@@ -104,6 +140,11 @@ class TrunkEngine:
 
     state_dict: reference key names (conv1.weight, bn1.*, layerL.B.convK.weight, ...); the depth is read from it (`.layers`).
     """
+
+    FEAT_C = 512                                 # channels of the last stage (the head's input width)
+    WEIGHTS = native.WsiTrunkWeights             # the C struct and entry points of this architecture
+    ENTRY = 'wsi_trunk'
+    PLANES_OK = (1, 2, 3)
 
     def __init__(self, state_dict, device, planes=MX, head=None, max_batch=None,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), streams=2):
@@ -113,6 +154,9 @@ class TrunkEngine:
             raise RuntimeError('TrunkEngine needs a GPU device, got %s' % device)
         if planes not in (1, 2, 3):
             raise ValueError('planes must be 1 (speed), 2 (parity, fp16 pair) or 3 (mx, fp16 + MX-fp6)')
+        if planes not in self.PLANES_OK:
+            raise NotImplementedError('%s has no mx mode (planes 3): there is no pointwise-conv kernel in that mode; use parity (2) '
+                                      'or speed (1)' % type(self).__name__)
         self.planes = planes
         # images per trunk call; None = the tuned size (6200 patches of 256 x 256, scaled by patch area: what bench.py measures) as far
         # as the free HBM allows - the workspace is ~8.3 MB per 256 x 256 patch, one per stream slot (`_auto_cap`; r01-r04: 2000 and
@@ -123,10 +167,10 @@ class TrunkEngine:
         self._streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(streams)))] if streams > 1 else []
         self._keep = []                          # device tensors referenced by raw pointers
         self._ws = {}
-        self.wt = native.WsiTrunkWeights()
+        self.wt = self.WEIGHTS()
         self.wt.planes = planes
         sd = state_dict
-        self.layers = trunk_layers(sd)
+        self.layers = self._layers_of(sd)
         for L in range(4):
             self.wt.blocks[L] = self.layers[L]
 
@@ -169,6 +213,15 @@ class TrunkEngine:
                                                    cout, cin, k, planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_conv')
             return dev(pk).data_ptr(), dev(bias).data_ptr()
 
+        self._fill_convs(conv)
+        self.set_head(head)
+        self.lut = dev(normalize_lut(mean, std))
+
+    def _layers_of(self, sd):
+        return trunk_layers(sd)
+
+    def _fill_convs(self, conv):
+        """The conv tables of the C struct; conv(weight key, bn prefix, k) -> (packed weights, bias) device pointers."""
         for L in range(1, 5):
             for B in range(self.layers[L - 1]):
                 for K in (1, 2):
@@ -178,20 +231,23 @@ class TrunkEngine:
             if L > 1:
                 p = 'layer%d.0.downsample' % L
                 self.wt.down_w[L - 2], self.wt.down_b[L - 2] = conv(p + '.0.weight', p + '.1', 1)
-        self.set_head(head)
-        self.lut = dev(normalize_lut(mean, std))
+
+    def _tap_shape(self, tap, h, w):
+        """(channels, height, width) of tap `tap` (0 = pool, 1.. = blocks in network order)."""
+        stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 0 = pool, 1..4 = layer of block `tap`
+        return 64 << max(stage - 1, 0), h >> (2 + max(stage - 1, 0)), w >> (2 + max(stage - 1, 0))
 
     # ------------------------------------------------------------------ configuration
     def set_head(self, head):
-        """head = (weight (K,512), bias (K,)) tensors/arrays or None."""
+        """head = (weight (K, FEAT_C), bias (K,)) tensors/arrays or None (FEAT_C = 512; Bottleneck nets: 2048)."""
         if head is None:
             self.wt.head_w, self.wt.head_b, self.wt.head_k = None, None, 0
             self.head_k = 0
             return
         w = torch.as_tensor(head[0]).detach().to(self.device, torch.float32).contiguous()
         b = torch.as_tensor(head[1]).detach().to(self.device, torch.float32).contiguous()
-        if w.dim() != 2 or w.shape[1] != 512 or b.shape[0] != w.shape[0]:
-            raise ValueError('head must be Linear(512 -> K)')
+        if w.dim() != 2 or w.shape[1] != self.FEAT_C or b.shape[0] != w.shape[0]:
+            raise ValueError('head must be Linear(%d -> K)' % self.FEAT_C)
         self._head = (w, b)
         self.wt.head_w, self.wt.head_b, self.wt.head_k = w.data_ptr(), b.data_ptr(), int(w.shape[0])
         self.head_k = int(w.shape[0])
@@ -203,15 +259,15 @@ class TrunkEngine:
         key = (h, w, slot)
         ent = self._ws.get(key)
         if ent is None or ent[1] < n:
-            nbytes = self.lib.wsi_trunk_workspace_bytes(n, h, w, self.planes)
+            nbytes = getattr(self.lib, self.ENTRY + '_workspace_bytes')(n, h, w, self.planes)
             if nbytes == 0:
                 raise ValueError('unsupported patch shape %dx%d (need multiples of 32) or batch %d' % (h, w, n))
             self._drop_workspace(key)                       # a smaller plan of the same shape is released first
             if len(self._ws) >= 4 * max(1, len(self._streams)):   # keep the plan cache small
                 self._drop_workspace(next(iter(self._ws)))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            native.check(self.lib.wsi_trunk_workspace_init(_ptr(ws), n, h, w, self.planes, _stream()),
-                         'wsi_trunk_workspace_init')
+            native.check(getattr(self.lib, self.ENTRY + '_workspace_init')(_ptr(ws), n, h, w, self.planes, _stream()),
+                         self.ENTRY + '_workspace_init')
             ent = self._ws[key] = (ws, n)
         return ent
 
@@ -236,9 +292,9 @@ class TrunkEngine:
     def _run(self, n, h, w, in_f32, slide, tile_xy, want_feat, want_logits, want_fmap, tap=None, slot=0):
         ws, cap = self._workspace(n, h, w, slot)
         dev = self.device
-        feat = torch.empty((n, 512), dtype=torch.float32, device=dev) if want_feat else None
+        feat = torch.empty((n, self.FEAT_C), dtype=torch.float32, device=dev) if want_feat else None
         logits = torch.empty((n, self.head_k), dtype=torch.float32, device=dev) if want_logits else None
-        fmap = torch.empty((n, 512, h // 32, w // 32), dtype=torch.float32, device=dev) if want_fmap else None
+        fmap = torch.empty((n, self.FEAT_C, h // 32, w // 32), dtype=torch.float32, device=dev) if want_fmap else None
         if slide is not None:
             sp, pitch, sh, sw = _ptr(slide), slide.stride(0), slide.shape[0], slide.shape[1]
         else:
@@ -246,18 +302,15 @@ class TrunkEngine:
         if tap is not None:
             if not 0 <= tap <= sum(self.layers):
                 raise ValueError('tap must be 0 (pool) ... %d (the last block), got %r' % (sum(self.layers), tap))
-            stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 0 = pool, 1..4 = layer of block `tap`
-            c = 64 << max(stage - 1, 0)
-            hh = h >> (2 + max(stage - 1, 0))
-            ww = w >> (2 + max(stage - 1, 0))
+            c, hh, ww = self._tap_shape(tap, h, w)
             out = torch.empty((n, c, hh, ww), dtype=torch.float32, device=dev)
-            native.check(self.lib.wsi_trunk_forward_tap(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
-                                                        _ptr(self.lut), n, h, w, _ptr(ws), cap, tap, _ptr(out), _stream()),
-                         'wsi_trunk_forward_tap')
+            native.check(getattr(self.lib, self.ENTRY + '_forward_tap')(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
+                                                                        _ptr(self.lut), n, h, w, _ptr(ws), cap, tap, _ptr(out), _stream()),
+                         self.ENTRY + '_forward_tap')
             return out
-        native.check(self.lib.wsi_trunk_forward(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
-                                                _ptr(self.lut), n, h, w, _ptr(ws), cap, _ptr(feat), _ptr(logits), _ptr(fmap),
-                                                _stream()), 'wsi_trunk_forward')
+        native.check(getattr(self.lib, self.ENTRY + '_forward')(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
+                                                                _ptr(self.lut), n, h, w, _ptr(ws), cap, _ptr(feat), _ptr(logits), _ptr(fmap),
+                                                                _stream()), self.ENTRY + '_forward')
         return feat, logits, fmap
 
     def forward_f32(self, x, feat=False, logits=False, fmap=False, tap=None):
@@ -296,7 +349,7 @@ class TrunkEngine:
         """Default images per trunk call: the tuned batch scaled by patch area, limited so that the workspaces of all stream slots
         stay inside 60 % of the memory that is free now (plus what this engine already holds)."""
         want = max(1, int(self.TUNED_BATCH_256 * 65536 // max(h * w, 1)))
-        per = self.lib.wsi_trunk_workspace_bytes(64, h, w, self.planes) / 64.0
+        per = getattr(self.lib, self.ENTRY + '_workspace_bytes')(64, h, w, self.planes) / 64.0
         if per <= 0:
             return want
         try:                                                 # free = what the driver reports + what torch's caching allocator holds unused
@@ -345,6 +398,42 @@ class TrunkEngine:
         native.check(self.lib.wsi_linear(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), x.shape[0], x.shape[1],
                                          weight.shape[0], int(relu), _stream()), 'wsi_linear')
         return y
+
+
+class BottleneckEngine(TrunkEngine):
+    """Bottleneck ResNet trunk (ResNet-50, ResNet-101, any [n1, n2, n3, n4] of three-conv blocks up to native.TRUNK_MAX_BLOCKS in all) of
+    the reference ``resnets_shift.ResNet(Bottleneck, layers)`` on HIP kernels: wsi_bneck_forward, whose 1x1 convs run on the
+    pointwise kernel.  Same surface as TrunkEngine; features and heads are 2048 wide; planes 2 (parity) or 1 (speed) - mx is refused.
+    `_auto_cap` sizes the batch from wsi_bneck_workspace_bytes (30.8 MB per 256 x 256 patch in parity mode)."""
+    FEAT_C = 2048
+    WEIGHTS = native.WsiBneckWeights
+    ENTRY = 'wsi_bneck'
+    PLANES_OK = (1, 2)
+
+    def _layers_of(self, sd):
+        arch, layers = trunk_arch(sd)
+        if arch != 'bottleneck':
+            raise ValueError('BottleneckEngine needs a Bottleneck state dict (layerL.B.conv3 keys); this one is a BasicBlock net: use TrunkEngine')
+        return layers
+
+    def _fill_convs(self, conv):
+        for L in range(1, 5):
+            for B in range(self.layers[L - 1]):
+                p = 'layer%d.%d' % (L, B)
+                for K in (1, 2, 3):
+                    i = 3 * (sum(self.layers[:L - 1]) + B) + (K - 1)      # block-major (include/wsi_hip.h wsi_bneck_weights)
+                    self.wt.conv_w[i], self.wt.conv_b[i] = conv('%s.conv%d.weight' % (p, K), '%s.bn%d' % (p, K), 3 if K == 2 else 1)
+            p = 'layer%d.0.downsample' % L
+            self.wt.down_w[L - 1], self.wt.down_b[L - 1] = conv(p + '.0.weight', p + '.1', 1)
+
+    def _tap_shape(self, tap, h, w):
+        if tap == 0:
+            return 64, h >> 2, w >> 2
+        stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 1..4 = layer of block `tap`
+        return 256 << (stage - 1), h >> (1 + stage), w >> (1 + stage)
+
+    def _drop_workspace(self, key):
+        self._ws.pop(key, None)                             # (the Bottleneck trunk keeps no layout tags: nothing to release)
 
 
 class AutoTrunkEngine:
@@ -572,6 +661,20 @@ def prepack_conv(weight, bn, planes, device):
     native.check(lib.wsi_prepack_conv(_np_ptr(w), *args, BN_EPS, cout, cin, k, planes, _np_ptr(pk), _np_ptr(bias)),
                  'wsi_prepack_conv')
     return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
+
+
+def conv1x1_bn_act(x_pf, n, h, w, cin, cout, wpk, bias, stride=1, resid_pf=None, relu=True, planes=2, out=None, check=True):
+    """wsi_conv1x1_bn_act (the Bottleneck 1x1 convs: pointwise kernel at stride 1 unless ConvMode.PW_GATHER) into `out` (a zeroed PF
+    buffer is made when None).  check=False returns (out, return code) instead of raising."""
+    lib = native.load()
+    if out is None:
+        out = pf_zeros(n, cout, h // stride, w // stride, planes, x_pf.device)
+    rc = lib.wsi_conv1x1_bn_act(_ptr(x_pf), _ptr(out), _ptr(resid_pf), _ptr(wpk), _ptr(bias), n, h, w, cin, cout, stride, int(relu), planes,
+                                _stream())
+    if not check:
+        return out, rc
+    native.check(rc, 'wsi_conv1x1_bn_act')
+    return out
 
 
 def conv_bn_act(x_pf, n, h, w, cin, cout, wpk, bias, stride=1, ksize=3, resid_pf=None, relu=True, planes=2):

@@ -36,6 +36,19 @@ class WsiTrunkWeights(C.Structure):
     ]
 
 
+class WsiBneckWeights(C.Structure):
+    """wsi_bneck_weights: `blocks` Bottleneck blocks per stage; layerL.B.convK at 3 * (sum(blocks[:L-1]) + B) + (K-1)."""
+    _fields_ = [
+        ('stem_w', C.c_void_p), ('stem_b', C.c_void_p),
+        ('stem_w_u8', C.c_void_p), ('stem_b_u8', C.c_void_p), ('norm', C.c_float * 6),
+        ('blocks', C.c_int * 4),
+        ('conv_w', C.c_void_p * (3 * TRUNK_MAX_BLOCKS)), ('conv_b', C.c_void_p * (3 * TRUNK_MAX_BLOCKS)),
+        ('down_w', C.c_void_p * 4), ('down_b', C.c_void_p * 4),
+        ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_k', C.c_int),
+        ('planes', C.c_int),
+    ]
+
+
 class WsiUnetDecoderWeights(C.Structure):
     _fields_ = [
         ('conv_w', C.c_void_p * 10), ('conv_b', C.c_void_p * 10), ('cin', C.c_int * 10), ('cout', C.c_int * 10),
@@ -72,6 +85,7 @@ SIGNATURES = {
     'wsi_conv3x3s2_ds_fused_split': (_i, [_vp] * 7 + [_i] * 6 + [_vp]),
     'wsi_conv_set_mode': (_i, [_i]),
     'wsi_conv1x1_bn': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    'wsi_conv1x1_bn_act': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     'wsi_avgpool_fc': (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     'wsi_linear': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     'wsi_pf_pack': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
@@ -82,6 +96,10 @@ SIGNATURES = {
     'wsi_trunk_forward': (_i, [C.POINTER(WsiTrunkWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     'wsi_trunk_forward_tap': (_i, [C.POINTER(WsiTrunkWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'wsi_trunk_set_chunks': (_i, [_i, _i]),
+    'wsi_bneck_workspace_bytes': (_sz, [_i, _i, _i, _i]),
+    'wsi_bneck_workspace_init': (_i, [_vp, _i, _i, _i, _i, _vp]),
+    'wsi_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    'wsi_bneck_forward_tap': (_i, [C.POINTER(WsiBneckWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     'wsi_prof_begin': (_i, [_i]),
     'wsi_prof_end': (_i, [_vp, _vp, _vp, _i]),
     'wsi_tile_gather': (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _i, _i, _i, _vp]),
@@ -189,6 +207,7 @@ class ConvMode(enum.IntFlag):
     S2_NT2 = 32768
     UNET_CONCAT_PASS = 65536
     WIDE_NO_D8 = 131072
+    PW_GATHER = 262144
     L1_PERSISTENT = 1048576
     UNET_NO_TAIL = 2097152
     UNET_TAIL_FORM1 = 4194304

@@ -65,6 +65,76 @@ def resnet_key_shapes(layers, n_bag=16, include_aux_heads=True):
     return out
 
 
+RESNET50_LAYERS = (3, 4, 6, 3)                      # Bottleneck blocks per stage
+RESNET101_LAYERS = (3, 4, 23, 3)
+
+
+def bottleneck_key_shapes(layers, n_bag=16, include_aux_heads=True):
+    """[(key, shape, kind)] of ``ResNet(Bottleneck, layers)`` in the reference's state-dict order (resnets_shift.py:68-108, 169-187):
+    328 keys for [3, 4, 6, 3].  Every stage's block 0 has a downsample branch (layer 1's is 64 -> 256 at stride 1)."""
+    if len(layers) != 4 or any(int(nb) < 1 for nb in layers):
+        raise ValueError('layers must be four positive block counts, got %r' % (layers,))
+    out = []
+
+    def bn(prefix, c):
+        out.append((prefix + '.weight', (c,), 'bn_w'))
+        out.append((prefix + '.bias', (c,), 'bn_b'))
+        out.append((prefix + '.running_mean', (c,), 'bn_m'))
+        out.append((prefix + '.running_var', (c,), 'bn_v'))
+        out.append((prefix + '.num_batches_tracked', (), 'bn_n'))
+
+    out.append(('conv1.weight', (64, 3, 7, 7), 'conv'))
+    bn('bn1', 64)
+    inpl = 64
+    for li, (planes, _stride) in enumerate(_STAGES, start=1):
+        for bi in range(int(layers[li - 1])):
+            p = 'layer%d.%d' % (li, bi)
+            out.append((p + '.conv1.weight', (planes, inpl, 1, 1), 'conv'))
+            bn(p + '.bn1', planes)
+            out.append((p + '.conv2.weight', (planes, planes, 3, 3), 'conv'))
+            bn(p + '.bn2', planes)
+            out.append((p + '.conv3.weight', (4 * planes, planes, 1, 1), 'conv'))
+            bn(p + '.bn3', 4 * planes)
+            if bi == 0:
+                out.append((p + '.downsample.0.weight', (4 * planes, inpl, 1, 1), 'conv'))
+                bn(p + '.downsample.1', 4 * planes)
+            inpl = 4 * planes
+    n = 2048 * n_bag
+    out.append(('fc.0.weight', (n // 2, n), 'lin_w'))
+    out.append(('fc.0.bias', (n // 2,), 'lin_b'))
+    out.append(('fc.2.weight', (4, n // 2), 'lin_w'))
+    out.append(('fc.2.bias', (4,), 'lin_b'))
+    out.append(('fc0.weight', (4, 2048), 'lin_w'))
+    out.append(('fc0.bias', (4,), 'lin_b'))
+    if include_aux_heads:
+        out.append(('fc1.0.weight', (16, 2048), 'lin_w'))
+        out.append(('fc1.0.bias', (16,), 'lin_b'))
+        out.append(('fc2.0.weight', (4, 16 * n_bag), 'lin_w'))
+        out.append(('fc2.0.bias', (4,), 'lin_b'))
+    return out
+
+
+def make_bottleneck_state_dict(seed, layers, with_fc=True, head_scales=None):
+    """Seeded state dict of ``ResNet(Bottleneck, layers)``: one generator, drawn in state-dict order (so ``with_fc=False`` changes what
+    the keys after ``fc.*`` get - as in make_resnet_state_dict).  At expansion 4 ``fc.0`` is 32768 x 16384 (2.1 GB in fp32, ~10 s):
+    only end-to-end bag tests build it.  head_scales = (s0, s): ``fc0.{weight,bias}`` are multiplied by s0 and ``fc.2.{weight,bias}``
+    by s - the powers of two tools/gen_golden_resnet50.py records to bring the logits into the range the contract is stated for."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    sd = {}
+    for key, shape, kind in bottleneck_key_shapes(layers):
+        if not with_fc and key.startswith('fc.'):
+            continue
+        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
+    if head_scales is not None:
+        s0, s2 = (float(v) for v in head_scales)
+        for key in ('fc0.weight', 'fc0.bias'):
+            sd[key] = sd[key] * s0
+        for key in ('fc.2.weight', 'fc.2.bias'):
+            if key in sd:
+                sd[key] = sd[key] * s2
+    return sd
+
+
 def _fill(rng, shape, kind):
     if kind == 'conv':          # kaiming-normal, fan_out, relu gain (resnets_shift.py:154)
         fan_out = shape[0] * shape[2] * shape[3]
