@@ -209,7 +209,12 @@ int wsi_pf_unpack(const void* in_pf, float* out_nchw, int n, int c, int h, int w
  * [3,4,6,3] = ResNet-34); anything else is -22 before any launch.  Convs are indexed block-major: layerL.B.convK sits at
  *   2 * (blocks[0] + ... + blocks[L-2] + B) + (K-1)
  * which for [2,2,2,2] is (L-1)*4 + B*2 + (K-1).  Channel counts (64/128/256/512) and map sizes do not depend on the depth, and
- * neither does the workspace: three rotating buffers per stage carry any number of blocks. */
+ * neither does the workspace: three rotating buffers per stage carry any number of blocks.
+ * What is checked before any launch - and before the workspace is touched at all (no memset, no layout tag rewritten) - is the same
+ * for every entry that runs a net (wsi_trunk_forward, wsi_trunk_forward_tap, wsi_unet_forward, wsi_bneck_forward,
+ * wsi_bneck_forward_tap): the depth table; the input source (in_f32, or slide with tile_xy and lut); stem_w and stem_b; conv_w[i] and
+ * conv_b[i] for every i below (convs per block) * (blocks in all), whatever stop_after says; every down_w / down_b pair of the struct.
+ * A NULL among them is -22 and nothing has run.  stem_w_u8 / stem_b_u8 may be NULL; head_w / head_b only matter with logits_out. */
 #define WSI_TRUNK_MAX_BLOCKS 36
 typedef struct {
     const void* stem_w;   const float* stem_b;
@@ -271,9 +276,11 @@ typedef struct {
  * at planes 2. */
 size_t wsi_bneck_workspace_bytes(int n, int h, int w, int planes);
 /* resnets_shift.py:68-108, 169-187: zero-fills the workspace once before the first forward.  No layout tags are kept (every
- * tensor is an ordinary 128-byte-line PF tensor), so there is nothing to release: wsi_trunk_workspace_release is not needed. */
+ * tensor is an ordinary 128-byte-line PF tensor), so there is nothing to release: wsi_trunk_workspace_release is not needed
+ * (and harmless: it returns 0 for an address it has no tag of). */
 int wsi_bneck_workspace_init(void* workspace, int n, int h, int w, int planes, void* stream);
-/* resnets_shift.py:68-108, 169-187, 194-212: arguments as wsi_trunk_forward; feat_out [n][2048], fmap_out [n][2048][h/32][w/32]. */
+/* resnets_shift.py:68-108, 169-187, 194-212: arguments and validation as wsi_trunk_forward (-22 before any launch, see
+ * wsi_trunk_weights); feat_out [n][2048], fmap_out [n][2048][h/32][w/32]. */
 int wsi_bneck_forward(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide,
                       long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
                       int n, int h, int w, void* workspace, int workspace_n, float* feat_out, float* logits_out,

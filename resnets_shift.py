@@ -162,25 +162,13 @@ class ResNet(nn.Module):
 
     # ------------------------------------------------------------------ HIP engine plumbing
     def hip_engine(self, device=None):
-        """TrunkEngine over the current parameters (rebuilt when they change or move)."""
-        from wsi_segmentation_pipeline_amd.engine import AutoTrunkEngine, BottleneckEngine, TrunkEngine
+        """The HIP engine (engine.trunk_engine) over the current parameters, rebuilt when they change or move."""
+        from wsi_segmentation_pipeline_amd.engine import trunk_engine
         device = torch.device(device) if device is not None else self.conv1.weight.device
         sig = (str(device), self.precision) + tuple((p.data_ptr(), p._version) for p in self.parameters()) \
             + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._engine is None or sig != self._engine_sig:
-            if self.bottleneck:
-                if self.precision not in ('auto', 'parity', 'speed'):
-                    raise NotImplementedError("Bottleneck nets run in 'parity', 'speed' or 'auto' precision, not %r" % (self.precision,))
-                self._engine = BottleneckEngine(self.state_dict(), device, planes=1 if self.precision == 'speed' else 2,
-                                                head=(self.fc0.weight, self.fc0.bias))
-                if self.precision == 'auto':
-                    self._engine.report = {'mode': 'parity', 'probe_error': None,
-                                           'reason': 'Bottleneck nets have no mx mode (no pointwise-conv kernel in planes 3): auto resolves to parity'}
-            elif self.precision == 'auto':
-                self._engine = AutoTrunkEngine(self.state_dict(), device, head=(self.fc0.weight, self.fc0.bias))
-            else:
-                self._engine = TrunkEngine(self.state_dict(), device, planes={'parity': 2, 'mx': 3, 'speed': 1}[self.precision],
-                                           head=(self.fc0.weight, self.fc0.bias))
+            self._engine = trunk_engine(self.state_dict(), device, self.precision, head=(self.fc0.weight, self.fc0.bias))
             self._engine_sig = sig
         return self._engine
 

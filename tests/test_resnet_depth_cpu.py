@@ -177,7 +177,11 @@ def test_unet_module_surface_takes_the_encoder_name():
 
 def test_abi_9_and_depth_table_validation():
     """The library reports ABI 9 and the struct mirror agrees with the header; a trunk call whose depth table is out of range is
-    refused by argument validation (-22) - before any device work, so this runs without a GPU (no pointer is ever followed)."""
+    refused by argument validation (-22) - before any device work, so this runs without a GPU (no pointer is ever followed).
+    So is one with a valid table that lacks a pointer the run would read (a conv, a downsample bias, the stem bias) or an input
+    source: wsi_trunk_forward, wsi_trunk_forward_tap and wsi_unet_forward return -22 before the workspace's layout tag is rewritten and
+    before any memset or launch.  (Before the entries shared one rule, these calls got as far as hipMemsetAsync on the fake
+    workspace: that part of the test is not meant to be run against older libraries.)"""
     if not os.path.exists(native.LIB_PATH):
         native.build()
     lib = native.load()
@@ -205,3 +209,35 @@ def test_abi_9_and_depth_table_validation():
         wt.blocks[i] = R34[i]
     assert lib.wsi_trunk_forward_tap(C.byref(wt), fake, None, 0, 0, 0, None, None, 1, 64, 64, fake, 1, 17, fake, None) == -22
     assert lib.wsi_trunk_forward_tap(C.byref(wt), fake, None, 0, 0, 0, None, None, 1, 64, 64, fake, 1, -1, fake, None) == -22
+    # a valid table, but a pointer the run would read is missing, or the input source: -22 before the workspace is touched
+    for i in range(2 * native.TRUNK_MAX_BLOCKS):
+        wt.conv_w[i] = wt.conv_b[i] = 4096
+    for i in range(3):
+        wt.down_w[i] = wt.down_b[i] = 4096
+    dw = native.WsiUnetDecoderWeights()
+    for i, (cin, cout) in enumerate(((768, 256), (256, 256), (384, 128), (128, 128), (192, 64), (64, 64), (128, 32), (32, 32), (32, 32), (32, 32))):
+        dw.conv_w[i] = dw.conv_b[i] = 4096
+        dw.cin[i], dw.cout[i] = cin, cout
+    dw.head_w = dw.head_b = 4096
+    dw.head_cin, dw.classes = 16, 4
+    assert lib.wsi_unet_workspace_bytes(C.byref(dw), 1, 64, 64, 2) > 0                     # (the decoder table itself is accepted)
+
+    def calls(src=fake):
+        return (lib.wsi_trunk_forward(C.byref(wt), src, None, 0, 0, 0, None, None, 1, 64, 64, fake, 1, fake, None, None, None),
+                lib.wsi_trunk_forward_tap(C.byref(wt), src, None, 0, 0, 0, None, None, 1, 64, 64, fake, 1, 3, fake, None),
+                lib.wsi_unet_forward(C.byref(wt), C.byref(dw), src, None, 0, 0, 0, None, None, 1, 64, 64, fake, 1, fake, None, None))
+
+    def without(table, i):
+        keep, table[i] = table[i], None
+        try:
+            return calls()
+        finally:
+            table[i] = keep
+    assert without(wt.conv_w, 2 * 16 - 1) == (-22, -22, -22)
+    assert without(wt.conv_b, 0) == (-22, -22, -22)
+    assert without(wt.down_b, 2) == (-22, -22, -22)
+    wt.stem_b = None
+    assert calls() == (-22, -22, -22)
+    wt.stem_b = 4096
+    assert calls(src=None) == (-22, -22, -22)                                              # neither in_f32 nor slide
+    assert lib.wsi_trunk_forward(C.byref(wt), None, fake, 0, 64, 64, None, fake, 1, 64, 64, fake, 1, fake, None, None, None) == -22  # a slide without tile corners

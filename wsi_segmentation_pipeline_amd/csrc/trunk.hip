@@ -1,13 +1,13 @@
 // The model-level entries of libwsi_hip.so (include/wsi_hip.h): the profiler, the trunk workspace and its layout tags, the trunk
-// launch sequence (wsi_trunk_forward, wsi_trunk_forward_tap) and the U-Net host sequence.  No device allocation, no
-// synchronisation, no exceptions.
+// launch sequences of both architectures (trunk_run: BasicBlock, bneck_run: Bottleneck), the four forward entries over them and the
+// U-Net host sequence.  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "../../include/wsi_hip.h"
+#include <iterator>
 #include <mutex>
 #include <unordered_map>
 
-extern "C" {
-
+// (every exported function here is declared in wsi_hip.h, whose extern "C" its definition inherits)
 // ------------------------------------------------------------------------------------ profiler
 // Optional HIP-event timing of every conv launch made by wsi_trunk_forward, on the stream the
 // kernels run on (bench.py's roofline leg).  Off by default; never active inside graph capture.
@@ -42,7 +42,7 @@ int wsi_prof_end(float* ms_out, int* kind_out, double* flops_out, int cap) {
 }
 
 // One record: an event on `st` when the scope opens and one when it closes, so a scope holds exactly the launch it times
-// (an early `return rc` inside it closes first).  Kinds and FLOP conventions: trunk_run, unet_decoder_run.
+// (an early `return rc` inside it closes first).  Kinds and FLOP conventions: trunk_run, bneck_run, unet_decoder_run.
 struct ProfScope {
     const hipStream_t st;
     int i = -1;                                        // record index, -1 = not recording
@@ -57,6 +57,12 @@ struct ProfScope {
 };
 // 2*M*N*K of a conv over real output pixels (padding taps counted)
 static inline double conv_flops(int n, int ho, int wo, int ci, int co, int taps) { return 2.0 * n * ho * wo * (double)co * ci * taps; }
+// one conv launch = one profiler record of `kind`; a 1x1 call goes through conv1x1_common, which keeps the stride-1 ones of planes 1 / 2
+// for the pointwise kernel and hands every other one (the stride-2 downsamples) to conv_common
+static int run_conv(hipStream_t st, int kind, const ConvCall& c) {
+    ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
+    return c.ksize == 1 ? conv1x1_common(c) : conv_common(c);
+}
 
 // ------------------------------------------------------------------------------------ trunk
 // Layer-1 tensors of a full mode-3 trunk run live in 96-byte lines (common.h CONV_IN96): the pad positions of a PF buffer sit at
@@ -136,26 +142,39 @@ int wsi_trunk_workspace_init(void* workspace, int n, int h, int w, int planes, v
                : WSI_EFAULT;
 }
 
-// What a trunk run leaves in the workspace: byte offset and stage of the last tensor produced, and the offset of every stage's
-// output (ordinary PF only when allow_split was off).
-struct TrunkResult { size_t last_off; int last_stage; size_t stage_off[4]; };
-// The depth table of a trunk (wsi_trunk_weights.blocks): blocks per stage, the index of each stage's first conv in the block-major conv
-// tables, and the block count of the whole net.  valid() is what every entry checks before its first launch.
+// What a run of either architecture leaves in the workspace: the last tensor it produced (an ordinary PF tensor), as byte offset and shape.
+struct TrunkOut { size_t off; int c, h, w; };
+// The depth table of a net (the `blocks` of wsi_trunk_weights / wsi_bneck_weights): blocks per stage, blocks before each stage and in the
+// whole net.  Block b of stage s is block first[s] + b in network order, and with CONVS convs per block its conv k sits at
+// CONVS * (first[s] + b) + k of the block-major conv tables.  A bad entry makes total negative and keeps it there: no sum overflows.
 struct TrunkDepth {
-    int nb[4], conv0[4], total;
-    explicit TrunkDepth(const wsi_trunk_weights* wt) : total(0) {
+    int nb[4], first[4], total;
+    explicit TrunkDepth(const int blocks[4]) : total(0) {
         for (int s = 0; s < 4; ++s) {
-            nb[s] = wt->blocks[s];
-            conv0[s] = 2 * total;
+            nb[s] = blocks[s];
+            first[s] = total;
             total = nb[s] >= 1 && nb[s] <= WSI_TRUNK_MAX_BLOCKS && total >= 0 ? total + nb[s] : -1;
         }
     }
     bool valid() const { return total >= 1 && total <= WSI_TRUNK_MAX_BLOCKS; }
 };
+// What every entry that runs a net checks before it touches the workspace or launches anything: a valid depth table, an input source,
+// and every pointer a run of `d` reads - the stem's, the convs of all d.total blocks (the tables hold room for
+// WSI_TRUNK_MAX_BLOCKS blocks, so their size says how many convs a block has) and every downsample pair the struct carries (three
+// in a BasicBlock net, four in a Bottleneck net).  The u8 stem weights are optional; the head is the caller's check.
+template <class Weights>
+static bool trunk_ready(const Weights* wt, const TrunkDepth& d, const TileSource& src) {
+    if (!d.valid() || !src.valid() || !wt->stem_w || !wt->stem_b) return false;
+    const int convs = (int)std::size(wt->conv_w) / WSI_TRUNK_MAX_BLOCKS * d.total;
+    for (int i = 0; i < convs; ++i) if (!wt->conv_w[i] || !wt->conv_b[i]) return false;
+    for (size_t s = 0; s < std::size(wt->down_w); ++s) if (!wt->down_w[s] || !wt->down_b[s]) return false;
+    return true;
+}
 // What the U-Net asks of the trunk beyond a plain run.
 struct TrunkOpts {
     bool allow_split = true;      // stage outputs may be handed over phase-split (off: every stage output stays an ordinary PF tensor)
     char* x0_out = nullptr;       // the fused stem kernel also stores the conv map before the pool here (PF, h / 2 x w / 2 x 64)
+    size_t* stage_off = nullptr;  // [4], out: the byte offset of every stage's output (ordinary PF only when allow_split is off)
 };
 // Runs stem + residual stages; stops after stage `stop_after` (0 = pool, 1..total = blocks in network order, >= total all); `d` is the
 // (valid) depth table of `wt`.
@@ -170,7 +189,8 @@ struct TrunkOpts {
 // what images >= n still hold from an earlier, larger batch is never read: the zero row / column that close image
 // n-1 belong to its own block).
 static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const TileSource& src, int n, int cap, int h, int w, void* workspace,
-                     int stop_after, hipStream_t st, const TrunkPlan& p, TrunkResult& res, const TrunkOpts& opt = {}) {
+                     int stop_after, hipStream_t st, const TrunkPlan& p, TrunkOut& res, const TrunkOpts& opt = {}) {
+    constexpr int CONVS = 2;                           // convs per block
     char* ws = (char*)workspace;
     const int planes = wt->planes;
     int rc = WSI_OK;
@@ -182,10 +202,7 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
         return ConvCall{.in = in, .out = out, .resid = resid, .wpk = wt->conv_w[wi], .bias = wt->conv_b[wi], .n = n0, .h = H, .w = W, .cin = C,
                         .cout = C, .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
     };
-    auto run = [&](int kind, const ConvCall& c) {      // one conv launch = one profiler record
-        ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
-        return conv_common(c);
-    };
+    auto run = [&](int kind, const ConvCall& c) { return run_conv(st, kind, c); };
     const size_t bpc = planes == 1 ? PFmt<1>::BPC : PFmt<2>::BPC;     // bytes per channel: 2 (speed) or 4 (parity, mx)
     // ---- stem + maxpool + layer1 run in sub-batches so that the 4 MB/patch fp32 stem scratch and
     //      the 1 MB/patch layer-1 tensors stay resident in the 256 MiB Infinity Cache; the deeper
@@ -236,10 +253,10 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
             char *x = ws + p.buf[0][cur] + img_off(0, n1), *mid = ws + p.buf[0][m] + img_off(0, n1),
                  *out = ws + p.buf[0][o] + img_off(0, n1);
             const int f_in = l96 ? CONV_IN96 : 0, f_res = l96 ? CONV_RESID96 : 0;
-            ConvCall c = conv3(x, mid, nullptr, 2 * b, nn1, H1, W1, 64);
+            ConvCall c = conv3(x, mid, nullptr, CONVS * b, nn1, H1, W1, 64);
             c.line_flags = f_in | (l96 ? CONV_OUT96 : 0); c.plane96 = plane96;
             if ((rc = run(5, c))) return rc;
-            c = conv3(mid, out, x, 2 * b + 1, nn1, H1, W1, 64);
+            c = conv3(mid, out, x, CONVS * b + 1, nn1, H1, W1, 64);
             c.line_flags = f_in | f_res | (l96 && !last ? CONV_OUT96 : 0); c.plane96 = plane96;
             if (last && split0) {                      // layer1's output feeds only the stride-2 entry of layer2
                 c.out = ws + p.buf[0][3] + split_off(n1);
@@ -250,7 +267,8 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
         }
         l1_out = cur;
     }
-    res.last_off = res.stage_off[0] = p.buf[0][l1_out]; res.last_stage = 0;
+    res = {p.buf[0][l1_out], p.sc[0], H1, W1};
+    if (opt.stage_off) opt.stage_off[0] = res.off;
     if (stop_after >= 0 && stop_after <= d.nb[0]) return WSI_OK;
 
     int cur = l1_out;
@@ -260,7 +278,7 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
     for (int s = 1; s < 4; ++s) {
         const int H = p.sh[s], W = p.sw[s], C = p.sc[s];
         for (int b = 0; b < d.nb[s]; ++b) {
-            const int wi = d.conv0[s] + b * 2;
+            const int wi = CONVS * (d.first[s] + b);
             const bool last = b == d.nb[s] - 1;
             void *mid, *out;
             const void* resid;
@@ -289,7 +307,6 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
                 }
                 resid = ds;
                 cur = 0;
-                res.last_off = p.buf[s][0];
             } else {
                 const int m = (cur + 1) % 3, o = (cur + 2) % 3;
                 mid = ws + p.buf[s][m];
@@ -297,8 +314,8 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
                 if ((rc = run(1, conv3(x, mid, nullptr, wi, n, H, W, C)))) return rc;
                 resid = x;
                 cur = o;
-                res.last_off = p.buf[s][o];
             }
+            res = {p.buf[s][cur], C, H, W};            // (a tap's tensor: only full runs hand a stage over phase-split, and never the last)
             x_split = !fold_in2 && last && can_split(s);                          // the stage's output feeds only the next stage's stride-2 entry
             if (x_split) out = ws + p.buf[s][3];
             ConvCall c = conv3(mid, out, resid, wi + 1, n, H, W, C);
@@ -310,56 +327,11 @@ static int trunk_run(const wsi_trunk_weights* wt, const TrunkDepth& d, const Til
             } else if ((rc = run(1, c)))
                 return rc;
             x = out;
-            if (last) res.stage_off[s] = (size_t)((char*)out - ws);
-            ++block;
-            res.last_stage = s;
-            if (block == stop_after) return WSI_OK;
+            if (last && opt.stage_off) opt.stage_off[s] = (size_t)((char*)out - ws);
+            if (++block == stop_after) return WSI_OK;
         }
     }
     return WSI_OK;
-}
-
-int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide,
-                      long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
-                      int n, int h, int w, void* workspace, int workspace_n, float* feat_out, float* logits_out,
-                      float* fmap_out, void* stream) {
-    TrunkPlan p;
-    const int cap = workspace_n > 0 ? workspace_n : n;
-    if (!wt || !workspace || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
-    const TrunkDepth d(wt);
-    if (!d.valid()) return WSI_EINVAL;
-    if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
-    TrunkResult res;
-    int rc = trunk_run(wt, d, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace, d.total,
-                       (hipStream_t)stream, p, res);
-    if (rc) return rc;
-    const char* last = (const char*)workspace + res.last_off;
-    if (feat_out || logits_out) {
-        rc = wsi_avgpool_fc(last, n, p.sh[3], p.sw[3], 512, wt->head_w, wt->head_b, wt->head_k, feat_out, logits_out,
-                            wt->planes, stream);
-        if (rc) return rc;
-    }
-    if (fmap_out) rc = wsi_pf_unpack(last, fmap_out, n, 512, p.sh[3], p.sw[3], wt->planes, stream);
-    return rc;
-}
-
-int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide,
-                          long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut,
-                          int n, int h, int w, void* workspace, int workspace_n, int stop_after, float* tap_out_nchw,
-                          void* stream) {
-    TrunkPlan p;
-    const int cap = workspace_n > 0 ? workspace_n : n;
-    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || n <= 0 || cap < n || trunk_plan(cap, h, w, wt->planes, p))
-        return WSI_EINVAL;
-    const TrunkDepth d(wt);
-    if (!d.valid() || stop_after > d.total) return WSI_EINVAL;
-    TrunkResult res;
-    int rc = trunk_run(wt, d, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, cap, h, w, workspace,
-                       stop_after, (hipStream_t)stream, p, res);
-    if (rc) return rc;
-    const int stage = res.last_stage;
-    return wsi_pf_unpack((const char*)workspace + res.last_off, tap_out_nchw, n, p.sc[stage], p.sh[stage], p.sw[stage], wt->planes,
-                         stream);
 }
 
 // ------------------------------------------------------------------------------------ Bottleneck trunk (ResNet-50 / -101)
@@ -400,31 +372,12 @@ int wsi_bneck_workspace_init(void* workspace, int n, int h, int w, int planes, v
     if (!workspace || bneck_plan(n, h, w, planes, p)) return WSI_EINVAL;
     return hipMemsetAsync((char*)workspace + p.pool, 0, p.total - p.pool, (hipStream_t)stream) == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
-// the depth table of a Bottleneck trunk: as TrunkDepth, three convs per block
-struct BneckDepth {
-    int nb[4], blk0[4], total;
-    explicit BneckDepth(const wsi_bneck_weights* wt) : total(0) {
-        for (int s = 0; s < 4; ++s) {
-            nb[s] = wt->blocks[s];
-            blk0[s] = total;
-            total = nb[s] >= 1 && nb[s] <= WSI_TRUNK_MAX_BLOCKS && total >= 0 ? total + nb[s] : -1;
-        }
-    }
-    bool valid() const { return total >= 1 && total <= WSI_TRUNK_MAX_BLOCKS; }
-};
-// every pointer a run of `d` reads is there (checked before the first launch)
-static bool bneck_weights_ok(const wsi_bneck_weights* wt, const BneckDepth& d) {
-    if (!wt->stem_w || !wt->stem_b) return false;
-    for (int i = 0; i < 3 * d.total; ++i) if (!wt->conv_w[i] || !wt->conv_b[i]) return false;
-    for (int s = 0; s < 4; ++s) if (!wt->down_w[s] || !wt->down_b[s]) return false;
-    return true;
-}
-struct BneckResult { size_t last_off; int last_c, last_h, last_w; };
 // stem + blocks; stops after `stop_after` (0 = pool, 1..total = blocks in network order, >= total all).  `p`: the plan for cap >= n images.
 // ProfScope kinds: 4 = stem+maxpool, 11 = stride-1 1x1 (conv1, conv3, layer 1's downsample), 1 = 3x3 stride 1, 2 = 3x3 stride 2,
 // 3 = 1x1 stride-2 downsample
-static int bneck_run(const wsi_bneck_weights* wt, const BneckDepth& d, const TileSource& src, int n, int h, int w, void* workspace,
-                     int stop_after, hipStream_t st, const BneckPlan& p, BneckResult& res) {
+static int bneck_run(const wsi_bneck_weights* wt, const TrunkDepth& d, const TileSource& src, int n, int /* cap: no address depends on it */,
+                     int h, int w, void* workspace, int stop_after, hipStream_t st, const BneckPlan& p, TrunkOut& res) {
+    constexpr int CONVS = 3;                           // convs per block
     char* ws = (char*)workspace;
     const int planes = wt->planes;
     int rc;
@@ -436,17 +389,14 @@ static int bneck_run(const wsi_bneck_weights* wt, const BneckDepth& d, const Til
     }
     res = {p.pool, 64, p.sh[0], p.sw[0]};
     if (stop_after == 0) return WSI_OK;
-    auto run = [&](int kind, const ConvCall& c) {      // one conv launch = one profiler record
-        ProfScope ps(st, kind, conv_flops(c.n, c.h / c.stride, c.w / c.stride, c.cin, c.cout, c.ksize * c.ksize));
-        return c.ksize == 1 ? conv1x1_common(c) : conv_common(c);
-    };
+    auto run = [&](int kind, const ConvCall& c) { return run_conv(st, kind, c); };
     const void* x = ws + p.pool;
     int xc = 64, block = 0;
     for (int s = 0; s < 4; ++s) {
         const int H = p.sh[s], W = p.sw[s], C = p.sc[s], M = p.mc[s];
         int cur = 0;
         for (int b = 0; b < d.nb[s]; ++b) {
-            const int wi = 3 * (d.blk0[s] + b);
+            const int wi = CONVS * (d.first[s] + b);
             const int stride = (b == 0 && s > 0) ? 2 : 1;                          // (the stride sits on conv2: resnets_shift.py:86)
             const int Hi = H * stride, Wi = W * stride;                            // the block input's map
             auto conv = [&](const void* in, void* out, const void* resid, int k, int hh, int ww, int ci, int co, int str, int ks, int relu) {
@@ -480,43 +430,81 @@ static int bneck_run(const wsi_bneck_weights* wt, const BneckDepth& d, const Til
     return WSI_OK;
 }
 
+// ------------------------------------------------------------------------------------ the forward entries of both architectures
+// What the entries need to know of an architecture: its weight struct, its workspace plan and its run function.
+struct BasicNet {
+    using Weights = wsi_trunk_weights;
+    using Plan = TrunkPlan;
+    static constexpr auto plan = trunk_plan;
+    template <class... A> static int run(A&&... a) { return trunk_run(a...); }          // (a plain run: no TrunkOpts)
+};
+struct BneckNet {
+    using Weights = wsi_bneck_weights;
+    using Plan = BneckPlan;
+    static constexpr auto plan = bneck_plan;
+    static constexpr auto run = bneck_run;
+};
+// Checks every argument (-22 before the workspace is touched and before any launch: trunk_ready), then runs the net through block
+// `stop_after` (0 = pool; negative: the whole net) in a workspace planned for workspace_n (0: n) images; `res`: where its last tensor is.
+template <class Net>
+static int run_checked(const typename Net::Weights* wt, const TileSource& src, int n, int h, int w, void* workspace, int workspace_n,
+                       int stop_after, void* stream, TrunkOut& res) {
+    typename Net::Plan p;
+    const int cap = workspace_n > 0 ? workspace_n : n;
+    if (!wt || !workspace || n <= 0 || cap < n || Net::plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
+    const TrunkDepth d(wt->blocks);
+    if (!trunk_ready(wt, d, src) || stop_after > d.total) return WSI_EINVAL;
+    return Net::run(wt, d, src, n, cap, h, w, workspace, stop_after < 0 ? d.total : stop_after, (hipStream_t)stream, p, res);
+}
+// the whole net, then average pool + head and / or the last feature map as f32 NCHW; the feature width is the last tensor's
+template <class Net>
+static int forward(const typename Net::Weights* wt, const TileSource& src, int n, int h, int w, void* workspace, int workspace_n,
+                   float* feat_out, float* logits_out, float* fmap_out, void* stream) {
+    if (wt && logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
+    TrunkOut res;
+    int rc = run_checked<Net>(wt, src, n, h, w, workspace, workspace_n, -1, stream, res);
+    if (rc) return rc;
+    const char* last = (const char*)workspace + res.off;
+    if (feat_out || logits_out) {
+        rc = wsi_avgpool_fc(last, n, res.h, res.w, res.c, wt->head_w, wt->head_b, wt->head_k, feat_out, logits_out, wt->planes, stream);
+        if (rc) return rc;
+    }
+    if (fmap_out) rc = wsi_pf_unpack(last, fmap_out, n, res.c, res.h, res.w, wt->planes, stream);
+    return rc;
+}
+// the net through block `stop_after`, that tensor as f32 NCHW
+template <class Net>
+static int forward_tap(const typename Net::Weights* wt, const TileSource& src, int n, int h, int w, void* workspace, int workspace_n,
+                       int stop_after, float* tap_out_nchw, void* stream) {
+    if (!tap_out_nchw || stop_after < 0) return WSI_EINVAL;
+    TrunkOut res;
+    const int rc = run_checked<Net>(wt, src, n, h, w, workspace, workspace_n, stop_after, stream, res);
+    return rc ? rc : wsi_pf_unpack((const char*)workspace + res.off, tap_out_nchw, n, res.c, res.h, res.w, wt->planes, stream);
+}
+
+int wsi_trunk_forward(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
+                      int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
+                      float* feat_out, float* logits_out, float* fmap_out, void* stream) {
+    return forward<BasicNet>(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n, feat_out,
+                             logits_out, fmap_out, stream);
+}
+int wsi_trunk_forward_tap(const wsi_trunk_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
+                          int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
+                          int stop_after, float* tap_out_nchw, void* stream) {
+    return forward_tap<BasicNet>(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n,
+                                 stop_after, tap_out_nchw, stream);
+}
 int wsi_bneck_forward(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
                       int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
                       float* feat_out, float* logits_out, float* fmap_out, void* stream) {
-    BneckPlan p;
-    const int cap = workspace_n > 0 ? workspace_n : n;
-    if (!wt || !workspace || n <= 0 || cap < n || bneck_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
-    const BneckDepth d(wt);
-    if (!d.valid() || !bneck_weights_ok(wt, d)) return WSI_EINVAL;
-    if (logits_out && (!wt->head_w || !wt->head_b || wt->head_k <= 0)) return WSI_EINVAL;
-    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
-    if (!src.valid()) return WSI_EINVAL;
-    BneckResult res;
-    int rc = bneck_run(wt, d, src, n, h, w, workspace, d.total, (hipStream_t)stream, p, res);
-    if (rc) return rc;
-    const char* last = (const char*)workspace + res.last_off;
-    if (feat_out || logits_out) {
-        rc = wsi_avgpool_fc(last, n, p.sh[3], p.sw[3], 2048, wt->head_w, wt->head_b, wt->head_k, feat_out, logits_out, wt->planes, stream);
-        if (rc) return rc;
-    }
-    if (fmap_out) rc = wsi_pf_unpack(last, fmap_out, n, 2048, p.sh[3], p.sw[3], wt->planes, stream);
-    return rc;
+    return forward<BneckNet>(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n, feat_out,
+                             logits_out, fmap_out, stream);
 }
-
 int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, const uint8_t* slide, long long slide_pitch_bytes, int slide_h,
                           int slide_w, const int* tile_xy, const float* lut, int n, int h, int w, void* workspace, int workspace_n,
                           int stop_after, float* tap_out_nchw, void* stream) {
-    BneckPlan p;
-    const int cap = workspace_n > 0 ? workspace_n : n;
-    if (!wt || !workspace || !tap_out_nchw || stop_after < 0 || n <= 0 || cap < n || bneck_plan(cap, h, w, wt->planes, p)) return WSI_EINVAL;
-    const BneckDepth d(wt);
-    if (!d.valid() || stop_after > d.total || !bneck_weights_ok(wt, d)) return WSI_EINVAL;
-    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
-    if (!src.valid()) return WSI_EINVAL;
-    BneckResult res;
-    int rc = bneck_run(wt, d, src, n, h, w, workspace, stop_after, (hipStream_t)stream, p, res);
-    if (rc) return rc;
-    return wsi_pf_unpack((const char*)workspace + res.last_off, tap_out_nchw, n, res.last_c, res.last_h, res.last_w, wt->planes, stream);
+    return forward_tap<BneckNet>(wt, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n,
+                                 stop_after, tap_out_nchw, stream);
 }
 
 // ------------------------------------------------------------------------------------ U-Net (dense 'seg' path)
@@ -625,21 +613,21 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     if (!wt || !dw || !workspace || n <= 0 || cap < n || (!logits_out && !enc_out) || h % 32 || w % 32) return WSI_EINVAL;
     if (trunk_plan(cap, h, w, wt->planes, p) || unet_plan(dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
     const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
-    if (!src.valid()) return WSI_EINVAL;
-    const TrunkDepth d(wt);
-    if (!d.valid()) return WSI_EINVAL;
+    const TrunkDepth d(wt->blocks);
+    if (!trunk_ready(wt, d, src)) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
     const int planes = wt->planes;
     // encoder: the trunk with every stage output kept as an ordinary PF tensor (no phase-split hand-over) ...
-    TrunkResult res;
+    TrunkOut res;
+    size_t stage_off[4];
     // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
     // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
     const ConvRoutes& r = g_routes;
     const bool x0_fused = r.unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
                           r.stem_shared_weights;
-    int rc = trunk_run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr});
+    int rc = trunk_run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr, .stage_off = stage_off});
     if (rc) return rc;
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
     // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines
@@ -656,7 +644,7 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
         }
     }
     if (rc) return rc;
-    const void* enc[5] = {ws + res.stage_off[3], ws + res.stage_off[2], ws + res.stage_off[1], ws + res.stage_off[0], dec + u.x0};
+    const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], dec + u.x0};
     if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first
         for (int i = 0; i < 5 && !rc; ++i) {
             const EncMap m = enc_map(i, h, w);
@@ -689,5 +677,3 @@ int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_
     }
     return rc ? rc : unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, (hipStream_t)stream);
 }
-
-}  // extern "C"

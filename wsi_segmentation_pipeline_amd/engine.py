@@ -3,6 +3,7 @@
 PyTorch is used only as plumbing (device memory, streams); all compute goes through
 libwsi_hip.so (include/wsi_hip.h).  There is no CPU fallback: tensors must live on a GPU.
 """
+import collections
 import ctypes as C
 import weakref
 
@@ -67,11 +68,16 @@ def batch_sizes(n, cap, h=256, w=256):
     return [min(mb, n - i) for i in range(0, n, mb)]
 
 
-def trunk_layers(state_dict):
-    """Blocks per stage of a BasicBlock ResNet state dict (reference key names): the count of ``layerL.B.conv1.weight`` keys, e.g.
-    [2, 2, 2, 2] for ResNet-18 and [3, 4, 6, 3] for ResNet-34.  ValueError for Bottleneck checkpoints (a ``conv3`` key), for block
-    numbers with gaps, for a stage without blocks and for more blocks than the C ABI carries (native.TRUNK_MAX_BLOCKS)."""
-    found = [set(), set(), set(), set()]
+# What the host layer knows of an architecture: convs per block and their kernel sizes, the width factor of a block's output, the first
+# layer whose block 0 has a downsample branch (slot 0 of the C struct's down_w / down_b), the C struct, the prefix of its entry points
+# (include/wsi_hip.h) and the planes values its kernels take.
+Arch = collections.namedtuple('Arch', 'convs ksizes expansion first_down weights entry planes_ok')
+ARCHS = {'basic': Arch(2, (3, 3), 1, 2, native.WsiTrunkWeights, 'wsi_trunk', (1, 2, 3)),
+         'bottleneck': Arch(3, (1, 3, 1), 4, 1, native.WsiBneckWeights, 'wsi_bneck', (1, 2))}
+
+
+def _block_keys(state_dict):
+    """(key, layer 1..4, block, rest of the key as a list) of every ``layerL.B.<...>`` key; ValueError for a layer outside 1..4."""
     for key in state_dict:
         parts = key.split('.')
         if len(parts) < 4 or not parts[0].startswith('layer') or not parts[0][5:].isdigit() or not parts[1].isdigit():
@@ -79,45 +85,23 @@ def trunk_layers(state_dict):
         L = int(parts[0][5:])
         if not 1 <= L <= 4:
             raise ValueError('state dict key %r: a ResNet trunk has layer1 ... layer4' % key)
-        if parts[2] == 'conv3':
-            raise ValueError('state dict key %r belongs to a Bottleneck block (ResNet-50 and deeper): the HIP trunk runs BasicBlock '
-                             'ResNets (resnet18, resnet34, any [n1, n2, n3, n4] of two-conv blocks) only' % key)
-        if parts[2:] == ['conv1', 'weight']:
-            found[L - 1].add(int(parts[1]))
-    layers = []
-    for L, blocks in enumerate(found, start=1):
-        if not blocks:
-            raise ValueError('state dict has no layer%d.0.conv1.weight: not a ResNet trunk' % L)
-        if blocks != set(range(len(blocks))):
-            raise ValueError('state dict has gaps in the blocks of layer%d: found %s' % (L, sorted(blocks)))
-        layers.append(len(blocks))
-    if sum(layers) > native.TRUNK_MAX_BLOCKS:
-        raise ValueError('%s = %d residual blocks: the C ABI carries at most %d (include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS)'
-                         % (layers, sum(layers), native.TRUNK_MAX_BLOCKS))
-    return layers
+        yield key, L, int(parts[1]), parts[2:]
 
 
 def trunk_arch(state_dict):
-    """('basic' | 'bottleneck', blocks per stage) of a ResNet state dict with the reference's key names.  A trunk whose every block has a
-    ``conv3`` key is a Bottleneck net (ResNet-50: [3, 4, 6, 3], ResNet-101: [3, 4, 23, 3]), one without any is a BasicBlock net
-    (`trunk_layers`); ValueError for a mixture, for gaps in the block numbers, for a stage without blocks and for more than
+    """('basic' | 'bottleneck', blocks per stage) of a ResNet state dict with the reference's key names: the count of
+    ``layerL.B.conv1.weight`` keys per layer.  A trunk whose every block has a ``conv3`` key is a Bottleneck net (ResNet-50:
+    [3, 4, 6, 3], ResNet-101: [3, 4, 23, 3]), one without any is a BasicBlock net ([2, 2, 2, 2] for ResNet-18, [3, 4, 6, 3] for
+    ResNet-34); ValueError for a mixture, for gaps in the block numbers, for a stage without blocks and for more than
     native.TRUNK_MAX_BLOCKS blocks (ResNet-152 has 50)."""
     found = [set(), set(), set(), set()]
     third = [set(), set(), set(), set()]
-    for key in state_dict:
-        parts = key.split('.')
-        if len(parts) < 4 or not parts[0].startswith('layer') or not parts[0][5:].isdigit() or not parts[1].isdigit():
-            continue
-        L = int(parts[0][5:])
-        if not 1 <= L <= 4:
-            raise ValueError('state dict key %r: a ResNet trunk has layer1 ... layer4' % key)
-        if parts[2:] == ['conv1', 'weight']:
-            found[L - 1].add(int(parts[1]))
-        if parts[2:] == ['conv3', 'weight']:
-            third[L - 1].add(int(parts[1]))
-    if not any(third):
-        return 'basic', trunk_layers(state_dict)
-    if third != found:
+    for _, L, B, rest in _block_keys(state_dict):
+        if rest == ['conv1', 'weight']:
+            found[L - 1].add(B)
+        if rest == ['conv3', 'weight']:
+            third[L - 1].add(B)
+    if any(third) and third != found:
         raise ValueError('state dict mixes blocks with and without conv3 (blocks with conv1: %s, with conv3: %s): neither a BasicBlock '
                          'nor a Bottleneck ResNet' % ([sorted(b) for b in found], [sorted(b) for b in third]))
     layers = []
@@ -128,9 +112,42 @@ def trunk_arch(state_dict):
             raise ValueError('state dict has gaps in the blocks of layer%d: found %s' % (L, sorted(blocks)))
         layers.append(len(blocks))
     if sum(layers) > native.TRUNK_MAX_BLOCKS:
-        raise ValueError('%s = %d Bottleneck blocks: the C ABI carries at most %d (include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS; ResNet-152 '
-                         'is not supported)' % (layers, sum(layers), native.TRUNK_MAX_BLOCKS))
-    return 'bottleneck', layers
+        raise ValueError('%s = %d blocks: the C ABI carries at most %d (include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS; ResNet-152 is not '
+                         'supported)' % (layers, sum(layers), native.TRUNK_MAX_BLOCKS))
+    return ('bottleneck' if any(third) else 'basic'), layers
+
+
+def trunk_layers(state_dict):
+    """Blocks per stage of a BasicBlock ResNet state dict, e.g. [2, 2, 2, 2] for ResNet-18 and [3, 4, 6, 3] for ResNet-34: `trunk_arch`
+    with a ValueError of its own for a Bottleneck checkpoint (any ``conv3`` key)."""
+    for key, _, _, rest in _block_keys(state_dict):
+        if rest[0] == 'conv3':
+            raise ValueError('state dict key %r belongs to a Bottleneck block (ResNet-50 and deeper): the HIP trunk runs BasicBlock '
+                             'ResNets (resnet18, resnet34, any [n1, n2, n3, n4] of two-conv blocks) only' % key)
+    return trunk_arch(state_dict)[1]
+
+
+def conv_table(arch, layers):
+    """The conv tables of a net's C struct, from the state dict's side: ([(index, weight key, bn prefix, kernel size)] in network order,
+    the index block-major as include/wsi_hip.h states it; [(downsample slot, weight key, bn prefix)])."""
+    a = ARCHS[arch]
+    convs, downs = [], []
+    for L in range(1, 5):
+        for B in range(layers[L - 1]):
+            for K, ksize in enumerate(a.ksizes, start=1):
+                convs.append((a.convs * (sum(layers[:L - 1]) + B) + (K - 1), 'layer%d.%d.conv%d.weight' % (L, B, K),
+                              'layer%d.%d.bn%d' % (L, B, K), ksize))
+        if L >= a.first_down:
+            downs.append((L - a.first_down, 'layer%d.0.downsample.0.weight' % L, 'layer%d.0.downsample.1' % L))
+    return convs, downs
+
+
+def tap_shape(arch, layers, tap, h, w):
+    """(channels, height, width) of tap `tap` (0 = pool, 1.. = blocks in network order) of an h x w input."""
+    stage = sum(tap > sum(layers[:L]) for L in range(4))                   # 0 = pool, 1..4 = layer of block `tap`
+    if stage == 0:
+        return 64, h >> 2, w >> 2
+    return (64 << (stage - 1)) * ARCHS[arch].expansion, h >> (1 + stage), w >> (1 + stage)
 
 
 class TrunkEngine:
@@ -141,14 +158,16 @@ class TrunkEngine:
     state_dict: reference key names (conv1.weight, bn1.*, layerL.B.convK.weight, ...); the depth is read from it (`.layers`).
     """
 
-    FEAT_C = 512                                 # channels of the last stage (the head's input width)
-    WEIGHTS = native.WsiTrunkWeights             # the C struct and entry points of this architecture
-    ENTRY = 'wsi_trunk'
-    PLANES_OK = (1, 2, 3)
+    ARCH = 'basic'                               # the row of ARCHS this engine runs
+    FEAT_C = 512 * ARCHS[ARCH].expansion         # channels of the last stage (the head's input width)
+    PLANES_OK = ARCHS[ARCH].planes_ok
 
     def __init__(self, state_dict, device, planes=MX, head=None, max_batch=None,
                  mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), streams=2):
         self.lib = native.load()
+        arch = ARCHS[self.ARCH]
+        self._ws_bytes, self._ws_init, self._forward, self._forward_tap = (
+            getattr(self.lib, arch.entry + s) for s in ('_workspace_bytes', '_workspace_init', '_forward', '_forward_tap'))
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise RuntimeError('TrunkEngine needs a GPU device, got %s' % device)
@@ -167,7 +186,7 @@ class TrunkEngine:
         self._streams = [torch.cuda.Stream(device=self.device) for _ in range(max(1, int(streams)))] if streams > 1 else []
         self._keep = []                          # device tensors referenced by raw pointers
         self._ws = {}
-        self.wt = self.WEIGHTS()
+        self.wt = arch.weights()
         self.wt.planes = planes
         sd = state_dict
         self.layers = self._layers_of(sd)
@@ -213,29 +232,24 @@ class TrunkEngine:
                                                    cout, cin, k, planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_conv')
             return dev(pk).data_ptr(), dev(bias).data_ptr()
 
-        self._fill_convs(conv)
+        convs, downs = conv_table(self.ARCH, self.layers)
+        for i, wkey, bnkey, k in convs:
+            self.wt.conv_w[i], self.wt.conv_b[i] = conv(wkey, bnkey, k)
+        for i, wkey, bnkey in downs:
+            self.wt.down_w[i], self.wt.down_b[i] = conv(wkey, bnkey, 1)
         self.set_head(head)
         self.lut = dev(normalize_lut(mean, std))
 
     def _layers_of(self, sd):
-        return trunk_layers(sd)
-
-    def _fill_convs(self, conv):
-        """The conv tables of the C struct; conv(weight key, bn prefix, k) -> (packed weights, bias) device pointers."""
-        for L in range(1, 5):
-            for B in range(self.layers[L - 1]):
-                for K in (1, 2):
-                    p = 'layer%d.%d' % (L, B)
-                    i = 2 * (sum(self.layers[:L - 1]) + B) + (K - 1)      # block-major (include/wsi_hip.h wsi_trunk_weights)
-                    self.wt.conv_w[i], self.wt.conv_b[i] = conv('%s.conv%d.weight' % (p, K), '%s.bn%d' % (p, K), 3)
-            if L > 1:
-                p = 'layer%d.0.downsample' % L
-                self.wt.down_w[L - 2], self.wt.down_b[L - 2] = conv(p + '.0.weight', p + '.1', 1)
+        if self.ARCH == 'basic':
+            return trunk_layers(sd)                         # (refuses a Bottleneck checkpoint in its own words)
+        arch, layers = trunk_arch(sd)
+        if arch != self.ARCH:
+            raise ValueError('BottleneckEngine needs a Bottleneck state dict (layerL.B.conv3 keys); this one is a BasicBlock net: use TrunkEngine')
+        return layers
 
     def _tap_shape(self, tap, h, w):
-        """(channels, height, width) of tap `tap` (0 = pool, 1.. = blocks in network order)."""
-        stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 0 = pool, 1..4 = layer of block `tap`
-        return 64 << max(stage - 1, 0), h >> (2 + max(stage - 1, 0)), w >> (2 + max(stage - 1, 0))
+        return tap_shape(self.ARCH, self.layers, tap, h, w)
 
     # ------------------------------------------------------------------ configuration
     def set_head(self, head):
@@ -259,21 +273,21 @@ class TrunkEngine:
         key = (h, w, slot)
         ent = self._ws.get(key)
         if ent is None or ent[1] < n:
-            nbytes = getattr(self.lib, self.ENTRY + '_workspace_bytes')(n, h, w, self.planes)
+            nbytes = self._ws_bytes(n, h, w, self.planes)
             if nbytes == 0:
                 raise ValueError('unsupported patch shape %dx%d (need multiples of 32) or batch %d' % (h, w, n))
             self._drop_workspace(key)                       # a smaller plan of the same shape is released first
             if len(self._ws) >= 4 * max(1, len(self._streams)):   # keep the plan cache small
                 self._drop_workspace(next(iter(self._ws)))
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            native.check(getattr(self.lib, self.ENTRY + '_workspace_init')(_ptr(ws), n, h, w, self.planes, _stream()),
-                         self.ENTRY + '_workspace_init')
+            native.check(self._ws_init(_ptr(ws), n, h, w, self.planes, _stream()), self._ws_init.__name__)
             ent = self._ws[key] = (ws, n)
         return ent
 
     def _drop_workspace(self, key):
         ent = self._ws.pop(key, None)
-        if ent is not None:                                 # the library forgets the address before the allocator can reuse it
+        if ent is not None:                                 # the library forgets the address before the allocator can reuse it (a no-op for
+                                                            # a Bottleneck workspace, which carries no layout tag)
             self.lib.wsi_trunk_workspace_release(_ptr(ent[0]))
 
     def release_workspaces(self):
@@ -304,13 +318,11 @@ class TrunkEngine:
                 raise ValueError('tap must be 0 (pool) ... %d (the last block), got %r' % (sum(self.layers), tap))
             c, hh, ww = self._tap_shape(tap, h, w)
             out = torch.empty((n, c, hh, ww), dtype=torch.float32, device=dev)
-            native.check(getattr(self.lib, self.ENTRY + '_forward_tap')(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
-                                                                        _ptr(self.lut), n, h, w, _ptr(ws), cap, tap, _ptr(out), _stream()),
-                         self.ENTRY + '_forward_tap')
+            native.check(self._forward_tap(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy), _ptr(self.lut), n, h, w,
+                                           _ptr(ws), cap, tap, _ptr(out), _stream()), self._forward_tap.__name__)
             return out
-        native.check(getattr(self.lib, self.ENTRY + '_forward')(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
-                                                                _ptr(self.lut), n, h, w, _ptr(ws), cap, _ptr(feat), _ptr(logits), _ptr(fmap),
-                                                                _stream()), self.ENTRY + '_forward')
+        native.check(self._forward(C.byref(self.wt), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy), _ptr(self.lut), n, h, w, _ptr(ws), cap,
+                                   _ptr(feat), _ptr(logits), _ptr(fmap), _stream()), self._forward.__name__)
         return feat, logits, fmap
 
     def forward_f32(self, x, feat=False, logits=False, fmap=False, tap=None):
@@ -349,7 +361,7 @@ class TrunkEngine:
         """Default images per trunk call: the tuned batch scaled by patch area, limited so that the workspaces of all stream slots
         stay inside 60 % of the memory that is free now (plus what this engine already holds)."""
         want = max(1, int(self.TUNED_BATCH_256 * 65536 // max(h * w, 1)))
-        per = getattr(self.lib, self.ENTRY + '_workspace_bytes')(64, h, w, self.planes) / 64.0
+        per = self._ws_bytes(64, h, w, self.planes) / 64.0
         if per <= 0:
             return want
         try:                                                 # free = what the driver reports + what torch's caching allocator holds unused
@@ -405,35 +417,9 @@ class BottleneckEngine(TrunkEngine):
     the reference ``resnets_shift.ResNet(Bottleneck, layers)`` on HIP kernels: wsi_bneck_forward, whose 1x1 convs run on the
     pointwise kernel.  Same surface as TrunkEngine; features and heads are 2048 wide; planes 2 (parity) or 1 (speed) - mx is refused.
     `_auto_cap` sizes the batch from wsi_bneck_workspace_bytes (30.8 MB per 256 x 256 patch in parity mode)."""
-    FEAT_C = 2048
-    WEIGHTS = native.WsiBneckWeights
-    ENTRY = 'wsi_bneck'
-    PLANES_OK = (1, 2)
-
-    def _layers_of(self, sd):
-        arch, layers = trunk_arch(sd)
-        if arch != 'bottleneck':
-            raise ValueError('BottleneckEngine needs a Bottleneck state dict (layerL.B.conv3 keys); this one is a BasicBlock net: use TrunkEngine')
-        return layers
-
-    def _fill_convs(self, conv):
-        for L in range(1, 5):
-            for B in range(self.layers[L - 1]):
-                p = 'layer%d.%d' % (L, B)
-                for K in (1, 2, 3):
-                    i = 3 * (sum(self.layers[:L - 1]) + B) + (K - 1)      # block-major (include/wsi_hip.h wsi_bneck_weights)
-                    self.wt.conv_w[i], self.wt.conv_b[i] = conv('%s.conv%d.weight' % (p, K), '%s.bn%d' % (p, K), 3 if K == 2 else 1)
-            p = 'layer%d.0.downsample' % L
-            self.wt.down_w[L - 1], self.wt.down_b[L - 1] = conv(p + '.0.weight', p + '.1', 1)
-
-    def _tap_shape(self, tap, h, w):
-        if tap == 0:
-            return 64, h >> 2, w >> 2
-        stage = sum(tap > sum(self.layers[:L]) for L in range(4))         # 1..4 = layer of block `tap`
-        return 256 << (stage - 1), h >> (1 + stage), w >> (1 + stage)
-
-    def _drop_workspace(self, key):
-        self._ws.pop(key, None)                             # (the Bottleneck trunk keeps no layout tags: nothing to release)
+    ARCH = 'bottleneck'
+    FEAT_C = 512 * ARCHS[ARCH].expansion
+    PLANES_OK = ARCHS[ARCH].planes_ok
 
 
 class AutoTrunkEngine:
@@ -615,6 +601,23 @@ class AutoTrunkEngine:
         if self._mx is not None and (self._chosen is None or not self._same_slide(slide_u8, key)):
             self.decide(self.probe_tiles(slide_u8, tile_xy, ph, pw, slide_id=slide_id))
         return self._chosen.forward_tiles(slide_u8, tile_xy, ph, pw, feat=feat, logits=logits, fmap=fmap, tap=tap)
+
+
+def trunk_engine(state_dict, device, precision=AUTO, head=None, **kw):
+    """The engine for a net (`trunk_arch` of its state dict) and a precision name: BasicBlock nets 'auto' (AutoTrunkEngine), 'parity',
+    'mx' or 'speed' (TrunkEngine); Bottleneck nets 'parity' or 'speed' (BottleneckEngine), 'auto' resolving to parity with a `report`
+    that says why.  **kw goes to the engine's constructor."""
+    if trunk_arch(state_dict)[0] == 'basic':
+        if precision == AUTO:
+            return AutoTrunkEngine(state_dict, device, head=head, **kw)
+        return TrunkEngine(state_dict, device, planes={'parity': PARITY, 'mx': MX, 'speed': SPEED}[precision], head=head, **kw)
+    if precision not in (AUTO, 'parity', 'speed'):
+        raise NotImplementedError("Bottleneck nets run in 'parity', 'speed' or 'auto' precision, not %r" % (precision,))
+    eng = BottleneckEngine(state_dict, device, planes=SPEED if precision == 'speed' else PARITY, head=head, **kw)
+    if precision == AUTO:
+        eng.report = {'mode': 'parity', 'probe_error': None,
+                      'reason': 'Bottleneck nets have no mx mode (no pointwise-conv kernel in planes 3): auto resolves to parity'}
+    return eng
 
 
 # ---------------------------------------------------------------------- standalone device ops

@@ -23,30 +23,24 @@ class NativeLibraryMissing(RuntimeError):
 TRUNK_MAX_BLOCKS = 36                    # include/wsi_hip.h WSI_TRUNK_MAX_BLOCKS: residual blocks of one trunk, all stages together
 
 
-class WsiTrunkWeights(C.Structure):
-    """wsi_trunk_weights: `blocks` residual blocks per stage; layerL.B.convK at 2 * (sum(blocks[:L-1]) + B) + (K-1)."""
-    _fields_ = [
+def _trunk_weights(name, convs, downs, doc):
+    """The ctypes mirror of a net's weight struct: one field list, `convs` convs per block and `downs` downsample slots."""
+    fields = [
         ('stem_w', C.c_void_p), ('stem_b', C.c_void_p),
         ('stem_w_u8', C.c_void_p), ('stem_b_u8', C.c_void_p), ('norm', C.c_float * 6),
         ('blocks', C.c_int * 4),
-        ('conv_w', C.c_void_p * (2 * TRUNK_MAX_BLOCKS)), ('conv_b', C.c_void_p * (2 * TRUNK_MAX_BLOCKS)),
-        ('down_w', C.c_void_p * 3), ('down_b', C.c_void_p * 3),
+        ('conv_w', C.c_void_p * (convs * TRUNK_MAX_BLOCKS)), ('conv_b', C.c_void_p * (convs * TRUNK_MAX_BLOCKS)),
+        ('down_w', C.c_void_p * downs), ('down_b', C.c_void_p * downs),
         ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_k', C.c_int),
         ('planes', C.c_int),
     ]
+    return type(name, (C.Structure,), {'_fields_': fields, '__doc__': doc})
 
 
-class WsiBneckWeights(C.Structure):
-    """wsi_bneck_weights: `blocks` Bottleneck blocks per stage; layerL.B.convK at 3 * (sum(blocks[:L-1]) + B) + (K-1)."""
-    _fields_ = [
-        ('stem_w', C.c_void_p), ('stem_b', C.c_void_p),
-        ('stem_w_u8', C.c_void_p), ('stem_b_u8', C.c_void_p), ('norm', C.c_float * 6),
-        ('blocks', C.c_int * 4),
-        ('conv_w', C.c_void_p * (3 * TRUNK_MAX_BLOCKS)), ('conv_b', C.c_void_p * (3 * TRUNK_MAX_BLOCKS)),
-        ('down_w', C.c_void_p * 4), ('down_b', C.c_void_p * 4),
-        ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_k', C.c_int),
-        ('planes', C.c_int),
-    ]
+WsiTrunkWeights = _trunk_weights('WsiTrunkWeights', 2, 3, 'wsi_trunk_weights: `blocks` residual blocks per stage; layerL.B.convK at '
+                                 '2 * (sum(blocks[:L-1]) + B) + (K-1); downsamples of layer2..4.')
+WsiBneckWeights = _trunk_weights('WsiBneckWeights', 3, 4, 'wsi_bneck_weights: `blocks` Bottleneck blocks per stage; layerL.B.convK at '
+                                 '3 * (sum(blocks[:L-1]) + B) + (K-1); downsamples of layer1..4.')
 
 
 class WsiUnetDecoderWeights(C.Structure):
