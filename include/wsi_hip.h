@@ -489,6 +489,32 @@ int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_
  * contiguous fp32 (hs, ws) planes */
 int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, void* stream);
 
+/* ---- test-time views and the MLP head over them (cellularity scoring) -------------------------
+ * The reference scores a patch in four orientations and averages (utils/eval.py:308-313 predict_reg, :392-397
+ * predict_breastpathq): image, image.transpose(2, 3), image.flip(2), image.transpose(2, 3).flip(3).
+ * View id = T (1) | FY (2) | FX (4): transpose first if T, then reverse the rows of the result if FY, then its columns if FX.  For a
+ * source tile s of ph x pw pixels the view has (hv, wv) = T ? (pw, ph) : (ph, pw) and view[y][x] = s[sy][sx] with
+ * y' = FY ? hv-1-y : y, x' = FX ? wv-1-x : x, (sy, sx) = T ? (x', y') : (y', x').  The reference's four views are ids 0, 1, 2, 5.
+ * tile_views_u8: n tiles of packed-RGB u8 at the device-resident corners tile_xy (as wsi_trunk_forward reads them; a pixel outside
+ *   the slide reads 0) -> nviews * n oriented tiles, view-major (tile k * n + i is view views[k] of tile i), each a dense
+ *   hv x wv x 3 block, stacked vertically in `out`: an (nviews * n * hv, wv, 3) packed-RGB "slide" whose tile k * n + i has the
+ *   corner (0, (k * n + i) * hv).  `views` is a host array of 1 to 8 ids (repeats allowed) that share one output shape (all with
+ *   T, all without, or ph == pw).
+ * views_f32: the same for normalised fp32 [n][3][h][w] -> [nviews * n][3][hv][wv].
+ * -22 before any launch: a NULL pointer, n <= 0, ph or pw no positive multiple of 32, nviews outside 1..8, an id outside 0..7,
+ *   views of two shapes, slide_pitch_bytes < 3 * slide_w. */
+int wsi_tile_views_u8(const uint8_t* slide, long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, int n, int ph,
+                      int pw, const int* views, int nviews, uint8_t* out, void* stream);
+int wsi_views_f32(const float* in_nchw, int n, int h, int w, const int* views, int nviews, float* out_nchw, void* stream);
+/* mlp_views: feat [nviews * n][f] fp32, view-major (what wsi_trunk_forward / wsi_bneck_forward write to feat_out for the batch of
+ *   views).  Per row y = W2 . relu(W1 . x + b1) + b2 with w1 [j][f], w2 [k][j] (Regressor.fc, models/models.py:46-50); j == 0: one
+ *   Linear, y = W2 . x + b2 with w2 [k][f] (Classifier.fc; w1 and b1 are ignored).  views_out [nviews * n][k] (may be NULL) takes
+ *   every row's y; mean_out [n][k] = ((y0 + y1) + y2 + ...) / (float)nviews over a patch's views in view order (utils/eval.py:321,
+ *   :336), then fminf(fmaxf(., clamp_lo), clamp_hi) if clamp (utils/eval.py:409-410).  All arithmetic fp32.
+ * -22 before any launch: NULL feat, w2, b2 or mean_out; NULL w1 or b1 with j > 0; n, f or k <= 0; j < 0; nviews outside 1..8. */
+int wsi_mlp_views(const float* feat, int n, int nviews, int f, const float* w1, const float* b1, int j, const float* w2, const float* b2,
+                  int k, int clamp, float clamp_lo, float clamp_hi, float* views_out, float* mean_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

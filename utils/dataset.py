@@ -1,5 +1,6 @@
-"""Drop-in for the sliding-window datasets of the reference's ``utils.dataset``
-(/root/reference/utils/dataset.py:83-201): Dataset_wsis, Dataset_wsi, GenerateIterator_wsi.
+"""Drop-in for the datasets of the reference's ``utils.dataset``: the sliding-window ones
+(/root/reference/utils/dataset.py:83-201: Dataset_wsis, Dataset_wsi, GenerateIterator_wsi) and the patch
+Dataset / GenerateIterator (:13-80) that feed utils.eval.predict_reg / predict_cls (host code).
 
 The tile producer is MI355X-native: the chosen pyramid level is resident in HBM as packed u8 RGB
 and batches are produced on the device by wsi_tile_gather (read + ToTensor + Normalize fused), or
@@ -11,11 +12,54 @@ import os
 
 import numpy as np
 import torch
+import torch.utils.data
 
 from myargs import args
 from utils import preprocessing
 from wsi_segmentation_pipeline_amd import engine as E
 from wsi_segmentation_pipeline_amd import slide as S
+
+
+class Dataset(torch.utils.data.Dataset):
+    """Patches listed by <impth>/gt.npy (reference utils/dataset.py:13-68): a pickled dict {key: {tile_id: {'wsi': image path,
+    'label': int (class) | float (cellularity) | str (path of a label image)}}}.  An item is (image fp32 CHW normalised, label
+    int64 HW - zeros without a label image -, is_cls, is_reg, is_seg, cls_code = the label, -1 for a label image).  Train mode
+    (eval=False) lists every item `duplicate_dataset` times, rotates image and label by a random multiple of 90 degrees and resizes
+    both to (args.tile_w, args.tile_h); its ColorJitter is not provided (preprocessing.standard_augmentor), so both modes apply
+    the eval transform."""
+
+    def __init__(self, impth, eval, duplicate_dataset):
+        self.eval = eval
+        self.image_aug = preprocessing.standard_augmentor(True)
+        gt = np.load('{}/gt.npy'.format(impth), allow_pickle=True).flatten()[0]
+        self.datalist = [{'wsi': item['wsi'], 'label': item['label']} for key in gt for item in gt[key].values()]
+        if not self.eval:
+            self.datalist = [item for item in self.datalist for _ in range(duplicate_dataset)]
+
+    def __len__(self):
+        return len(self.datalist)
+
+    def __getitem__(self, index):
+        from PIL import Image
+        item = self.datalist[index]
+        image = Image.open(item['wsi'])
+        if isinstance(item['label'], str):
+            label = Image.open(item['label'])
+        else:
+            label = Image.fromarray(np.zeros((image.size[1], image.size[0]), dtype=np.uint8))
+        if not self.eval:
+            degree = int(torch.randint(0, 4, (1,))) * 90
+            image, label = image.rotate(degree, expand=True), label.rotate(degree, expand=True)
+            image, label = image.resize((args.tile_w, args.tile_h)), label.resize((args.tile_w, args.tile_h))
+        label = torch.from_numpy(np.asarray(label).astype(np.uint8)).long()
+        is_cls, is_reg, is_seg = (isinstance(item['label'], t) for t in (int, float, str))
+        return self.image_aug(image.convert('RGB')), label, is_cls, is_reg, is_seg, (item['label'] if not is_seg else -1)
+
+
+def GenerateIterator(impth, eval=False, duplicate_dataset=1):
+    """DataLoader over Dataset with the reference's settings (:71-80): args.batch_size, shuffled, args.workers, pinned memory."""
+    return torch.utils.data.DataLoader(Dataset(impth, eval=eval, duplicate_dataset=duplicate_dataset), batch_size=args.batch_size,
+                                       shuffle=True, num_workers=args.workers, pin_memory=True)
 
 
 def _open_slide_default(path):

@@ -1,6 +1,7 @@
 """Drop-in for the whole-slide evaluation drivers of the reference's ``utils.eval``:
 predict_tumorbed (/root/reference/utils/eval.py:155-286) and predict_wsis (:22-152), plus the
-region-paint stage that the reference keeps as module-level code in scannet.py:145-155.
+region-paint stage that the reference keeps as module-level code in scannet.py:145-155, and the
+patch scoring drivers predict_reg (:289-351), predict_breastpathq (:354-412) and predict_cls (:415-449).
 
 Everything between "tile list" and "u8 heat map" stays on the GPU: batches come from the device
 tile producer, the encoder/classifier run on the HIP trunk, per-tile logits are accumulated into
@@ -60,6 +61,26 @@ class SlideClassifierModel(torch.nn.Module):
             eng.set_head((lin.weight, lin.bias))
             self._head_sig = (id(eng), sig)
         return eng
+
+
+    def _views_mlp(self, name):
+        """The Linear tensors of `regressor.fc` / `classifier.fc` as wsi_mlp_views takes them, rebuilt when a tensor changes."""
+        fc = getattr(self, name).fc
+        lins = [m for m in fc if isinstance(m, torch.nn.Linear)]
+        sig = tuple((t.data_ptr(), t._version) for m in lins for t in (m.weight, m.bias))
+        cache = self.__dict__.setdefault('_views_mlp_cache', {})
+        if cache.get(name, (None, None))[0] != sig:
+            cache[name] = (sig, tuple(t.detach().to(torch.float32).contiguous() for m in lins for t in (m.weight, m.bias)))
+        return cache[name][1]
+
+    def regress_views(self, device=None, **kw):
+        """engine.forward_views with ``regressor.fc`` (Linear, ReLU, Linear) as the MLP head: the mean regressor output over the views
+        (default: the reference's four) of every patch; kw: x= or slide_u8=, tile_xy=, ph=, pw=; views=, clamp=, per_view=."""
+        return self.encoder.net.hip_engine(device).forward_views(mlp=self._views_mlp('regressor'), **kw)
+
+    def classify_views(self, device=None, **kw):
+        """regress_views with ``classifier.fc`` (one Linear) as the head: mean logits over the views."""
+        return self.encoder.net.hip_engine(device).forward_views(mlp=self._views_mlp('classifier'), **kw)
 
 
 def _device_of(model):
@@ -369,3 +390,172 @@ def predict_regions(model, iterator, metadata, label_shape, class_probs=None, ra
     if was_training:
         model.train()
     return pred_mask
+
+
+# ---------------------------------------------------------------------------------------------- patch scoring drivers
+def torch_view(image, v):
+    """View `v` (include/wsi_hip.h: T = 1, FY = 2, FX = 4) of an (N, C, H, W) tensor with torch ops; ids 0, 1, 2, 5 are the reference's
+    image, image.transpose(2, 3), image.flip(2), image.transpose(2, 3).flip(3) (utils/eval.py:308-313)."""
+    if v & E.VIEW_T:
+        image = image.transpose(2, 3)
+    if v & E.VIEW_FY:
+        image = image.flip(2)
+    if v & E.VIEW_FX:
+        image = image.flip(3)
+    return image
+
+
+def module_loop_views(model, head, image, views=E.VIEWS_REFERENCE):
+    """The reference's loop as it writes it (utils/eval.py:307-321, :336): `head(model.encoder(view)[0])` per view with torch views,
+    summed in view order and divided by their number.  The path of any GPU model exposing .encoder and the head, and the baseline
+    the fused path is measured against."""
+    acc = None
+    for v in views:
+        pred = head(model.encoder(torch_view(image, v).contiguous())[0])
+        acc = pred.clone() if acc is None else acc.add_(pred)
+    return acc / len(views)
+
+
+def _fused_head(model, name):
+    from models import models as M
+    return isinstance(model, SlideClassifierModel) and isinstance(getattr(model, name), M.Regressor if name == 'regressor' else M.Classifier)
+
+
+def _score_views(model, name, views, clamp=None, **source):
+    """Mean head output (N, K) over `views`: the fused HIP path for a SlideClassifierModel with models.models heads, the module loop
+    for any other model (fp32 input only)."""
+    if _fused_head(model, name):
+        return (model.regress_views if name == 'regressor' else model.classify_views)(views=views, clamp=clamp, **source)
+    out = module_loop_views(model, getattr(model, name), source['x'], views)
+    return out.clamp(clamp[0], clamp[1]) if clamp is not None else out
+
+
+def cls_scores(gts, preds):
+    """(accuracy, F1 of class 1) of integer labels: what the reference prints from np.mean(preds == gts) and sklearn's
+    f1_score(gts, preds) (binary default: 2 TP / (2 TP + FP + FN), 0 where that is undefined), restated in NumPy."""
+    gts, preds = np.asarray(gts).reshape(-1), np.asarray(preds).reshape(-1)
+    if gts.shape != preds.shape:
+        raise ValueError('%d labels for %d predictions' % (gts.size, preds.size))
+    tp = int(np.sum((preds == 1) & (gts == 1)))
+    fp = int(np.sum((preds == 1) & (gts != 1)))
+    fn = int(np.sum((preds != 1) & (gts == 1)))
+    acc = float(np.mean(preds == gts)) if gts.size else float('nan')
+    return acc, (2.0 * tp / (2 * tp + fp + fn) if 2 * tp + fp + fn else 0.0)
+
+
+def predict_reg(model, dataset, ep):
+    """Cellularity regression over a patch iterator (reference utils/eval.py:289-351).  `dataset` yields (image, label, is_cls, is_reg,
+    is_seg, cls_code) batches (utils.dataset.GenerateIterator); every image is scored as the mean of `model.regressor` over the
+    reference's four views.  Prints the reference's l1 / mse line and returns {'preds', 'gts', 'l1', 'mse'}; the model's
+    train / eval state is restored.  A SlideClassifierModel with a models.models.Regressor runs the fused path
+    (engine.forward_views); any other GPU model with .encoder / .regressor runs the reference's module loop.
+    Out of scope: the segmentation overlay PNGs the reference writes to a hard-coded data/cell_seg/ (:323-334) - no decoder runs."""
+    dev = _device_of(model)
+    was_training = model.training
+    model.eval()
+    preds, gts = [], []
+    with torch.no_grad():
+        for image, label, is_cls, is_reg, is_seg, cls_code in dataset:
+            pred = _score_views(model, 'regressor', E.VIEWS_REFERENCE, x=image.to(dev))
+            preds.extend(pred.reshape(-1).cpu().numpy())
+            gts.extend(np.asarray(cls_code).reshape(-1))
+    preds, gts = np.asarray(preds), np.asarray(gts)
+    l1, mse = float(np.mean(np.abs(preds - gts))), float(np.mean((preds - gts) ** 2))
+    print('Ep. {}, l1 {:.3f}, mse {:.3f}, '.format(ep, l1, mse))
+    if was_training:
+        model.train()
+    return {'preds': preds, 'gts': gts, 'l1': l1, 'mse': mse}
+
+
+def predict_cls(model, dataset, ep):
+    """Patch classification over the same iterator (reference utils/eval.py:415-449): arg-max of `model.classifier` on the items
+    flagged is_cls, accuracy and the binary F1 of class 1 (`cls_scores`).  Prints the reference's line and returns {'preds', 'gts',
+    'acc', 'f1'}.
+    Deviation from the reference: `preds` and `gts` both hold the is_cls items only.  The reference extends `gts` with EVERY item's
+    code and, for a batch without any is_cls item, extends `preds` with the previous batch's stale predictions, so its two lists
+    only line up when every item is a classification item - the case in which both agree."""
+    dev = _device_of(model)
+    was_training = model.training
+    model.eval()
+    preds, gts = [], []
+    with torch.no_grad():
+        for image, label, is_cls, is_reg, is_seg, cls_code in dataset:
+            keep = torch.as_tensor(is_cls).to(torch.bool)
+            if not bool(keep.any()):
+                continue
+            logits = _score_views(model, 'classifier', (0,), x=image[keep].to(dev))
+            preds.extend(torch.argmax(logits, 1).cpu().numpy())
+            gts.extend(np.asarray(cls_code)[keep.numpy()])
+    preds, gts = np.asarray(preds), np.asarray(gts)
+    acc, f1 = cls_scores(gts, preds)
+    print('Ep. {}, acc {:.3f},f1 {:.3f}'.format(ep, acc, f1))
+    if was_training:
+        model.train()
+    return {'preds': preds, 'gts': gts, 'acc': acc, 'f1': f1}
+
+
+def breastpathq_rows(label_csv_path):
+    """[(image id, region id)] of the label file in its row order (header skipped), as the reference reads it (:373-381)."""
+    import csv
+    with open(label_csv_path) as f:
+        reader = csv.reader(f, delimiter=',')
+        next(reader)
+        return [(int(row[0]), int(row[1])) for row in reader if row]
+
+
+def breastpathq_image(dataset_path, image_id, region_id):
+    """<dataset_path>/<image>_<region>.tif as RGB u8 (tile_h, tile_w, 3): Pillow's Image.resize((tile_w, tile_h), Image.BILINEAR), which
+    is what torchvision.transforms.Resize((tile_h, tile_w)) does to a PIL image (:358, :385-386)."""
+    from PIL import Image
+    image = Image.open('{}/{}_{}.tif'.format(dataset_path, image_id, region_id)).convert('RGB')
+    return np.asarray(image.resize((args.tile_w, args.tile_h), Image.BILINEAR))
+
+
+def predict_breastpathq(model, ep, dataset_path, label_csv_path, out_csv=None, batch=None, score=None):
+    """BreastPathQ submission table (reference utils/eval.py:354-412): every <image>_<region>.tif of the label file, in its row order,
+    resized to (tile_h, tile_w), scored as the mean of `model.regressor` over the reference's four views and clamped to [0, 1];
+    writes Ozan_Results_<ep>.csv (or `out_csv`) with the header slide,rid,p and returns the rows [(image id, region id, p)].
+    The regions travel as u8: `batch` of them (default: what fills the engine's batch with four views each) are uploaded as one
+    packed-RGB stack and scored through the u8 view path, the clamp inside wsi_mlp_views; a model without the fused heads gets the
+    normalised fp32 batch and the module loop.  `score(u8 (B, tile_h, tile_w, 3) ndarray) -> B scores` replaces the scoring (tests)."""
+    import csv
+    views = E.VIEWS_REFERENCE
+    was_training = model.training if model is not None else False
+    if score is None:
+        dev = _device_of(model)
+        model.eval()
+        fused = _fused_head(model, 'regressor')
+        if batch is None and fused:
+            eng = model.encoder.net.hip_engine(dev)
+            batch = getattr(eng, '_par', eng)._views_chunk(args.tile_h, args.tile_w, len(views))
+        lut = torch.from_numpy(E.normalize_lut(args.dataset_mean, args.dataset_std)).to(dev)
+
+        def score(u8):
+            b, h, w, _ = u8.shape
+            stack = S._upload(u8.reshape(b * h, w, 3), torch.uint8, dev)
+            xy = torch.zeros((b, 2), dtype=torch.int32, device=dev)
+            xy[:, 1] = torch.arange(b, dtype=torch.int32, device=dev) * h
+            if fused:
+                out = model.regress_views(slide_u8=stack, tile_xy=xy, ph=h, pw=w, views=views, clamp=(0.0, 1.0))
+            else:
+                out = _score_views(model, 'regressor', views, clamp=(0.0, 1.0), x=E.tile_gather(stack, xy, h, w, lut))
+            return out.reshape(-1).cpu().numpy()
+    batch = int(batch) if batch else 64
+    ids = breastpathq_rows(label_csv_path)
+    rows = []
+    with torch.no_grad():
+        for i in range(0, len(ids), batch):
+            part = ids[i:i + batch]
+            u8 = np.stack([breastpathq_image(dataset_path, a, b) for a, b in part])
+            p = np.asarray(score(u8), dtype=np.float32).reshape(-1)
+            if p.shape[0] != len(part):
+                raise ValueError('the scoring function returned %d scores for %d regions' % (p.shape[0], len(part)))
+            rows.extend((a, b, v) for (a, b), v in zip(part, p))
+    with open(out_csv if out_csv is not None else 'Ozan_Results_{}.csv'.format(ep), 'w', newline='') as f:
+        writer = csv.DictWriter(f, fieldnames=['slide', 'rid', 'p'])
+        writer.writeheader()
+        for a, b, v in rows:
+            writer.writerow({'slide': a, 'rid': b, 'p': v})
+    if was_training:
+        model.train()
+    return rows

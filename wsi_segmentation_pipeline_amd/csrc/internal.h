@@ -47,6 +47,9 @@ int wsi_linear_dispatch(const float* x, const float* w, const float* bias, float
                         hipStream_t st);
 int wsi_pf_pack_dispatch(const float* in, void* out, const PFGeom& g, int planes, hipStream_t st);
 int wsi_pf_unpack_dispatch(const void* in, float* out, const PFGeom& g, int planes, hipStream_t st);
+// views.hip (it also holds the C entries wsi_tile_views_u8, wsi_views_f32 and wsi_mlp_views)
+int wsi_views_dispatch(bool u8, const void* src, long long pitch, int SH, int SW, const int* tile_xy, int nplanes, int ph, int pw,
+                       const int* views, int nviews, void* out, hipStream_t st);
 // unet.hip, tail.hip
 int wsi_upsample_concat_dispatch(const void* x, const void* skip, void* out, int n, int h, int w, int cx, int cs, int planes, hipStream_t st);
 int wsi_nhwc_to_pf_dispatch(const float* in, void* out, int n, int h, int w, int c, int planes, hipStream_t st);

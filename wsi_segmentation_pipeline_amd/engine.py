@@ -15,6 +15,9 @@ from . import native
 BN_EPS = 1e-5                                   # nn.BatchNorm2d default (reference resnets_shift.py:117)
 PARITY, SPEED, MX = 2, 1, 3                     # planes: fp16 hi + fp16 lo pair (3 passes; r01-r04: bf16 pair) / single bf16 / fp16 + MX-fp6 cross terms
 AUTO = 'auto'                                   # AutoTrunkEngine: mx unless a stratified two-mode probe of the slide says parity
+# View ids (include/wsi_hip.h): transpose first if T, then reverse the rows of the result if FY, then its columns if FX.
+VIEW_T, VIEW_FY, VIEW_FX = 1, 2, 4
+VIEWS_REFERENCE = (0, 1, 2, 5)                  # image, transpose(2, 3), flip(2), transpose(2, 3).flip(3) (reference utils/eval.py:308-313)
 
 
 def _np_ptr(a):
@@ -66,6 +69,93 @@ def batch_sizes(n, cap, h=256, w=256):
         return [base] * (k - 1) + [n - base * (k - 1)]
     mb = -(-n // k)                                        # equal-sized batches: ceil(n / ceil(n / cap))
     return [min(mb, n - i) for i in range(0, n, mb)]
+
+
+def view_ids(views):
+    """The view list as 1 to 8 ints of 0 to 7 (repeats allowed); ValueError otherwise."""
+    ids = [int(v) for v in views]
+    if not 1 <= len(ids) <= 8 or any(not 0 <= v <= 7 for v in ids):
+        raise ValueError('a view list has 1 to 8 ids of 0 to 7 (T = 1, FY = 2, FX = 4), got %r' % (views,))
+    return ids
+
+
+def view_groups(ids, h, w):
+    """Positions of `ids` grouped by output shape: one group for square patches, else the untransposed and the transposed views."""
+    if h == w:
+        return [list(range(len(ids)))]
+    return [g for g in ([k for k, v in enumerate(ids) if not v & VIEW_T], [k for k, v in enumerate(ids) if v & VIEW_T]) if g]
+
+
+def _view_shape(ids, h, w):
+    if h != w and len({v & VIEW_T for v in ids}) > 1:
+        raise ValueError('views %r of a %d x %d patch have two shapes: pass the transposed and the untransposed ones separately' % (ids, h, w))
+    return (w, h) if ids[0] & VIEW_T else (h, w)
+
+
+def tile_views(slide_u8, tile_xy, ph, pw, views):
+    """wsi_tile_views_u8: the views `views` of the n tiles of ph x pw at tile_xy (N,2) int32 of the (SH,SW,3) u8 slide -> (atlas,
+    atlas_xy): an (V * n * hv, wv, 3) u8 "slide" of dense oriented tiles, view-major, and their corners (V * n, 2) int32 =
+    (0, (k * n + i) * hv), ready for forward_tiles."""
+    lib = native.load()
+    _require_gpu(slide_u8, 'slide')
+    _require_gpu(tile_xy, 'tile list')
+    if slide_u8.dtype != torch.uint8 or slide_u8.dim() != 3 or slide_u8.shape[2] != 3 or slide_u8.stride(2) != 1 or slide_u8.stride(1) != 3:
+        raise ValueError('slide must be (H,W,3) uint8 with packed RGB pixels')
+    ids = view_ids(views)
+    hv, wv = _view_shape(ids, ph, pw)
+    tile_xy = tile_xy.to(torch.int32).contiguous()
+    n = int(tile_xy.shape[0])
+    rows = len(ids) * n
+    atlas = torch.empty((rows * hv, wv, 3), dtype=torch.uint8, device=slide_u8.device)
+    arr = (C.c_int * len(ids))(*ids)
+    native.check(lib.wsi_tile_views_u8(_ptr(slide_u8), slide_u8.stride(0), slide_u8.shape[0], slide_u8.shape[1], _ptr(tile_xy), n, ph, pw,
+                                       arr, len(ids), _ptr(atlas), _stream()), 'wsi_tile_views_u8')
+    atlas_xy = torch.zeros((rows, 2), dtype=torch.int32, device=slide_u8.device)
+    atlas_xy[:, 1] = torch.arange(rows, dtype=torch.int32, device=slide_u8.device) * hv
+    return atlas, atlas_xy
+
+
+def views_f32(x, views):
+    """wsi_views_f32: (N,3,H,W) fp32 on the GPU -> the stacked views (V * N, 3, hv, wv), view-major."""
+    lib = native.load()
+    _require_gpu(x, 'input batch')
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise ValueError('expected (N,3,H,W), got %s' % (tuple(x.shape),))
+    x = x.to(torch.float32).contiguous()
+    ids = view_ids(views)
+    n, _, h, w = x.shape
+    hv, wv = _view_shape(ids, h, w)
+    out = torch.empty((len(ids) * n, 3, hv, wv), dtype=torch.float32, device=x.device)
+    arr = (C.c_int * len(ids))(*ids)
+    native.check(lib.wsi_views_f32(_ptr(x), n, h, w, arr, len(ids), _ptr(out), _stream()), 'wsi_views_f32')
+    return out
+
+
+def mlp_views(feat, n, nviews, mlp, clamp=None, per_view=False):
+    """wsi_mlp_views: feat (V * n, F) fp32 view-major -> (mean (n, K), per-view outputs (V * n, K) or None).  mlp = (w1, b1, w2, b2)
+    (Regressor.fc: Linear, ReLU, Linear) or (w, b) (Classifier.fc: one Linear); clamp = (lo, hi) or None."""
+    lib = native.load()
+    _require_gpu(feat, 'features')
+    feat = feat.to(torch.float32).contiguous()
+    t = [torch.as_tensor(a).detach().to(feat.device, torch.float32).contiguous() for a in mlp]
+    if len(t) == 4:
+        w1, b1, w2, b2 = t
+        j = int(w1.shape[0])
+        ok = w1.dim() == 2 and w1.shape[1] == feat.shape[1] and b1.shape == (j,) and w2.dim() == 2 and w2.shape[1] == j
+    elif len(t) == 2:
+        (w2, b2), w1, b1, j = t, None, None, 0
+        ok = w2.dim() == 2 and w2.shape[1] == feat.shape[1]
+    else:
+        raise ValueError('mlp is (w1, b1, w2, b2) or (w, b)')
+    if not ok or b2.shape != (w2.shape[0],) or feat.dim() != 2 or feat.shape[0] != nviews * n:
+        raise ValueError('mlp shapes do not match features %s of %d views x %d patches' % (tuple(feat.shape), nviews, n))
+    k = int(w2.shape[0])
+    mean = torch.empty((n, k), dtype=torch.float32, device=feat.device)
+    pv = torch.empty((nviews * n, k), dtype=torch.float32, device=feat.device) if per_view else None
+    lo, hi = (float(clamp[0]), float(clamp[1])) if clamp is not None else (0.0, 0.0)
+    native.check(lib.wsi_mlp_views(_ptr(feat), n, nviews, int(feat.shape[1]), _ptr(w1), _ptr(b1), j, _ptr(w2), _ptr(b2), k,
+                                   int(clamp is not None), lo, hi, _ptr(pv), _ptr(mean), _stream()), 'wsi_mlp_views')
+    return mean, pv
 
 
 # What the host layer knows of an architecture: convs per block and their kernel sizes, the width factor of a block's output, the first
@@ -400,6 +490,74 @@ class TrunkEngine:
                         t.record_stream(cur)
         return tuple(None if o[0] is None else (o[0] if len(o) == 1 else torch.cat(o)) for o in zip(*outs))
 
+    # ------------------------------------------------------------------ test-time views
+    def _views_input(self, x, slide_u8, tile_xy, ph, pw):
+        """(n, h, w) of a forward_views input: either x (N,3,H,W) fp32 or a u8 slide with tile corners and the patch shape."""
+        if (x is None) == (slide_u8 is None):
+            raise ValueError('forward_views takes either x= or slide_u8=, tile_xy=, ph=, pw=')
+        if x is not None:
+            _require_gpu(x, 'input batch')
+            if x.dim() != 4 or x.shape[1] != 3:
+                raise ValueError('expected (N,3,H,W), got %s' % (tuple(x.shape),))
+            return int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+        if tile_xy is None or ph is None or pw is None:
+            raise ValueError('the u8 path needs tile_xy, ph and pw')
+        _require_gpu(slide_u8, 'slide')
+        _require_gpu(tile_xy, 'tile list')
+        return int(tile_xy.shape[0]), int(ph), int(pw)
+
+    def _views_chunk(self, h, w, nviews):
+        """Patches per chunk of forward_views: all views of a patch in one chunk, V * chunk within the trunk's batch."""
+        cap = self.max_batch if self.max_batch else self._auto_cap(h, w)
+        return max(1, cap // nviews)
+
+    def views_features(self, ids, x, slide_u8, tile_xy, h, w):
+        """Pooled features (V * m, FEAT_C), view-major, of the views `ids` of m patches: the view producer, then the existing
+        forward with feat=True.  Non-square patches: one trunk pass for the untransposed and one for the transposed views, the
+        features put back in view order."""
+        groups = view_groups(ids, h, w)
+        m = int(x.shape[0]) if x is not None else int(tile_xy.shape[0])
+        parts = [None] * len(ids)
+        for g in groups:
+            gv = [ids[k] for k in g]
+            if x is not None:
+                f = self.forward_f32(views_f32(x, gv), feat=True)[0]
+            else:
+                atlas, axy = tile_views(slide_u8, tile_xy, h, w, gv)
+                hv, wv = _view_shape(gv, h, w)
+                f = self.forward_tiles(atlas, axy, hv, wv, feat=True, logits=False)[0]
+            if len(groups) == 1:
+                return f
+            for i, k in enumerate(g):
+                parts[k] = f[i * m:(i + 1) * m]
+        return torch.cat(parts)
+
+    def forward_views(self, x=None, slide_u8=None, tile_xy=None, ph=None, pw=None, views=VIEWS_REFERENCE, mlp=None, clamp=None,
+                      per_view=False):
+        """The reference's test-time augmentation loop (utils/eval.py:307-336, :391-410) on the HIP path: the views `views` of every
+        patch - x (N,3,H,W) normalised fp32, or the N tiles of ph x pw at tile_xy of a u8 slide - through the trunk, the MLP head
+        `mlp` = (w1, b1, w2, b2) or (w, b) over the pooled features of every view, and their mean over the views (wsi_mlp_views),
+        clamped to `clamp` = (lo, hi) if given.  Returns mean (N, K); with per_view, (mean, outputs (N, V, K))."""
+        if mlp is None:
+            raise ValueError('forward_views needs mlp=(w1, b1, w2, b2) or (w, b)')
+        n, h, w = self._views_input(x, slide_u8, tile_xy, ph, pw)
+        ids = view_ids(views)
+        step = self._views_chunk(h, w, len(ids))
+        means, pvs = [], []
+        for i in range(0, n, step):
+            m = min(step, n - i)
+            f = self.views_features(ids, None if x is None else x[i:i + m], slide_u8, None if tile_xy is None else tile_xy[i:i + m], h, w)
+            mean, pv = mlp_views(f, m, len(ids), mlp, clamp, per_view)
+            means.append(mean)
+            if per_view:
+                pvs.append(pv.view(len(ids), m, -1).permute(1, 0, 2))
+        if not means:
+            raise ValueError('forward_views needs at least one patch')
+        mean = means[0] if len(means) == 1 else torch.cat(means)
+        if not per_view:
+            return mean
+        return mean, (pvs[0] if len(pvs) == 1 else torch.cat(pvs)).contiguous()
+
     # ------------------------------------------------------------------ small ops
     def linear(self, x, weight, bias, relu=False):
         _require_gpu(x, 'linear input')
@@ -601,6 +759,25 @@ class AutoTrunkEngine:
         if self._mx is not None and (self._chosen is None or not self._same_slide(slide_u8, key)):
             self.decide(self.probe_tiles(slide_u8, tile_xy, ph, pw, slide_id=slide_id))
         return self._chosen.forward_tiles(slide_u8, tile_xy, ph, pw, feat=feat, logits=logits, fmap=fmap, tap=tap)
+
+
+    def forward_views(self, x=None, slide_u8=None, tile_xy=None, ph=None, pw=None, views=VIEWS_REFERENCE, **kw):
+        """TrunkEngine.forward_views in the mode decided ONCE: without a decision, the views of the first chunk are probed in both
+        modes on the pooled features (the feature-relative probe, whatever fused head is set: the MLP reads the features), under the
+        constant slide id 'forward_views' - every call builds a new atlas tensor, which must not probe again.  The decision holds
+        until reset()."""
+        if self._mx is not None and self._chosen is None:
+            n, h, w = self._par._views_input(x, slide_u8, tile_xy, ph, pw)
+            ids = view_ids(views)
+            m = min(n, self._par._views_chunk(h, w, len(ids)))
+            idx = self._stratified(m)                         # a stratified sample of the chunk's patches, all their views
+            sub = None if x is None else x[:m][idx]
+            xy = None if tile_xy is None else tile_xy[:m][idx].contiguous()
+            run = lambda e: (e.views_features(ids, sub, slide_u8, xy, h, w), None, None)
+            err, self._what, self._n = self._probe(run)
+            self._probed = (('id', 'forward_views'), None)
+            self.decide(err, scope='views')
+        return self._chosen.forward_views(x=x, slide_u8=slide_u8, tile_xy=tile_xy, ph=ph, pw=pw, views=views, **kw)
 
 
 def trunk_engine(state_dict, device, precision=AUTO, head=None, **kw):
