@@ -443,7 +443,8 @@ int wsi_esp(const double* pts_xy, int n, int num_pts, double* out_xy, double* sc
 
 /* ---- U-Net decoder: the dense 'seg' path (utils/eval.py:51 `model(batch_image)`, :196-200 `model.decoder(model.encoder(x))`) ----
  * The reference drives segmentation_models_pytorch's Unet(args.arch_encoder) here (eval_tumorbed.py:21-28; 'resnet18' by default - the
- * encoder is the trunk at whatever depth wsi_trunk_weights.blocks states, its five maps keep their channels): third-party, absent and
+ * encoder is the trunk at whatever depth wsi_trunk_weights.blocks states, its five maps keep their channels; Bottleneck encoders -
+ * 'resnet50', 'resnet101' - have entries of their own below, wsi_unet_bneck_*): third-party, absent and
  * un-pinned, so the architecture is restated from the published 0.0.x source (parity unpinned):
  * encoder maps [x4 512 ch /32, x3 256 /16, x2 128 /8, x1 64 /4, x0 64 /2 (conv1+bn1+relu before the max pool)]; five decoder
  * blocks L = 1..5: nearest x2 upsample, concat the next skip, 2 x (conv3x3 + BN + ReLU) to 256/128/64/32/16 channels;
@@ -452,7 +453,9 @@ int wsi_esp(const double* pts_xy, int n, int num_pts, double* out_xy, double* sc
  * cout = {256,256, 128,128, 64,64, 64,64, 64,64}; head_w [classes][head_cin] fp32 with head_cin = 16.
  * wsi_unet_forward: stem + trunk + decoder for n patches (inputs as wsi_trunk_forward); logits_out [n][classes][h][w] fp32 and /
  *   or enc_out[5] = the five encoder maps as fp32 NCHW (either may be NULL).  Workspace: wsi_unet_workspace_bytes, zero-filled
- *   once by wsi_unet_workspace_init; workspace_n as in wsi_trunk_forward.
+ *   once by wsi_unet_workspace_init; workspace_n as in wsi_trunk_forward.  -22 before the workspace is touched: what wsi_trunk_forward
+ *   refuses, a cin / cout table that disagrees with the widths above and, when logits are asked for, a NULL decoder conv (convs 0-7;
+ *   convs 8-9 and the head too unless tail_w stands in for them).
  * wsi_unet_decoder: the decoder alone on caller-held fp32 NCHW encoder maps (same workspace). */
 typedef struct {
     const void* conv_w[10]; const float* conv_b[10];
@@ -485,6 +488,22 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
                      int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
 int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
                      void* workspace, int workspace_n, float* logits_out, void* stream);
+/* The same U-Net on a Bottleneck encoder (ResNet-50 / ResNet-101: wsi_bneck_weights at whatever depth its `blocks` state; planes 1 or 2,
+ * as wsi_bneck_forward).  Encoder maps [x4 2048 ch /32, x3 1024 /16, x2 512 /8, x1 256 /4, x0 64 /2]; the decoder's channels stay
+ * 256/128/64/32/16, so only the first conv of blocks 1-4 changes its input: (c_up, c_skip) = (2048, 1024), (256, 512), (128, 256),
+ * (64, 64), (32, 0), i.e. cin = {3072,256, 768,128, 384,64, 128,32, 32,32} and cout = {256,256, 128,128, 64,64, 32,32, 32,32} in parity
+ * mode (planes 1 pads 32 to 64).  Same wsi_unet_decoder_weights, same fused tail, same launches: every block's first conv takes
+ * the fused upsample + concat route of the slab3 kernels.  The four entries mirror the four above argument for argument; the workspace is
+ * wsi_bneck_workspace_bytes + the decoder's part and carries no layout tag.  -22 before the workspace is touched: what
+ * wsi_bneck_forward refuses (depth table, planes, shape, a NULL pointer a run would read, no input source), a cin / cout table that
+ * disagrees with the widths above, a NULL decoder conv. */
+size_t wsi_unet_bneck_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_unet_bneck_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_unet_bneck_forward(const wsi_bneck_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                           long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                           int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_unet_bneck_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                           void* workspace, int workspace_n, float* logits_out, void* stream);
 /* F.interpolate(pred_src, (tile_h * r, tile_w * r)) of utils/eval.py:202-206 (default mode 'nearest') on planes_n
  * contiguous fp32 (hs, ws) planes */
 int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, void* stream);

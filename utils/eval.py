@@ -29,7 +29,7 @@ class TrunkEncoder(torch.nn.Module):
     encoder(x) -> [deepest feature map] (the reference indexes ``encoding[0]`` for the 512-channel map, utils/eval.py:196-198;
     2048 channels for a Bottleneck net).  ``out_shapes`` lists the channels of the net's five maps, deepest first, as smp's encoders
     do; only the deepest is produced here.  The full five-map encoder of the dense 'seg' model is
-    wsi_segmentation_pipeline_amd.unet.UNetEncoder (BasicBlock nets only)."""
+    wsi_segmentation_pipeline_amd.unet.UNetEncoder (BasicBlock nets) / UNetBottleneckEncoder."""
 
     def __init__(self, resnet):
         super().__init__()

@@ -373,10 +373,12 @@ int wsi_bneck_workspace_init(void* workspace, int n, int h, int w, int planes, v
     return hipMemsetAsync((char*)workspace + p.pool, 0, p.total - p.pool, (hipStream_t)stream) == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 // stem + blocks; stops after `stop_after` (0 = pool, 1..total = blocks in network order, >= total all).  `p`: the plan for cap >= n images.
+// `opt` (U-Net): x0_out and stage_off as in trunk_run - the last block of a stage writes into one of the stage's own two `wide` buffers,
+// which no later stage touches, so all four stage outputs are still there after the run (allow_split has nothing to switch off here).
 // ProfScope kinds: 4 = stem+maxpool, 11 = stride-1 1x1 (conv1, conv3, layer 1's downsample), 1 = 3x3 stride 1, 2 = 3x3 stride 2,
 // 3 = 1x1 stride-2 downsample
 static int bneck_run(const wsi_bneck_weights* wt, const TrunkDepth& d, const TileSource& src, int n, int /* cap: no address depends on it */,
-                     int h, int w, void* workspace, int stop_after, hipStream_t st, const BneckPlan& p, TrunkOut& res) {
+                     int h, int w, void* workspace, int stop_after, hipStream_t st, const BneckPlan& p, TrunkOut& res, const TrunkOpts& opt = {}) {
     constexpr int CONVS = 3;                           // convs per block
     char* ws = (char*)workspace;
     const int planes = wt->planes;
@@ -384,7 +386,7 @@ static int bneck_run(const wsi_bneck_weights* wt, const TrunkDepth& d, const Til
     {
         ProfScope ps(st, 4, 2.0 * n * (h / 2) * (w / 2) * 64.0 * 147.0);
         rc = stem_run(src, wt->stem_w, wt->stem_b, wt->stem_w_u8, wt->stem_b_u8, wt->norm, n, h, w, (float*)(ws + p.stem_scratch), ws + p.pool,
-                      planes, st, 0);
+                      planes, st, 0, 0, opt.x0_out);
         if (rc) return rc;
     }
     res = {p.pool, 64, p.sh[0], p.sw[0]};
@@ -424,6 +426,7 @@ static int bneck_run(const wsi_bneck_weights* wt, const TrunkDepth& d, const Til
             if ((rc = run(11, conv(m2, out, resid, 2, H, W, M, C, 1, 1, 1)))) return rc;
             x = out; xc = C;
             res = {(size_t)(out - ws), C, H, W};
+            if (b == d.nb[s] - 1 && opt.stage_off) opt.stage_off[s] = res.off;
             if (++block == stop_after) return WSI_OK;
         }
     }
@@ -432,17 +435,26 @@ static int bneck_run(const wsi_bneck_weights* wt, const TrunkDepth& d, const Til
 
 // ------------------------------------------------------------------------------------ the forward entries of both architectures
 // What the entries need to know of an architecture: its weight struct, its workspace plan and its run function.
+// For the U-Net: the channels of its five encoder maps, deepest first (x4 at / 32, x3, x2, x1 at / 4 = the last block of layer4..1, x0 at
+// / 2 = the stem conv before the pool), the workspace's zero-fill, and the buffer of stage s into which wsi_unet_*_decoder packs a
+// caller-held map of that stage.
 struct BasicNet {
     using Weights = wsi_trunk_weights;
     using Plan = TrunkPlan;
     static constexpr auto plan = trunk_plan;
-    template <class... A> static int run(A&&... a) { return trunk_run(a...); }          // (a plain run: no TrunkOpts)
+    template <class... A> static int run(A&&... a) { return trunk_run(a...); }          // (with or without TrunkOpts)
+    static constexpr int enc_c[5] = {512, 256, 128, 64, 64};
+    static constexpr auto ws_init = wsi_trunk_workspace_init;
+    static size_t stage_buf(const Plan& p, int s) { return p.buf[s][0]; }
 };
 struct BneckNet {
     using Weights = wsi_bneck_weights;
     using Plan = BneckPlan;
     static constexpr auto plan = bneck_plan;
-    static constexpr auto run = bneck_run;
+    template <class... A> static int run(A&&... a) { return bneck_run(a...); }
+    static constexpr int enc_c[5] = {2048, 1024, 512, 256, 64};
+    static constexpr auto ws_init = wsi_bneck_workspace_init;
+    static size_t stage_buf(const Plan& p, int s) { return p.wide[s][0]; }
 };
 // Checks every argument (-22 before the workspace is touched and before any launch: trunk_ready), then runs the net through block
 // `stop_after` (0 = pool; negative: the whole net) in a workspace planned for workspace_n (0: n) images; `res`: where its last tensor is.
@@ -508,28 +520,27 @@ int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, cons
 }
 
 // ------------------------------------------------------------------------------------ U-Net (dense 'seg' path)
-// smp-style decoder on the BasicBlock trunk (any depth: the five encoder maps keep their channels): five blocks of [nearest x2 upsample, concat skip, 2 x (3x3 conv + BN + ReLU)]
-// at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the split-precision modes, 64 in
-// speed mode; the padding channels carry zero weights), 1x1 head.
-static const int kUnetSkipC[5] = {256, 128, 64, 64, 0};      // encoder maps x3, x2, x1, x0 (and none for the last block)
-// encoder map i of an h x w input, deepest first: x4 (512 channels, / 32), x3, x2, x1 (64, / 4), x0 (64, / 2: the stem conv before the pool)
+// smp-style decoder on either trunk (any depth: the five encoder maps keep their channels, Net::enc_c): five blocks of [nearest x2 upsample,
+// concat skip, 2 x (3x3 conv + BN + ReLU)] at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the
+// split-precision modes, 64 in speed mode; the padding channels carry zero weights), 1x1 head.  Everything below reads the encoder's
+// channels from the one table it is handed: block L takes the previous block's output (x4 = ec[0] for the first) and skips ec[L + 1].
+// encoder map i of an h x w input, deepest first: x4 (/ 32), x3, x2, x1 (/ 4), x0 (/ 2: the stem conv before the pool)
 struct EncMap { int c, h, w; };
-static EncMap enc_map(int i, int h, int w) {
-    static const int ec[5] = {512, 256, 128, 64, 64};
+static EncMap enc_map(const int ec[5], int i, int h, int w) {
     return {ec[i], i < 4 ? h >> (5 - i) : h / 2, i < 4 ? w >> (5 - i) : w / 2};
 }
 struct UnetPlan {
     size_t x0, cat[5], mid[5], out[5], total;
-    int r_h[5], r_w[5], cx[5];                               // resolution of block L; channels of its upsampled input
+    int r_h[5], r_w[5], cx[5], cs[5];                        // resolution of block L; channels of its upsampled input and of its skip (0: none)
 };
-static int unet_plan(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes, UnetPlan& u) {
+static int unet_plan(const int ec[5], const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes, UnetPlan& u) {
     if (!dw || n <= 0 || h % 32 || w % 32 || planes < 1 || planes > 3) return WSI_EINVAL;
     size_t off = 0;
-    u.x0 = off; off += align_up(wsi_pf_bytes(n, h / 2, w / 2, 64, planes), 256);
-    int cprev = 512;
+    u.x0 = off; off += align_up(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes), 256);
+    int cprev = ec[0];
     for (int L = 0; L < 5; ++L) {
-        u.r_h[L] = (h / 16) << L; u.r_w[L] = (w / 16) << L; u.cx[L] = cprev;
-        const int cin = cprev + kUnetSkipC[L], cout = dw->cout[2 * L];
+        u.r_h[L] = (h / 16) << L; u.r_w[L] = (w / 16) << L; u.cx[L] = cprev; u.cs[L] = L < 4 ? ec[L + 1] : 0;
+        const int cin = cprev + u.cs[L], cout = dw->cout[2 * L];
         if (dw->cin[2 * L] != cin || dw->cin[2 * L + 1] != cout || dw->cout[2 * L + 1] != cout || cout % (planes == 1 ? 64 : 32) || cout <= 0) return WSI_EINVAL;
         u.cat[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cin, planes), 256);
         u.mid[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cout, planes), 256);
@@ -540,19 +551,27 @@ static int unet_plan(const wsi_unet_decoder_weights* dw, int n, int h, int w, in
     u.total = off;
     return WSI_OK;
 }
-
-size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
-    UnetPlan u;
-    const size_t t = wsi_trunk_workspace_bytes(n, h, w, planes);
-    return (!t || unet_plan(dw, n, h, w, planes, u)) ? 0 : align_up(t, 256) + u.total;
+// every pointer a decoder run reads: the eight convs of blocks 1-4 always; the last block's two and the head unless the fused tail's blob
+// stands in for them (where the tail then does not apply, conv_common refuses the null pointer)
+static bool decoder_ready(const wsi_unet_decoder_weights* dw) {
+    for (int i = 0; i < (dw->tail_w ? 8 : 10); ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    return dw->tail_w || (dw->head_w && dw->head_b);
 }
 
-int wsi_unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+template <class Net>
+static size_t unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
+    typename Net::Plan p;
     UnetPlan u;
-    if (!workspace || unet_plan(dw, n, h, w, planes, u)) return WSI_EINVAL;
-    int rc = wsi_trunk_workspace_init(workspace, n, h, w, planes, stream);
+    return (Net::plan(n, h, w, planes, p) || unet_plan(Net::enc_c, dw, n, h, w, planes, u)) ? 0 : align_up(p.total, 256) + u.total;
+}
+template <class Net>
+static int unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    typename Net::Plan p;
+    UnetPlan u;
+    if (!workspace || Net::plan(n, h, w, planes, p) || unet_plan(Net::enc_c, dw, n, h, w, planes, u)) return WSI_EINVAL;
+    int rc = Net::ws_init(workspace, n, h, w, planes, stream);
     if (rc) return rc;
-    char* base = (char*)workspace + align_up(wsi_trunk_workspace_bytes(n, h, w, planes), 256);
+    char* base = (char*)workspace + align_up(p.total, 256);
     return hipMemsetAsync(base, 0, u.total, (hipStream_t)stream) == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
@@ -565,7 +584,7 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
     // caller's business: the record carries 2 * N * H * W * cin_stored * cout_stored * 9), 7 = upsample + concat glue, 8 = 1x1 head
     // r05: parity mode runs the last block and the head as ONE kernel (tail.hip) when the caller prepacked its weights
     // (wsi_unet_tail_prepack -> dw->tail_w) and the map is at most 256 wide; A/B: WSI_CONV_MODE_UNET_NO_TAIL
-    const bool tail = planes == 2 && dw->tail_w && g_routes.unet_tail && u.cx[4] == 32 && kUnetSkipC[4] == 0 && dw->classes <= 4 &&
+    const bool tail = planes == 2 && dw->tail_w && g_routes.unet_tail && u.cx[4] == 32 && u.cs[4] == 0 && dw->classes <= 4 &&
                       u.r_w[3] % 32 == 0 && u.r_w[3] <= 128 &&
                       (size_t)pf_alloc_pixels(n, u.r_h[3], u.r_w[3]) * 128 <= (size_t)0x7fffffff;      // (32-bit buffer offsets into x4: ~1000 tiles of 256 x 256)
     for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
@@ -581,12 +600,12 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
         {
             ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
             rc = g_routes.unet_fuse_up ? wsi_conv3x3_up_concat_bn_act(x, L < 4 ? enc[L + 1] : nullptr, dec + u.mid[L], dw->conv_w[2 * L], dw->conv_b[2 * L],
-                                                                      n, H, W, u.cx[L], kUnetSkipC[L], cout, 1, planes, st)
+                                                                      n, H, W, u.cx[L], u.cs[L], cout, 1, planes, st)
                                        : WSI_EINVAL;
             if (rc == WSI_EINVAL) ps.relabel(9);          // (a refused launch: its empty record is not a decoder conv)
         }
         if (rc == WSI_EINVAL) {
-            { ProfScope ps(st, 7, 0.0); rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], kUnetSkipC[L], planes, st); }
+            { ProfScope ps(st, 7, 0.0); rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], u.cs[L], planes, st); }
             ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
             if (!rc) rc = conv_common(conv3(dec + u.cat[L], dec + u.mid[L], 2 * L, cin));
         }
@@ -604,17 +623,17 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
     return rc;
 }
 
-int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
-                     long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
-                     int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
-    TrunkPlan p;
+// stem + trunk + decoder of either architecture.  Every argument is checked before the workspace is touched (run_checked's rule).
+template <class Net>
+static int unet_forward(const typename Net::Weights* wt, const wsi_unet_decoder_weights* dw, const TileSource& src, int n, int h, int w,
+                        void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    typename Net::Plan p;
     UnetPlan u;
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!wt || !dw || !workspace || n <= 0 || cap < n || (!logits_out && !enc_out) || h % 32 || w % 32) return WSI_EINVAL;
-    if (trunk_plan(cap, h, w, wt->planes, p) || unet_plan(dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
-    const TileSource src = {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut};
+    if (Net::plan(cap, h, w, wt->planes, p) || unet_plan(Net::enc_c, dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
     const TrunkDepth d(wt->blocks);
-    if (!trunk_ready(wt, d, src)) return WSI_EINVAL;
+    if (!trunk_ready(wt, d, src) || (logits_out && !decoder_ready(dw))) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
@@ -625,9 +644,10 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
     // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
     // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
     const ConvRoutes& r = g_routes;
-    const bool x0_fused = r.unet_x0_fused && !in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
+    const bool x0_fused = r.unet_x0_fused && !src.in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
                           r.stem_shared_weights;
-    int rc = trunk_run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res, {.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr, .stage_off = stage_off});
+    int rc = Net::run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res,
+                      TrunkOpts{.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr, .stage_off = stage_off});
     if (rc) return rc;
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
     // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines
@@ -640,14 +660,14 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
             rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
         } else {
             rc = wsi_stem_dispatch(a, planes == 1 ? 1 : 2, st);
-            if (!rc) rc = wsi_nhwc_to_pf_dispatch(a.out, dec + u.x0, n, h / 2, w / 2, 64, planes, st);
+            if (!rc) rc = wsi_nhwc_to_pf_dispatch(a.out, dec + u.x0, n, h / 2, w / 2, Net::enc_c[4], planes, st);
         }
     }
     if (rc) return rc;
     const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], dec + u.x0};
     if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first
         for (int i = 0; i < 5 && !rc; ++i) {
-            const EncMap m = enc_map(i, h, w);
+            const EncMap m = enc_map(Net::enc_c, i, h, w);
             if (enc_out[i]) rc = wsi_pf_unpack(enc[i], enc_out[i], n, m.c, m.h, m.w, planes, stream);
         }
         if (rc) return rc;
@@ -656,24 +676,58 @@ int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights
 }
 
 // `model.decoder(encoding)` with caller-held fp32 NCHW maps (deepest first): pack, then the same decoder launches
-int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
-                     int workspace_n, float* logits_out, void* stream) {
-    TrunkPlan p;
+template <class Net>
+static int unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                        int workspace_n, float* logits_out, void* stream) {
+    typename Net::Plan p;
     UnetPlan u;
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!dw || !enc_nchw || !workspace || !logits_out || n <= 0 || cap < n) return WSI_EINVAL;
-    if (trunk_plan(cap, h, w, planes, p) || unet_plan(dw, cap, h, w, planes, u)) return WSI_EINVAL;
+    if (Net::plan(cap, h, w, planes, p) || unet_plan(Net::enc_c, dw, cap, h, w, planes, u) || !decoder_ready(dw)) return WSI_EINVAL;
+    for (int i = 0; i < 5; ++i) if (!enc_nchw[i]) return WSI_EINVAL;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
-    // encoder maps are packed into the trunk part of the workspace (stage buffers 0 of stages 3..0) and x0
+    // encoder maps are packed into the trunk part of the workspace (one buffer of each of stages 3..0) and x0
     const void* enc[5];
     int rc = WSI_OK;
     for (int i = 0; i < 5 && !rc; ++i) {
-        if (!enc_nchw[i]) return WSI_EINVAL;
-        char* dst = i < 4 ? ws + p.buf[3 - i][0] : dec + u.x0;
-        const EncMap m = enc_map(i, h, w);
+        char* dst = i < 4 ? ws + Net::stage_buf(p, 3 - i) : dec + u.x0;
+        const EncMap m = enc_map(Net::enc_c, i, h, w);
         rc = wsi_pf_pack(enc_nchw[i], dst, n, m.c, m.h, m.w, planes, stream);
         enc[i] = dst;
     }
     return rc ? rc : unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, (hipStream_t)stream);
+}
+
+size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BasicNet>(dw, n, h, w, planes);
+}
+int wsi_unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BasicNet>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_unet_forward(const wsi_trunk_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                     long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                     int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BasicNet>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n,
+                                  logits_out, enc_out, stream);
+}
+int wsi_unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                     int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BasicNet>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
+}
+size_t wsi_unet_bneck_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BneckNet>(dw, n, h, w, planes);
+}
+int wsi_unet_bneck_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BneckNet>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_unet_bneck_forward(const wsi_bneck_weights* wt, const wsi_unet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                           long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                           int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BneckNet>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace, workspace_n,
+                                  logits_out, enc_out, stream);
+}
+int wsi_unet_bneck_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                           int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BneckNet>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
 }

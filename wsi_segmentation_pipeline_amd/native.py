@@ -143,6 +143,11 @@ SIGNATURES = {
     'wsi_unet_workspace_init': (_i, [C.POINTER(WsiUnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
     'wsi_unet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiUnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
                               _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_unet_bneck_workspace_bytes': (_sz, [C.POINTER(WsiUnetDecoderWeights), _i, _i, _i, _i]),
+    'wsi_unet_bneck_workspace_init': (_i, [C.POINTER(WsiUnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_unet_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiUnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                                    _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_unet_bneck_decoder': (_i, [C.POINTER(WsiUnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_resize_nearest_f32': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _vp]),
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),

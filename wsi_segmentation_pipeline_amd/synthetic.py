@@ -260,3 +260,15 @@ def make_unet_resnet_state_dict(seed, layers, classes=4):
     for key, shape, kind in decoder_key_shapes(classes):
         sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
     return sd
+
+
+def make_unet_bottleneck_state_dict(seed, layers, classes=4):
+    """make_unet_resnet_state_dict with a Bottleneck encoder (encoder.* = make_bottleneck_state_dict(seed, layers, with_fc=False) without
+    its heads): the decoder is drawn for encoder maps of 2048 / 1024 / 512 / 256 / 64 channels."""
+    from .unet import ENC_CH, decoder_key_shapes
+    sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
+          if not k.startswith('fc')}
+    rng = np.random.Generator(np.random.PCG64(seed + 5000))
+    for key, shape, kind in decoder_key_shapes(classes, ENC_CH['bottleneck']):
+        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
+    return sd

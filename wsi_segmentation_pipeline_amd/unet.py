@@ -12,6 +12,9 @@ oracle/unet_oracle.py (torch fp32 CPU) and the HIP path is held to it:
   decoder  ``decoder.layer{1..5}.block.{0,1}.block.0.weight`` (3x3 conv, no bias) + ``.block.1.*`` (BatchNorm) + ReLU, each block
            preceded by nearest x2 upsampling and (blocks 1-4) concatenation of the next skip; channels 256/128/64/32/16;
            ``decoder.final_conv.{weight,bias}`` (1x1 to `classes`)
+Bottleneck encoders (``Unet('resnet50' | 'resnet101', classes=C)``, the smp factory signature; class UNetSegBottleneck): the same decoder on
+the maps of ``ResNet(Bottleneck, layers)`` - 2048 / 1024 / 512 / 256 / 64 channels - so only the first conv of decoder blocks 1-4 is wider
+(``cat([up2(x), skip])`` of (2048, 1024), (256, 512), (128, 256), (64, 64)); key names as above; 'parity' and 'speed' only.
 Eval-mode forwards run on libwsi_hip.so only (conv3x3 MFMA kernels + upsample/concat, head kernels: csrc/unet.hip); training
 mode uses torch ops so ``train.py``-style callers still run.
 """
@@ -23,11 +26,13 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import native
-from .engine import BN_EPS, MX, PARITY, SPEED, TrunkEngine, _np_ptr, _ptr, _require_gpu, _stream
+from .engine import BN_EPS, MX, PARITY, SPEED, BottleneckEngine, TrunkEngine, _np_ptr, _ptr, _require_gpu, _stream, trunk_arch
 
 DEC_CH = (256, 128, 64, 32, 16)
-SKIP_CH = (256, 128, 64, 64, 0)
+ENC_CH = {'basic': (512, 256, 128, 64, 64), 'bottleneck': (2048, 1024, 512, 256, 64)}     # channels of [x4, x3, x2, x1, x0] per block type
+SKIP_CH = ENC_CH['basic'][1:] + (0,)
 ENCODER_LAYERS = {'resnet18': [2, 2, 2, 2], 'resnet34': [3, 4, 6, 3]}      # smp encoder names -> BasicBlocks per stage
+BOTTLENECK_ENCODER_LAYERS = {'resnet50': [3, 4, 6, 3], 'resnet101': [3, 4, 23, 3]}      # ... -> Bottleneck blocks per stage
 
 
 def encoder_layers(encoder):
@@ -50,11 +55,22 @@ def equal_batches(n, cap):
     return [(i, min(i + mb, n)) for i in range(0, n, mb)]
 
 
-def decoder_key_shapes(classes):
-    """[(key, shape, kind)] of the decoder in state-dict order."""
-    out, cprev = [], 512
+def bottleneck_encoder_layers(encoder):
+    if encoder not in BOTTLENECK_ENCODER_LAYERS:
+        raise ValueError('encoder must be one of %s (Bottleneck ResNets), got %r' % (sorted(BOTTLENECK_ENCODER_LAYERS), encoder))
+    return BOTTLENECK_ENCODER_LAYERS[encoder]
+
+
+def _skip_ch(enc_ch):
+    """channels of the skip each decoder block concatenates: encoder maps x3, x2, x1, x0, and none for the last block"""
+    return tuple(enc_ch[1:]) + (0,)
+
+
+def decoder_key_shapes(classes, enc_ch=ENC_CH['basic']):
+    """[(key, shape, kind)] of the decoder in state-dict order, on an encoder whose maps [x4, x3, x2, x1, x0] have `enc_ch` channels."""
+    out, cprev, skip = [], enc_ch[0], _skip_ch(enc_ch)
     for L in range(5):
-        cin, cout = cprev + SKIP_CH[L], DEC_CH[L]
+        cin, cout = cprev + skip[L], DEC_CH[L]
         for j, ci in enumerate((cin, cout)):
             p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
             out.append((p + '.0.weight', (cout, ci, 3, 3), 'conv'))
@@ -68,17 +84,31 @@ def decoder_key_shapes(classes):
 
 
 class UNetEngine:
-    """BasicBlock ResNet encoder (TrunkEngine) + smp-style decoder on HIP kernels.  state_dict: ``encoder.*`` + ``decoder.*`` keys.
-    The encoder's depth is read from the state dict; `encoder` ('resnet18' | 'resnet34'), when given, must agree with it."""
+    """ResNet encoder + smp-style decoder on HIP kernels.  state_dict: ``encoder.*`` + ``decoder.*`` keys.  The encoder's block type and
+    depth are read from the state dict (`engine.trunk_arch`): BasicBlock nets run on a TrunkEngine and wsi_unet_*, Bottleneck nets on a
+    BottleneckEngine and wsi_unet_bneck_* (parity and speed only).  `encoder` (an smp name), when given, must agree with the state dict."""
 
     def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
         self._ws = {}
         self.lib = native.load()
         self.device = torch.device(device)
         enc_sd = {k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')}
-        self.trunk = TrunkEngine(enc_sd, device, planes=planes)
-        if encoder is not None and self.trunk.layers != encoder_layers(encoder):
-            raise ValueError('state dict holds a %s encoder, not %s' % (self.trunk.layers, encoder))
+        self.arch = trunk_arch(enc_sd)[0]
+        if self.arch == 'bottleneck':
+            if planes == MX:
+                raise ValueError("a U-Net on a Bottleneck encoder runs in precision 'parity' or 'speed': there is no mx mode")
+            self.trunk = BottleneckEngine(enc_sd, device, planes=planes)
+        else:
+            self.trunk = TrunkEngine(enc_sd, device, planes=planes)
+        if encoder is not None:
+            named = BOTTLENECK_ENCODER_LAYERS.get(encoder) or encoder_layers(encoder)
+            if self.trunk.layers != named or (encoder in BOTTLENECK_ENCODER_LAYERS) != (self.arch == 'bottleneck'):
+                raise ValueError('state dict holds a %s %s encoder, not %s' % (self.arch, self.trunk.layers, encoder))
+        self.enc_ch = ENC_CH[self.arch]
+        skip_ch = _skip_ch(self.enc_ch)
+        entry = 'wsi_unet_bneck' if self.arch == 'bottleneck' else 'wsi_unet'
+        self._ws_bytes, self._ws_init, self._forward, self._decoder = (
+            getattr(self.lib, entry + s) for s in ('_workspace_bytes', '_workspace_init', '_forward', '_decoder'))
         self.planes = planes
         self.classes = int(classes if classes is not None else state_dict['decoder.final_conv.weight'].shape[0])
         self.max_batch = max_batch
@@ -93,7 +123,7 @@ class UNetEngine:
             self._keep.append(t)
             return t
 
-        cprev_real, cprev_pad = 512, 512
+        cprev_real, cprev_pad = self.enc_ch[0], self.enc_ch[0]
         for L in range(5):
             cout = DEC_CH[L]
             cout_pad = _pad64(cout) if planes == 1 else -(-cout // 32) * 32        # whole 128-byte lines: 64 channels in speed mode, 32 otherwise
@@ -101,10 +131,10 @@ class UNetEngine:
                 p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
                 w = f32(p + '.0.weight')
                 if j == 0:                                     # input = [upsampled x (real cprev of cprev_pad) | skip]
-                    cin_pad = cprev_pad + SKIP_CH[L]
+                    cin_pad = cprev_pad + skip_ch[L]
                     wp = np.zeros((cout_pad, cin_pad, 3, 3), np.float32)
                     wp[:cout, :cprev_real] = w[:, :cprev_real]
-                    wp[:cout, cprev_pad:cprev_pad + SKIP_CH[L]] = w[:, cprev_real:]
+                    wp[:cout, cprev_pad:cprev_pad + skip_ch[L]] = w[:, cprev_real:]
                 else:
                     cin_pad = cout_pad
                     wp = np.zeros((cout_pad, cin_pad, 3, 3), np.float32)
@@ -143,18 +173,17 @@ class UNetEngine:
         key = (h, w)
         ent = self._ws.get(key)
         if ent is None or ent[1] < n:
-            nbytes = self.lib.wsi_unet_workspace_bytes(C.byref(self.dw), n, h, w, self.planes)
+            nbytes = self._ws_bytes(C.byref(self.dw), n, h, w, self.planes)
             if nbytes == 0:
                 raise ValueError('unsupported patch shape %dx%d (need multiples of 32)' % (h, w))
             self.release_workspaces()                          # the library forgets the addresses before the allocator can reuse them
             ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-            native.check(self.lib.wsi_unet_workspace_init(C.byref(self.dw), _ptr(ws), n, h, w, self.planes, _stream()),
-                         'wsi_unet_workspace_init')
+            native.check(self._ws_init(C.byref(self.dw), _ptr(ws), n, h, w, self.planes, _stream()), self._ws_init.__name__)
             ent = self._ws[key] = (ws, n)
         return ent
 
     def release_workspaces(self):
-        """Free every planned workspace and make the library forget its layout tag (trunk.hip g_ws_layout)."""
+        """Free every planned workspace and make the library forget its layout tag (trunk.hip g_ws_layout; a Bottleneck workspace has none)."""
         for ws, _ in self._ws.values():
             self.lib.wsi_trunk_workspace_release(_ptr(ws))
         self._ws.clear()
@@ -170,11 +199,13 @@ class UNetEngine:
     def _batch(self, h, w):
         """Tiles per U-Net call: `max_batch`, else the tuned size scaled by patch area (r05 sweep at 256 x 256, parity: 128 / 256 / 512
         tiles -> 28.1 / 31.2 / 33.1 k patches/s: at 128 the 8 x 8 and 16 x 16 levels launch fewer workgroups than the chip has CUs)
-        as far as half of the free HBM allows - ~77 MB of workspace per 256 x 256 tile, 39 GB of the 288 GB at 512."""
+        as far as half of the free HBM allows - ~77 MB of workspace per 256 x 256 tile, 39 GB of the 288 GB at 512.  A Bottleneck encoder
+        keeps the same rule with its own workspace size (wsi_unet_bneck_workspace_bytes, ~94 MB per tile); ResNet-50 sweep at 256 x 256,
+        parity, u8 tiles: 128 / 256 / 512 tiles -> 10.3 / 11.1 / 11.7 k patches/s (profiles/unet_resnet50_bench.json), so it keeps 512."""
         if self.max_batch:
             return self.max_batch
         want = max(1, int(self.TUNED_BATCH_256 * 65536 // max(h * w, 1)))
-        per = self.lib.wsi_unet_workspace_bytes(C.byref(self.dw), 16, h, w, self.planes) / 16.0
+        per = self._ws_bytes(C.byref(self.dw), 16, h, w, self.planes) / 16.0
         if per <= 0:
             return want
         try:
@@ -190,16 +221,16 @@ class UNetEngine:
         enc = None
         enc_ptrs = None
         if want_enc:
-            shapes = [(512, h // 32, w // 32), (256, h // 16, w // 16), (128, h // 8, w // 8), (64, h // 4, w // 4), (64, h // 2, w // 2)]
+            shapes = [(c, h >> k, w >> k) for c, k in zip(self.enc_ch, (5, 4, 3, 2, 1))]
             enc = [torch.empty((n,) + s, dtype=torch.float32, device=self.device) for s in shapes]
             enc_ptrs = (C.c_void_p * 5)(*[t.data_ptr() for t in enc])
         if slide is not None:
             sp, pitch, sh, sw = _ptr(slide), slide.stride(0), slide.shape[0], slide.shape[1]
         else:
             sp, pitch, sh, sw = None, 0, 0, 0
-        native.check(self.lib.wsi_unet_forward(C.byref(self.trunk.wt), C.byref(self.dw), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
-                                               _ptr(self.trunk.lut), n, h, w, _ptr(ws), cap, _ptr(logits),
-                                               C.byref(enc_ptrs) if enc_ptrs is not None else None, _stream()), 'wsi_unet_forward')
+        native.check(self._forward(C.byref(self.trunk.wt), C.byref(self.dw), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
+                                   _ptr(self.trunk.lut), n, h, w, _ptr(ws), cap, _ptr(logits),
+                                   C.byref(enc_ptrs) if enc_ptrs is not None else None, _stream()), self._forward.__name__)
         return logits, enc
 
     def forward_f32(self, x, logits=True, enc=False):
@@ -232,8 +263,8 @@ class UNetEngine:
         ws, cap = self._workspace(n, h, w)
         logits = torch.empty((n, self.classes, h, w), dtype=torch.float32, device=self.device)
         ptrs = (C.c_void_p * 5)(*[t.data_ptr() for t in enc])
-        native.check(self.lib.wsi_unet_decoder(C.byref(self.dw), C.byref(ptrs), n, h, w, self.planes, _ptr(ws), cap, _ptr(logits), _stream()),
-                     'wsi_unet_decoder')
+        native.check(self._decoder(C.byref(self.dw), C.byref(ptrs), n, h, w, self.planes, _ptr(ws), cap, _ptr(logits), _stream()),
+                     self._decoder.__name__)
         return logits
 
 
@@ -260,11 +291,11 @@ class _DecoderBlock(nn.Module):
 
 
 class UNetDecoder(nn.Module):
-    def __init__(self, classes, owner=None):
+    def __init__(self, classes, owner=None, enc_ch=ENC_CH['basic']):
         super().__init__()
-        cprev = 512
+        cprev, skip = enc_ch[0], _skip_ch(enc_ch)
         for L in range(5):
-            setattr(self, 'layer%d' % (L + 1), _DecoderBlock(cprev + SKIP_CH[L], DEC_CH[L]))
+            setattr(self, 'layer%d' % (L + 1), _DecoderBlock(cprev + skip[L], DEC_CH[L]))
             cprev = DEC_CH[L]
         self.final_conv = nn.Conv2d(DEC_CH[4], classes, 1)
         self._owner = [owner]                                  # list: not registered as a sub-module
@@ -282,14 +313,20 @@ class UNetDecoder(nn.Module):
 class UNetEncoder(nn.Module):
     """ResNet-18 / ResNet-34 trunk with the smp encoder surface: forward(x) -> [x4, x3, x2, x1, x0]; ``out_shapes``."""
 
+    ARCH = 'basic'
+
     def __init__(self, owner=None, encoder='resnet18'):
         super().__init__()
-        import resnets_shift
-        net = resnets_shift.ResNet(resnets_shift.BasicBlock, encoder_layers(encoder))
+        net = self._net(encoder)
         for name in ('conv1', 'bn1', 'relu', 'maxpool', 'layer1', 'layer2', 'layer3', 'layer4'):
             setattr(self, name, getattr(net, name))
-        self.out_shapes = (512, 256, 128, 64, 64)
+        self.out_shapes = ENC_CH[self.ARCH]
         self._owner = [owner]
+
+    @staticmethod
+    def _net(encoder):
+        import resnets_shift
+        return resnets_shift.ResNet(resnets_shift.BasicBlock, encoder_layers(encoder))
 
     def forward(self, x):
         if not self.training:
@@ -302,15 +339,44 @@ class UNetEncoder(nn.Module):
         return [x4, x3, x2, x1, x0]
 
 
+class UNetBottleneckEncoder(UNetEncoder):
+    """ResNet-50 / ResNet-101 trunk with the same surface; ``out_shapes`` = (2048, 1024, 512, 256, 64)."""
+    ARCH = 'bottleneck'
+
+    @staticmethod
+    def _net(encoder):
+        """conv1 ... layer4 of ``resnets_shift.ResNet(Bottleneck, layers)``, built as its __init__ / _make_layer build them (same modules,
+        same initialisation) but without the bag heads, which are no part of an encoder: fc.0 alone is 32768 x 16384 at expansion 4."""
+        import resnets_shift as rs
+        net = nn.Module()
+        net.conv1, net.bn1, net.relu, net.maxpool = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1)
+        inplanes = 64
+        for i, (planes, stride, blocks) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), bottleneck_encoder_layers(encoder)), start=1):
+            width = planes * rs.Bottleneck.expansion
+            down = nn.Sequential(rs.conv1x1(inplanes, width, stride), nn.BatchNorm2d(width))
+            seq = [rs.Bottleneck(inplanes, planes, stride, down)] + [rs.Bottleneck(width, planes) for _ in range(1, blocks)]
+            setattr(net, 'layer%d' % i, nn.Sequential(*seq))
+            inplanes = width
+        for mod in net.modules():
+            if isinstance(mod, nn.Conv2d):
+                nn.init.kaiming_normal_(mod.weight, mode='fan_out', nonlinearity='relu')
+        return net
+
+
 class UNetSeg(nn.Module):
     """Drop-in for ``smp.Unet(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34' as the reference
     uses it: ``model(x)`` -> (B,C,H,W) logits; ``model.encoder`` / ``model.decoder`` callable separately; ``classifier`` /
     ``regressor`` heads attachable."""
 
+    ENCODER = UNetEncoder
+    PRECISIONS = ('parity', 'mx', 'speed')
+
     def __init__(self, classes=4, precision='parity', encoder='resnet18'):
         super().__init__()
-        self.encoder = UNetEncoder(self, encoder)
-        self.decoder = UNetDecoder(classes, self)
+        if precision not in self.PRECISIONS:
+            raise ValueError('precision must be one of %s for a %s encoder, got %r' % (' / '.join(self.PRECISIONS), encoder, precision))
+        self.encoder = self.ENCODER(self, encoder)
+        self.decoder = UNetDecoder(classes, self, self.encoder.out_shapes)
         self.classes, self.precision, self.encoder_name = classes, precision, encoder
         self._engine, self._engine_sig = None, None
 
@@ -330,3 +396,29 @@ class UNetSeg(nn.Module):
         if not x.is_cuda:
             raise RuntimeError('UNetSeg eval forward runs on HIP kernels only: move the model and the input to the GPU')
         return self.hip_engine(x.device).forward_f32(x)[0]
+
+
+class UNetSegBottleneck(UNetSeg):
+    """``smp.Unet('resnet50' | 'resnet101', classes=C, activation=None)``: UNetSeg on a Bottleneck encoder (``model.encoder.out_shapes`` =
+    (2048, 1024, 512, 256, 64)); precision 'parity' or 'speed'.  A UNetSeg to every caller that asks (utils.eval's fused tile path)."""
+    ENCODER = UNetBottleneckEncoder
+    PRECISIONS = ('parity', 'speed')
+
+    def __init__(self, classes=4, precision='parity', encoder='resnet50'):
+        super().__init__(classes, precision, encoder)
+
+
+def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
+    """The factory with smp's own signature, so the reference's ``smp.Unet(args.arch_encoder, encoder_weights=None, classes=C,
+    activation=None)`` becomes ``unet.Unet(...)``: UNetSeg for 'resnet18' / 'resnet34', UNetSegBottleneck for 'resnet50' / 'resnet101'.
+    The model returns logits: `activation` must be None, as the reference passes it; `encoder_weights` must be None (nothing is
+    downloaded: load a checkpoint with ``load_state_dict``)."""
+    if encoder_weights is not None:
+        raise ValueError('encoder_weights must be None (got %r): pretrained weights are not downloaded; load a state dict' % (encoder_weights,))
+    if activation is not None:
+        raise ValueError('activation must be None (got %r): the model returns logits, as the reference builds it' % (activation,))
+    if encoder_name in ENCODER_LAYERS:
+        return UNetSeg(classes, precision, encoder_name)
+    if encoder_name in BOTTLENECK_ENCODER_LAYERS:
+        return UNetSegBottleneck(classes, precision, encoder_name)
+    raise ValueError('encoder_name must be one of %s, got %r' % (list(ENCODER_LAYERS) + list(BOTTLENECK_ENCODER_LAYERS), encoder_name))
