@@ -178,7 +178,8 @@ enum {
     WSI_CONV_MODE_L1_PERSISTENT = 1048576,  /* 64-channel layer 1 on the persistent producer-fed kernel (r05 study route: bit-identical, 30-45 % slower) */
     WSI_CONV_MODE_UNET_NO_TAIL = 2097152,   /* U-Net decoder's last block and head as three launches even with fused-tail weights (planes 2; equal to fp32 rounding) */
     WSI_CONV_MODE_UNET_TAIL_FORM1 = 4194304,/* the fused U-Net tail in its first form (every wave does both convs), not the specialised one */
-    WSI_CONV_MODE_UNET_X0_UNFUSED = 8388608 /* U-Net skip x0 from a separate unfused stem conv, not stored by the fused stem kernel (planes 2, u8 input) */
+    WSI_CONV_MODE_UNET_X0_UNFUSED = 8388608,/* U-Net skip x0 from a separate unfused stem conv, not stored by the fused stem kernel (planes 2, u8 input) */
+    WSI_CONV_MODE_LINKNET_NO_TAIL = 16777216 /* Linknet decoder's last block and head as three launches + the head kernel even with fused-tail weights (planes 2; equal to fp32 / fp16-pair rounding) */
 };
 int wsi_conv_set_mode(int mode);
 /* tuning hook: same as wsi_conv3x3_bn_act with an explicit tile configuration for the stride-1
@@ -297,7 +298,7 @@ int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, cons
  * wsi_trunk_forward; wsi_prof_end disarms, waits for the events and returns the number of records
  * copied: ms, kind (1 = 3x3 stride 1 of layers 2-4, 5 = 3x3 stride 1 of layer 1, 2 = 3x3 stride 2, 3 = 1x1 downsample,
  * 4 = stem+maxpool; the U-Net decoder adds 6-10; 11 = stride-1 1x1 conv of the Bottleneck trunk, whose 3x3 convs are kind 1
- * and 2 and whose strided 1x1 downsamples are kind 3)
+ * and 2 and whose strided 1x1 downsamples are kind 3; the Linknet decoder adds 12 = 1x1 conv, 13 = transposed conv and 14 = fused last block + head)
  * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch.  The records follow the depth table: per stage one entry
  * (kind 2, plus 3 on the gather route) and 2 * blocks - 1 stride-1 convs, layer 1 2 * blocks[0] of kind 5. */
 int wsi_prof_begin(int max_records);
@@ -504,6 +505,77 @@ int wsi_unet_bneck_forward(const wsi_bneck_weights* wt, const wsi_unet_decoder_w
                            int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
 int wsi_unet_bneck_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
                            void* workspace, int workspace_n, float* logits_out, void* stream);
+/* ---- Linknet: the light decoder of the dense 'seg' path ------------------------------------------------------------
+ * The reference builds its segmentation model as `eval('smp.' + args.model_name)(args.arch_encoder, ...)` (eval.py:22,
+ * eval_tumorbed.py:21, eval_spie.py:11, train*.py; myargs.py:9 `--model_name`, default 'Unet'); 'Linknet' is smp's transposed-conv
+ * decoder.  Third-party, absent and un-pinned like the U-Net, so the architecture is restated from the published 0.0.x source (parity
+ * unpinned; the numerical spec is tests/linknet_oracle.py):
+ *   encoder  the BasicBlock trunk at whatever depth wsi_trunk_weights.blocks states; maps [x4 512 ch /32, x3 256 /16, x2 128 /8,
+ *            x1 64 /4, x0 64 /2] as for the U-Net
+ *   decoder  `decoder.layer{1..5}`, each a DecoderBlock(cin, cout) with mid = cin / 4:
+ *              block.0  1x1 conv cin -> mid (no bias) + BN + ReLU              weight [mid][cin][1][1]
+ *              block.1  ConvTranspose2d(mid, mid, kernel 4, stride 2, padding 1, bias=False) + BN + ReLU   weight [mid in][mid out][4][4]
+ *              block.2  1x1 conv mid -> cout (no bias) + BN + ReLU             weight [cout][mid][1][1]
+ *            and the skip added AFTER the block, no ReLU behind the add: x = block(x) + skip; layers 1-4 add x3, x2, x1, x0, layer 5
+ *            none.  (cin, mid, cout) = (512, 128, 256), (256, 64, 128), (128, 32, 64), (64, 16, 64), (64, 16, 32)
+ *   head     `decoder.final_conv` 1x1 32 -> classes + bias
+ * The transposed conv as four 2x2 convs (csrc/linknet.hip): output pixel (2i + a, 2j + b) sums input rows {(i - 1, ky = 3), (i, ky = 1)}
+ * for a = 0 and {(i, ky = 2), (i + 1, ky = 0)} for a = 1, columns alike with b and kx; inputs outside the map are zero (the PF pad ring).
+ *
+ * wsi_prepack_tconv: w [c][c][4][4] fp32 as torch keeps a ConvTranspose2d weight ([in][out][ky][kx]) + the BN vectors (NULL: none) of the
+ *   OUTPUT channels -> wsi_prepack_tconv_bytes(c, planes) bytes (the conv pack with 16 taps; planes 2 ends in c inverse channel scales)
+ *   and c bias floats.  c a multiple of 64 (narrower layers: zero weights in the padding), planes 1 or 2; 0 / -22 otherwise.
+ * wsi_tconv4x4s2_bn_relu: in_pf PF (h, w, c) -> out_pf PF (2h, 2w, c) = relu(bn(conv_transpose(in))); planes 2 clamps to +-65504.
+ *   -22: a NULL pointer, in_pf == out_pf, c no positive multiple of 64, planes outside 1-2, n, h or w <= 0.
+ * wsi_conv1x1_bn_relu_add: out = relu(bn(conv1x1(in))) + skip - the ReLU BEFORE the add, where wsi_conv1x1_bn_act computes
+ *   act(bn(conv) + resid).  Stride 1, planes 1 / 2, skip_pf shaped like out_pf and not NULL; routes and widths as wsi_conv1x1_bn_act. */
+size_t wsi_prepack_tconv_bytes(int c, int planes);
+int wsi_prepack_tconv(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                      int c, int planes, void* wpk_out, float* bias_out);
+int wsi_tconv4x4s2_bn_relu(const void* in_pf, void* out_pf, const void* wpk, const float* bias, int n, int h, int w, int c, int planes,
+                           void* stream);
+int wsi_conv1x1_bn_relu_add(const void* in_pf, void* out_pf, const void* skip_pf, const void* wpk, const float* bias,
+                            int n, int h, int w, int cin, int cout, int planes, void* stream);
+/* Decoder weights: conv 3(L-1)+J = decoder.layerL.block.J (J = 0, 2: wsi_prepack_conv with k = 1; J = 1: wsi_prepack_tconv), on widths
+ * padded to at least 64 channels with zero weights (padding channels then hold relu(0) = 0):
+ *   cin  = {512,128,128, 256,64,64, 128,64,64, 64,64,64, 64,64,64}
+ *   cout = {128,128,256,  64,64,128, 64,64,64, 64,64,64, 64,64,64}
+ * head_w [classes][32] fp32, head_cin = 32, classes 1 ... 16.  tail_w: device copy of wsi_linknet_tail_prepack's blob, or NULL.
+ * Fused last block + head (csrc/linknet.hip linknet_tail_kernel): layer 5 (1x1 64 -> 16 on the half-resolution map, the transposed conv
+ *   to full resolution, 1x1 16 -> 32) and final_conv as ONE kernel that reads layer 4's output and writes only the logits; both
+ *   intermediates stay in LDS / registers (fp32), one halo row of the 16-channel tensor per band edge.  wsi_linknet_tail_prepack: w0
+ *   [cmid][cin][1][1], wt [cmid][cmid][4][4] ([in][out]), w2 [cout][cmid][1][1] fp32 with their BatchNorm vectors (NULL: none), head_w
+ *   [classes][cout], head_b [classes] (NULL: zeros); cin = 64, cmid <= 16, cout <= 32, classes <= 4, else -22.  `out` =
+ *   wsi_linknet_tail_prepack_bytes() bytes of host memory: copy it to the device and store the pointer in tail_w.
+ *   Bands: a workgroup takes 4 half-resolution rows (8 output rows) of one image, so an h x w tile runs as h / 8 bands.
+ *   The three launches + the head kernel stay in force when tail_w is NULL, at planes 1, for tiles wider than 256, with more than 4
+ *   classes, and under WSI_CONV_MODE_LINKNET_NO_TAIL.  No workgroup hands anything to another: there is no timeout counter.
+ * The four entries mirror wsi_unet_* argument for argument (workspace: the trunk's + the decoder's part, ~70 MB per 256 x 256 tile at
+ * planes 2, the three-launch route's two full-resolution 64-channel tensors being half of it; zero-filled once by wsi_linknet_workspace_init; release with wsi_trunk_workspace_release).  planes 1 or 2.
+ * -22 before the workspace is touched: what wsi_unet_forward refuses (depth table, shape, input source, a NULL trunk pointer, neither
+ * output asked for), planes 3, a cin / cout table or head_cin that disagrees with the widths above and, when logits are asked for, a
+ * NULL decoder conv (convs 0-11; convs 12-14 and the head too unless tail_w stands in for them).
+ * Profiler kinds (wsi_prof_end): 12 = a 1x1 conv of the Linknet decoder, 13 = its transposed conv, 14 = the fused last block + head,
+ * 8 = the head kernel of the three-launch route. */
+size_t wsi_linknet_tail_prepack_bytes(void);
+int wsi_linknet_tail_prepack(const float* w0, const float* bn0_weight, const float* bn0_bias, const float* bn0_mean, const float* bn0_var,
+                             const float* wt, const float* bnt_weight, const float* bnt_bias, const float* bnt_mean, const float* bnt_var,
+                             const float* w2, const float* bn2_weight, const float* bn2_bias, const float* bn2_mean, const float* bn2_var,
+                             float eps, const float* head_w, const float* head_b, int cin, int cmid, int cout, int classes, void* out);
+typedef struct {
+    const void* conv_w[15]; const float* conv_b[15];
+    int cin[15], cout[15];
+    const float* head_w; const float* head_b;
+    int head_cin, classes;
+    const void* tail_w;
+} wsi_linknet_decoder_weights;
+size_t wsi_linknet_workspace_bytes(const wsi_linknet_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_linknet_workspace_init(const wsi_linknet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_linknet_forward(const wsi_trunk_weights* wt, const wsi_linknet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                        long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                        int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_linknet_decoder(const wsi_linknet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                        void* workspace, int workspace_n, float* logits_out, void* stream);
 /* F.interpolate(pred_src, (tile_h * r, tile_w * r)) of utils/eval.py:202-206 (default mode 'nearest') on planes_n
  * contiguous fp32 (hs, ws) planes */
 int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, void* stream);

@@ -76,6 +76,10 @@ int conv_common(const ConvCall& c) {
     if (c.relu & ~1) return WSI_EINVAL;
 #endif
     a.flags |= c.line_flags;
+    if (c.resid_post) {                                // relu(bn(conv)) + resid (common.h CONV_RESID_POST): never dropped, never another conv's epilogue
+        if (c.ksize != 1 || c.stride != 1 || !c.resid || c.resid == c.out || !(c.relu & 1) || c.planes == 3 || c.split_out || c.in2 || c.in_up || c.line_flags) return WSI_EINVAL;
+        a.flags |= CONV_RESID_POST;
+    }
     if (c.in_up) {                                     // fused nearest x2 upsample + concat input (common.h ConvArgs.in_up): stride-1 3x3, slab3 kernels
         if (c.stride != 1 || c.ksize != 3 || c.h % 2 || c.w % 2 || c.up_c <= 0 || c.up_c > c.cin || c.resid || c.in2 || c.line_flags || c.split_out) return WSI_EINVAL;
         a.in_up = c.in_up; a.up_c = c.up_c; a.gup = pf_geom_fd(c.n, c.h / 2, c.w / 2, c.up_c);
@@ -103,7 +107,11 @@ int conv1x1_common(const ConvCall& c) {
     if (!g_routes.pw_gather && c.stride == 1 && (c.planes == 1 || c.planes == 2) && c.cin > 0 && c.cout > 0 && c.h > 0 && c.w > 0) {
         if (!c.in || !c.out || !c.wpk || !c.bias || c.in == c.out || c.resid == c.out || c.n <= 0 || (c.relu & ~1)) return WSI_EINVAL;
         if (c.split_out || c.in2 || c.in_up || c.line_flags) return WSI_EINVAL;
-        const ConvArgs a = conv_args(c);               // a channel count outside the pointwise kernel's range -> gather kernel; a launch
+        ConvArgs a = conv_args(c);                     // a channel count outside the pointwise kernel's range -> gather kernel; a launch
+        if (c.resid_post) {
+            if (!c.resid || !(c.relu & 1)) return WSI_EINVAL;
+            a.flags |= CONV_RESID_POST;
+        }
         if (wsi_pw_takes(a, c.planes)) return wsi_pw_dispatch(a, c.planes, (hipStream_t)c.stream);   // error is returned, not routed around
     }
     return conv_common(c);
@@ -282,6 +290,7 @@ int wsi_conv_set_mode(int mode) {
     r.unet_tail_form = (mode & WSI_CONV_MODE_UNET_TAIL_FORM1) ? 1 : 2;
     r.unet_x0_fused = (mode & WSI_CONV_MODE_UNET_X0_UNFUSED) ? 0 : 1;
     r.pw_gather = (mode & WSI_CONV_MODE_PW_GATHER) ? 1 : 0;
+    r.linknet_tail = (mode & WSI_CONV_MODE_LINKNET_NO_TAIL) ? 0 : 1;
     return WSI_OK;
 }
 
@@ -295,6 +304,22 @@ int wsi_conv1x1_bn_act(const void* in_pf, void* out_pf, const void* resid_pf, co
                        int n, int h_in, int w_in, int cin, int cout, int stride, int relu, int planes, void* stream) {
     return conv1x1_common({.in = in_pf, .out = out_pf, .resid = resid_pf, .wpk = wpk, .bias = bias, .n = n, .h = h_in, .w = w_in, .cin = cin,
                            .cout = cout, .stride = stride, .ksize = 1, .relu = relu, .planes = planes, .stream = stream});
+}
+
+int wsi_conv1x1_bn_relu_add(const void* in_pf, void* out_pf, const void* skip_pf, const void* wpk, const float* bias,
+                            int n, int h, int w, int cin, int cout, int planes, void* stream) {
+    if (!skip_pf) return WSI_EINVAL;
+    return conv1x1_common({.in = in_pf, .out = out_pf, .resid = skip_pf, .wpk = wpk, .bias = bias, .n = n, .h = h, .w = w, .cin = cin,
+                           .cout = cout, .stride = 1, .ksize = 1, .relu = 1, .planes = planes, .stream = stream, .resid_post = 1});
+}
+
+int wsi_tconv4x4s2_bn_relu(const void* in_pf, void* out_pf, const void* wpk, const float* bias, int n, int h, int w, int c, int planes,
+                           void* stream) {
+    if (!in_pf || !out_pf || !wpk || !bias || in_pf == out_pf || n <= 0 || h <= 0 || w <= 0 || c <= 0) return WSI_EINVAL;
+    ConvArgs a = conv_args({.in = in_pf, .out = out_pf, .wpk = wpk, .bias = bias, .n = n, .h = h, .w = w, .cin = c, .cout = c, .stride = 1,
+                            .ksize = 4, .relu = 1});
+    a.go = pf_geom_fd(n, 2 * h, 2 * w, c);
+    return wsi_tconv_dispatch(a, planes, (hipStream_t)stream);
 }
 
 int wsi_avgpool_fc(const void* in_pf, int n, int h, int w, int c, const float* fc_w, const float* fc_b, int k,

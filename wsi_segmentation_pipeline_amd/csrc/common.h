@@ -163,6 +163,9 @@ enum : int {
     // plane, is not stored; a consumer rebuilds it in LDS after its slab has landed (conv_dev.h mx96_rebuild_hi6), where lines
     // keep their 128-byte pitch.  The tensor is line-planar (ConvArgs.plane96): pixel stride 96 bytes inside a line plane.
     CONV_IN96 = 16, CONV_OUT96 = 32, CONV_RESID96 = 64,
+    // Linknet's skip (`x = block(x) + skip`, no ReLU after the add): out = relu(bn(conv)) + resid instead of act(bn(conv) + resid).
+    // Stride-1 1x1 convs of planes 1 / 2 only (the gather and the pointwise kernel: conv_dev.h conv_epilogue_q<.., POST>).
+    CONV_RESID_POST = 128,
     CONV_ABL_NO_STORE = 1 << 8, CONV_ABL_DISPATCH_ONLY = 1 << 9, CONV_ABL_NO_MAINLOOP = 1 << 10, CONV_NONTEMPORAL = 1 << 11,
     CONV_WCOPIES_SHIFT = 16,   // bits 16-19: back-to-back copies of the packed weights minus one
 };
@@ -409,5 +412,6 @@ struct ConvRoutes {
     int unet_tail_form = 2;        // 2: unet_tail2_kernel, 1: the first form (unet_tail_kernel)
     int unet_x0_fused = 1;         // U-Net: the fused stem kernel stores the half-resolution skip x0 itself
     int pw_gather = 0;             // stride-1 1x1 convs (wsi_conv1x1_bn_act, Bottleneck trunk) on the gather kernel, not conv_pw.hip
+    int linknet_tail = 1;          // Linknet decoder: last block + head as one kernel (linknet.hip linknet_tail_kernel)
 };
 extern ConvRoutes g_routes;

@@ -19,7 +19,7 @@
 // Generic gather kernel (3x3 stride 2, 1x1 stride 2, also stride 1): per (line, tap) step the BM
 // input pixels are gathered into an LDS tile by per-lane source addresses.  Pad output positions
 // gather pixel 0 (always a zero guard) and are dropped by the epilogue.
-template <int MT, int WM, int WN, int PLANES>
+template <int MT, int WM, int WN, int PLANES, bool POST = false>
 __global__ __launch_bounds__(WM* WN * 64) void conv_gather_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int BM = WM * MT * 32;
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(WM* WN * 64) void conv_gather_kernel(ConvArgs a) {
             mfma_line<MT, PLANES>(acc, wf, smem, xbase);
         }
     }
-    conv_epilogue<MT, PLANES>(a, acc, q0 + wm * MT * 32, ntile, lane);
+    conv_epilogue<MT, PLANES, POST>(a, acc, q0 + wm * MT * 32, ntile, lane);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1423,13 +1423,13 @@ int wsi_s2_dispatch(const ConvArgs& a_in, int planes, hipStream_t st) {
     return by_planes<P123>(planes, [&](auto p) { return fuse ? launch_s2slab<4, 1, 4, p(), 2, true>(a, st) : launch_s2slab<4, 1, 4, p(), 2, false>(a, st); });
 }
 
-template <int MT, int WM, int WN, int PLANES>
+template <int MT, int WM, int WN, int PLANES, bool POST = false>
 static int launch_gather(const ConvArgs& a, hipStream_t st) {
     constexpr int BM = WM * MT * 32;
     if (a.go.C % (WN * 32)) return WSI_EINVAL;
     const int mtiles = (a.go.NS + BM - 1) / BM;
     const int nblocks = a.go.C / (WN * 32);
-    return conv_launch(conv_gather_kernel<MT, WM, WN, PLANES>, conv_grid(mtiles, nblocks, 0), WM * WN * 64, (size_t)BM * 128, st, a);
+    return conv_launch(conv_gather_kernel<MT, WM, WN, PLANES, POST>, conv_grid(mtiles, nblocks, 0), WM * WN * 64, (size_t)BM * 128, st, a);
 }
 
 // Slab tile configurations (cfg index -> MT, WM, WN, min waves/SIMD, dense).  Every wave owns 32 output channels and
@@ -1554,6 +1554,11 @@ int wsi_conv_dispatch(const ConvArgs& a, int planes, int cfg, hipStream_t st) {
     if (a.gi.C % cmul || cout % cmul) return WSI_EINVAL;
     if ((a.gi.C % 64 || cout % 64) && !(a.ksize == 3 && a.stride == 1)) return WSI_EINVAL;
     if (planes == 3 && !(a.ksize == 3 && a.stride == 1)) return WSI_EINVAL;      // mode 3: slab kernels only
+    if (a.flags & CONV_RESID_POST) {                         // relu(bn(conv)) + resid: stride-1 1x1 convs on the gather kernel (or conv_pw.hip)
+        if (a.ksize != 1 || a.stride != 1 || !a.resid || a.gi.H != a.go.H || a.gi.W != a.go.W || a.gi.N != a.go.N) return WSI_EINVAL;
+        if (cout % 128 == 0) return planes == 2 ? launch_gather<8, 1, 4, 2, true>(a, st) : launch_gather<8, 1, 4, 1, true>(a, st);
+        return planes == 2 ? launch_gather<4, 2, 2, 2, true>(a, st) : launch_gather<4, 2, 2, 1, true>(a, st);
+    }
     if (a.ksize == 3 && a.stride == 1) {
         if (a.gi.H != a.go.H || a.gi.W != a.go.W || a.gi.N != a.go.N) return WSI_EINVAL;
         if (cfg >= 0) return wsi_slab_dispatch_cfg(a, planes, cfg, st);

@@ -119,7 +119,9 @@ static __device__ __forceinline__ void resid_tile_dma_buf96(__amdgpu_buffer_rsrc
     }
 }
 
-template <int MT, int PLANES>
+// POST (Linknet's `block(x) + skip`, CONV_RESID_POST): the ReLU comes BEFORE the residual add - out = relu(bn(conv)) + resid, no ReLU
+// after it; every other instantiation keeps act(bn(conv) + resid).
+template <int MT, int PLANES, bool POST = false>
 static __device__ __forceinline__ void conv_epilogue_q(const ConvArgs& a, f32x16 (&acc)[MT], const int (&qs)[MT],
                                                        const bool (&valid)[MT], int ntile, int lane, char* scratch = nullptr) {
     typedef typename PairElem<PLANES>::T E;                                       // fp16 in mode 2 (fp16 pair), bf16 in mode 1
@@ -192,6 +194,12 @@ static __device__ __forceinline__ void conv_epilogue_q(const ConvArgs& a, f32x16
                 if constexpr (PLANES == 2) v[i] = acc[mt][4 * g + i] * wsi[4 * g + i] + bias[4 * g + i];
                 else v[i] = acc[mt][4 * g + i] + bias[4 * g + i];
             }
+            if constexpr (POST) {
+                if (a.relu) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
+                }
+            }
             if (a.resid) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] += (float)rh[mt][g][i];
@@ -202,7 +210,7 @@ static __device__ __forceinline__ void conv_epilogue_q(const ConvArgs& a, f32x16
             }
             Ex4 hi, lo;
             if constexpr (PLANES == 2) {
-                const float lo_clamp = a.relu ? 0.f : -65504.f;                    // ReLU (if any) + fp16-range clamp in one op
+                const float lo_clamp = (a.relu && !POST) ? 0.f : -65504.f;         // ReLU (if any) + fp16-range clamp in one op
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     v[i] = __builtin_amdgcn_fmed3f(v[i], lo_clamp, 65504.f);
@@ -210,7 +218,7 @@ static __device__ __forceinline__ void conv_epilogue_q(const ConvArgs& a, f32x16
                     lo[i] = (E)(v[i] - (float)hi[i]);
                 }
             } else {
-                if (a.relu) {
+                if (a.relu && !POST) {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i], 0.f);
                 }
@@ -414,7 +422,7 @@ static __device__ __forceinline__ void conv_tail_mx(const ConvArgs& a, f32x16 (&
 }
 
 // contiguous-position form: tile rows are PF positions q_base + mt*32 + (lane&31), pads filtered here
-template <int MT, int PLANES>
+template <int MT, int PLANES, bool POST = false>
 static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[MT], int q_base, int ntile,
                                                      int lane) {
     int qs[MT];
@@ -424,7 +432,7 @@ static __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (
         qs[mt] = q_base + mt * 32 + (lane & 31);
         valid[mt] = pf_is_pixel(a.go, qs[mt]);
     }
-    conv_epilogue_q<MT, PLANES>(a, acc, qs, valid, ntile, lane);
+    conv_epilogue_q<MT, PLANES, POST>(a, acc, qs, valid, ntile, lane);
 }
 
 template <int MT, int PLANES>

@@ -31,7 +31,7 @@
 #include "conv_dev.h"
 #include "internal.h"
 
-template <int PLANES, int WM, int WN, int NT, int MT>
+template <int PLANES, int WM, int WN, int NT, int MT, bool POST = false>
 __global__ __launch_bounds__(512) void conv_pw_kernel(ConvArgs a, int resident, int stage_resid) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(WM * WN == 8, "eight waves");
@@ -130,11 +130,11 @@ __global__ __launch_bounds__(512) void conv_pw_kernel(ConvArgs a, int resident, 
         wl(wb[1], pass + 1, 1);
         asm volatile("" ::: "memory");
 #pragma unroll
-        for (int j = 0; j < NT; ++j) conv_epilogue_q<MT, PLANES>(a, acc[j], qs, valid, (pass * WN + wn) * NT + j, lane, scratch);
+        for (int j = 0; j < NT; ++j) conv_epilogue_q<MT, PLANES, POST>(a, acc[j], qs, valid, (pass * WN + wn) * NT + j, lane, scratch);
     }
 }
 
-template <int PLANES, int WM, int WN, int NT>
+template <int PLANES, int WM, int WN, int NT, bool POST = false>
 static int launch_pw(const ConvArgs& a, hipStream_t st) {
     constexpr int MT = 2, BM = WM * MT * 32, LINE = BM * 128;
     const int NC = a.gi.C / PFmt<PLANES>::CPL, passes = a.go.C / (WN * NT * 32);
@@ -144,7 +144,7 @@ static int launch_pw(const ConvArgs& a, hipStream_t st) {
     const int stage_resid = PLANES == 2 && a.resid && lds + 8 * 8192 <= 160 * 1024;
     if (stage_resid) lds += 8 * 8192;
     const int mtiles = (a.gi.NS + BM - 1) / BM;
-    return conv_launch(conv_pw_kernel<PLANES, WM, WN, NT, MT>, mtiles, 512, lds, st, a, resident, stage_resid);
+    return conv_launch(conv_pw_kernel<PLANES, WM, WN, NT, MT, POST>, mtiles, 512, lds, st, a, resident, stage_resid);
 }
 
 // What this kernel takes: stride-1 1x1 conv, planes 1 / 2, cin a multiple of 64 and cout a multiple of 128, up to 2048.  Everything else
@@ -153,13 +153,20 @@ bool wsi_pw_takes(const ConvArgs& a, int planes) {
     if (planes != 1 && planes != 2) return false;
     if (a.ksize != 1 || a.stride != 1 || a.gi.H != a.go.H || a.gi.W != a.go.W || a.gi.N != a.go.N) return false;
     if (a.gi.C % 64 || a.go.C % 128 || a.gi.C < 64 || a.go.C < 128 || a.gi.C > 2048 || a.go.C > 2048) return false;
-    return !(a.out_split_pixels || a.in_split_pixels || a.in2 || a.in_up || a.flags);
+    if ((a.flags & CONV_RESID_POST) && !a.resid) return false;
+    return !(a.out_split_pixels || a.in_split_pixels || a.in2 || a.in_up || (a.flags & ~CONV_RESID_POST));
 }
 // ... and its launch; an error of the launch itself (WSI_EINVAL when the LDS limit cannot be raised) is the caller's error, never a
 // reason to take the slower route silently
 int wsi_pw_dispatch(const ConvArgs& a, int planes, hipStream_t st) {
     if (!wsi_pw_takes(a, planes)) return WSI_EINVAL;
     const int co = a.go.C;
+    if (a.flags & CONV_RESID_POST)                           // relu(bn(conv)) + resid (common.h CONV_RESID_POST): the same tile shapes
+        return by_planes<P1 | P2>(planes, [&](auto p) {
+            return co % 512 == 0   ? launch_pw<p(), 1, 8, 2, true>(a, st)
+                   : co % 256 == 0 ? launch_pw<p(), 1, 8, 1, true>(a, st)
+                                   : launch_pw<p(), 2, 4, 1, true>(a, st);
+        });
     return by_planes<P1 | P2>(planes, [&](auto p) {
         return co % 512 == 0   ? launch_pw<p(), 1, 8, 2>(a, st)
                : co % 256 == 0 ? launch_pw<p(), 1, 8, 1>(a, st)

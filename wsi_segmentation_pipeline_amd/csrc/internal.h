@@ -57,6 +57,10 @@ int wsi_unet_head_dispatch(const void* in, int n, int h, int w, int c_pf, const 
                            int planes, hipStream_t st);
 int wsi_resize_nearest_dispatch(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, hipStream_t st);
 int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w, int classes, float* logits, hipStream_t st);
+// linknet.hip: ConvTranspose2d(4, stride 2, padding 1) + folded BN + ReLU; a.gi = the (n, h, w, c) input, a.go = (n, 2h, 2w, c), a.ksize = 4
+int wsi_tconv_dispatch(const ConvArgs& a, int planes, hipStream_t st);
+// ... and the fused last block + head (planes 2): x = PF (n, hh, wh, 64), blob = wsi_linknet_tail_prepack's; WSI_EINVAL outside its range
+int wsi_linknet_tail_dispatch(const void* x, const void* blob, int n, int hh, int wh, int classes, float* logits, hipStream_t st);
 // slide_ops.hip
 int wsi_tile_gather_dispatch(const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, const float* lut,
                              float* out, int N, int ph, int pw, hipStream_t st);
@@ -137,6 +141,7 @@ struct ConvCall {
     // tensor (null when up_c == cin)
     const void* in_up = nullptr; int up_c = 0;
     long long plane96 = 0;           // bytes between the line planes of 96-byte-line tensors (0 = the tight distance for n images)
+    int resid_post = 0;              // out = relu(bn(conv)) + resid (common.h CONV_RESID_POST): stride-1 1x1, planes 1 / 2, resid and relu set
 };
 int conv_common(const ConvCall& c);
 // a 1x1 conv call (ksize 1): stride 1 in planes 1 / 2 on the pointwise kernel unless g_routes.pw_gather, everything else conv_common

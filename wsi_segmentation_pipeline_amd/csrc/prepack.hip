@@ -57,19 +57,49 @@ static void pow2_channel_scale(float amax, float& mul, float& inv) {
     inv = ldexpf(1.0f, -e);
 }
 
-extern "C" {
-
-size_t wsi_prepack_conv_bytes(int cout, int cin, int k, int planes) {
-    if (planes < 1 || planes > 3 || cout % 32 || cin % (planes == 1 ? 64 : 32) || (k != 1 && k != 3)) return 0;     // (whole 128-byte lines)
+// bytes of a pack of k x k taps (wsi_prepack_conv_bytes: k in {1, 3}; wsi_prepack_tconv_bytes: k = 4)
+static size_t prepack_taps_bytes(int cout, int cin, int k, int planes) {
+    if (planes < 1 || planes > 3 || cout <= 0 || cin <= 0 || cout % 32 || cin % (planes == 1 ? 64 : 32)) return 0;     // (whole 128-byte lines)
     // [cout/32][lines][k*k][4 frags][64 lanes][16 bytes]; lines = cin/64 (planes 1) or cin/32 (planes 2, 3)
     // planes 2: + cout floats, the inverse per-channel weight scales (common.h conv_wscale_inv)
     return (size_t)(cout / 32) * (planes == 1 ? cin / 64 : cin / 32) * k * k * 4 * 64 * 16 + (planes == 2 ? (size_t)cout * sizeof(float) : 0);
+}
+static int prepack_taps(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                        int cout, int cin, int k, int planes, void* wpk_out, float* bias_out);
+
+extern "C" {
+
+size_t wsi_prepack_conv_bytes(int cout, int cin, int k, int planes) {
+    return (k != 1 && k != 3) ? 0 : prepack_taps_bytes(cout, cin, k, planes);
 }
 
 int wsi_prepack_conv(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean,
                      const float* bn_var, float eps, int cout, int cin, int k, int planes, void* wpk_out,
                      float* bias_out) {
     if (!w || !wpk_out || !bias_out || wsi_prepack_conv_bytes(cout, cin, k, planes) == 0) return WSI_EINVAL;
+    return prepack_taps(w, bn_weight, bn_bias, bn_mean, bn_var, eps, cout, cin, k, planes, wpk_out, bias_out);
+}
+
+// ConvTranspose2d(c, c, kernel 4, stride 2, padding 1, bias=False) + BatchNorm (csrc/linknet.hip): w [cin][cout][4][4] fp32 as torch keeps
+// it; the pack is the conv pack with 16 taps, tap ky * 4 + kx holding w[ci][co][ky][kx] (BN folded per OUTPUT channel, planes 2: one
+// power-of-two scale per output channel over all its 16 * cin weights).  planes 1 / 2.
+size_t wsi_prepack_tconv_bytes(int c, int planes) {
+    return (planes != 1 && planes != 2) || c % 64 ? 0 : prepack_taps_bytes(c, c, 4, planes);
+}
+int wsi_prepack_tconv(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                      int c, int planes, void* wpk_out, float* bias_out) {
+    if (!w || !wpk_out || !bias_out || wsi_prepack_tconv_bytes(c, planes) == 0) return WSI_EINVAL;
+    std::vector<float> wt((size_t)c * c * 16);                                    // [cout][cin][4][4]
+    for (int ci = 0; ci < c; ++ci)
+        for (int co = 0; co < c; ++co)
+            memcpy(&wt[((size_t)co * c + ci) * 16], &w[((size_t)ci * c + co) * 16], 16 * sizeof(float));
+    return prepack_taps(wt.data(), bn_weight, bn_bias, bn_mean, bn_var, eps, c, c, 4, planes, wpk_out, bias_out);
+}
+
+}  // extern "C"
+
+static int prepack_taps(const float* w, const float* bn_weight, const float* bn_bias, const float* bn_mean, const float* bn_var, float eps,
+                        int cout, int cin, int k, int planes, void* wpk_out, float* bias_out) {
     uint16_t* o = (uint16_t*)wpk_out;
     const int NL = planes == 1 ? cin / 64 : cin / 32, NT = k * k;
     const size_t per = (size_t)cin * NT;                                          // weights per output channel
@@ -86,7 +116,7 @@ int wsi_prepack_conv(const float* w, const float* bn_weight, const float* bn_bia
         // frag 2: dwords 0-3 of the lane's fp6 plane - lanes h=0 carry Wh6, h=1 carry Wl6 (the two K halves of the MX
         // instruction pair with Xl6 / Xh6), K position = activation field order (mx6_field_chan); frag 3: {dwords 4-5 of
         // the plane, the plane's block scale byte, 0}.
-        memset(wpk_out, 0, wsi_prepack_conv_bytes(cout, cin, k, planes));
+        memset(wpk_out, 0, prepack_taps_bytes(cout, cin, k, planes));
         for (int nt = 0; nt < cout / 32; ++nt)
             for (int l = 0; l < NL; ++l)
                 for (int t = 0; t < NT; ++t) {
@@ -157,6 +187,8 @@ int wsi_prepack_conv(const float* w, const float* bn_weight, const float* bn_bia
                 }
     return WSI_OK;
 }
+
+extern "C" {
 
 // Weights of the fused decoder tail (tail.hip): the last decoder block's two 3x3 convs (BN folded) and the 1x1 head, parity mode.
 //   conv1 [2 py][6 taps = 2 low rows x 3 low columns][4 fragments] x 1 KiB: A rows 0-15 = output channels at px = 0, rows 16-31 at px = 1;
@@ -254,6 +286,39 @@ int wsi_unet_tail_prepack(const float* w1, const float* bn1_weight, const float*
         for (int c = 0; c < cmid; ++c) fl[64 + k * 16 + c] = head_w[(size_t)k * cmid + c];
         fl[128 + k] = head_b ? head_b[k] : 0.f;
     }
+    return WSI_OK;
+}
+
+// Weights of the Linknet's fused last block + head (linknet.hip linknet_tail_kernel), fp32 with the BatchNorm scale folded in (the product
+// in float64, rounded once), zero in the padding of narrower layers.  Floats: W0 [64 ci][16 co], B0 [16], WT [16 taps ky * 4 + kx][16 ci]
+// [16 co], BT [16], W2 [16 ci][32 co], B2 [32], WH [32 ci][4 k], BH [4] - the LT_* offsets of linknet.hip.
+size_t wsi_linknet_tail_prepack_bytes(void) { return (size_t)5828 * sizeof(float); }
+
+int wsi_linknet_tail_prepack(const float* w0, const float* bn0_weight, const float* bn0_bias, const float* bn0_mean, const float* bn0_var,
+                             const float* wt, const float* bnt_weight, const float* bnt_bias, const float* bnt_mean, const float* bnt_var,
+                             const float* w2, const float* bn2_weight, const float* bn2_bias, const float* bn2_mean, const float* bn2_var,
+                             float eps, const float* head_w, const float* head_b, int cin, int cmid, int cout, int classes, void* out) {
+    if (!w0 || !wt || !w2 || !head_w || !out || cin != 64 || cmid < 1 || cmid > 16 || cout < 1 || cout > 32 || classes < 1 || classes > 4) return WSI_EINVAL;
+    memset(out, 0, wsi_linknet_tail_prepack_bytes());
+    float* fl = (float*)out;
+    float *W0 = fl, *B0 = fl + 1024, *WT = fl + 1040, *BT = fl + 5136, *W2 = fl + 5152, *B2 = fl + 5664, *WH = fl + 5696, *BH = fl + 5824;
+    double sc, sh;
+    for (int co = 0; co < cmid; ++co) {
+        bn_fold(bn0_weight, bn0_bias, bn0_mean, bn0_var, eps, co, sc, sh);
+        B0[co] = (float)sh;
+        for (int ci = 0; ci < cin; ++ci) W0[ci * 16 + co] = fold_w(w0[(size_t)co * cin + ci], sc);
+        bn_fold(bnt_weight, bnt_bias, bnt_mean, bnt_var, eps, co, sc, sh);
+        BT[co] = (float)sh;
+        for (int ci = 0; ci < cmid; ++ci)
+            for (int t = 0; t < 16; ++t) WT[(t * 16 + ci) * 16 + co] = fold_w(wt[((size_t)ci * cmid + co) * 16 + t], sc);     // [in][out][ky][kx]
+    }
+    for (int c2 = 0; c2 < cout; ++c2) {
+        bn_fold(bn2_weight, bn2_bias, bn2_mean, bn2_var, eps, c2, sc, sh);
+        B2[c2] = (float)sh;
+        for (int co = 0; co < cmid; ++co) W2[co * 32 + c2] = fold_w(w2[(size_t)c2 * cmid + co], sc);
+        for (int k = 0; k < classes; ++k) WH[c2 * 4 + k] = head_w[(size_t)k * cout + c2];
+    }
+    for (int k = 0; k < classes; ++k) BH[k] = head_b ? head_b[k] : 0.f;
     return WSI_OK;
 }
 

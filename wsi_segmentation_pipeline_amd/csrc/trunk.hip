@@ -1,6 +1,6 @@
 // The model-level entries of libwsi_hip.so (include/wsi_hip.h): the profiler, the trunk workspace and its layout tags, the trunk
 // launch sequences of both architectures (trunk_run: BasicBlock, bneck_run: Bottleneck), the four forward entries over them and the
-// U-Net host sequence.  No device allocation, no synchronisation, no exceptions.
+// U-Net and Linknet host sequences (one templated sequence, two decoders).  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "../../include/wsi_hip.h"
 #include <iterator>
@@ -558,17 +558,30 @@ static bool decoder_ready(const wsi_unet_decoder_weights* dw) {
     return dw->tail_w || (dw->head_w && dw->head_b);
 }
 
-template <class Net>
-static size_t unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {
+static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                            float* logits_out, hipStream_t st);
+// What the four entries of a segmentation model need to know of its decoder: the weight struct, the plan of the decoder's part of the
+// workspace (`x0`: the half-resolution skip; `total`), whether every pointer a run reads is there, and the launch sequence.  The U-Net's
+// here; the Linknet's (LinknetDec) below.
+struct UnetDec {
+    using Weights = wsi_unet_decoder_weights;
+    using Plan = UnetPlan;
+    static constexpr auto plan = unet_plan;
+    static constexpr auto ready = decoder_ready;
+    static constexpr auto run = unet_decoder_run;
+};
+
+template <class Net, class Dec = UnetDec>
+static size_t unet_workspace_bytes(const typename Dec::Weights* dw, int n, int h, int w, int planes) {
     typename Net::Plan p;
-    UnetPlan u;
-    return (Net::plan(n, h, w, planes, p) || unet_plan(Net::enc_c, dw, n, h, w, planes, u)) ? 0 : align_up(p.total, 256) + u.total;
+    typename Dec::Plan u;
+    return (Net::plan(n, h, w, planes, p) || Dec::plan(Net::enc_c, dw, n, h, w, planes, u)) ? 0 : align_up(p.total, 256) + u.total;
 }
-template <class Net>
-static int unet_workspace_init(const wsi_unet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+template <class Net, class Dec = UnetDec>
+static int unet_workspace_init(const typename Dec::Weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
     typename Net::Plan p;
-    UnetPlan u;
-    if (!workspace || Net::plan(n, h, w, planes, p) || unet_plan(Net::enc_c, dw, n, h, w, planes, u)) return WSI_EINVAL;
+    typename Dec::Plan u;
+    if (!workspace || Net::plan(n, h, w, planes, p) || Dec::plan(Net::enc_c, dw, n, h, w, planes, u)) return WSI_EINVAL;
     int rc = Net::ws_init(workspace, n, h, w, planes, stream);
     if (rc) return rc;
     char* base = (char*)workspace + align_up(p.total, 256);
@@ -624,16 +637,16 @@ static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& 
 }
 
 // stem + trunk + decoder of either architecture.  Every argument is checked before the workspace is touched (run_checked's rule).
-template <class Net>
-static int unet_forward(const typename Net::Weights* wt, const wsi_unet_decoder_weights* dw, const TileSource& src, int n, int h, int w,
+template <class Net, class Dec = UnetDec>
+static int unet_forward(const typename Net::Weights* wt, const typename Dec::Weights* dw, const TileSource& src, int n, int h, int w,
                         void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
     typename Net::Plan p;
-    UnetPlan u;
+    typename Dec::Plan u;
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!wt || !dw || !workspace || n <= 0 || cap < n || (!logits_out && !enc_out) || h % 32 || w % 32) return WSI_EINVAL;
-    if (Net::plan(cap, h, w, wt->planes, p) || unet_plan(Net::enc_c, dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
+    if (Net::plan(cap, h, w, wt->planes, p) || Dec::plan(Net::enc_c, dw, cap, h, w, wt->planes, u)) return WSI_EINVAL;
     const TrunkDepth d(wt->blocks);
-    if (!trunk_ready(wt, d, src) || (logits_out && !decoder_ready(dw))) return WSI_EINVAL;
+    if (!trunk_ready(wt, d, src) || (logits_out && !Dec::ready(dw))) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
@@ -672,18 +685,18 @@ static int unet_forward(const typename Net::Weights* wt, const wsi_unet_decoder_
         }
         if (rc) return rc;
     }
-    return logits_out ? unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, st) : WSI_OK;
+    return logits_out ? Dec::run(dw, u, enc, n, planes, dec, logits_out, st) : WSI_OK;
 }
 
 // `model.decoder(encoding)` with caller-held fp32 NCHW maps (deepest first): pack, then the same decoder launches
-template <class Net>
-static int unet_decoder(const wsi_unet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+template <class Net, class Dec = UnetDec>
+static int unet_decoder(const typename Dec::Weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
                         int workspace_n, float* logits_out, void* stream) {
     typename Net::Plan p;
-    UnetPlan u;
+    typename Dec::Plan u;
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!dw || !enc_nchw || !workspace || !logits_out || n <= 0 || cap < n) return WSI_EINVAL;
-    if (Net::plan(cap, h, w, planes, p) || unet_plan(Net::enc_c, dw, cap, h, w, planes, u) || !decoder_ready(dw)) return WSI_EINVAL;
+    if (Net::plan(cap, h, w, planes, p) || Dec::plan(Net::enc_c, dw, cap, h, w, planes, u) || !Dec::ready(dw)) return WSI_EINVAL;
     for (int i = 0; i < 5; ++i) if (!enc_nchw[i]) return WSI_EINVAL;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
@@ -696,7 +709,104 @@ static int unet_decoder(const wsi_unet_decoder_weights* dw, const float* const e
         rc = wsi_pf_pack(enc_nchw[i], dst, n, m.c, m.h, m.w, planes, stream);
         enc[i] = dst;
     }
-    return rc ? rc : unet_decoder_run(dw, u, enc, n, planes, dec, logits_out, (hipStream_t)stream);
+    return rc ? rc : Dec::run(dw, u, enc, n, planes, dec, logits_out, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ Linknet (dense 'seg' path, light decoder)
+// smp's Linknet decoder on the BasicBlock trunk (include/wsi_hip.h "Linknet"): five blocks of [1x1 conv cin -> cin / 4, ConvTranspose2d
+// 4x4 stride 2, 1x1 conv -> cout], each + BN + ReLU, the next encoder map added AFTER the block (no ReLU behind the add), 1x1 head.
+// Stored widths: every tensor at least 64 channels wide (mid 32 and 16, cout 32: zero weights in the padding, whose outputs are
+// relu(0) = 0), so the 1x1 convs keep the existing routes - the pointwise kernel where cout % 128 == 0, the gather kernel otherwise.
+// Block L (0-based) reads an (h / 32 << L) map: a[L] = its first 1x1 at that size, b[L] and c[L] the transposed conv and the second 1x1
+// at twice the size.
+static const int LINKNET_CIN[15] = {512, 128, 128, 256, 64, 64, 128, 64, 64, 64, 64, 64, 64, 64, 64};
+static const int LINKNET_COUT[15] = {128, 128, 256, 64, 64, 128, 64, 64, 64, 64, 64, 64, 64, 64, 64};
+constexpr int LINKNET_HEAD_CIN = 32;                  // real channels of the last block
+struct LinknetPlan {
+    size_t x0, a[5], b[5], c[5], total;
+    int r_h[5], r_w[5];                               // the map block L reads
+};
+static int linknet_plan(const int ec[5], const wsi_linknet_decoder_weights* dw, int n, int h, int w, int planes, LinknetPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    for (int i = 0; i < 15; ++i) if (dw->cin[i] != LINKNET_CIN[i] || dw->cout[i] != LINKNET_COUT[i]) return WSI_EINVAL;
+    if (ec[0] != LINKNET_CIN[0] || dw->head_cin != LINKNET_HEAD_CIN || dw->classes <= 0 || dw->classes > 16) return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    for (int L = 0; L < 5; ++L) {
+        u.r_h[L] = (h / 32) << L; u.r_w[L] = (w / 32) << L;
+        if (L < 4 && ec[L + 1] != LINKNET_COUT[3 * L + 2]) return WSI_EINVAL;         // the skip is added channel for channel
+        u.a[L] = take(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], LINKNET_COUT[3 * L], planes));
+        u.b[L] = take(wsi_pf_bytes(n, 2 * u.r_h[L], 2 * u.r_w[L], LINKNET_COUT[3 * L + 1], planes));
+        u.c[L] = take(wsi_pf_bytes(n, 2 * u.r_h[L], 2 * u.r_w[L], LINKNET_COUT[3 * L + 2], planes));
+    }
+    u.total = off;
+    return WSI_OK;
+}
+// every pointer a decoder run reads: the convs of blocks 1-4 always; the last block's three and the head unless the fused tail's blob
+// stands in for them (where the tail then does not apply, conv_common refuses the null pointer)
+static bool linknet_ready(const wsi_linknet_decoder_weights* dw) {
+    for (int i = 0; i < (dw->tail_w ? 12 : 15); ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    return dw->tail_w || (dw->head_w && dw->head_b);
+}
+// wsi_prof kinds: 12 = a Linknet 1x1 conv (2 * N * H * W * cin_stored * cout_stored), 13 = transposed conv (per output pixel 4 of the 16
+// taps: 2 * N * 2H * 2W * c * c * 4), 14 = the fused last block + head (the FLOPs of its REAL channels), 8 = the 1x1 head
+static int linknet_decoder_run(const wsi_linknet_decoder_weights* dw, const LinknetPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                               float* logits_out, hipStream_t st) {
+    const void* x = enc[0];
+    int rc = WSI_OK;
+    // parity mode runs the last block and the head as ONE kernel (linknet.hip linknet_tail_kernel) when the caller prepacked its weights
+    // (wsi_linknet_tail_prepack -> dw->tail_w), the tile is at most 256 wide and the head has at most 4 classes; A/B: WSI_CONV_MODE_LINKNET_NO_TAIL
+    const bool tail = planes == 2 && dw->tail_w && g_routes.linknet_tail && dw->classes <= 4 && u.r_w[4] <= 128 && u.r_h[4] % 4 == 0;
+    for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
+        const int H = u.r_h[L], W = u.r_w[L], i = 3 * L, mid = dw->cout[i];
+        auto conv1 = [&](const void* in, void* out, const void* skip, int j, int hh, int ww) {
+            return ConvCall{.in = in, .out = out, .resid = skip, .wpk = dw->conv_w[j], .bias = dw->conv_b[j], .n = n, .h = hh, .w = ww,
+                            .cin = dw->cin[j], .cout = dw->cout[j], .stride = 1, .ksize = 1, .relu = 1, .planes = planes, .stream = st,
+                            .resid_post = skip ? 1 : 0};
+        };
+        if ((rc = run_conv(st, 12, conv1(x, dec + u.a[L], nullptr, i, H, W)))) break;
+        {
+            ProfScope ps(st, 13, conv_flops(n, 2 * H, 2 * W, mid, mid, 4));
+            rc = wsi_tconv4x4s2_bn_relu(dec + u.a[L], dec + u.b[L], dw->conv_w[i + 1], dw->conv_b[i + 1], n, H, W, mid, planes, st);
+        }
+        if (rc) break;
+        rc = run_conv(st, 12, conv1(dec + u.b[L], dec + u.c[L], L < 4 ? enc[L + 1] : nullptr, i + 2, 2 * H, 2 * W));
+        x = dec + u.c[L];
+    }
+    if (rc) return rc;
+    if (tail) {                                           // per output pixel: a quarter of the 64 -> 16 conv, 4 taps x 16 x 16, 16 -> 32, the head
+        ProfScope ps(st, 14, 2.0 * n * (2 * u.r_h[4]) * (2 * u.r_w[4]) * (64.0 * 16.0 / 4.0 + 4.0 * 16.0 * 16.0 + 16.0 * 32.0 + 32.0 * dw->classes));
+        return wsi_linknet_tail_dispatch(x, dw->tail_w, n, u.r_h[4], u.r_w[4], dw->classes, logits_out, st);
+    }
+    if (!dw->head_w || !dw->head_b) return WSI_EINVAL;    // (a blob without the plain head, on a shape the fused kernel does not take)
+    ProfScope ps(st, 8, 2.0 * n * (2 * u.r_h[4]) * (2 * u.r_w[4]) * (double)dw->head_cin * dw->classes);
+    return wsi_unet_head_dispatch(x, n, 2 * u.r_h[4], 2 * u.r_w[4], dw->cout[14], dw->head_w, dw->head_b, dw->head_cin, dw->classes, logits_out,
+                                  planes, st);
+}
+struct LinknetDec {
+    using Weights = wsi_linknet_decoder_weights;
+    using Plan = LinknetPlan;
+    static constexpr auto plan = linknet_plan;
+    static constexpr auto ready = linknet_ready;
+    static constexpr auto run = linknet_decoder_run;
+};
+
+size_t wsi_linknet_workspace_bytes(const wsi_linknet_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BasicNet, LinknetDec>(dw, n, h, w, planes);
+}
+int wsi_linknet_workspace_init(const wsi_linknet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BasicNet, LinknetDec>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_linknet_forward(const wsi_trunk_weights* wt, const wsi_linknet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                        long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                        int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BasicNet, LinknetDec>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace,
+                                              workspace_n, logits_out, enc_out, stream);
+}
+int wsi_linknet_decoder(const wsi_linknet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                        int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BasicNet, LinknetDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
 }
 
 size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {

@@ -843,6 +843,42 @@ def prepack_conv(weight, bn, planes, device):
     return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
 
 
+def prepack_tconv(weight, bn, planes, device):
+    """ConvTranspose2d(c, c, 4, stride 2, padding 1) weight (c in, c out, 4, 4) fp32 as torch keeps it; bn = (gamma, beta, mean, var)
+    of the output channels or None -> (wpk, bias) device tensors (wsi_prepack_tconv; c a multiple of 64)."""
+    lib = native.load()
+    w = np.ascontiguousarray(torch.as_tensor(weight).detach().cpu().to(torch.float32).numpy())
+    if w.ndim != 4 or w.shape[0] != w.shape[1] or w.shape[2:] != (4, 4):
+        raise ValueError('expected a (c, c, 4, 4) transposed-conv weight, got %s' % (w.shape,))
+    c = w.shape[0]
+    nbytes = lib.wsi_prepack_tconv_bytes(c, planes)
+    if nbytes == 0:
+        raise ValueError('unsupported transposed-conv width %d for planes %d (a multiple of 64; planes 1 or 2)' % (c, planes))
+    pk = np.empty(nbytes, np.uint8)
+    bias = np.empty(c, np.float32)
+    keep = [] if bn is None else [np.ascontiguousarray(torch.as_tensor(t).detach().cpu().to(torch.float32).numpy()) for t in bn]
+    args = [_np_ptr(a) for a in keep] if keep else [None] * 4
+    native.check(lib.wsi_prepack_tconv(_np_ptr(w), *args, BN_EPS, c, planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_tconv')
+    return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
+
+
+def tconv4x4s2_bn_relu(x_pf, n, h, w, c, wpk, bias, planes=2):
+    """wsi_tconv4x4s2_bn_relu: PF (n, h, w, c) -> a new zeroed PF buffer (n, 2h, 2w, c) = relu(bn(conv_transpose2d(x)))."""
+    lib = native.load()
+    out = pf_zeros(n, c, 2 * h, 2 * w, planes, x_pf.device)
+    native.check(lib.wsi_tconv4x4s2_bn_relu(_ptr(x_pf), _ptr(out), _ptr(wpk), _ptr(bias), n, h, w, c, planes, _stream()), 'wsi_tconv4x4s2_bn_relu')
+    return out
+
+
+def conv1x1_bn_relu_add(x_pf, skip_pf, n, h, w, cin, cout, wpk, bias, planes=2):
+    """wsi_conv1x1_bn_relu_add: relu(bn(conv1x1(x))) + skip (the ReLU before the add) into a new zeroed PF buffer."""
+    lib = native.load()
+    out = pf_zeros(n, cout, h, w, planes, x_pf.device)
+    native.check(lib.wsi_conv1x1_bn_relu_add(_ptr(x_pf), _ptr(out), _ptr(skip_pf), _ptr(wpk), _ptr(bias), n, h, w, cin, cout, planes, _stream()),
+                 'wsi_conv1x1_bn_relu_add')
+    return out
+
+
 def conv1x1_bn_act(x_pf, n, h, w, cin, cout, wpk, bias, stride=1, resid_pf=None, relu=True, planes=2, out=None, check=True):
     """wsi_conv1x1_bn_act (the Bottleneck 1x1 convs: pointwise kernel at stride 1 unless ConvMode.PW_GATHER) into `out` (a zeroed PF
     buffer is made when None).  check=False returns (out, return code) instead of raising."""

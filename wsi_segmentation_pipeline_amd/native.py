@@ -50,6 +50,14 @@ class WsiUnetDecoderWeights(C.Structure):
     ]
 
 
+class WsiLinknetDecoderWeights(C.Structure):
+    """wsi_linknet_decoder_weights: conv 3 * (L - 1) + J = decoder.layerL.block.J; tail_w = wsi_linknet_tail_prepack's blob or NULL."""
+    _fields_ = [
+        ('conv_w', C.c_void_p * 15), ('conv_b', C.c_void_p * 15), ('cin', C.c_int * 15), ('cout', C.c_int * 15),
+        ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_cin', C.c_int), ('classes', C.c_int), ('tail_w', C.c_void_p),
+    ]
+
+
 _vp, _i, _ll, _sz, _f, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double
 # name -> (restype, argtypes); must list every symbol include/wsi_hip.h declares
 SIGNATURES = {
@@ -148,6 +156,17 @@ SIGNATURES = {
     'wsi_unet_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiUnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
                                     _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
     'wsi_unet_bneck_decoder': (_i, [C.POINTER(WsiUnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'wsi_prepack_tconv_bytes': (_sz, [_i, _i]),
+    'wsi_prepack_tconv': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
+    'wsi_linknet_tail_prepack_bytes': (_sz, []),
+    'wsi_linknet_tail_prepack': (_i, [_vp] * 15 + [_f, _vp, _vp, _i, _i, _i, _i, _vp]),
+    'wsi_tconv4x4s2_bn_relu': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'wsi_conv1x1_bn_relu_add': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'wsi_linknet_workspace_bytes': (_sz, [C.POINTER(WsiLinknetDecoderWeights), _i, _i, _i, _i]),
+    'wsi_linknet_workspace_init': (_i, [C.POINTER(WsiLinknetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_linknet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiLinknetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                                 _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_linknet_decoder': (_i, [C.POINTER(WsiLinknetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_resize_nearest_f32': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _vp]),
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
@@ -214,6 +233,7 @@ class ConvMode(enum.IntFlag):
     UNET_NO_TAIL = 2097152
     UNET_TAIL_FORM1 = 4194304
     UNET_X0_UNFUSED = 8388608
+    LINKNET_NO_TAIL = 16777216
 
 
 class StemMode(enum.IntEnum):

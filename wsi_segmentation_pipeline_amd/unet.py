@@ -17,6 +17,9 @@ the maps of ``ResNet(Bottleneck, layers)`` - 2048 / 1024 / 512 / 256 / 64 channe
 (``cat([up2(x), skip])`` of (2048, 1024), (256, 512), (128, 256), (64, 64)); key names as above; 'parity' and 'speed' only.
 Eval-mode forwards run on libwsi_hip.so only (conv3x3 MFMA kernels + upsample/concat, head kernels: csrc/unet.hip); training
 mode uses torch ops so ``train.py``-style callers still run.
+The reference picks the model family by name (``eval('smp.' + args.model_name)``, ``--model_name``): this module serves 'Unet' (above) and
+'Linknet' (`Linknet`, `LinknetSeg`, `LinknetEngine` below: smp's transposed-conv decoder, csrc/linknet.hip), so
+``import wsi_segmentation_pipeline_amd.unet as smp`` keeps that line working.
 """
 import ctypes as C
 
@@ -88,6 +91,8 @@ class UNetEngine:
     depth are read from the state dict (`engine.trunk_arch`): BasicBlock nets run on a TrunkEngine and wsi_unet_*, Bottleneck nets on a
     BottleneckEngine and wsi_unet_bneck_* (parity and speed only).  `encoder` (an smp name), when given, must agree with the state dict."""
 
+    ENTRY = {'basic': 'wsi_unet', 'bottleneck': 'wsi_unet_bneck'}      # prefix of the four C entries, per encoder architecture
+
     def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
         self._ws = {}
         self.lib = native.load()
@@ -105,15 +110,13 @@ class UNetEngine:
             if self.trunk.layers != named or (encoder in BOTTLENECK_ENCODER_LAYERS) != (self.arch == 'bottleneck'):
                 raise ValueError('state dict holds a %s %s encoder, not %s' % (self.arch, self.trunk.layers, encoder))
         self.enc_ch = ENC_CH[self.arch]
-        skip_ch = _skip_ch(self.enc_ch)
-        entry = 'wsi_unet_bneck' if self.arch == 'bottleneck' else 'wsi_unet'
+        entry = self.ENTRY[self.arch]
         self._ws_bytes, self._ws_init, self._forward, self._decoder = (
             getattr(self.lib, entry + s) for s in ('_workspace_bytes', '_workspace_init', '_forward', '_decoder'))
         self.planes = planes
         self.classes = int(classes if classes is not None else state_dict['decoder.final_conv.weight'].shape[0])
         self.max_batch = max_batch
         self._keep, self._ws = [], {}
-        self.dw = native.WsiUnetDecoderWeights()
 
         def f32(key):
             return np.ascontiguousarray(state_dict[key].detach().to('cpu', torch.float32).numpy())
@@ -123,6 +126,13 @@ class UNetEngine:
             self._keep.append(t)
             return t
 
+        self._pack_decoder(f32, dev)
+
+    def _pack_decoder(self, f32, dev):
+        """Fill self.dw from the decoder.* keys: f32(key) -> contiguous fp32 array, dev(array) -> device tensor kept alive."""
+        planes = self.planes
+        skip_ch = _skip_ch(self.enc_ch)
+        self.dw = native.WsiUnetDecoderWeights()
         cprev_real, cprev_pad = self.enc_ch[0], self.enc_ch[0]
         for L in range(5):
             cout = DEC_CH[L]
@@ -369,6 +379,7 @@ class UNetSeg(nn.Module):
     ``regressor`` heads attachable."""
 
     ENCODER = UNetEncoder
+    ENGINE = UNetEngine
     PRECISIONS = ('parity', 'mx', 'speed')
 
     def __init__(self, classes=4, precision='parity', encoder='resnet18'):
@@ -376,17 +387,20 @@ class UNetSeg(nn.Module):
         if precision not in self.PRECISIONS:
             raise ValueError('precision must be one of %s for a %s encoder, got %r' % (' / '.join(self.PRECISIONS), encoder, precision))
         self.encoder = self.ENCODER(self, encoder)
-        self.decoder = UNetDecoder(classes, self, self.encoder.out_shapes)
+        self.decoder = self._make_decoder(classes)
         self.classes, self.precision, self.encoder_name = classes, precision, encoder
         self._engine, self._engine_sig = None, None
+
+    def _make_decoder(self, classes):
+        return UNetDecoder(classes, self, self.encoder.out_shapes)
 
     def hip_engine(self, device=None):
         device = torch.device(device) if device is not None else self.decoder.final_conv.weight.device
         sig = (str(device), self.precision) + tuple((p.data_ptr(), p._version) for p in self.parameters()) \
             + tuple((b.data_ptr(), b._version) for b in self.buffers())
         if self._engine is None or sig != self._engine_sig:
-            self._engine = UNetEngine(self.state_dict(), device, planes={'parity': PARITY, 'mx': MX, 'speed': SPEED}[self.precision],
-                                      classes=self.classes, encoder=self.encoder_name)
+            self._engine = self.ENGINE(self.state_dict(), device, planes={'parity': PARITY, 'mx': MX, 'speed': SPEED}[self.precision],
+                                       classes=self.classes, encoder=self.encoder_name)
             self._engine_sig = sig
         return self._engine
 
@@ -406,6 +420,170 @@ class UNetSegBottleneck(UNetSeg):
 
     def __init__(self, classes=4, precision='parity', encoder='resnet50'):
         super().__init__(classes, precision, encoder)
+
+
+# ---------------------------------------------------------------------------------------------- Linknet
+# smp's light decoder (``--model_name Linknet``, the reference's myargs.py:9; built by ``eval('smp.' + args.model_name)(...)`` at
+# eval.py:22, eval_tumorbed.py:21).  Restated from the published 0.0.x source like the U-Net above - parity unpinned, the numerical spec is
+# tests/linknet_oracle.py.  ``decoder.layer{1..5}`` = DecoderBlock(cin, cout) with mid = cin // 4:
+#   block.0  1x1 conv cin -> mid (no bias) + BN + ReLU
+#   block.1  ConvTranspose2d(mid, mid, kernel 4, stride 2, padding 1, bias=False) + BN + ReLU     weight [mid in][mid out][4][4]
+#   block.2  1x1 conv mid -> cout (no bias) + BN + ReLU
+# and ``x = block(x) + skip`` (no ReLU after the add) with skips x3, x2, x1, x0 for layers 1-4, none for layer 5; ``decoder.final_conv``
+# 1x1 32 -> classes + bias.  BasicBlock encoders only ('resnet18', 'resnet34'); precision 'parity' or 'speed'.
+LINKNET_CH = ((512, 128, 256), (256, 64, 128), (128, 32, 64), (64, 16, 64), (64, 16, 32))      # (cin, mid, cout) of layer1..5
+
+
+def linknet_decoder_key_shapes(classes):
+    """[(key, shape, kind)] of the Linknet decoder in state-dict order: 92 keys.  kind 'tconv' = the transposed-conv weight [in][out][4][4]."""
+    out = []
+    for L, (cin, mid, cout) in enumerate(LINKNET_CH):
+        for j, (shape, kind, c) in enumerate((((mid, cin, 1, 1), 'conv', mid), ((mid, mid, 4, 4), 'tconv', mid), ((cout, mid, 1, 1), 'conv', cout))):
+            p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
+            out.append((p + '.0.weight', shape, kind))
+            for suffix, bn_kind in (('weight', 'bn_w'), ('bias', 'bn_b'), ('running_mean', 'bn_m'), ('running_var', 'bn_v')):
+                out.append(('%s.1.%s' % (p, suffix), (c,), bn_kind))
+            out.append((p + '.1.num_batches_tracked', (), 'bn_n'))
+    out.append(('decoder.final_conv.weight', (classes, LINKNET_CH[4][2], 1, 1), 'conv'))
+    out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
+    return out
+
+
+class LinknetEngine(UNetEngine):
+    """BasicBlock ResNet encoder + Linknet decoder on HIP kernels (wsi_linknet_*; csrc/linknet.hip): the surface of UNetEngine -
+    forward_f32, forward_tiles, decode, release_workspaces - with the batch sized by the Linknet workspace (~70 MB per 256 x 256 tile in
+    parity mode).  Every stored tensor is at least 64 channels wide: layers narrower than that carry zero weights in the padding."""
+
+    ENTRY = {'basic': 'wsi_linknet'}
+
+    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
+        if planes not in (PARITY, SPEED):
+            raise ValueError("a Linknet runs in precision 'parity' or 'speed': there is no mx mode")
+        if encoder is not None:
+            encoder_layers(encoder)
+        if trunk_arch({k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')})[0] != 'basic':
+            raise ValueError('a Linknet runs on BasicBlock encoders only (%s)' % sorted(ENCODER_LAYERS))
+        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+
+    def _pack_decoder(self, f32, dev):
+        planes = self.planes
+        self.dw = native.WsiLinknetDecoderWeights()
+
+        def pad(c):
+            return max(64, c)
+
+        for L, (cin, mid, cout) in enumerate(LINKNET_CH):
+            cin_s = cin if L == 0 else pad(LINKNET_CH[L - 1][2])           # stored width of the block's input
+            for j, (co, ci, co_s, ci_s) in enumerate(((mid, cin, pad(mid), cin_s), (mid, mid, pad(mid), pad(mid)), (cout, mid, pad(cout), pad(mid)))):
+                p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
+                w = f32(p + '.0.weight')
+                k = 4 if j == 1 else 1
+                wp = np.zeros((ci_s, co_s, 4, 4) if j == 1 else (co_s, ci_s, 1, 1), np.float32)
+                if j == 1:
+                    wp[:ci, :co] = w                                   # ConvTranspose2d keeps [in][out][ky][kx]
+                else:
+                    wp[:co, :ci] = w
+                bn = []
+                for suffix, fill in (('weight', 1.0), ('bias', 0.0), ('running_mean', 0.0), ('running_var', 1.0)):
+                    a = np.full(co_s, fill, np.float32)                # padding channels: scale ~1, shift 0 -> relu(0) = 0
+                    a[:co] = f32('%s.1.%s' % (p, suffix))
+                    bn.append(a)
+                bias = np.empty(co_s, np.float32)
+                if k == 4:
+                    pk = np.empty(self.lib.wsi_prepack_tconv_bytes(co_s, planes), np.uint8)
+                    native.check(self.lib.wsi_prepack_tconv(_np_ptr(wp), *[_np_ptr(a) for a in bn], BN_EPS, co_s, planes, _np_ptr(pk), _np_ptr(bias)),
+                                 'wsi_prepack_tconv')
+                else:
+                    pk = np.empty(self.lib.wsi_prepack_conv_bytes(co_s, ci_s, 1, planes), np.uint8)
+                    native.check(self.lib.wsi_prepack_conv(_np_ptr(wp), *[_np_ptr(a) for a in bn], BN_EPS, co_s, ci_s, 1, planes, _np_ptr(pk),
+                                                           _np_ptr(bias)), 'wsi_prepack_conv')
+                i = 3 * L + j
+                self.dw.conv_w[i], self.dw.conv_b[i] = dev(pk).data_ptr(), dev(bias).data_ptr()
+                self.dw.cin[i], self.dw.cout[i] = ci_s, co_s
+        head_cin = LINKNET_CH[4][2]
+        hw = f32('decoder.final_conv.weight').reshape(self.classes, head_cin)
+        self.dw.head_w = dev(np.ascontiguousarray(hw)).data_ptr()
+        self.dw.head_b = dev(f32('decoder.final_conv.bias')).data_ptr()
+        self.dw.head_cin, self.dw.classes = head_cin, self.classes
+        self.dw.tail_w = None
+        if planes == PARITY and self.classes <= 4:
+            # the last block + head as one kernel (csrc/linknet.hip linknet_tail_kernel) on the block's REAL channels
+            cin, mid, cout = LINKNET_CH[4]
+            ps = ['decoder.layer5.block.%d.block' % j for j in range(3)]
+            args = []
+            for p in ps:
+                args.append(_np_ptr(f32(p + '.0.weight')))
+                args += [_np_ptr(f32('%s.1.%s' % (p, sfx))) for sfx in ('weight', 'bias', 'running_mean', 'running_var')]
+            blob = np.empty(self.lib.wsi_linknet_tail_prepack_bytes(), np.uint8)
+            native.check(self.lib.wsi_linknet_tail_prepack(*args, BN_EPS, _np_ptr(np.ascontiguousarray(hw)), _np_ptr(f32('decoder.final_conv.bias')),
+                                                           cin, mid, cout, self.classes, _np_ptr(blob)), 'wsi_linknet_tail_prepack')
+            self.dw.tail_w = dev(blob).data_ptr()
+
+
+class _ConvBnReLU(nn.Module):
+    """``.block`` = Sequential(conv, BatchNorm2d, ReLU): the state-dict keys ``block.0.weight``, ``block.1.*``."""
+
+    def __init__(self, conv, c):
+        super().__init__()
+        self.block = nn.Sequential(conv, nn.BatchNorm2d(c), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        return self.block(x)
+
+
+class _LinknetBlock(nn.Module):
+    def __init__(self, cin, cout):
+        super().__init__()
+        mid = cin // 4
+        self.block = nn.Sequential(_ConvBnReLU(nn.Conv2d(cin, mid, 1, bias=False), mid),
+                                   _ConvBnReLU(nn.ConvTranspose2d(mid, mid, 4, stride=2, padding=1, bias=False), mid),
+                                   _ConvBnReLU(nn.Conv2d(mid, cout, 1, bias=False), cout))
+
+    def forward(self, x, skip=None):
+        x = self.block(x)
+        return x if skip is None else x + skip
+
+
+class LinknetDecoder(nn.Module):
+    def __init__(self, classes, owner=None):
+        super().__init__()
+        for L, (cin, _mid, cout) in enumerate(LINKNET_CH):
+            setattr(self, 'layer%d' % (L + 1), _LinknetBlock(cin, cout))
+        self.final_conv = nn.Conv2d(LINKNET_CH[4][2], classes, 1)
+        self._owner = [owner]                                  # list: not registered as a sub-module
+
+    def forward(self, enc):
+        if not self.training:
+            return self._owner[0].hip_engine(enc[0].device).decode(list(enc))
+        x = enc[0]
+        skips = list(enc[1:]) + [None]
+        for L in range(5):
+            x = getattr(self, 'layer%d' % (L + 1))(x, skips[L])
+        return self.final_conv(x)
+
+
+class LinknetSeg(UNetSeg):
+    """Drop-in for ``smp.Linknet(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of
+    UNetSeg (``model(x)``, ``model.encoder``, ``model.decoder``, ``hip_engine``), so every caller that takes a UNetSeg - utils.eval's
+    fused tile path, multi-rank stitching - takes it too.  Precision 'parity' or 'speed'."""
+    PRECISIONS = ('parity', 'speed')
+    ENGINE = LinknetEngine
+
+    def _make_decoder(self, classes):
+        return LinknetDecoder(classes, self)
+
+
+def Linknet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
+    """smp's factory signature for the Linknet, so with ``import wsi_segmentation_pipeline_amd.unet as smp`` the reference's
+    ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None, classes=C, activation=None)`` serves 'Unet' and 'Linknet'.
+    Refusals as `Unet`; encoders 'resnet18' and 'resnet34' only."""
+    if encoder_weights is not None:
+        raise ValueError('encoder_weights must be None (got %r): pretrained weights are not downloaded; load a state dict' % (encoder_weights,))
+    if activation is not None:
+        raise ValueError('activation must be None (got %r): the model returns logits, as the reference builds it' % (activation,))
+    if encoder_name not in ENCODER_LAYERS:
+        raise ValueError('encoder_name must be one of %s for a Linknet, got %r' % (list(ENCODER_LAYERS), encoder_name))
+    return LinknetSeg(classes, precision, encoder_name)
 
 
 def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
