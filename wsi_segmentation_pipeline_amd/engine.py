@@ -32,8 +32,49 @@ def _stream(st=None):
     return C.c_void_p((st or torch.cuda.current_stream()).cuda_stream)
 
 
+def _np32(t):
+    return np.ascontiguousarray(torch.as_tensor(t).detach().to('cpu', torch.float32).numpy())
+
+
 def _f32(sd, key):
-    return np.ascontiguousarray(sd[key].detach().to('cpu', torch.float32).numpy())
+    return _np32(sd[key])
+
+
+BN_KEYS = ('weight', 'bias', 'running_mean', 'running_var')      # the four vectors of a BatchNorm, in the order every prepack entry takes them
+
+
+def _bn(sd, prefix):
+    return [_f32(sd, '%s.%s' % (prefix, s)) for s in BN_KEYS]
+
+
+def _slide_args(slide):
+    """(pointer, row pitch, height, width) of an optional (SH,SW,3) u8 slide, as the forward entries take them"""
+    if slide is None:
+        return None, 0, 0, 0
+    return _ptr(slide), slide.stride(0), slide.shape[0], slide.shape[1]
+
+
+def pack_conv(lib, w, bn, planes, tconv=False):
+    """A conv weight (cout, cin, k, k) - or, with `tconv`, a ConvTranspose2d(c, c, 4, stride 2, padding 1) weight (c in, c out, 4, 4) as
+    torch keeps it - with its BatchNorm folded in: fp32 numpy `w`, `bn` = [gamma, beta, mean, var] fp32 numpy or None -> (packed uint8
+    array, bias fp32 array) as wsi_prepack_conv / wsi_prepack_tconv write them.  Host work only: no device, no engine."""
+    w = np.ascontiguousarray(w, np.float32)
+    if tconv:
+        if w.ndim != 4 or w.shape[0] != w.shape[1] or w.shape[2:] != (4, 4):
+            raise ValueError('expected a (c, c, 4, 4) transposed-conv weight, got %s' % (w.shape,))
+        cout, dims, entry = w.shape[0], (w.shape[0],), 'wsi_prepack_tconv'
+    else:
+        cout, dims, entry = w.shape[0], w.shape[:3], 'wsi_prepack_conv'
+    nbytes = getattr(lib, entry + '_bytes')(*dims, planes)
+    if nbytes == 0:
+        if tconv:
+            raise ValueError('unsupported transposed-conv width %d for planes %d (a multiple of 64; planes 1 or 2)' % (cout, planes))
+        raise ValueError('unsupported conv shape %s' % (w.shape,))
+    bn = [] if bn is None else [np.ascontiguousarray(a, np.float32) for a in bn]
+    pk, bias = np.empty(nbytes, np.uint8), np.empty(cout, np.float32)
+    native.check(getattr(lib, entry)(_np_ptr(w), *([_np_ptr(a) for a in bn] or [None] * 4), BN_EPS, *dims, planes, _np_ptr(pk),
+                                     _np_ptr(bias)), entry)
+    return pk, bias
 
 
 def normalize_lut(mean, std):
@@ -283,9 +324,6 @@ class TrunkEngine:
         for L in range(4):
             self.wt.blocks[L] = self.layers[L]
 
-        def bn(prefix):
-            return [_f32(sd, prefix + s) for s in ('.weight', '.bias', '.running_mean', '.running_var')]
-
         def dev(a):
             t = torch.from_numpy(a).to(self.device)
             self._keep.append(t)
@@ -295,7 +333,7 @@ class TrunkEngine:
         w = _f32(sd, 'conv1.weight')
         pk = np.empty(self.lib.wsi_prepack_stem_bytes(planes), np.uint8)
         bias = np.empty(64, np.float32)
-        g, b, m, v = bn('bn1')
+        g, b, m, v = _bn(sd, 'bn1')
         native.check(self.lib.wsi_prepack_stem(_np_ptr(w), _np_ptr(g), _np_ptr(b), _np_ptr(m), _np_ptr(v), BN_EPS,
                                                planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_stem')
         self.wt.stem_w = dev(pk).data_ptr()
@@ -314,12 +352,9 @@ class TrunkEngine:
 
         def conv(wkey, bnkey, k):
             w = _f32(sd, wkey)
-            cout, cin = w.shape[0], w.shape[1]
-            pk = np.empty(self.lib.wsi_prepack_conv_bytes(cout, cin, k, planes), np.uint8)
-            bias = np.empty(cout, np.float32)
-            g, b, m, v = bn(bnkey)
-            native.check(self.lib.wsi_prepack_conv(_np_ptr(w), _np_ptr(g), _np_ptr(b), _np_ptr(m), _np_ptr(v), BN_EPS,
-                                                   cout, cin, k, planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_conv')
+            if w.shape[2] != k:
+                raise ValueError('%s: expected a %d x %d conv, got %s' % (wkey, k, k, w.shape))
+            pk, bias = pack_conv(self.lib, w, _bn(sd, bnkey), planes)
             return dev(pk).data_ptr(), dev(bias).data_ptr()
 
         convs, downs = conv_table(self.ARCH, self.layers)
@@ -399,10 +434,7 @@ class TrunkEngine:
         feat = torch.empty((n, self.FEAT_C), dtype=torch.float32, device=dev) if want_feat else None
         logits = torch.empty((n, self.head_k), dtype=torch.float32, device=dev) if want_logits else None
         fmap = torch.empty((n, self.FEAT_C, h // 32, w // 32), dtype=torch.float32, device=dev) if want_fmap else None
-        if slide is not None:
-            sp, pitch, sh, sw = _ptr(slide), slide.stride(0), slide.shape[0], slide.shape[1]
-        else:
-            sp, pitch, sh, sw = None, 0, 0, 0
+        sp, pitch, sh, sw = _slide_args(slide)
         if tap is not None:
             if not 0 <= tap <= sum(self.layers):
                 raise ValueError('tap must be 0 (pool) ... %d (the last block), got %r' % (sum(self.layers), tap))
@@ -822,44 +854,20 @@ def pf_zeros(n, c, h, w, planes, device):
     return torch.zeros(lib.wsi_pf_bytes(n, h, w, c, planes), dtype=torch.uint8, device=device)
 
 
+def _prepack(weight, bn, planes, device, tconv):
+    pk, bias = pack_conv(native.load(), _np32(weight), None if bn is None else [_np32(t) for t in bn], planes, tconv)
+    return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
+
+
 def prepack_conv(weight, bn, planes, device):
     """weight (cout,cin,k,k) fp32; bn = (gamma, beta, mean, var) or None -> (wpk, bias) device tensors."""
-    lib = native.load()
-    w = np.ascontiguousarray(torch.as_tensor(weight).detach().cpu().to(torch.float32).numpy())
-    cout, cin, k = w.shape[0], w.shape[1], w.shape[2]
-    nbytes = lib.wsi_prepack_conv_bytes(cout, cin, k, planes)
-    if nbytes == 0:
-        raise ValueError('unsupported conv shape %s' % (w.shape,))
-    pk = np.empty(nbytes, np.uint8)
-    bias = np.empty(cout, np.float32)
-    if bn is None:
-        args = [None] * 4
-        keep = []
-    else:
-        keep = [np.ascontiguousarray(torch.as_tensor(t).detach().cpu().to(torch.float32).numpy()) for t in bn]
-        args = [_np_ptr(a) for a in keep]
-    native.check(lib.wsi_prepack_conv(_np_ptr(w), *args, BN_EPS, cout, cin, k, planes, _np_ptr(pk), _np_ptr(bias)),
-                 'wsi_prepack_conv')
-    return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
+    return _prepack(weight, bn, planes, device, False)
 
 
 def prepack_tconv(weight, bn, planes, device):
     """ConvTranspose2d(c, c, 4, stride 2, padding 1) weight (c in, c out, 4, 4) fp32 as torch keeps it; bn = (gamma, beta, mean, var)
     of the output channels or None -> (wpk, bias) device tensors (wsi_prepack_tconv; c a multiple of 64)."""
-    lib = native.load()
-    w = np.ascontiguousarray(torch.as_tensor(weight).detach().cpu().to(torch.float32).numpy())
-    if w.ndim != 4 or w.shape[0] != w.shape[1] or w.shape[2:] != (4, 4):
-        raise ValueError('expected a (c, c, 4, 4) transposed-conv weight, got %s' % (w.shape,))
-    c = w.shape[0]
-    nbytes = lib.wsi_prepack_tconv_bytes(c, planes)
-    if nbytes == 0:
-        raise ValueError('unsupported transposed-conv width %d for planes %d (a multiple of 64; planes 1 or 2)' % (c, planes))
-    pk = np.empty(nbytes, np.uint8)
-    bias = np.empty(c, np.float32)
-    keep = [] if bn is None else [np.ascontiguousarray(torch.as_tensor(t).detach().cpu().to(torch.float32).numpy()) for t in bn]
-    args = [_np_ptr(a) for a in keep] if keep else [None] * 4
-    native.check(lib.wsi_prepack_tconv(_np_ptr(w), *args, BN_EPS, c, planes, _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_tconv')
-    return torch.from_numpy(pk).to(device), torch.from_numpy(bias).to(device)
+    return _prepack(weight, bn, planes, device, True)
 
 
 def tconv4x4s2_bn_relu(x_pf, n, h, w, c, wpk, bias, planes=2):

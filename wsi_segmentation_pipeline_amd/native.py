@@ -43,19 +43,19 @@ WsiBneckWeights = _trunk_weights('WsiBneckWeights', 3, 4, 'wsi_bneck_weights: `b
                                  '3 * (sum(blocks[:L-1]) + B) + (K-1); downsamples of layer1..4.')
 
 
-class WsiUnetDecoderWeights(C.Structure):
-    _fields_ = [
-        ('conv_w', C.c_void_p * 10), ('conv_b', C.c_void_p * 10), ('cin', C.c_int * 10), ('cout', C.c_int * 10),
+def _decoder_weights(name, convs, doc):
+    """The ctypes mirror of a decoder's weight struct: one field list, `convs` conv slots."""
+    fields = [
+        ('conv_w', C.c_void_p * convs), ('conv_b', C.c_void_p * convs), ('cin', C.c_int * convs), ('cout', C.c_int * convs),
         ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_cin', C.c_int), ('classes', C.c_int), ('tail_w', C.c_void_p),
     ]
+    return type(name, (C.Structure,), {'_fields_': fields, '__doc__': doc})
 
 
-class WsiLinknetDecoderWeights(C.Structure):
-    """wsi_linknet_decoder_weights: conv 3 * (L - 1) + J = decoder.layerL.block.J; tail_w = wsi_linknet_tail_prepack's blob or NULL."""
-    _fields_ = [
-        ('conv_w', C.c_void_p * 15), ('conv_b', C.c_void_p * 15), ('cin', C.c_int * 15), ('cout', C.c_int * 15),
-        ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('head_cin', C.c_int), ('classes', C.c_int), ('tail_w', C.c_void_p),
-    ]
+WsiUnetDecoderWeights = _decoder_weights('WsiUnetDecoderWeights', 10, 'wsi_unet_decoder_weights: conv 2 * (L - 1) + J = decoder.layerL.block.J; '
+                                         "tail_w = wsi_unet_tail_prepack's blob or NULL.")
+WsiLinknetDecoderWeights = _decoder_weights('WsiLinknetDecoderWeights', 15, 'wsi_linknet_decoder_weights: conv 3 * (L - 1) + J = '
+                                            "decoder.layerL.block.J; tail_w = wsi_linknet_tail_prepack's blob or NULL.")
 
 
 _vp, _i, _ll, _sz, _f, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double

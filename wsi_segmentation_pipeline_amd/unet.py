@@ -1,26 +1,32 @@
-"""U-Net segmentation model on the HIP path: the dense per-pixel ('seg') counterpart of the reference's
-``smp.Unet('resnet18', classes=C)`` (/root/reference/eval_tumorbed.py:21-28, /root/reference/eval.py:22-27), driven by
+"""Segmentation models on the HIP path: the dense per-pixel ('seg') counterpart of the reference's
+``smp.Unet('resnet18', classes=C)`` (the reference's eval_tumorbed.py:21-28 and eval.py:22-27), driven by
 ``predict_wsis`` (utils/eval.py:51 ``model(batch_image)``) and ``predict_tumorbed(mode='seg')`` (:196-200
-``model.decoder(model.encoder(batch_image))``).
-
-segmentation_models_pytorch is third-party, absent here and un-pinned in the reference, so the architecture
-and the state-dict key names are restated from its published 0.0.x source - **parity unpinned**; the numerical spec is
-oracle/unet_oracle.py (torch fp32 CPU) and the HIP path is held to it:
-  encoder  ResNet-18 or ResNet-34 (``encoder='resnet18' | 'resnet34'``; torchvision key names ``encoder.layerL.B.*``); forward
-           returns [x4, x3, x2, x1, x0] (deepest first): x1..x4 = the LAST block of layer1..4, x0 = relu(bn1(conv1(x))) at half
-           resolution.  Both depths give the same channels (512, 256, 128, 64, 64), so the decoder does not depend on the choice
-  decoder  ``decoder.layer{1..5}.block.{0,1}.block.0.weight`` (3x3 conv, no bias) + ``.block.1.*`` (BatchNorm) + ReLU, each block
-           preceded by nearest x2 upsampling and (blocks 1-4) concatenation of the next skip; channels 256/128/64/32/16;
-           ``decoder.final_conv.{weight,bias}`` (1x1 to `classes`)
-Bottleneck encoders (``Unet('resnet50' | 'resnet101', classes=C)``, the smp factory signature; class UNetSegBottleneck): the same decoder on
-the maps of ``ResNet(Bottleneck, layers)`` - 2048 / 1024 / 512 / 256 / 64 channels - so only the first conv of decoder blocks 1-4 is wider
-(``cat([up2(x), skip])`` of (2048, 1024), (256, 512), (128, 256), (64, 64)); key names as above; 'parity' and 'speed' only.
-Eval-mode forwards run on libwsi_hip.so only (conv3x3 MFMA kernels + upsample/concat, head kernels: csrc/unet.hip); training
-mode uses torch ops so ``train.py``-style callers still run.
-The reference picks the model family by name (``eval('smp.' + args.model_name)``, ``--model_name``): this module serves 'Unet' (above) and
-'Linknet' (`Linknet`, `LinknetSeg`, `LinknetEngine` below: smp's transposed-conv decoder, csrc/linknet.hip), so
+``model.decoder(model.encoder(batch_image))``).  The reference picks the model family by name (``eval('smp.' + args.model_name)``,
+``--model_name``) and the encoder by ``--arch_encoder``: this module serves 'Unet' and 'Linknet' on the encoders of `ENCODERS`, so
 ``import wsi_segmentation_pipeline_amd.unet as smp`` keeps that line working.
+
+segmentation_models_pytorch is third-party, absent here and un-pinned in the reference, so the architectures and the
+state-dict key names are restated from its published 0.0.x source - **parity unpinned**; the numerical specs are
+oracle/unet_oracle.py and tests/linknet_oracle.py (torch fp32 CPU) and the HIP path is held to them:
+  encoder  a ResNet of `ENCODERS` (torchvision key names ``encoder.layerL.B.*``); forward returns [x4, x3, x2, x1, x0] (deepest first):
+           x1..x4 = the LAST block of layer1..4, x0 = relu(bn1(conv1(x))) at half resolution, with `ENC_CH` channels: the same for
+           every depth of a block type, so a decoder depends on the block type only
+  decoder  ``decoder.layer{1..5}.block.J.block.0.weight`` (conv, no bias) + ``.block.1.*`` (BatchNorm) + ReLU per conv J, then
+           ``decoder.final_conv.{weight,bias}`` (1x1 to `classes`)
+    Unet     two 3x3 convs per block, each block preceded by nearest x2 upsampling and (blocks 1-4) concatenation of the next skip;
+             channels `DEC_CH`.  On a Bottleneck encoder only the first conv of blocks 1-4 is wider (``cat([up2(x), skip])`` of
+             (2048, 1024), (256, 512), (128, 256), (64, 64)); 'parity' and 'speed' only there
+    Linknet  per block (cin, mid = cin // 4, cout) of `LINKNET_CH`: 1x1 conv cin -> mid, ConvTranspose2d(mid, mid, kernel 4, stride 2,
+             padding 1, bias=False; weight [mid in][mid out][4][4]), 1x1 conv mid -> cout, and ``x = block(x) + skip`` (no ReLU after
+             the add) with skips x3, x2, x1, x0 for blocks 1-4, none for block 5.  BasicBlock encoders, 'parity' and 'speed' only
+
+What a decoder consists of is written once, as a `Decoder` description (`unet_decoder`, `linknet_decoder`): its convs in state-dict
+order with real and stored widths.  The key lists (`decoder_key_shapes`, `linknet_decoder_key_shapes`), the packing of the device
+weights (`pack_decoder`, host work only) and the layers of the ``nn.Module`` decoders are read from it.
+Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/tail.hip behind one entry prefix per model and
+encoder block type); training mode uses torch ops so ``train.py``-style callers still run.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -29,23 +35,26 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import native
-from .engine import BN_EPS, MX, PARITY, SPEED, BottleneckEngine, TrunkEngine, _np_ptr, _ptr, _require_gpu, _stream, trunk_arch
+from .engine import (BN_EPS, BN_KEYS, MX, PARITY, SPEED, BottleneckEngine, TrunkEngine, _bn, _f32, _np_ptr, _ptr, _require_gpu, _slide_args,
+                     _stream, pack_conv, trunk_arch)
 
 DEC_CH = (256, 128, 64, 32, 16)
 ENC_CH = {'basic': (512, 256, 128, 64, 64), 'bottleneck': (2048, 1024, 512, 256, 64)}     # channels of [x4, x3, x2, x1, x0] per block type
-SKIP_CH = ENC_CH['basic'][1:] + (0,)
-ENCODER_LAYERS = {'resnet18': [2, 2, 2, 2], 'resnet34': [3, 4, 6, 3]}      # smp encoder names -> BasicBlocks per stage
-BOTTLENECK_ENCODER_LAYERS = {'resnet50': [3, 4, 6, 3], 'resnet101': [3, 4, 23, 3]}      # ... -> Bottleneck blocks per stage
+LINKNET_CH = ((512, 128, 256), (256, 64, 128), (128, 32, 64), (64, 16, 64), (64, 16, 32))      # (cin, mid, cout) of layer1..5
+# smp encoder name -> (block type, blocks per stage)
+ENCODERS = {'resnet18': ('basic', [2, 2, 2, 2]), 'resnet34': ('basic', [3, 4, 6, 3]),
+            'resnet50': ('bottleneck', [3, 4, 6, 3]), 'resnet101': ('bottleneck', [3, 4, 23, 3])}
+ENCODER_LAYERS = {name: layers for name, (arch, layers) in ENCODERS.items() if arch == 'basic'}
+BOTTLENECK_ENCODER_LAYERS = {name: layers for name, (arch, layers) in ENCODERS.items() if arch == 'bottleneck'}
+BLOCK_RESNETS = {'basic': ' (BasicBlock ResNets)', 'bottleneck': ' (Bottleneck ResNets)'}      # how a refusal names the encoders of one block type
 
 
-def encoder_layers(encoder):
-    if encoder not in ENCODER_LAYERS:
-        raise ValueError('encoder must be one of %s (BasicBlock ResNets), got %r' % (sorted(ENCODER_LAYERS), encoder))
-    return ENCODER_LAYERS[encoder]
-
-
-def _pad64(c):
-    return (c + 63) // 64 * 64
+def encoder_spec(name, archs, what='encoder', where=''):
+    """(block type, blocks per stage) of the smp encoder `name`, which must be one of block type `archs`; ValueError otherwise."""
+    names = [n for n, (arch, _) in ENCODERS.items() if arch in archs]
+    if name not in names:
+        raise ValueError('%s must be one of %s%s, got %r' % (what, names, where, name))
+    return ENCODERS[name]
 
 
 def equal_batches(n, cap):
@@ -58,32 +67,105 @@ def equal_batches(n, cap):
     return [(i, min(i + mb, n)) for i in range(0, n, mb)]
 
 
-def bottleneck_encoder_layers(encoder):
-    if encoder not in BOTTLENECK_ENCODER_LAYERS:
-        raise ValueError('encoder must be one of %s (Bottleneck ResNets), got %r' % (sorted(BOTTLENECK_ENCODER_LAYERS), encoder))
-    return BOTTLENECK_ENCODER_LAYERS[encoder]
+# ---------------------------------------------------------------------------------------------- what a decoder consists of
+# One conv + BatchNorm + ReLU of a decoder: state-dict prefix (``<prefix>.0.weight``, ``<prefix>.1.*``), kind (a key of KINDS), real and
+# stored (cout, cin), and where the real input channels land in the stored weight as [(src_lo, src_hi, dst_lo)].
+Conv = collections.namedtuple('Conv', 'prefix kind real stored place')
+KINDS = {'conv3': ('conv', 3), 'conv1': ('conv', 1), 'tconv': ('tconv', 4)}      # -> (kind in the key lists, kernel size); tconv = 4x4 stride 2
+# The last block + head as one kernel on the block's REAL channels, in parity mode up to 4 classes: the prepack entry (its size is
+# ``<entry>_bytes()``), the prefixes of the block's convs and the dimension arguments between the head and `classes`.
+Tail = collections.namedtuple('Tail', 'entry prefixes dims')
+# A decoder: its Conv rows in state-dict order (slot i of the C struct = row i), the head's input width, its Tail and its C struct.
+Decoder = collections.namedtuple('Decoder', 'rows head_cin tail weights')
+BN_IDENTITY = (1.0, 0.0, 0.0, 1.0)               # BN_KEYS of a padding channel: scale ~1, shift 0 -> relu(0) = 0
 
 
-def _skip_ch(enc_ch):
-    """channels of the skip each decoder block concatenates: encoder maps x3, x2, x1, x0, and none for the last block"""
-    return tuple(enc_ch[1:]) + (0,)
+def _row(L, j, kind, real, stored, place=None):
+    return Conv('decoder.layer%d.block.%d.block' % (L + 1, j), kind, real, stored, place or [(0, real[1], 0)])
+
+
+def unet_decoder(enc_ch=ENC_CH['basic'], planes=PARITY):
+    """The U-Net decoder on an encoder whose maps [x4, x3, x2, x1, x0] have `enc_ch` channels.  Stored widths are whole 128-byte lines:
+    multiples of 64 channels in speed mode, of 32 otherwise."""
+    line = 64 if planes == SPEED else 32
+    rows, real, stored = [], enc_ch[0], enc_ch[0]
+    for L, (cout, skip) in enumerate(zip(DEC_CH, tuple(enc_ch[1:]) + (0,))):       # skips x3, x2, x1, x0, and none for the last block
+        cout_s = -(-cout // line) * line
+        # first conv: input = [upsampled x (`real` of `stored` channels) | skip]
+        rows.append(_row(L, 0, 'conv3', (cout, real + skip), (cout_s, stored + skip), [(0, real, 0), (real, real + skip, stored)]))
+        rows.append(_row(L, 1, 'conv3', (cout, cout), (cout_s, cout_s)))
+        real, stored = cout, cout_s
+    tail = Tail('wsi_unet_tail_prepack', [r.prefix for r in rows[8:]], DEC_CH[3:])       # csrc/tail.hip: 32 -> 16 -> 16 channels
+    return Decoder(rows, DEC_CH[4], tail, native.WsiUnetDecoderWeights)
+
+
+def linknet_decoder():
+    """The Linknet decoder (BasicBlock encoders).  Every stored tensor is at least 64 channels wide: layers narrower than that carry
+    zero weights in the padding."""
+    def pad(c):
+        return max(64, c)
+
+    rows, cin_s = [], LINKNET_CH[0][0]                                           # stored width of the block's input
+    for L, (cin, mid, cout) in enumerate(LINKNET_CH):
+        rows += [_row(L, 0, 'conv1', (mid, cin), (pad(mid), cin_s)), _row(L, 1, 'tconv', (mid, mid), (pad(mid), pad(mid))),
+                 _row(L, 2, 'conv1', (cout, mid), (pad(cout), pad(mid)))]
+        cin_s = pad(cout)
+    tail = Tail('wsi_linknet_tail_prepack', [r.prefix for r in rows[12:]], LINKNET_CH[4])       # csrc/linknet.hip linknet_tail_kernel
+    return Decoder(rows, LINKNET_CH[4][2], tail, native.WsiLinknetDecoderWeights)
+
+
+def _key_shapes(dec, classes):
+    out = []
+    for r in dec.rows:
+        (kind, k), (cout, cin) = KINDS[r.kind], r.real
+        out.append((r.prefix + '.0.weight', (cin, cout, k, k) if kind == 'tconv' else (cout, cin, k, k), kind))      # ConvTranspose2d keeps [in][out]
+        out += [('%s.1.%s' % (r.prefix, s), (cout,), bn_kind) for s, bn_kind in zip(BN_KEYS, ('bn_w', 'bn_b', 'bn_m', 'bn_v'))]
+        out.append((r.prefix + '.1.num_batches_tracked', (), 'bn_n'))
+    out.append(('decoder.final_conv.weight', (classes, dec.head_cin, 1, 1), 'conv'))
+    out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
+    return out
 
 
 def decoder_key_shapes(classes, enc_ch=ENC_CH['basic']):
     """[(key, shape, kind)] of the decoder in state-dict order, on an encoder whose maps [x4, x3, x2, x1, x0] have `enc_ch` channels."""
-    out, cprev, skip = [], enc_ch[0], _skip_ch(enc_ch)
-    for L in range(5):
-        cin, cout = cprev + skip[L], DEC_CH[L]
-        for j, ci in enumerate((cin, cout)):
-            p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
-            out.append((p + '.0.weight', (cout, ci, 3, 3), 'conv'))
-            for suffix, kind in (('weight', 'bn_w'), ('bias', 'bn_b'), ('running_mean', 'bn_m'), ('running_var', 'bn_v')):
-                out.append(('%s.1.%s' % (p, suffix), (cout,), kind))
-            out.append((p + '.1.num_batches_tracked', (), 'bn_n'))
-        cprev = cout
-    out.append(('decoder.final_conv.weight', (classes, DEC_CH[4], 1, 1), 'conv'))
-    out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
-    return out
+    return _key_shapes(unet_decoder(enc_ch), classes)
+
+
+def linknet_decoder_key_shapes(classes):
+    """[(key, shape, kind)] of the Linknet decoder in state-dict order: 92 keys.  kind 'tconv' = the transposed-conv weight [in][out][4][4]."""
+    return _key_shapes(linknet_decoder(), classes)
+
+
+PackedDecoder = collections.namedtuple('PackedDecoder', 'convs cin cout head_w head_b tail')
+
+
+def pack_decoder(lib, state_dict, dec, planes, classes):
+    """The device weights of decoder `dec` from the ``decoder.*`` keys, as numpy arrays (host work only): convs = [(packed, bias)] per
+    row, the stored cin / cout tables, the head's (classes, head_cin) weight and its bias, and the fused tail's blob or None."""
+    convs = []
+    for r in dec.rows:
+        (kind, k), (cout, cin), (cout_s, cin_s) = KINDS[r.kind], r.real, r.stored
+        tconv = kind == 'tconv'
+        w = _f32(state_dict, r.prefix + '.0.weight')
+        wp = np.zeros((cin_s, cout_s, k, k) if tconv else (cout_s, cin_s, k, k), np.float32)
+        src, dst = (w.swapaxes(0, 1), wp.swapaxes(0, 1)) if tconv else (w, wp)         # both as [out][in]: ConvTranspose2d keeps [in][out]
+        for lo, hi, at in r.place:
+            dst[:cout, at:at + hi - lo] = src[:, lo:hi]
+        bn = []
+        for a, fill in zip(_bn(state_dict, r.prefix + '.1'), BN_IDENTITY):
+            padded = np.full(cout_s, fill, np.float32)
+            padded[:cout] = a
+            bn.append(padded)
+        convs.append(pack_conv(lib, wp, bn, planes, tconv))
+    head_w = np.ascontiguousarray(_f32(state_dict, 'decoder.final_conv.weight').reshape(classes, dec.head_cin))
+    head_b = _f32(state_dict, 'decoder.final_conv.bias')
+    tail = None
+    if planes == PARITY and classes <= 4:
+        args = [a for p in dec.tail.prefixes for a in [_f32(state_dict, p + '.0.weight')] + _bn(state_dict, p + '.1')]
+        tail = np.empty(getattr(lib, dec.tail.entry + '_bytes')(), np.uint8)
+        native.check(getattr(lib, dec.tail.entry)(*[_np_ptr(a) for a in args], BN_EPS, _np_ptr(head_w), _np_ptr(head_b), *dec.tail.dims,
+                                                  classes, _np_ptr(tail)), dec.tail.entry)
+    return PackedDecoder(convs, [r.stored[1] for r in dec.rows], [r.stored[0] for r in dec.rows], head_w, head_b, tail)
 
 
 class UNetEngine:
@@ -105,10 +187,8 @@ class UNetEngine:
             self.trunk = BottleneckEngine(enc_sd, device, planes=planes)
         else:
             self.trunk = TrunkEngine(enc_sd, device, planes=planes)
-        if encoder is not None:
-            named = BOTTLENECK_ENCODER_LAYERS.get(encoder) or encoder_layers(encoder)
-            if self.trunk.layers != named or (encoder in BOTTLENECK_ENCODER_LAYERS) != (self.arch == 'bottleneck'):
-                raise ValueError('state dict holds a %s %s encoder, not %s' % (self.arch, self.trunk.layers, encoder))
+        if encoder is not None and encoder_spec(encoder, tuple(ENC_CH)) != (self.arch, self.trunk.layers):
+            raise ValueError('state dict holds a %s %s encoder, not %s' % (self.arch, self.trunk.layers, encoder))
         self.enc_ch = ENC_CH[self.arch]
         entry = self.ENTRY[self.arch]
         self._ws_bytes, self._ws_init, self._forward, self._decoder = (
@@ -117,67 +197,27 @@ class UNetEngine:
         self.classes = int(classes if classes is not None else state_dict['decoder.final_conv.weight'].shape[0])
         self.max_batch = max_batch
         self._keep, self._ws = [], {}
+        self._pack_decoder(state_dict)
 
-        def f32(key):
-            return np.ascontiguousarray(state_dict[key].detach().to('cpu', torch.float32).numpy())
+    def _describe(self):
+        return unet_decoder(self.enc_ch, self.planes)
+
+    def _pack_decoder(self, state_dict):
+        """Fill self.dw from the decoder.* keys: `pack_decoder`'s arrays, uploaded in its order and kept alive."""
+        dec = self._describe()
+        pk = pack_decoder(self.lib, state_dict, dec, self.planes, self.classes)
 
         def dev(a):
-            t = torch.from_numpy(a).to(self.device)
-            self._keep.append(t)
-            return t
+            self._keep.append(torch.from_numpy(a).to(self.device))
+            return self._keep[-1].data_ptr()
 
-        self._pack_decoder(f32, dev)
-
-    def _pack_decoder(self, f32, dev):
-        """Fill self.dw from the decoder.* keys: f32(key) -> contiguous fp32 array, dev(array) -> device tensor kept alive."""
-        planes = self.planes
-        skip_ch = _skip_ch(self.enc_ch)
-        self.dw = native.WsiUnetDecoderWeights()
-        cprev_real, cprev_pad = self.enc_ch[0], self.enc_ch[0]
-        for L in range(5):
-            cout = DEC_CH[L]
-            cout_pad = _pad64(cout) if planes == 1 else -(-cout // 32) * 32        # whole 128-byte lines: 64 channels in speed mode, 32 otherwise
-            for j in range(2):
-                p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
-                w = f32(p + '.0.weight')
-                if j == 0:                                     # input = [upsampled x (real cprev of cprev_pad) | skip]
-                    cin_pad = cprev_pad + skip_ch[L]
-                    wp = np.zeros((cout_pad, cin_pad, 3, 3), np.float32)
-                    wp[:cout, :cprev_real] = w[:, :cprev_real]
-                    wp[:cout, cprev_pad:cprev_pad + skip_ch[L]] = w[:, cprev_real:]
-                else:
-                    cin_pad = cout_pad
-                    wp = np.zeros((cout_pad, cin_pad, 3, 3), np.float32)
-                    wp[:cout, :cout] = w
-                bn = []
-                for suffix, fill in (('weight', 1.0), ('bias', 0.0), ('running_mean', 0.0), ('running_var', 1.0)):
-                    a = np.full(cout_pad, fill, np.float32)    # padding channels: scale ~1, shift 0 -> relu(0) = 0
-                    a[:cout] = f32('%s.1.%s' % (p, suffix))
-                    bn.append(a)
-                pk = np.empty(self.lib.wsi_prepack_conv_bytes(cout_pad, cin_pad, 3, planes), np.uint8)
-                bias = np.empty(cout_pad, np.float32)
-                native.check(self.lib.wsi_prepack_conv(_np_ptr(wp), *[_np_ptr(a) for a in bn], BN_EPS, cout_pad, cin_pad, 3, planes,
-                                                       _np_ptr(pk), _np_ptr(bias)), 'wsi_prepack_conv')
-                i = 2 * L + j
-                self.dw.conv_w[i], self.dw.conv_b[i] = dev(pk).data_ptr(), dev(bias).data_ptr()
-                self.dw.cin[i], self.dw.cout[i] = cin_pad, cout_pad
-            cprev_real, cprev_pad = cout, cout_pad
-        hw = f32('decoder.final_conv.weight').reshape(self.classes, DEC_CH[4])
-        self.dw.head_w = dev(np.ascontiguousarray(hw)).data_ptr()
-        self.dw.head_b = dev(f32('decoder.final_conv.bias')).data_ptr()
-        self.dw.head_cin, self.dw.classes = DEC_CH[4], self.classes
-        self.dw.tail_w = None
-        if planes == PARITY and DEC_CH[3] == 32 and DEC_CH[4] <= 16 and self.classes <= 4:
-            # r05: the last block + head as one kernel (csrc/tail.hip) on the block's REAL channels
-            p0, p1 = ('decoder.layer5.block.%d.block' % j for j in range(2))
-            bn = [[f32('%s.1.%s' % (p, sfx)) for sfx in ('weight', 'bias', 'running_mean', 'running_var')] for p in (p0, p1)]
-            blob = np.empty(self.lib.wsi_unet_tail_prepack_bytes(), np.uint8)
-            hb = f32('decoder.final_conv.bias')
-            native.check(self.lib.wsi_unet_tail_prepack(_np_ptr(f32(p0 + '.0.weight')), *[_np_ptr(a) for a in bn[0]],
-                                                        _np_ptr(f32(p1 + '.0.weight')), *[_np_ptr(a) for a in bn[1]], BN_EPS,
-                                                        _np_ptr(np.ascontiguousarray(hw)), _np_ptr(hb), DEC_CH[3], DEC_CH[4], self.classes,
-                                                        _np_ptr(blob)), 'wsi_unet_tail_prepack')
-            self.dw.tail_w = dev(blob).data_ptr()
+        dw = self.dw = dec.weights()
+        for i, (w, bias) in enumerate(pk.convs):
+            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
+            dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
+        dw.head_w, dw.head_b = dev(pk.head_w), dev(pk.head_b)
+        dw.head_cin, dw.classes = dec.head_cin, self.classes
+        dw.tail_w = None if pk.tail is None else dev(pk.tail)
 
     def _workspace(self, n, h, w):
         key = (h, w)
@@ -234,10 +274,7 @@ class UNetEngine:
             shapes = [(c, h >> k, w >> k) for c, k in zip(self.enc_ch, (5, 4, 3, 2, 1))]
             enc = [torch.empty((n,) + s, dtype=torch.float32, device=self.device) for s in shapes]
             enc_ptrs = (C.c_void_p * 5)(*[t.data_ptr() for t in enc])
-        if slide is not None:
-            sp, pitch, sh, sw = _ptr(slide), slide.stride(0), slide.shape[0], slide.shape[1]
-        else:
-            sp, pitch, sh, sw = None, 0, 0, 0
+        sp, pitch, sh, sw = _slide_args(slide)
         native.check(self._forward(C.byref(self.trunk.wt), C.byref(self.dw), _ptr(in_f32), sp, pitch, sh, sw, _ptr(tile_xy),
                                    _ptr(self.trunk.lut), n, h, w, _ptr(ws), cap, _ptr(logits),
                                    C.byref(enc_ptrs) if enc_ptrs is not None else None, _stream()), self._forward.__name__)
@@ -278,46 +315,89 @@ class UNetEngine:
         return logits
 
 
+class LinknetEngine(UNetEngine):
+    """BasicBlock ResNet encoder + Linknet decoder on HIP kernels (wsi_linknet_*; csrc/linknet.hip): the surface of UNetEngine -
+    forward_f32, forward_tiles, decode, release_workspaces - with the batch sized by the Linknet workspace (~70 MB per 256 x 256 tile in
+    parity mode)."""
+
+    ENTRY = {'basic': 'wsi_linknet'}
+
+    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
+        if planes not in (PARITY, SPEED):
+            raise ValueError("a Linknet runs in precision 'parity' or 'speed': there is no mx mode")
+        if encoder is not None:
+            encoder_spec(encoder, ('basic',), where=BLOCK_RESNETS['basic'])
+        if trunk_arch({k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')})[0] != 'basic':
+            raise ValueError('a Linknet runs on BasicBlock encoders only (%s)' % sorted(ENCODER_LAYERS))
+        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+
+    def _describe(self):
+        return linknet_decoder()
+
+
 # ---------------------------------------------------------------------------------------------- nn.Module surface
-class _Conv2dReLU(nn.Module):
-    def __init__(self, cin, cout):
+class _ConvBnReLU(nn.Module):
+    """``.block`` = Sequential(conv, BatchNorm2d, ReLU) of one `Conv` row: the state-dict keys ``block.0.weight``, ``block.1.*``."""
+
+    def __init__(self, row):
         super().__init__()
-        self.block = nn.Sequential(nn.Conv2d(cin, cout, 3, padding=1, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
+        (cout, cin), k = row.real, KINDS[row.kind][1]
+        conv = nn.ConvTranspose2d(cin, cout, k, stride=2, padding=1, bias=False) if row.kind == 'tconv' \
+            else nn.Conv2d(cin, cout, k, padding=k // 2, bias=False)
+        self.block = nn.Sequential(conv, nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
 
     def forward(self, x):
         return self.block(x)
 
 
 class _DecoderBlock(nn.Module):
-    def __init__(self, cin, cout):
+    def __init__(self, rows):
         super().__init__()
-        self.block = nn.Sequential(_Conv2dReLU(cin, cout), _Conv2dReLU(cout, cout))
+        self.block = nn.Sequential(*[_ConvBnReLU(row) for row in rows])
 
-    def forward(self, x, skip=None):
-        x = F.interpolate(x, scale_factor=2, mode='nearest')
-        if skip is not None:
-            x = torch.cat([x, skip], 1)
+    def forward(self, x):
         return self.block(x)
 
 
-class UNetDecoder(nn.Module):
-    def __init__(self, classes, owner=None, enc_ch=ENC_CH['basic']):
+class _Decoder(nn.Module):
+    """``layer1`` ... ``layer5`` and ``final_conv`` of a `Decoder` description.  Eval mode hands the five maps to the owner's HIP engine;
+    training mode runs the blocks as torch ops, a subclass's `_level` saying how a block combines its skip."""
+
+    def __init__(self, dec, classes, owner):
         super().__init__()
-        cprev, skip = enc_ch[0], _skip_ch(enc_ch)
+        per = len(dec.rows) // 5
         for L in range(5):
-            setattr(self, 'layer%d' % (L + 1), _DecoderBlock(cprev + skip[L], DEC_CH[L]))
-            cprev = DEC_CH[L]
-        self.final_conv = nn.Conv2d(DEC_CH[4], classes, 1)
+            setattr(self, 'layer%d' % (L + 1), _DecoderBlock(dec.rows[per * L:per * (L + 1)]))
+        self.final_conv = nn.Conv2d(dec.head_cin, classes, 1)
         self._owner = [owner]                                  # list: not registered as a sub-module
 
     def forward(self, enc):
         if not self.training:
             return self._owner[0].hip_engine(enc[0].device).decode(list(enc))
         x = enc[0]
-        skips = list(enc[1:]) + [None]
-        for L in range(5):
-            x = getattr(self, 'layer%d' % (L + 1))(x, skips[L])
+        for L, skip in enumerate(list(enc[1:]) + [None]):
+            x = self._level(getattr(self, 'layer%d' % (L + 1)), x, skip)
         return self.final_conv(x)
+
+
+class UNetDecoder(_Decoder):
+    def __init__(self, classes, owner=None, enc_ch=ENC_CH['basic']):
+        super().__init__(unet_decoder(enc_ch), classes, owner)
+
+    @staticmethod
+    def _level(block, x, skip):
+        x = F.interpolate(x, scale_factor=2, mode='nearest')
+        return block(x if skip is None else torch.cat([x, skip], 1))
+
+
+class LinknetDecoder(_Decoder):
+    def __init__(self, classes, owner=None):
+        super().__init__(linknet_decoder(), classes, owner)
+
+    @staticmethod
+    def _level(block, x, skip):
+        x = block(x)
+        return x if skip is None else x + skip
 
 
 class UNetEncoder(nn.Module):
@@ -327,16 +407,16 @@ class UNetEncoder(nn.Module):
 
     def __init__(self, owner=None, encoder='resnet18'):
         super().__init__()
-        net = self._net(encoder)
+        net = self._net(encoder_spec(encoder, (self.ARCH,), where=BLOCK_RESNETS[self.ARCH])[1])
         for name in ('conv1', 'bn1', 'relu', 'maxpool', 'layer1', 'layer2', 'layer3', 'layer4'):
             setattr(self, name, getattr(net, name))
         self.out_shapes = ENC_CH[self.ARCH]
         self._owner = [owner]
 
     @staticmethod
-    def _net(encoder):
+    def _net(layers):
         import resnets_shift
-        return resnets_shift.ResNet(resnets_shift.BasicBlock, encoder_layers(encoder))
+        return resnets_shift.ResNet(resnets_shift.BasicBlock, layers)
 
     def forward(self, x):
         if not self.training:
@@ -354,14 +434,14 @@ class UNetBottleneckEncoder(UNetEncoder):
     ARCH = 'bottleneck'
 
     @staticmethod
-    def _net(encoder):
+    def _net(layers):
         """conv1 ... layer4 of ``resnets_shift.ResNet(Bottleneck, layers)``, built as its __init__ / _make_layer build them (same modules,
         same initialisation) but without the bag heads, which are no part of an encoder: fc.0 alone is 32768 x 16384 at expansion 4."""
         import resnets_shift as rs
         net = nn.Module()
         net.conv1, net.bn1, net.relu, net.maxpool = nn.Conv2d(3, 64, 7, 2, 3, bias=False), nn.BatchNorm2d(64), nn.ReLU(inplace=True), nn.MaxPool2d(3, 2, 1)
         inplanes = 64
-        for i, (planes, stride, blocks) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), bottleneck_encoder_layers(encoder)), start=1):
+        for i, (planes, stride, blocks) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), layers), start=1):
             width = planes * rs.Bottleneck.expansion
             down = nn.Sequential(rs.conv1x1(inplanes, width, stride), nn.BatchNorm2d(width))
             seq = [rs.Bottleneck(inplanes, planes, stride, down)] + [rs.Bottleneck(width, planes) for _ in range(1, blocks)]
@@ -422,146 +502,6 @@ class UNetSegBottleneck(UNetSeg):
         super().__init__(classes, precision, encoder)
 
 
-# ---------------------------------------------------------------------------------------------- Linknet
-# smp's light decoder (``--model_name Linknet``, the reference's myargs.py:9; built by ``eval('smp.' + args.model_name)(...)`` at
-# eval.py:22, eval_tumorbed.py:21).  Restated from the published 0.0.x source like the U-Net above - parity unpinned, the numerical spec is
-# tests/linknet_oracle.py.  ``decoder.layer{1..5}`` = DecoderBlock(cin, cout) with mid = cin // 4:
-#   block.0  1x1 conv cin -> mid (no bias) + BN + ReLU
-#   block.1  ConvTranspose2d(mid, mid, kernel 4, stride 2, padding 1, bias=False) + BN + ReLU     weight [mid in][mid out][4][4]
-#   block.2  1x1 conv mid -> cout (no bias) + BN + ReLU
-# and ``x = block(x) + skip`` (no ReLU after the add) with skips x3, x2, x1, x0 for layers 1-4, none for layer 5; ``decoder.final_conv``
-# 1x1 32 -> classes + bias.  BasicBlock encoders only ('resnet18', 'resnet34'); precision 'parity' or 'speed'.
-LINKNET_CH = ((512, 128, 256), (256, 64, 128), (128, 32, 64), (64, 16, 64), (64, 16, 32))      # (cin, mid, cout) of layer1..5
-
-
-def linknet_decoder_key_shapes(classes):
-    """[(key, shape, kind)] of the Linknet decoder in state-dict order: 92 keys.  kind 'tconv' = the transposed-conv weight [in][out][4][4]."""
-    out = []
-    for L, (cin, mid, cout) in enumerate(LINKNET_CH):
-        for j, (shape, kind, c) in enumerate((((mid, cin, 1, 1), 'conv', mid), ((mid, mid, 4, 4), 'tconv', mid), ((cout, mid, 1, 1), 'conv', cout))):
-            p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
-            out.append((p + '.0.weight', shape, kind))
-            for suffix, bn_kind in (('weight', 'bn_w'), ('bias', 'bn_b'), ('running_mean', 'bn_m'), ('running_var', 'bn_v')):
-                out.append(('%s.1.%s' % (p, suffix), (c,), bn_kind))
-            out.append((p + '.1.num_batches_tracked', (), 'bn_n'))
-    out.append(('decoder.final_conv.weight', (classes, LINKNET_CH[4][2], 1, 1), 'conv'))
-    out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
-    return out
-
-
-class LinknetEngine(UNetEngine):
-    """BasicBlock ResNet encoder + Linknet decoder on HIP kernels (wsi_linknet_*; csrc/linknet.hip): the surface of UNetEngine -
-    forward_f32, forward_tiles, decode, release_workspaces - with the batch sized by the Linknet workspace (~70 MB per 256 x 256 tile in
-    parity mode).  Every stored tensor is at least 64 channels wide: layers narrower than that carry zero weights in the padding."""
-
-    ENTRY = {'basic': 'wsi_linknet'}
-
-    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
-        if planes not in (PARITY, SPEED):
-            raise ValueError("a Linknet runs in precision 'parity' or 'speed': there is no mx mode")
-        if encoder is not None:
-            encoder_layers(encoder)
-        if trunk_arch({k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')})[0] != 'basic':
-            raise ValueError('a Linknet runs on BasicBlock encoders only (%s)' % sorted(ENCODER_LAYERS))
-        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
-
-    def _pack_decoder(self, f32, dev):
-        planes = self.planes
-        self.dw = native.WsiLinknetDecoderWeights()
-
-        def pad(c):
-            return max(64, c)
-
-        for L, (cin, mid, cout) in enumerate(LINKNET_CH):
-            cin_s = cin if L == 0 else pad(LINKNET_CH[L - 1][2])           # stored width of the block's input
-            for j, (co, ci, co_s, ci_s) in enumerate(((mid, cin, pad(mid), cin_s), (mid, mid, pad(mid), pad(mid)), (cout, mid, pad(cout), pad(mid)))):
-                p = 'decoder.layer%d.block.%d.block' % (L + 1, j)
-                w = f32(p + '.0.weight')
-                k = 4 if j == 1 else 1
-                wp = np.zeros((ci_s, co_s, 4, 4) if j == 1 else (co_s, ci_s, 1, 1), np.float32)
-                if j == 1:
-                    wp[:ci, :co] = w                                   # ConvTranspose2d keeps [in][out][ky][kx]
-                else:
-                    wp[:co, :ci] = w
-                bn = []
-                for suffix, fill in (('weight', 1.0), ('bias', 0.0), ('running_mean', 0.0), ('running_var', 1.0)):
-                    a = np.full(co_s, fill, np.float32)                # padding channels: scale ~1, shift 0 -> relu(0) = 0
-                    a[:co] = f32('%s.1.%s' % (p, suffix))
-                    bn.append(a)
-                bias = np.empty(co_s, np.float32)
-                if k == 4:
-                    pk = np.empty(self.lib.wsi_prepack_tconv_bytes(co_s, planes), np.uint8)
-                    native.check(self.lib.wsi_prepack_tconv(_np_ptr(wp), *[_np_ptr(a) for a in bn], BN_EPS, co_s, planes, _np_ptr(pk), _np_ptr(bias)),
-                                 'wsi_prepack_tconv')
-                else:
-                    pk = np.empty(self.lib.wsi_prepack_conv_bytes(co_s, ci_s, 1, planes), np.uint8)
-                    native.check(self.lib.wsi_prepack_conv(_np_ptr(wp), *[_np_ptr(a) for a in bn], BN_EPS, co_s, ci_s, 1, planes, _np_ptr(pk),
-                                                           _np_ptr(bias)), 'wsi_prepack_conv')
-                i = 3 * L + j
-                self.dw.conv_w[i], self.dw.conv_b[i] = dev(pk).data_ptr(), dev(bias).data_ptr()
-                self.dw.cin[i], self.dw.cout[i] = ci_s, co_s
-        head_cin = LINKNET_CH[4][2]
-        hw = f32('decoder.final_conv.weight').reshape(self.classes, head_cin)
-        self.dw.head_w = dev(np.ascontiguousarray(hw)).data_ptr()
-        self.dw.head_b = dev(f32('decoder.final_conv.bias')).data_ptr()
-        self.dw.head_cin, self.dw.classes = head_cin, self.classes
-        self.dw.tail_w = None
-        if planes == PARITY and self.classes <= 4:
-            # the last block + head as one kernel (csrc/linknet.hip linknet_tail_kernel) on the block's REAL channels
-            cin, mid, cout = LINKNET_CH[4]
-            ps = ['decoder.layer5.block.%d.block' % j for j in range(3)]
-            args = []
-            for p in ps:
-                args.append(_np_ptr(f32(p + '.0.weight')))
-                args += [_np_ptr(f32('%s.1.%s' % (p, sfx))) for sfx in ('weight', 'bias', 'running_mean', 'running_var')]
-            blob = np.empty(self.lib.wsi_linknet_tail_prepack_bytes(), np.uint8)
-            native.check(self.lib.wsi_linknet_tail_prepack(*args, BN_EPS, _np_ptr(np.ascontiguousarray(hw)), _np_ptr(f32('decoder.final_conv.bias')),
-                                                           cin, mid, cout, self.classes, _np_ptr(blob)), 'wsi_linknet_tail_prepack')
-            self.dw.tail_w = dev(blob).data_ptr()
-
-
-class _ConvBnReLU(nn.Module):
-    """``.block`` = Sequential(conv, BatchNorm2d, ReLU): the state-dict keys ``block.0.weight``, ``block.1.*``."""
-
-    def __init__(self, conv, c):
-        super().__init__()
-        self.block = nn.Sequential(conv, nn.BatchNorm2d(c), nn.ReLU(inplace=True))
-
-    def forward(self, x):
-        return self.block(x)
-
-
-class _LinknetBlock(nn.Module):
-    def __init__(self, cin, cout):
-        super().__init__()
-        mid = cin // 4
-        self.block = nn.Sequential(_ConvBnReLU(nn.Conv2d(cin, mid, 1, bias=False), mid),
-                                   _ConvBnReLU(nn.ConvTranspose2d(mid, mid, 4, stride=2, padding=1, bias=False), mid),
-                                   _ConvBnReLU(nn.Conv2d(mid, cout, 1, bias=False), cout))
-
-    def forward(self, x, skip=None):
-        x = self.block(x)
-        return x if skip is None else x + skip
-
-
-class LinknetDecoder(nn.Module):
-    def __init__(self, classes, owner=None):
-        super().__init__()
-        for L, (cin, _mid, cout) in enumerate(LINKNET_CH):
-            setattr(self, 'layer%d' % (L + 1), _LinknetBlock(cin, cout))
-        self.final_conv = nn.Conv2d(LINKNET_CH[4][2], classes, 1)
-        self._owner = [owner]                                  # list: not registered as a sub-module
-
-    def forward(self, enc):
-        if not self.training:
-            return self._owner[0].hip_engine(enc[0].device).decode(list(enc))
-        x = enc[0]
-        skips = list(enc[1:]) + [None]
-        for L in range(5):
-            x = getattr(self, 'layer%d' % (L + 1))(x, skips[L])
-        return self.final_conv(x)
-
-
 class LinknetSeg(UNetSeg):
     """Drop-in for ``smp.Linknet(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of
     UNetSeg (``model(x)``, ``model.encoder``, ``model.decoder``, ``hip_engine``), so every caller that takes a UNetSeg - utils.eval's
@@ -573,16 +513,20 @@ class LinknetSeg(UNetSeg):
         return LinknetDecoder(classes, self)
 
 
-def Linknet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
-    """smp's factory signature for the Linknet, so with ``import wsi_segmentation_pipeline_amd.unet as smp`` the reference's
-    ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None, classes=C, activation=None)`` serves 'Unet' and 'Linknet'.
-    Refusals as `Unet`; encoders 'resnet18' and 'resnet34' only."""
+def _factory_refusals(encoder_weights, activation):
+    """What both smp factories refuse: the model returns logits, as the reference builds it, and nothing is downloaded."""
     if encoder_weights is not None:
         raise ValueError('encoder_weights must be None (got %r): pretrained weights are not downloaded; load a state dict' % (encoder_weights,))
     if activation is not None:
         raise ValueError('activation must be None (got %r): the model returns logits, as the reference builds it' % (activation,))
-    if encoder_name not in ENCODER_LAYERS:
-        raise ValueError('encoder_name must be one of %s for a Linknet, got %r' % (list(ENCODER_LAYERS), encoder_name))
+
+
+def Linknet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
+    """smp's factory signature for the Linknet, so with ``import wsi_segmentation_pipeline_amd.unet as smp`` the reference's
+    ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None, classes=C, activation=None)`` serves 'Unet' and 'Linknet'.
+    Refusals as `Unet`; encoders 'resnet18' and 'resnet34' only."""
+    _factory_refusals(encoder_weights, activation)
+    encoder_spec(encoder_name, ('basic',), 'encoder_name', ' for a Linknet')
     return LinknetSeg(classes, precision, encoder_name)
 
 
@@ -591,12 +535,6 @@ def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=No
     activation=None)`` becomes ``unet.Unet(...)``: UNetSeg for 'resnet18' / 'resnet34', UNetSegBottleneck for 'resnet50' / 'resnet101'.
     The model returns logits: `activation` must be None, as the reference passes it; `encoder_weights` must be None (nothing is
     downloaded: load a checkpoint with ``load_state_dict``)."""
-    if encoder_weights is not None:
-        raise ValueError('encoder_weights must be None (got %r): pretrained weights are not downloaded; load a state dict' % (encoder_weights,))
-    if activation is not None:
-        raise ValueError('activation must be None (got %r): the model returns logits, as the reference builds it' % (activation,))
-    if encoder_name in ENCODER_LAYERS:
-        return UNetSeg(classes, precision, encoder_name)
-    if encoder_name in BOTTLENECK_ENCODER_LAYERS:
-        return UNetSegBottleneck(classes, precision, encoder_name)
-    raise ValueError('encoder_name must be one of %s, got %r' % (list(ENCODER_LAYERS) + list(BOTTLENECK_ENCODER_LAYERS), encoder_name))
+    _factory_refusals(encoder_weights, activation)
+    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
+    return {'basic': UNetSeg, 'bottleneck': UNetSegBottleneck}[arch](classes, precision, encoder_name)
