@@ -298,7 +298,8 @@ int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, cons
  * wsi_trunk_forward; wsi_prof_end disarms, waits for the events and returns the number of records
  * copied: ms, kind (1 = 3x3 stride 1 of layers 2-4, 5 = 3x3 stride 1 of layer 1, 2 = 3x3 stride 2, 3 = 1x1 downsample,
  * 4 = stem+maxpool; the U-Net decoder adds 6-10; 11 = stride-1 1x1 conv of the Bottleneck trunk, whose 3x3 convs are kind 1
- * and 2 and whose strided 1x1 downsamples are kind 3; the Linknet decoder adds 12 = 1x1 conv, 13 = transposed conv and 14 = fused last block + head)
+ * and 2 and whose strided 1x1 downsamples are kind 3; the Linknet decoder adds 12 = 1x1 conv, 13 = transposed conv and 14 = fused last block + head;
+ * the FPN decoder adds 15 = GroupNorm statistics, 16 = GroupNorm apply (+ upsample) and 17 = merge + head)
  * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch.  The records follow the depth table: per stage one entry
  * (kind 2, plus 3 on the gather route) and 2 * blocks - 1 stride-1 convs, layer 1 2 * blocks[0] of kind 5. */
 int wsi_prof_begin(int max_records);
@@ -576,6 +577,70 @@ int wsi_linknet_forward(const wsi_trunk_weights* wt, const wsi_linknet_decoder_w
                         int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
 int wsi_linknet_decoder(const wsi_linknet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
                         void* workspace, int workspace_n, float* logits_out, void* stream);
+/* ---- FPN: the feature-pyramid decoder of the dense 'seg' path -------------------------------------------------------
+ * `--model_name FPN` of myargs.py:9, built by `eval('smp.' + args.model_name)(args.arch_encoder, ...)` (eval.py:22, eval_tumorbed.py:21-28)
+ * and driven by utils/eval.py:51 `model(batch_image)` and :196-200 `model.decoder(model.encoder(x))`.  Third-party, absent and un-pinned
+ * like the U-Net, so the architecture is restated from the published 0.0.x source (parity unpinned; the numerical spec is
+ * tests/fpn_oracle.py):
+ *   encoder  either trunk at whatever depth its `blocks` state; [c5, c4, c3, c2] = [x4 /32, x3 /16, x2 /8, x1 /4]; x0 is never read
+ *   decoder  p5 = conv1(c5), p_k = nearest_x2(p_{k+1}) + skip_conv(c_k) for k = 4, 3, 2: 1x1 convs to 256 channels WITH bias;
+ *            seg branch sK (K = 5, 4, 3, 2) = max(1, K - 2) units of [conv3x3 (256 | 128) -> 128 without bias, GroupNorm(32, 128), ReLU,
+ *            and - except in s2 - bilinear x2 with align_corners=True]; x = s5 + s4 + s3 + s2 at 1/4 resolution; Dropout2d (identity in
+ *            eval mode); final_conv 1x1 128 -> classes + bias; bilinear x4 with align_corners=True
+ *   GroupNorm: per image and group, biased variance over the 4 channels x H x W of the group, eps inside the root, then weight / bias.
+ *   Bilinear with align_corners=True: src = dst * (in - 1) / (out - 1) in fp32 as torch computes it (0 where in = 1), the two
+ *   neighbours clamped to the map.
+ * Single ops (csrc/fpn.hip; PF tensors of 128 channels, planes 1 / 2; whole 16-byte pieces, the pad ring is never written):
+ *   wsi_groupnorm_relu_up2: out_pf = relu(groupnorm(in_pf)) at (h, w), or its bilinear x2 at (2h, 2w) when up2 = 1 - every source pixel is
+ *     normalised and rectified first, then blended.  Statistics: two launches with a fixed summation order (the same bits every run, no
+ *     atomics), centred per chunk of 64 pixels (planes 1: 128) and merged in chunk order, so a group whose mean is many standard
+ *     deviations keeps its variance.  scratch = wsi_groupnorm_scratch_bytes(n, h, w) bytes of device memory (0: bad shape).
+ *     -22 before any launch: a NULL pointer, in_pf == out_pf, c != 128, groups not dividing c or != 32, eps <= 0, up2 outside 0 / 1,
+ *     planes outside 1-2, n, h or w <= 0.
+ *   wsi_fpn_merge_head_up4: logits_out [n][classes][4h][4w] fp32 = bilinear x4 of (head_b + head_w [classes][c] . (m0 + m1 + m2 + m3)) over
+ *     the four PF maps (n, h, w, c); quarter_scratch = n * classes * h * w floats of device memory.  -22: a NULL pointer or map, c != 128,
+ *     classes outside 1-16, planes outside 1-2, n, h or w <= 0.
+ *   wsi_upsample2_nearest: out_pf (2h, 2w, c) = F.interpolate(in_pf, scale_factor=2, mode='nearest'): whole lines are copied (c a
+ *     multiple of the line's channels); planes 1 / 2.
+ * Decoder weights: conv slots in state-dict order - 0 decoder.conv1, 1-3 decoder.p4 / p3 / p2.skip_conv (wsi_prepack_conv with k = 1 and
+ *   no BatchNorm; conv_b = the conv's own bias), 4-6 s5.block.0-2, 7-8 s4.block.0-1, 9 s3.block.0, 10 s2.block.0 (k = 3, no BatchNorm,
+ *   conv_b = zeros) - with cin = {enc[0], enc[1], enc[2], enc[3], 256,128,128, 256,128, 256, 256} and cout = {256 x 4, 128 x 7};
+ *   gn_w / gn_b [128] fp32 of the seven units in the same order; groups = 32; eps; head_w [classes][128], head_b, classes 1 ... 16.
+ * The four entries per block type mirror wsi_unet_* argument for argument (workspace: the trunk's + the decoder's part, zero-filled once by
+ *   the _workspace_init entry; release with wsi_trunk_workspace_release).  planes 1 or 2.  The half-resolution stem skip x0 is neither
+ *   computed nor stored unless enc_out asks for it; wsi_fpn_decoder ignores enc_nchw[4] (it may be NULL).
+ * -22 before the workspace is touched: what wsi_unet_forward / wsi_unet_bneck_forward refuse, planes 3, a cin / cout table that disagrees
+ *   with the widths above, groups != 32, eps <= 0, classes outside 1-16 and, when logits are asked for, a NULL conv, GroupNorm or head pointer.
+ * Profiler kinds (wsi_prof_end): 12 = a 1x1 lateral conv, 7 = a nearest x2 upsample, 6 = a 3x3 conv of a seg unit, 15 = GroupNorm
+ *   statistics, 16 = GroupNorm apply (+ upsample), 17 = merge + head + x4 (15-17 carry 0 FLOPs: they are memory-bound). */
+size_t wsi_groupnorm_scratch_bytes(int n, int h, int w);
+int wsi_groupnorm_relu_up2(const void* in_pf, void* out_pf, const float* gn_weight, const float* gn_bias, int n, int h, int w, int c, int groups,
+                           float eps, int up2, int planes, void* scratch, void* stream);
+int wsi_fpn_merge_head_up4(const void* const maps_pf[4], const float* head_w, const float* head_b, int n, int h, int w, int c, int classes,
+                           float* quarter_scratch, float* logits_out, int planes, void* stream);
+int wsi_upsample2_nearest(const void* in_pf, void* out_pf, int n, int h, int w, int c, int planes, void* stream);
+typedef struct {
+    const void* conv_w[11]; const float* conv_b[11];
+    int cin[11], cout[11];
+    const float* gn_w[7]; const float* gn_b[7];
+    int groups; float eps;
+    const float* head_w; const float* head_b;
+    int classes;
+} wsi_fpn_decoder_weights;
+size_t wsi_fpn_workspace_bytes(const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_fpn_workspace_init(const wsi_fpn_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_fpn_forward(const wsi_trunk_weights* wt, const wsi_fpn_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                    long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                    int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_fpn_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                    void* workspace, int workspace_n, float* logits_out, void* stream);
+size_t wsi_fpn_bneck_workspace_bytes(const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_fpn_bneck_workspace_init(const wsi_fpn_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_fpn_bneck_forward(const wsi_bneck_weights* wt, const wsi_fpn_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                          long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                          int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_fpn_bneck_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                          void* workspace, int workspace_n, float* logits_out, void* stream);
 /* F.interpolate(pred_src, (tile_h * r, tile_w * r)) of utils/eval.py:202-206 (default mode 'nearest') on planes_n
  * contiguous fp32 (hs, ws) planes */
 int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, void* stream);

@@ -61,6 +61,16 @@ int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w
 int wsi_tconv_dispatch(const ConvArgs& a, int planes, hipStream_t st);
 // ... and the fused last block + head (planes 2): x = PF (n, hh, wh, 64), blob = wsi_linknet_tail_prepack's; WSI_EINVAL outside its range
 int wsi_linknet_tail_dispatch(const void* x, const void* blob, int n, int hh, int wh, int classes, float* logits, hipStream_t st);
+// fpn.hip (it also holds the C entries wsi_groupnorm_relu_up2, wsi_fpn_merge_head_up4 and wsi_upsample2_nearest): GroupNorm(32, 128)
+// statistics of a PF tensor (n, h, w, 128) into `scratch` (wsi_gn_scratch_size(n, h, w) bytes, or one planned for a larger n, h, w),
+// relu(groupnorm(x)) (+ bilinear x2, align_corners) from those statistics, and the sum of four such maps + 1x1 head into q
+// [n][classes][h][w] fp32 + bilinear x4 into logits [n][classes][4h][4w]; planes 1 / 2
+size_t wsi_gn_scratch_size(int n, int h, int w);
+int wsi_gn_stats_dispatch(const void* in, int n, int h, int w, float eps, float* scratch, int planes, hipStream_t st);
+int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const float* beta, const float* scratch, int n, int h, int w, int up2,
+                          int planes, hipStream_t st);
+int wsi_fpn_head_dispatch(const void* const m[4], const float* head_w, const float* head_b, int n, int h, int w, int classes, float* q,
+                          float* logits, int planes, hipStream_t st);
 // slide_ops.hip
 int wsi_tile_gather_dispatch(const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, const float* lut,
                              float* out, int N, int ph, int pw, hipStream_t st);

@@ -1,6 +1,6 @@
 // The model-level entries of libwsi_hip.so (include/wsi_hip.h): the profiler, the trunk workspace and its layout tags, the trunk
 // launch sequences of both architectures (trunk_run: BasicBlock, bneck_run: Bottleneck), the four forward entries over them and the
-// U-Net and Linknet host sequences (one templated sequence, two decoders).  No device allocation, no synchronisation, no exceptions.
+// U-Net, Linknet and FPN host sequences (one templated sequence, three decoders).  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "../../include/wsi_hip.h"
 #include <iterator>
@@ -571,6 +571,11 @@ struct UnetDec {
     static constexpr auto run = unet_decoder_run;
 };
 
+// Whether a decoder reads the half-resolution stem skip x0 (default: it does).  A decoder that states `needs_x0 = false` (the FPN) makes
+// unet_forward neither run nor store x0 unless the caller's enc_out asks for the five maps; its plan still holds the buffer.
+template <class Dec, class = void> struct dec_needs_x0 : std::true_type {};
+template <class Dec> struct dec_needs_x0<Dec, std::void_t<decltype(Dec::needs_x0)>> : std::bool_constant<Dec::needs_x0> {};
+
 template <class Net, class Dec = UnetDec>
 static size_t unet_workspace_bytes(const typename Dec::Weights* dw, int n, int h, int w, int planes) {
     typename Net::Plan p;
@@ -657,7 +662,8 @@ static int unet_forward(const typename Net::Weights* wt, const typename Dec::Wei
     // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
     // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
     const ConvRoutes& r = g_routes;
-    const bool x0_fused = r.unet_x0_fused && !src.in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
+    const bool want_x0 = dec_needs_x0<Dec>::value || (enc_out && enc_out[4]);
+    const bool x0_fused = want_x0 && r.unet_x0_fused && !src.in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
                           r.stem_shared_weights;
     int rc = Net::run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res,
                       TrunkOpts{.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr, .stage_off = stage_off});
@@ -665,7 +671,7 @@ static int unet_forward(const typename Net::Weights* wt, const typename Dec::Wei
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
     // conv (bf16 hi/lo arithmetic) into the fp32 scratch, then PF lines
     StemArgs a = stem_args(src, wt->stem_w, wt->stem_b, (float*)(ws + p.stem_scratch), n, h, w);
-    {
+    if (want_x0) {
         ProfScope ps(st, 7, 0.0);                            // (glue: the unfused stem conv for the half-resolution skip x0)
         if (x0_fused) {
         } else if (r.unet_fuse_up) {                         // r04: the conv kernel writes PF lines itself (was: f32 scratch + nhwc_to_pf pass)
@@ -677,7 +683,7 @@ static int unet_forward(const typename Net::Weights* wt, const typename Dec::Wei
         }
     }
     if (rc) return rc;
-    const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], dec + u.x0};
+    const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], want_x0 ? dec + u.x0 : nullptr};
     if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first
         for (int i = 0; i < 5 && !rc; ++i) {
             const EncMap m = enc_map(Net::enc_c, i, h, w);
@@ -697,13 +703,14 @@ static int unet_decoder(const typename Dec::Weights* dw, const float* const enc_
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!dw || !enc_nchw || !workspace || !logits_out || n <= 0 || cap < n) return WSI_EINVAL;
     if (Net::plan(cap, h, w, planes, p) || Dec::plan(Net::enc_c, dw, cap, h, w, planes, u) || !Dec::ready(dw)) return WSI_EINVAL;
-    for (int i = 0; i < 5; ++i) if (!enc_nchw[i]) return WSI_EINVAL;
+    constexpr int maps = dec_needs_x0<Dec>::value ? 5 : 4;       // (a decoder that never reads x0 does not pack it either)
+    for (int i = 0; i < maps; ++i) if (!enc_nchw[i]) return WSI_EINVAL;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
     // encoder maps are packed into the trunk part of the workspace (one buffer of each of stages 3..0) and x0
-    const void* enc[5];
+    const void* enc[5] = {};
     int rc = WSI_OK;
-    for (int i = 0; i < 5 && !rc; ++i) {
+    for (int i = 0; i < maps && !rc; ++i) {
         char* dst = i < 4 ? ws + Net::stage_buf(p, 3 - i) : dec + u.x0;
         const EncMap m = enc_map(Net::enc_c, i, h, w);
         rc = wsi_pf_pack(enc_nchw[i], dst, n, m.c, m.h, m.w, planes, stream);
@@ -807,6 +814,127 @@ int wsi_linknet_forward(const wsi_trunk_weights* wt, const wsi_linknet_decoder_w
 int wsi_linknet_decoder(const wsi_linknet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
                         int workspace_n, float* logits_out, void* stream) {
     return unet_decoder<BasicNet, LinknetDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
+}
+
+// ------------------------------------------------------------------------------------ FPN (dense 'seg' path, GroupNorm + bilinear decoder)
+// smp's FPN decoder on either trunk (include/wsi_hip.h "FPN"): a top-down pyramid p5 ... p2 of 256 channels (1x1 laterals with bias, the
+// coarser level added after a nearest x2 upsample), four seg branches of [3x3 conv -> 128, GroupNorm(32), ReLU, bilinear x2] units that
+// all end at 1/4 resolution, their sum, the 1x1 head and a bilinear x4.  Level k = 0 ... 3 is the map at / 32 ... / 4.  The seven units in
+// state-dict order (s5.0-2, s4.0-1, s3.0, s2.0): the level a unit reads, and whether it reads the pyramid (else the unit before it).
+// Every unit but s2's upsamples, so a unit at level L writes level L + 1.
+static const int FPN_UNIT_LEVEL[7] = {0, 1, 2, 1, 2, 2, 3};
+static const int FPN_UNIT_FIRST[7] = {1, 0, 0, 1, 0, 1, 1};
+static const int FPN_MERGED[4] = {2, 4, 5, 6};        // the last unit of s5, s4, s3, s2
+static const int FPN_CIN[11] = {0, 0, 0, 0, 256, 128, 128, 256, 128, 256, 256};       // (slots 0-3: the encoder's channels)
+constexpr int FPN_PYRAMID = 256, FPN_SEG = 128;
+struct FpnPlan {
+    size_t x0, p[4], up[3], raw[7], out[7], stat, q, total;      // pyramid levels, their upsampled copies, the units' conv outputs and results
+    int lh[4], lw[4];
+};
+static int fpn_plan(const int ec[5], const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes, FpnPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (dw->cin[i] != (i < 4 ? ec[i] : FPN_CIN[i]) || dw->cout[i] != (i < 4 ? FPN_PYRAMID : FPN_SEG)) return WSI_EINVAL;
+    if (dw->groups != 32 || !(dw->eps > 0.f) || dw->classes <= 0 || dw->classes > 16) return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    for (int k = 0; k < 4; ++k) {
+        u.lh[k] = (h / 32) << k; u.lw[k] = (w / 32) << k;
+        u.p[k] = take(wsi_pf_bytes(n, u.lh[k], u.lw[k], FPN_PYRAMID, planes));
+        if (k) u.up[k - 1] = take(wsi_pf_bytes(n, u.lh[k], u.lw[k], FPN_PYRAMID, planes));
+    }
+    for (int i = 0; i < 7; ++i) {
+        const int L = FPN_UNIT_LEVEL[i], Lo = L < 3 ? L + 1 : 3;
+        u.raw[i] = take(wsi_pf_bytes(n, u.lh[L], u.lw[L], FPN_SEG, planes));
+        u.out[i] = take(wsi_pf_bytes(n, u.lh[Lo], u.lw[Lo], FPN_SEG, planes));
+    }
+    const size_t stat = wsi_gn_scratch_size(n, u.lh[3], u.lw[3]);
+    if (!stat) return WSI_EINVAL;
+    u.stat = take(stat);
+    u.q = take((size_t)n * dw->classes * u.lh[3] * u.lw[3] * sizeof(float));
+    u.total = off;
+    return WSI_OK;
+}
+static bool fpn_ready(const wsi_fpn_decoder_weights* dw) {
+    for (int i = 0; i < 11; ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    for (int i = 0; i < 7; ++i) if (!dw->gn_w[i] || !dw->gn_b[i]) return false;
+    return dw->head_w && dw->head_b;
+}
+// wsi_prof kinds: 12 = a 1x1 lateral conv, 7 = a nearest x2 upsample of the pyramid, 6 = a seg unit's 3x3 conv, and the three memory-bound
+// kinds of csrc/fpn.hip, which carry no FLOPs: 15 = GroupNorm statistics, 16 = GroupNorm apply (+ upsample), 17 = merge + head + x4
+static int fpn_decoder_run(const wsi_fpn_decoder_weights* dw, const FpnPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                           float* logits_out, hipStream_t st) {
+    int rc = WSI_OK;
+    // p5 = conv1(c5) + bias; p_k = skip_conv(c_k) + bias + nearest_x2(p_{k+1}): the upsampled level is the 1x1's residual, no ReLU
+    for (int k = 0; k < 4 && !rc; ++k) {
+        if (k) {
+            ProfScope ps(st, 7, 0.0);
+            rc = wsi_upsample_concat_dispatch(dec + u.p[k - 1], nullptr, dec + u.up[k - 1], n, u.lh[k - 1], u.lw[k - 1], FPN_PYRAMID, 0, planes, st);
+        }
+        if (!rc) rc = run_conv(st, 12, ConvCall{.in = enc[k], .out = dec + u.p[k], .resid = k ? dec + u.up[k - 1] : nullptr, .wpk = dw->conv_w[k],
+                                                .bias = dw->conv_b[k], .n = n, .h = u.lh[k], .w = u.lw[k], .cin = dw->cin[k], .cout = FPN_PYRAMID,
+                                                .stride = 1, .ksize = 1, .relu = 0, .planes = planes, .stream = st});
+    }
+    float* stat = (float*)(dec + u.stat);
+    for (int i = 0; i < 7 && !rc; ++i) {
+        const int L = FPN_UNIT_LEVEL[i], H = u.lh[L], W = u.lw[L];
+        const void* in = FPN_UNIT_FIRST[i] ? dec + u.p[L] : dec + u.out[i - 1];
+        // the raw conv output is signed: the line formats carry it, as they carry the downsample branch's
+        rc = run_conv(st, 6, ConvCall{.in = in, .out = dec + u.raw[i], .wpk = dw->conv_w[4 + i], .bias = dw->conv_b[4 + i], .n = n, .h = H, .w = W,
+                                      .cin = dw->cin[4 + i], .cout = FPN_SEG, .stride = 1, .ksize = 3, .relu = 0, .planes = planes, .stream = st});
+        if (rc) break;
+        { ProfScope ps(st, 15, 0.0); rc = wsi_gn_stats_dispatch(dec + u.raw[i], n, H, W, dw->eps, stat, planes, st); }
+        if (rc) break;
+        ProfScope ps(st, 16, 0.0);
+        rc = wsi_gn_apply_dispatch(dec + u.raw[i], dec + u.out[i], dw->gn_w[i], dw->gn_b[i], stat, n, H, W, L < 3, planes, st);
+    }
+    if (rc) return rc;
+    const void* merged[4];
+    for (int i = 0; i < 4; ++i) merged[i] = dec + u.out[FPN_MERGED[i]];
+    ProfScope ps(st, 17, 0.0);
+    return wsi_fpn_head_dispatch(merged, dw->head_w, dw->head_b, n, u.lh[3], u.lw[3], dw->classes, (float*)(dec + u.q), logits_out, planes, st);
+}
+struct FpnDec {
+    using Weights = wsi_fpn_decoder_weights;
+    using Plan = FpnPlan;
+    static constexpr auto plan = fpn_plan;
+    static constexpr auto ready = fpn_ready;
+    static constexpr auto run = fpn_decoder_run;
+    static constexpr bool needs_x0 = false;
+};
+
+size_t wsi_fpn_workspace_bytes(const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BasicNet, FpnDec>(dw, n, h, w, planes);
+}
+int wsi_fpn_workspace_init(const wsi_fpn_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BasicNet, FpnDec>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_fpn_forward(const wsi_trunk_weights* wt, const wsi_fpn_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                    long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                    int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BasicNet, FpnDec>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace,
+                                          workspace_n, logits_out, enc_out, stream);
+}
+int wsi_fpn_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                    int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BasicNet, FpnDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
+}
+size_t wsi_fpn_bneck_workspace_bytes(const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BneckNet, FpnDec>(dw, n, h, w, planes);
+}
+int wsi_fpn_bneck_workspace_init(const wsi_fpn_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BneckNet, FpnDec>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_fpn_bneck_forward(const wsi_bneck_weights* wt, const wsi_fpn_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                          long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                          int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BneckNet, FpnDec>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace,
+                                          workspace_n, logits_out, enc_out, stream);
+}
+int wsi_fpn_bneck_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                          int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BneckNet, FpnDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
 }
 
 size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {

@@ -887,6 +887,40 @@ def conv1x1_bn_relu_add(x_pf, skip_pf, n, h, w, cin, cout, wpk, bias, planes=2):
     return out
 
 
+def groupnorm_relu_up2(x_pf, gn_weight, gn_bias, n, h, w, up2, planes=2, c=128, groups=32, eps=1e-5):
+    """wsi_groupnorm_relu_up2: PF (n, h, w, 128) -> a new zeroed PF buffer = relu(group_norm(x)), bilinearly upsampled x2 (align_corners=True)
+    to (n, 2h, 2w, 128) when `up2`.  gn_weight / gn_bias: fp32 GPU tensors of 128."""
+    lib = native.load()
+    k = 2 if up2 else 1
+    out = pf_zeros(n, c, k * h, k * w, planes, x_pf.device)
+    scratch = torch.empty(max(1, lib.wsi_groupnorm_scratch_bytes(n, h, w)), dtype=torch.uint8, device=x_pf.device)
+    native.check(lib.wsi_groupnorm_relu_up2(_ptr(x_pf), _ptr(out), _ptr(gn_weight), _ptr(gn_bias), n, h, w, c, groups, eps, int(bool(up2)), planes,
+                                            _ptr(scratch), _stream()), 'wsi_groupnorm_relu_up2')
+    return out
+
+
+def fpn_merge_head_up4(maps_pf, head_w, head_b, n, h, w, planes=2, c=128, with_quarter=False):
+    """wsi_fpn_merge_head_up4: four PF maps (n, h, w, 128), head_w (classes, 128) and head_b fp32 GPU tensors -> logits (n, classes, 4h, 4w)
+    fp32 = bilinear x4 (align_corners=True) of the 1x1 head over the maps' sum; with_quarter: (logits, the (n, classes, h, w) map before
+    the upsample)."""
+    lib = native.load()
+    classes = int(head_w.shape[0])
+    quarter = torch.empty((n, classes, h, w), dtype=torch.float32, device=head_w.device)
+    out = torch.empty((n, classes, 4 * h, 4 * w), dtype=torch.float32, device=head_w.device)
+    ptrs = (C.c_void_p * 4)(*[t.data_ptr() for t in maps_pf])
+    native.check(lib.wsi_fpn_merge_head_up4(C.byref(ptrs), _ptr(head_w.contiguous()), _ptr(head_b.contiguous()), n, h, w, c, classes,
+                                            _ptr(quarter), _ptr(out), planes, _stream()), 'wsi_fpn_merge_head_up4')
+    return (out, quarter) if with_quarter else out
+
+
+def upsample2_nearest(x_pf, n, h, w, c, planes=2):
+    """wsi_upsample2_nearest: PF (n, h, w, c) -> a new zeroed PF buffer (n, 2h, 2w, c), every pixel repeated 2 x 2."""
+    lib = native.load()
+    out = pf_zeros(n, c, 2 * h, 2 * w, planes, x_pf.device)
+    native.check(lib.wsi_upsample2_nearest(_ptr(x_pf), _ptr(out), n, h, w, c, planes, _stream()), 'wsi_upsample2_nearest')
+    return out
+
+
 def conv1x1_bn_act(x_pf, n, h, w, cin, cout, wpk, bias, stride=1, resid_pf=None, relu=True, planes=2, out=None, check=True):
     """wsi_conv1x1_bn_act (the Bottleneck 1x1 convs: pointwise kernel at stride 1 unless ConvMode.PW_GATHER) into `out` (a zeroed PF
     buffer is made when None).  check=False returns (out, return code) instead of raising."""

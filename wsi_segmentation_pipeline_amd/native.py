@@ -58,7 +58,17 @@ WsiLinknetDecoderWeights = _decoder_weights('WsiLinknetDecoderWeights', 15, 'wsi
                                             "decoder.layerL.block.J; tail_w = wsi_linknet_tail_prepack's blob or NULL.")
 
 
-_vp, _i, _ll, _sz, _f, _d = C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double
+class WsiFpnDecoderWeights(C.Structure):
+    """wsi_fpn_decoder_weights: conv slots in state-dict order (conv1, p4 / p3 / p2.skip_conv, s5.block.0-2, s4.block.0-1, s3.block.0,
+    s2.block.0), the GroupNorm weight / bias of the seven seg units in the same order, the head."""
+    _fields_ = [
+        ('conv_w', C.c_void_p * 11), ('conv_b', C.c_void_p * 11), ('cin', C.c_int * 11), ('cout', C.c_int * 11),
+        ('gn_w', C.c_void_p * 7), ('gn_b', C.c_void_p * 7), ('groups', C.c_int), ('eps', C.c_float),
+        ('head_w', C.c_void_p), ('head_b', C.c_void_p), ('classes', C.c_int),
+    ]
+
+
+_vp, _i, _ll, _sz, _f, _d =C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double
 # name -> (restype, argtypes); must list every symbol include/wsi_hip.h declares
 SIGNATURES = {
     'wsi_hip_abi_version': (_i, []),
@@ -167,6 +177,20 @@ SIGNATURES = {
     'wsi_linknet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiLinknetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
                                  _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
     'wsi_linknet_decoder': (_i, [C.POINTER(WsiLinknetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'wsi_groupnorm_scratch_bytes': (_sz, [_i, _i, _i]),
+    'wsi_groupnorm_relu_up2': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
+    'wsi_fpn_merge_head_up4': (_i, [C.POINTER(C.c_void_p * 4), _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    'wsi_upsample2_nearest': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'wsi_fpn_workspace_bytes': (_sz, [C.POINTER(WsiFpnDecoderWeights), _i, _i, _i, _i]),
+    'wsi_fpn_workspace_init': (_i, [C.POINTER(WsiFpnDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_fpn_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiFpnDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                             _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_fpn_decoder': (_i, [C.POINTER(WsiFpnDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'wsi_fpn_bneck_workspace_bytes': (_sz, [C.POINTER(WsiFpnDecoderWeights), _i, _i, _i, _i]),
+    'wsi_fpn_bneck_workspace_init': (_i, [C.POINTER(WsiFpnDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_fpn_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiFpnDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                                   _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_fpn_bneck_decoder': (_i, [C.POINTER(WsiFpnDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_resize_nearest_f32': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _vp]),
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),

@@ -2,12 +2,12 @@
 ``smp.Unet('resnet18', classes=C)`` (the reference's eval_tumorbed.py:21-28 and eval.py:22-27), driven by
 ``predict_wsis`` (utils/eval.py:51 ``model(batch_image)``) and ``predict_tumorbed(mode='seg')`` (:196-200
 ``model.decoder(model.encoder(batch_image))``).  The reference picks the model family by name (``eval('smp.' + args.model_name)``,
-``--model_name``) and the encoder by ``--arch_encoder``: this module serves 'Unet' and 'Linknet' on the encoders of `ENCODERS`, so
+``--model_name``) and the encoder by ``--arch_encoder``: this module serves 'Unet', 'Linknet' and 'FPN' on the encoders of `ENCODERS`, so
 ``import wsi_segmentation_pipeline_amd.unet as smp`` keeps that line working.
 
 segmentation_models_pytorch is third-party, absent here and un-pinned in the reference, so the architectures and the
 state-dict key names are restated from its published 0.0.x source - **parity unpinned**; the numerical specs are
-oracle/unet_oracle.py and tests/linknet_oracle.py (torch fp32 CPU) and the HIP path is held to them:
+oracle/unet_oracle.py, tests/linknet_oracle.py and tests/fpn_oracle.py (torch on the CPU) and the HIP path is held to them:
   encoder  a ResNet of `ENCODERS` (torchvision key names ``encoder.layerL.B.*``); forward returns [x4, x3, x2, x1, x0] (deepest first):
            x1..x4 = the LAST block of layer1..4, x0 = relu(bn1(conv1(x))) at half resolution, with `ENC_CH` channels: the same for
            every depth of a block type, so a decoder depends on the block type only
@@ -19,11 +19,17 @@ oracle/unet_oracle.py and tests/linknet_oracle.py (torch fp32 CPU) and the HIP p
     Linknet  per block (cin, mid = cin // 4, cout) of `LINKNET_CH`: 1x1 conv cin -> mid, ConvTranspose2d(mid, mid, kernel 4, stride 2,
              padding 1, bias=False; weight [mid in][mid out][4][4]), 1x1 conv mid -> cout, and ``x = block(x) + skip`` (no ReLU after
              the add) with skips x3, x2, x1, x0 for blocks 1-4, none for block 5.  BasicBlock encoders, 'parity' and 'speed' only
+    FPN      other keys (`fpn_decoder`): ``decoder.conv1`` and ``decoder.p4|p3|p2.skip_conv`` (1x1 to 256 channels, with bias; p_k =
+             nearest_x2(p_{k+1}) + skip_conv(c_k)), ``decoder.s5|s4|s3|s2.block.J.block.{0,1}`` (3x3 conv to 128 channels without bias,
+             GroupNorm(32), ReLU, and a bilinear x2 upsample with align_corners=True per unit of s5 / s4 / s3), the sum of the four
+             branches at 1/4 resolution, Dropout2d, ``decoder.final_conv`` and a bilinear x4 upsample.  x0 is never read.  All four
+             encoders, 'parity' and 'speed' only
 
-What a decoder consists of is written once, as a `Decoder` description (`unet_decoder`, `linknet_decoder`): its convs in state-dict
-order with real and stored widths.  The key lists (`decoder_key_shapes`, `linknet_decoder_key_shapes`), the packing of the device
+What a decoder consists of is written once, as a `Decoder` description (`unet_decoder`, `linknet_decoder`, `fpn_decoder`): its convs in
+state-dict order with real and stored widths and what follows each (BatchNorm, GroupNorm or a bias).  The key lists (`decoder_key_shapes`,
+`linknet_decoder_key_shapes`, `fpn_decoder_key_shapes`), the packing of the device
 weights (`pack_decoder`, host work only) and the layers of the ``nn.Module`` decoders are read from it.
-Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/tail.hip behind one entry prefix per model and
+Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/fpn.hip, csrc/tail.hip behind one entry prefix per model and
 encoder block type); training mode uses torch ops so ``train.py``-style callers still run.
 """
 import collections
@@ -70,7 +76,10 @@ def equal_batches(n, cap):
 # ---------------------------------------------------------------------------------------------- what a decoder consists of
 # One conv + BatchNorm + ReLU of a decoder: state-dict prefix (``<prefix>.0.weight``, ``<prefix>.1.*``), kind (a key of KINDS), real and
 # stored (cout, cin), and where the real input channels land in the stored weight as [(src_lo, src_hi, dst_lo)].
-Conv = collections.namedtuple('Conv', 'prefix kind real stored place')
+# `norm` says what follows the conv: 'bn' (BatchNorm, folded into the packed weights: the keys above), 'gn' (GroupNorm, ``<prefix>.1.{weight,
+# bias}``: its statistics come from the data, so it stays a separate device op) or 'bias' (nothing but the conv's own bias: the conv is
+# ``<prefix>.{weight,bias}`` itself).
+Conv = collections.namedtuple('Conv', 'prefix kind real stored place norm', defaults=('bn',))
 KINDS = {'conv3': ('conv', 3), 'conv1': ('conv', 1), 'tconv': ('tconv', 4)}      # -> (kind in the key lists, kernel size); tconv = 4x4 stride 2
 # The last block + head as one kernel on the block's REAL channels, in parity mode up to 4 classes: the prepack entry (its size is
 # ``<entry>_bytes()``), the prefixes of the block's convs and the dimension arguments between the head and `classes`.
@@ -114,11 +123,35 @@ def linknet_decoder():
     return Decoder(rows, LINKNET_CH[4][2], tail, native.WsiLinknetDecoderWeights)
 
 
+FPN_PYRAMID_CH, FPN_SEG_CH, FPN_GROUPS, GN_EPS = 256, 128, 32, 1e-5       # smp's FPN defaults; nn.GroupNorm's default eps
+FPN_BRANCHES = (('s5', 3), ('s4', 2), ('s3', 1), ('s2', 0))                # seg branch on p5 ... p2 and its bilinear x2 upsamples
+
+
+def fpn_decoder(enc_ch=ENC_CH['basic']):
+    """The FPN decoder on an encoder whose maps [c5, c4, c3, c2, x0] = [x4, x3, x2, x1, x0] have `enc_ch` channels (x0 is never read):
+    the four 1x1 laterals with bias (conv1 on c5, p4 / p3 / p2.skip_conv), then per seg branch max(1, upsamples) units of 3x3 conv +
+    GroupNorm(32) + ReLU.  Every tensor is 128 or 256 channels wide: whole lines in both precision modes, no padding."""
+    rows = [Conv('decoder.conv1', 'conv1', (FPN_PYRAMID_CH, enc_ch[0]), (FPN_PYRAMID_CH, enc_ch[0]), [(0, enc_ch[0], 0)], 'bias')]
+    rows += [Conv('decoder.p%d.skip_conv' % k, 'conv1', (FPN_PYRAMID_CH, c), (FPN_PYRAMID_CH, c), [(0, c, 0)], 'bias')
+             for k, c in zip((4, 3, 2), enc_ch[1:4])]
+    for name, ups in FPN_BRANCHES:
+        for j in range(max(1, ups)):
+            cin = FPN_PYRAMID_CH if j == 0 else FPN_SEG_CH
+            rows.append(Conv('decoder.%s.block.%d.block' % (name, j), 'conv3', (FPN_SEG_CH, cin), (FPN_SEG_CH, cin), [(0, cin, 0)], 'gn'))
+    return Decoder(rows, FPN_SEG_CH, None, native.WsiFpnDecoderWeights)
+
+
 def _key_shapes(dec, classes):
     out = []
     for r in dec.rows:
         (kind, k), (cout, cin) = KINDS[r.kind], r.real
+        if r.norm == 'bias':
+            out += [(r.prefix + '.weight', (cout, cin, k, k), kind), (r.prefix + '.bias', (cout,), 'lin_b')]
+            continue
         out.append((r.prefix + '.0.weight', (cin, cout, k, k) if kind == 'tconv' else (cout, cin, k, k), kind))      # ConvTranspose2d keeps [in][out]
+        if r.norm == 'gn':
+            out += [(r.prefix + '.1.weight', (cout,), 'bn_w'), (r.prefix + '.1.bias', (cout,), 'bn_b')]
+            continue
         out += [('%s.1.%s' % (r.prefix, s), (cout,), bn_kind) for s, bn_kind in zip(BN_KEYS, ('bn_w', 'bn_b', 'bn_m', 'bn_v'))]
         out.append((r.prefix + '.1.num_batches_tracked', (), 'bn_n'))
     out.append(('decoder.final_conv.weight', (classes, dec.head_cin, 1, 1), 'conv'))
@@ -136,16 +169,35 @@ def linknet_decoder_key_shapes(classes):
     return _key_shapes(linknet_decoder(), classes)
 
 
-PackedDecoder = collections.namedtuple('PackedDecoder', 'convs cin cout head_w head_b tail')
+def fpn_decoder_key_shapes(classes, enc_ch=ENC_CH['basic']):
+    """[(key, shape, kind)] of the FPN decoder in state-dict order: 31 keys.  kind 'lin_b' = a conv's bias, 'bn_w' / 'bn_b' = a GroupNorm's
+    weight / bias."""
+    return _key_shapes(fpn_decoder(enc_ch), classes)
+
+
+PackedDecoder = collections.namedtuple('PackedDecoder', 'convs cin cout head_w head_b tail gn', defaults=((),))
 
 
 def pack_decoder(lib, state_dict, dec, planes, classes):
     """The device weights of decoder `dec` from the ``decoder.*`` keys, as numpy arrays (host work only): convs = [(packed, bias)] per
-    row, the stored cin / cout tables, the head's (classes, head_cin) weight and its bias, and the fused tail's blob or None."""
-    convs = []
+    row, the stored cin / cout tables, the head's (classes, head_cin) weight and its bias, the fused tail's blob or None, and gn =
+    [(weight, bias)] of the rows that a GroupNorm follows.  A row without BatchNorm is packed with scale 1; its bias array is the conv's
+    own bias (zeros where it has none)."""
+    convs, gn = [], []
     for r in dec.rows:
         (kind, k), (cout, cin), (cout_s, cin_s) = KINDS[r.kind], r.real, r.stored
         tconv = kind == 'tconv'
+        if r.norm != 'bn':
+            if r.real != r.stored:
+                raise ValueError('row %s: a conv without BatchNorm is stored at its real width' % r.prefix)
+            w = _f32(state_dict, r.prefix + ('.weight' if r.norm == 'bias' else '.0.weight'))
+            pk, bias = pack_conv(lib, w, None, planes, tconv)
+            if r.norm == 'bias':
+                bias = _f32(state_dict, r.prefix + '.bias')
+            else:
+                gn.append((_f32(state_dict, r.prefix + '.1.weight'), _f32(state_dict, r.prefix + '.1.bias')))
+            convs.append((pk, bias))
+            continue
         w = _f32(state_dict, r.prefix + '.0.weight')
         wp = np.zeros((cin_s, cout_s, k, k) if tconv else (cout_s, cin_s, k, k), np.float32)
         src, dst = (w.swapaxes(0, 1), wp.swapaxes(0, 1)) if tconv else (w, wp)         # both as [out][in]: ConvTranspose2d keeps [in][out]
@@ -160,12 +212,12 @@ def pack_decoder(lib, state_dict, dec, planes, classes):
     head_w = np.ascontiguousarray(_f32(state_dict, 'decoder.final_conv.weight').reshape(classes, dec.head_cin))
     head_b = _f32(state_dict, 'decoder.final_conv.bias')
     tail = None
-    if planes == PARITY and classes <= 4:
-        args = [a for p in dec.tail.prefixes for a in [_f32(state_dict, p + '.0.weight')] + _bn(state_dict, p + '.1')]
+    if dec.tail is not None and planes == PARITY and classes <= 4:
+        args =[a for p in dec.tail.prefixes for a in [_f32(state_dict, p + '.0.weight')] + _bn(state_dict, p + '.1')]
         tail = np.empty(getattr(lib, dec.tail.entry + '_bytes')(), np.uint8)
         native.check(getattr(lib, dec.tail.entry)(*[_np_ptr(a) for a in args], BN_EPS, _np_ptr(head_w), _np_ptr(head_b), *dec.tail.dims,
                                                   classes, _np_ptr(tail)), dec.tail.entry)
-    return PackedDecoder(convs, [r.stored[1] for r in dec.rows], [r.stored[0] for r in dec.rows], head_w, head_b, tail)
+    return PackedDecoder(convs, [r.stored[1] for r in dec.rows], [r.stored[0] for r in dec.rows], head_w, head_b, tail, tuple(gn))
 
 
 class UNetEngine:
@@ -315,6 +367,40 @@ class UNetEngine:
         return logits
 
 
+class FPNEngine(UNetEngine):
+    """ResNet encoder (either block type) + FPN decoder on HIP kernels (wsi_fpn_* / wsi_fpn_bneck_*; csrc/fpn.hip for the GroupNorm and
+    bilinear passes, the existing conv kernels for the rest): the surface of UNetEngine - forward_f32, forward_tiles, decode (the fifth
+    map, x0, is ignored), release_workspaces - with the batch sized by the FPN workspace (~45 MB per 256 x 256 tile on a BasicBlock encoder
+    in parity mode, ~64 MB on a Bottleneck one).  Precision 'parity' or 'speed'."""
+
+    ENTRY = {'basic': 'wsi_fpn', 'bottleneck': 'wsi_fpn_bneck'}
+
+    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
+        if planes not in (PARITY, SPEED):
+            raise ValueError("an FPN runs in precision 'parity' or 'speed': there is no mx mode")
+        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+
+    def _describe(self):
+        return fpn_decoder(self.enc_ch)
+
+    def _pack_decoder(self, state_dict):
+        dec = self._describe()
+        pk = pack_decoder(self.lib, state_dict, dec, self.planes, self.classes)
+
+        def dev(a):
+            self._keep.append(torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
+            return self._keep[-1].data_ptr()
+
+        dw = self.dw = dec.weights()
+        for i, (w, bias) in enumerate(pk.convs):
+            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
+            dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
+        for i, (g, b) in enumerate(pk.gn):
+            dw.gn_w[i], dw.gn_b[i] = dev(g), dev(b)
+        dw.groups, dw.eps = FPN_GROUPS, GN_EPS
+        dw.head_w, dw.head_b, dw.classes = dev(pk.head_w), dev(pk.head_b), self.classes
+
+
 class LinknetEngine(UNetEngine):
     """BasicBlock ResNet encoder + Linknet decoder on HIP kernels (wsi_linknet_*; csrc/linknet.hip): the surface of UNetEngine -
     forward_f32, forward_tiles, decode, release_workspaces - with the batch sized by the Linknet workspace (~70 MB per 256 x 256 tile in
@@ -398,6 +484,74 @@ class LinknetDecoder(_Decoder):
     def _level(block, x, skip):
         x = block(x)
         return x if skip is None else x + skip
+
+
+class _ConvGnReLU(nn.Module):
+    """``.block`` = Sequential(conv without bias, GroupNorm, ReLU) of one 'gn' `Conv` row: the keys ``block.0.weight``, ``block.1.{weight,bias}``."""
+
+    def __init__(self, row):
+        super().__init__()
+        (cout, cin), k = row.real, KINDS[row.kind][1]
+        self.block = nn.Sequential(nn.Conv2d(cin, cout, k, padding=k // 2, bias=False), nn.GroupNorm(FPN_GROUPS, cout, eps=GN_EPS), nn.ReLU(inplace=True))
+
+    def forward(self, x):
+        return self.block(x)
+
+
+class _SegBlock(nn.Module):
+    """One seg branch: its units, each followed by a bilinear x2 upsample (align_corners=True) when the branch upsamples at all."""
+
+    def __init__(self, rows, upsamples):
+        super().__init__()
+        self.block = nn.Sequential(*[_ConvGnReLU(row) for row in rows])
+        self.upsamples = upsamples
+
+    def forward(self, x):
+        for unit in self.block:
+            x = unit(x)
+            if self.upsamples:
+                x = F.interpolate(x, scale_factor=2, mode='bilinear', align_corners=True)
+        return x
+
+
+class _Lateral(nn.Module):
+    def __init__(self, row):
+        super().__init__()
+        self.skip_conv = nn.Conv2d(row.real[1], row.real[0], 1)
+
+    def forward(self, x, skip):
+        return F.interpolate(x, scale_factor=2, mode='nearest') + self.skip_conv(skip)
+
+
+class FPNDecoder(nn.Module):
+    """``conv1``, ``p4`` / ``p3`` / ``p2``, ``s5`` ... ``s2``, ``dropout`` (no keys) and ``final_conv`` of `fpn_decoder`.  Eval mode hands
+    the maps to the owner's HIP engine; training mode runs torch ops."""
+
+    def __init__(self, classes, owner=None, enc_ch=ENC_CH['basic'], dropout=0.2):
+        super().__init__()
+        rows = fpn_decoder(enc_ch).rows
+        self.conv1 = nn.Conv2d(rows[0].real[1], rows[0].real[0], 1)
+        for k, row in zip((4, 3, 2), rows[1:4]):
+            setattr(self, 'p%d' % k, _Lateral(row))
+        at = 4
+        for name, ups in FPN_BRANCHES:
+            setattr(self, name, _SegBlock(rows[at:at + max(1, ups)], ups))
+            at += max(1, ups)
+        self.dropout = nn.Dropout2d(dropout)
+        self.final_conv = nn.Conv2d(FPN_SEG_CH, classes, 1)
+        self._owner = [owner]                                  # list: not registered as a sub-module
+
+    def forward(self, enc):
+        if not self.training:
+            return self._owner[0].hip_engine(enc[0].device).decode(list(enc))
+        c5, c4, c3, c2 = enc[:4]
+        p5 = self.conv1(c5)
+        p4 = self.p4(p5, c4)
+        p3 = self.p3(p4, c3)
+        p2 = self.p2(p3, c2)
+        x = self.s5(p5) + self.s4(p4) + self.s3(p3) + self.s2(p2)
+        x = self.final_conv(self.dropout(x))
+        return F.interpolate(x, scale_factor=4, mode='bilinear', align_corners=True)
 
 
 class UNetEncoder(nn.Module):
@@ -513,6 +667,30 @@ class LinknetSeg(UNetSeg):
         return LinknetDecoder(classes, self)
 
 
+class FPNSeg(UNetSeg):
+    """Drop-in for ``smp.FPN(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of UNetSeg,
+    so every caller that takes a UNetSeg - utils.eval's fused tile path, multi-rank stitching - takes it too.  Precision 'parity' or 'speed'."""
+    PRECISIONS = ('parity', 'speed')
+    ENGINE = FPNEngine
+
+    def __init__(self, classes=4, precision='parity', encoder='resnet18', dropout=0.2):
+        if not 0.0 <= float(dropout) < 1.0:
+            raise ValueError('dropout must be in [0, 1), got %r' % (dropout,))
+        object.__setattr__(self, '_dropout_p', float(dropout))           # (read by _make_decoder, which the base constructor calls)
+        super().__init__(classes, precision, encoder)
+
+    def _make_decoder(self, classes):
+        return FPNDecoder(classes, self, self.encoder.out_shapes, self._dropout_p)
+
+
+class FPNSegBottleneck(FPNSeg):
+    """``smp.FPN('resnet50' | 'resnet101', classes=C, activation=None)``: FPNSeg on a Bottleneck encoder."""
+    ENCODER = UNetBottleneckEncoder
+
+    def __init__(self, classes=4, precision='parity', encoder='resnet50', dropout=0.2):
+        super().__init__(classes, precision, encoder, dropout)
+
+
 def _factory_refusals(encoder_weights, activation):
     """What both smp factories refuse: the model returns logits, as the reference builds it, and nothing is downloaded."""
     if encoder_weights is not None:
@@ -538,3 +716,18 @@ def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=No
     _factory_refusals(encoder_weights, activation)
     arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
     return {'basic': UNetSeg, 'bottleneck': UNetSegBottleneck}[arch](classes, precision, encoder_name)
+
+
+def FPN(encoder_name='resnet34', encoder_weights=None, decoder_pyramid_channels=256, decoder_segmentation_channels=128, classes=1, dropout=0.2,
+        activation=None, final_upsampling=4, precision='parity'):
+    """smp's factory signature for the FPN, so the reference's ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None,
+    classes=C, activation=None)`` serves 'FPN' on all four encoders: FPNSeg for 'resnet18' / 'resnet34', FPNSegBottleneck for 'resnet50' /
+    'resnet101'.  Refusals as `Unet`; the three decoder-size arguments are accepted at smp's defaults only (the kernels are built for
+    them); `dropout` in [0, 1) (it acts in training mode only)."""
+    _factory_refusals(encoder_weights, activation)
+    for name, got, want in (('decoder_pyramid_channels', decoder_pyramid_channels, FPN_PYRAMID_CH),
+                            ('decoder_segmentation_channels', decoder_segmentation_channels, FPN_SEG_CH), ('final_upsampling', final_upsampling, 4)):
+        if got != want:
+            raise ValueError('%s must be %d (got %r): the FPN kernels are built for smp\'s default decoder' % (name, want, got))
+    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
+    return {'basic': FPNSeg, 'bottleneck': FPNSegBottleneck}[arch](classes, precision, encoder_name, dropout)
