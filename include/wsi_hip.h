@@ -299,7 +299,9 @@ int wsi_bneck_forward_tap(const wsi_bneck_weights* wt, const float* in_f32, cons
  * copied: ms, kind (1 = 3x3 stride 1 of layers 2-4, 5 = 3x3 stride 1 of layer 1, 2 = 3x3 stride 2, 3 = 1x1 downsample,
  * 4 = stem+maxpool; the U-Net decoder adds 6-10; 11 = stride-1 1x1 conv of the Bottleneck trunk, whose 3x3 convs are kind 1
  * and 2 and whose strided 1x1 downsamples are kind 3; the Linknet decoder adds 12 = 1x1 conv, 13 = transposed conv and 14 = fused last block + head;
- * the FPN decoder adds 15 = GroupNorm statistics, 16 = GroupNorm apply (+ upsample) and 17 = merge + head)
+ * the FPN decoder adds 15 = GroupNorm statistics, 16 = GroupNorm apply (+ upsample) and 17 = merge + head;
+ * the PSPNet decoder adds 18 = pyramid pool, 19 = stage projection, 20 = pyramid expand and 21 = head x8 upsample, its fusing 1x1 conv is
+ * kind 12 and its 3x3 head conv kind 6)
  * and algorithmic FLOPs (2*M*N*K over real output pixels) per launch.  The records follow the depth table: per stage one entry
  * (kind 2, plus 3 on the gather route) and 2 * blocks - 1 stride-1 convs, layer 1 2 * blocks[0] of kind 5. */
 int wsi_prof_begin(int max_records);
@@ -641,6 +643,77 @@ int wsi_fpn_bneck_forward(const wsi_bneck_weights* wt, const wsi_fpn_decoder_wei
                           int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
 int wsi_fpn_bneck_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
                           void* workspace, int workspace_n, float* logits_out, void* stream);
+/* ---- PSPNet: the pyramid-pooling decoder of the dense 'seg' path ------------------------------------------------------
+ * `--model_name PSPNet` of myargs.py:9-10, built by `eval('smp.' + args.model_name)(args.arch_encoder, ...)` (eval.py:22,
+ * eval_tumorbed.py:21-28) and driven by utils/eval.py:51 `model(batch_image)` and :196-200 `model.decoder(model.encoder(x))`.  Third-party,
+ * absent and un-pinned like the other three families, so the architecture is restated from the published 0.0.x source (parity unpinned; the
+ * numerical spec is tests/pspnet_oracle.py) at smp's defaults psp_in_factor = 8, psp_out_channels = 512, psp_use_batchnorm = True:
+ *   encoder  either trunk at whatever depth its `blocks` state.  The decoder reads ONE map, f = x2 = the last block of layer 2 at
+ *            (h / 8, w / 8) with C = 128 (BasicBlock) or 512 (Bottleneck) channels: a forward stops there unless enc_out asks for a deeper map,
+ *            and x0 is neither computed nor stored unless enc_out asks for it.
+ *   decoder  decoder.psp.stages.I, I = 0..3, pool sizes S = (1, 2, 3, 6): AdaptiveAvgPool2d((S, S)), 1x1 conv C -> C / 4, ReLU, bilinear
+ *            resize back to (h / 8, w / 8) with align_corners=True.  Stage 0 has no BatchNorm and its conv has a bias; stages 1-3 have a
+ *            conv without bias + BatchNorm.  decoder.conv: 1x1 conv 2C -> 512 without bias + BatchNorm + ReLU on cat([stage0, stage1,
+ *            stage2, stage3, f], dim=1) - stages first, the feature map last.  Dropout2d (identity in eval mode), decoder.final_conv 3x3
+ *            512 -> classes with padding 1 and bias, bilinear x8 with align_corners=True.
+ *   Adaptive bin i of S over a length L covers [floor(i L / S), ceil((i + 1) L / S)): bins overlap when S does not divide L and repeat
+ *   pixels when L < S.  Bilinear with align_corners=True: src = dst * (S - 1) / (L - 1) in fp32 as torch computes it (0 where L = 1 or
+ *   S = 1), the two neighbours clamped - the FPN's definition above.
+ * On the device the 2C-wide concatenation is never made: the fusing conv and the resize are linear, so
+ *   conv(cat(up(s0..s3), f)) = Wf . f + sum_I up(W_I . s_I)
+ * with W_I (512 x C / 4) and Wf (512 x C, the LAST C input columns) the column slices of decoder.conv's weight, its BatchNorm scale folded
+ * in.  Wf . f runs on the stride-1 1x1 conv route with the BatchNorm shift as bias and the pyramid term as its pre-ReLU residual; the W_I
+ * products are 50 pixels per image (1 + 4 + 9 + 36 bins, in the order S = 1, 2, 3, 6, row-major within a size).
+ * Single ops (csrc/pspnet.hip; planes 1 / 2; PF tensors in whole 16-byte pieces, the pad ring is never written):
+ *   wsi_pyramid_pool: pooled_out [n][50][c] fp32 = the four adaptive average pools of the PF tensor (n, h, w, c), one launch and one pass
+ *     over the map, a fixed summation order (columns, then rows) without atomics: the same bits every run.  c a multiple of the line's
+ *     channels (32; planes 1: 64), any h, w >= 1.
+ *   wsi_pspnet_stage_project: proj_out [n][50][512] fp32 = proj_w[I]^T relu(stage_w[I]^T pooled + stage_b[I]) per bin, I the bin's stage;
+ *     stage_w[I] is [c][c / 4] (the conv's weight TRANSPOSED, BatchNorm scale folded in), stage_b[I] [c / 4] (stage 0: the conv's bias;
+ *     1-3: the BatchNorm shift), proj_w[I] [c / 4][512] (W_I transposed); mid_scratch = n * 50 * c / 4 floats of device memory.  fp32 FMA.
+ *     c = 128 or 512.
+ *   wsi_pyramid_expand: out_pf (n, h, w, 512) = per pixel the sum over the four sizes of the bilinear sample of proj's S x S grid; c = 512.
+ *   wsi_pspnet_head_up8: logits_out [n][classes][8h][8w] fp32 = bilinear x8 of the first `classes` channels of the 3x3 conv head_wpk
+ *     (wsi_prepack_conv of decoder.final_conv zero-padded to one line of output channels: 32, planes 1: 64; no BatchNorm) + head_b (padded
+ *     alike) over in_pf (n, h, w, 512); head_scratch_pf = a zero-initialised PF buffer (n, h, w, one line).  classes 1 ... 16.
+ *   -22 before any launch: a NULL pointer, aliased buffers, a width outside the above, planes outside 1-2, n, h or w <= 0.
+ * Decoder weights: conv slot 0 = Wf (wsi_prepack_conv, k = 1, of the last C input columns of decoder.conv.block.0 with decoder.conv.block.1
+ *   folded in; cin = C, cout = 512), slot 1 = decoder.final_conv as wsi_pspnet_head_up8 takes it (cin = 512, cout = one line); stage_w,
+ *   stage_b, proj_w as wsi_pspnet_stage_project takes them; classes 1 ... 16; feat_c = C.
+ * The four entries per block type mirror wsi_fpn_* argument for argument (workspace: the trunk's + the decoder's part, zero-filled once by the
+ *   _workspace_init entry; release with wsi_trunk_workspace_release).  planes 1 or 2; h and w multiples of 32.  wsi_pspnet_decoder reads
+ *   enc_nchw[2] only: the other four may be NULL.
+ * -22 before the workspace is touched: what wsi_unet_forward / wsi_unet_bneck_forward refuse, planes 3, a cin / cout table or feat_c that
+ *   disagrees with the encoder, classes outside 1-16 and, when logits are asked for, a NULL weight pointer.
+ * Profiler kinds (wsi_prof_end): 18 = pyramid pool, 19 = stage projection (two launches), 20 = pyramid expand, 12 = the fusing 1x1 conv,
+ *   6 = the 3x3 head conv, 21 = head x8 upsample (18-21 carry 0 FLOPs). */
+int wsi_pyramid_pool(const void* in_pf, float* pooled_out, int n, int h, int w, int c, int planes, void* stream);
+int wsi_pspnet_stage_project(const float* pooled, const float* const stage_w[4], const float* const stage_b[4], const float* const proj_w[4],
+                             float* mid_scratch, float* proj_out, int n, int c, void* stream);
+int wsi_pyramid_expand(const float* proj, void* out_pf, int n, int h, int w, int c, int planes, void* stream);
+int wsi_pspnet_head_up8(const void* in_pf, const void* head_wpk, const float* head_b, void* head_scratch_pf, float* logits_out, int n, int h,
+                        int w, int c, int classes, int planes, void* stream);
+typedef struct {
+    const void* conv_w[2]; const float* conv_b[2];
+    int cin[2], cout[2];
+    const float* stage_w[4]; const float* stage_b[4];
+    const float* proj_w[4];
+    int classes, feat_c;
+} wsi_pspnet_decoder_weights;
+size_t wsi_pspnet_workspace_bytes(const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_pspnet_workspace_init(const wsi_pspnet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_pspnet_forward(const wsi_trunk_weights* wt, const wsi_pspnet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                       long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                       int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_pspnet_decoder(const wsi_pspnet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                       void* workspace, int workspace_n, float* logits_out, void* stream);
+size_t wsi_pspnet_bneck_workspace_bytes(const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes);
+int wsi_pspnet_bneck_workspace_init(const wsi_pspnet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream);
+int wsi_pspnet_bneck_forward(const wsi_bneck_weights* wt, const wsi_pspnet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                             long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                             int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream);
+int wsi_pspnet_bneck_decoder(const wsi_pspnet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                             void* workspace, int workspace_n, float* logits_out, void* stream);
 /* F.interpolate(pred_src, (tile_h * r, tile_w * r)) of utils/eval.py:202-206 (default mode 'nearest') on planes_n
  * contiguous fp32 (hs, ws) planes */
 int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, void* stream);

@@ -19,42 +19,6 @@ constexpr int FPN_C = 128;                            // channels of every tenso
 constexpr int GN_GROUPS = 32;                         // 4 channels per group
 constexpr int GN_CHUNK = 64;                          // pixels per chunk of the planning bound (planes 2; planes 1 takes 128)
 
-// the 8 channels 8 * piece ... 8 * piece + 7 of a pixel record (16 pieces per pixel in both formats):
-//   planes 2: line piece / 4, hi plane at 16 * (piece % 4), lo plane 64 bytes behind; planes 1: byte 16 * piece
-template <int PLANES>
-static __device__ __forceinline__ void piece_load(const char* px, int piece, float (&v)[8]) {
-    if constexpr (PLANES == 2) {
-        const char* p = px + (piece >> 2) * 128 + (piece & 3) * 16;
-        const f16x8 hi = __builtin_bit_cast(f16x8, *(const uint4*)p), lo = __builtin_bit_cast(f16x8, *(const uint4*)(p + 64));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)hi[i] + (float)lo[i];
-    } else {
-        const bf16x8 a = __builtin_bit_cast(bf16x8, *(const uint4*)(px + piece * 16));
-#pragma unroll
-        for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
-    }
-}
-template <int PLANES>
-static __device__ __forceinline__ void piece_store(char* px, int piece, const float (&v)[8]) {
-    if constexpr (PLANES == 2) {
-        f16x8 hi, lo;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            _Float16 a, b;
-            split_f16(v[i], a, b);
-            hi[i] = a; lo[i] = b;
-        }
-        char* p = px + (piece >> 2) * 128 + (piece & 3) * 16;
-        *(uint4*)p = __builtin_bit_cast(uint4, hi);
-        *(uint4*)(p + 64) = __builtin_bit_cast(uint4, lo);
-    } else {
-        bf16x8 a;
-#pragma unroll
-        for (int i = 0; i < 8; ++i) a[i] = (__bf16)v[i];
-        *(uint4*)(px + piece * 16) = __builtin_bit_cast(uint4, a);
-    }
-}
-
 // ------------------------------------------------------------------------------------ GroupNorm statistics
 // Stage 1: workgroup (image, chunk) -> part[image][chunk][group] = (mean, M2) of the chunk's CP pixels x 4 channels; the last chunk of an
 // image may be short (its count follows from the chunk index).  Thread t holds piece t % 16 of pixel t / 16 of each of the CP / 16 rounds.
@@ -249,8 +213,6 @@ static int grid_for(long long total) {
     const long long g = (total + 255) / 256;
     return (int)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
 }
-// torch's area_pixel_compute_scale with align_corners=True
-static float corner_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 static int chunks_of(int h, int w, int cp) { return (int)(((long long)h * w + cp - 1) / cp); }
 static bool gn_shape_ok(int n, int h, int w, int planes) {
     return n > 0 && h > 0 && w > 0 && (planes == 1 || planes == 2) && (long long)h * w < (1ll << 30) &&

@@ -71,6 +71,17 @@ int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const f
                           int planes, hipStream_t st);
 int wsi_fpn_head_dispatch(const void* const m[4], const float* head_w, const float* head_b, int n, int h, int w, int classes, float* q,
                           float* logits, int planes, hipStream_t st);
+// pspnet.hip (it also holds the C entries wsi_pyramid_pool, wsi_pspnet_stage_project, wsi_pyramid_expand and wsi_pspnet_head_up8): the 50
+// adaptive-average bins (sizes 1, 2, 3, 6) of a PF tensor (n, h, w, c) as fp32 [n][50][c]; per bin relu(stage conv + folded BatchNorm) into
+// mid [n][50][c / 4] and its slice of the fusing conv into proj [n][50][512] (c = 128 or 512: wsi_psp_width_ok); the bilinear expansion
+// (align_corners) of the four grids, summed, into a PF tensor (n, h, w, 512); and the first `classes` channels of a one-line PF tensor
+// (n, h, w) as fp32 NCHW logits, bilinear x `factor`; planes 1 / 2
+bool wsi_psp_width_ok(int c);
+int wsi_psp_pool_dispatch(const void* in, float* pooled, int n, int h, int w, int c, int planes, hipStream_t st);
+int wsi_psp_project_dispatch(const float* pooled, const float* const stage_w[4], const float* const stage_b[4], const float* const proj_w[4],
+                             float* mid, float* proj, int n, int c, hipStream_t st);
+int wsi_psp_expand_dispatch(const float* proj, void* out, int n, int h, int w, int planes, hipStream_t st);
+int wsi_psp_up_dispatch(const void* in, float* logits, int n, int h, int w, int classes, int factor, int planes, hipStream_t st);
 // slide_ops.hip
 int wsi_tile_gather_dispatch(const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, const float* lut,
                              float* out, int N, int ph, int pw, hipStream_t st);
@@ -110,6 +121,8 @@ int wsi_esp_dispatch(const double* pts, int n, int num, double* out, double* scr
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+// torch's area_pixel_compute_scale with align_corners=True: the source step per output pixel of a bilinear resize from `in` to `out` (fpn.hip, pspnet.hip)
+static inline float corner_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }
 
 // Where a batch's tiles come from: f32 NCHW images (in_f32), or a u8 RGB slide + one (x, y) corner per tile + the normalisation
 // table.  The C-ABI entries fill it once; n images of h x w travel beside it.

@@ -1,5 +1,6 @@
 // Per-pixel line codecs of the padded-flat activation formats (common.h): one 128-byte line <-> its fp32 channel values.
-// Shared by the layout converters / heads (heads.hip) and the U-Net decoder glue (unet.hip).
+// Shared by the layout converters / heads (heads.hip), the U-Net decoder glue (unet.hip) and the memory-bound FPN and PSPNet kernels
+// (fpn.hip, pspnet.hip: piece_load / piece_store).
 #pragma once
 #include "common.h"
 
@@ -81,4 +82,40 @@ static __device__ __forceinline__ float pf_line_decode(const char* line, int cha
     if constexpr (PLANES == 3) return mx_line_decode(line, chan);
     else if constexpr (PLANES == 2) return (float)((const _Float16*)line)[chan] + (float)((const _Float16*)(line + 64))[chan];
     else return (float)((const __bf16*)line)[chan];
+}
+
+// the 8 channels 8 * piece ... 8 * piece + 7 of a pixel record (c / 8 pieces per pixel in both formats: 16 at 128 channels, 64 at 512):
+//   planes 2: line piece / 4, hi plane at 16 * (piece % 4), lo plane 64 bytes behind; planes 1: byte 16 * piece
+template <int PLANES>
+static __device__ __forceinline__ void piece_load(const char* px, int piece, float (&v)[8]) {
+    if constexpr (PLANES == 2) {
+        const char* p = px + (piece >> 2) * 128 + (piece & 3) * 16;
+        const f16x8 hi = __builtin_bit_cast(f16x8, *(const uint4*)p), lo = __builtin_bit_cast(f16x8, *(const uint4*)(p + 64));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (float)hi[i] + (float)lo[i];
+    } else {
+        const bf16x8 a = __builtin_bit_cast(bf16x8, *(const uint4*)(px + piece * 16));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = (float)a[i];
+    }
+}
+template <int PLANES>
+static __device__ __forceinline__ void piece_store(char* px, int piece, const float (&v)[8]) {
+    if constexpr (PLANES == 2) {
+        f16x8 hi, lo;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            _Float16 a, b;
+            split_f16(v[i], a, b);
+            hi[i] = a; lo[i] = b;
+        }
+        char* p = px + (piece >> 2) * 128 + (piece & 3) * 16;
+        *(uint4*)p = __builtin_bit_cast(uint4, hi);
+        *(uint4*)(p + 64) = __builtin_bit_cast(uint4, lo);
+    } else {
+        bf16x8 a;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) a[i] = (__bf16)v[i];
+        *(uint4*)(px + piece * 16) = __builtin_bit_cast(uint4, a);
+    }
 }

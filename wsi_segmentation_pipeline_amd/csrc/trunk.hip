@@ -1,6 +1,6 @@
 // The model-level entries of libwsi_hip.so (include/wsi_hip.h): the profiler, the trunk workspace and its layout tags, the trunk
 // launch sequences of both architectures (trunk_run: BasicBlock, bneck_run: Bottleneck), the four forward entries over them and the
-// U-Net, Linknet and FPN host sequences (one templated sequence, three decoders).  No device allocation, no synchronisation, no exceptions.
+// U-Net, Linknet, FPN and PSPNet host sequences (one templated sequence, four decoders).  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "../../include/wsi_hip.h"
 #include <iterator>
@@ -575,6 +575,11 @@ struct UnetDec {
 // unet_forward neither run nor store x0 unless the caller's enc_out asks for the five maps; its plan still holds the buffer.
 template <class Dec, class = void> struct dec_needs_x0 : std::true_type {};
 template <class Dec> struct dec_needs_x0<Dec, std::void_t<decltype(Dec::needs_x0)>> : std::bool_constant<Dec::needs_x0> {};
+// The one encoder stage whose last block a decoder reads, as a layer number 1 ... 4 (default 0: it reads all four).  A decoder that states
+// `only_stage = s` (the PSPNet: 2) makes unet_forward stop the net after the last block of layer s unless the caller's enc_out asks for a
+// deeper map, and makes unet_decoder pack that one map only.  Encoder map i (deepest first) is the output of layer 4 - i.
+template <class Dec, class = void> struct dec_only_stage : std::integral_constant<int, 0> {};
+template <class Dec> struct dec_only_stage<Dec, std::void_t<decltype(Dec::only_stage)>> : std::integral_constant<int, Dec::only_stage> {};
 
 template <class Net, class Dec = UnetDec>
 static size_t unet_workspace_bytes(const typename Dec::Weights* dw, int n, int h, int w, int planes) {
@@ -658,14 +663,21 @@ static int unet_forward(const typename Net::Weights* wt, const typename Dec::Wei
     const int planes = wt->planes;
     // encoder: the trunk with every stage output kept as an ordinary PF tensor (no phase-split hand-over) ...
     TrunkOut res;
-    size_t stage_off[4];
+    size_t stage_off[4] = {0, 0, 0, 0};
+    // the deepest layer this call needs: all four, or the decoder's one stage and whatever deeper map the caller wants back
+    int deepest = 4;
+    if constexpr (dec_only_stage<Dec>::value > 0) {
+        deepest = dec_only_stage<Dec>::value;
+        for (int i = 0; enc_out && i < 4; ++i) if (enc_out[i] && 4 - i > deepest) deepest = 4 - i;
+    }
+    const int stop_after = deepest >= 4 ? d.total : d.first[deepest];      // (blocks before layer deepest + 1 = the last block of layer deepest)
     // r05: on the product path (u8 slide, parity mode) the fused stem + pool kernel stores x0 = relu(bn1(conv1(x))) itself - the conv
     // values it pools anyway, exact integer arithmetic - instead of a second, unfused stem conv (A/B: WSI_CONV_MODE_UNET_X0_UNFUSED)
     const ConvRoutes& r = g_routes;
     const bool want_x0 = dec_needs_x0<Dec>::value || (enc_out && enc_out[4]);
     const bool x0_fused = want_x0 && r.unet_x0_fused && !src.in_f32 && planes == 2 && wt->stem_w_u8 && wt->stem_b_u8 && r.stem_u8x && r.stem_fused &&
                           r.stem_shared_weights;
-    int rc = Net::run(wt, d, src, n, cap, h, w, workspace, d.total, st, p, res,
+    int rc = Net::run(wt, d, src, n, cap, h, w, workspace, stop_after, st, p, res,
                       TrunkOpts{.allow_split = false, .x0_out = x0_fused ? dec + u.x0 : nullptr, .stage_off = stage_off});
     if (rc) return rc;
     // ... plus x0 = relu(bn1(conv1(x))) before the max pool, which the fused stem kernel never writes: the unfused stem
@@ -683,11 +695,12 @@ static int unet_forward(const typename Net::Weights* wt, const typename Dec::Wei
         }
     }
     if (rc) return rc;
-    const void* enc[5] = {ws + stage_off[3], ws + stage_off[2], ws + stage_off[1], ws + stage_off[0], want_x0 ? dec + u.x0 : nullptr};
+    const void* enc[5] = {nullptr, nullptr, nullptr, nullptr, want_x0 ? dec + u.x0 : nullptr};
+    for (int i = 0; i < 4; ++i) if (4 - i <= deepest) enc[i] = ws + stage_off[3 - i];       // (a layer that did not run has no map)
     if (enc_out) {                                           // the `model.encoder(x)` surface: five fp32 NCHW maps, deepest first
         for (int i = 0; i < 5 && !rc; ++i) {
             const EncMap m = enc_map(Net::enc_c, i, h, w);
-            if (enc_out[i]) rc = wsi_pf_unpack(enc[i], enc_out[i], n, m.c, m.h, m.w, planes, stream);
+            if (enc_out[i] && enc[i]) rc = wsi_pf_unpack(enc[i], enc_out[i], n, m.c, m.h, m.w, planes, stream);
         }
         if (rc) return rc;
     }
@@ -703,14 +716,19 @@ static int unet_decoder(const typename Dec::Weights* dw, const float* const enc_
     const int cap = workspace_n > 0 ? workspace_n : n;
     if (!dw || !enc_nchw || !workspace || !logits_out || n <= 0 || cap < n) return WSI_EINVAL;
     if (Net::plan(cap, h, w, planes, p) || Dec::plan(Net::enc_c, dw, cap, h, w, planes, u) || !Dec::ready(dw)) return WSI_EINVAL;
-    constexpr int maps = dec_needs_x0<Dec>::value ? 5 : 4;       // (a decoder that never reads x0 does not pack it either)
-    for (int i = 0; i < maps; ++i) if (!enc_nchw[i]) return WSI_EINVAL;
+    // (a decoder that never reads x0 does not pack it either; one that reads a single stage packs that map alone)
+    auto reads = [](int i) {
+        constexpr int only = dec_only_stage<Dec>::value;
+        return only > 0 ? i == 4 - only : (i < 4 || dec_needs_x0<Dec>::value);
+    };
+    for (int i = 0; i < 5; ++i) if (reads(i) && !enc_nchw[i]) return WSI_EINVAL;
     char* ws = (char*)workspace;
     char* dec = ws + align_up(p.total, 256);
     // encoder maps are packed into the trunk part of the workspace (one buffer of each of stages 3..0) and x0
     const void* enc[5] = {};
     int rc = WSI_OK;
-    for (int i = 0; i < maps && !rc; ++i) {
+    for (int i = 0; i < 5 && !rc; ++i) {
+        if (!reads(i)) continue;
         char* dst = i < 4 ? ws + Net::stage_buf(p, 3 - i) : dec + u.x0;
         const EncMap m = enc_map(Net::enc_c, i, h, w);
         rc = wsi_pf_pack(enc_nchw[i], dst, n, m.c, m.h, m.w, planes, stream);
@@ -935,6 +953,107 @@ int wsi_fpn_bneck_forward(const wsi_bneck_weights* wt, const wsi_fpn_decoder_wei
 int wsi_fpn_bneck_decoder(const wsi_fpn_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
                           int workspace_n, float* logits_out, void* stream) {
     return unet_decoder<BneckNet, FpnDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
+}
+
+// ------------------------------------------------------------------------------------ PSPNet (dense 'seg' path, pyramid-pooling decoder)
+// smp's PSPNet decoder on either trunk (include/wsi_hip.h "PSPNet") at psp_in_factor 8: it reads one map, f = the last block of layer 2 at
+// / 8 (only_stage = 2: the net stops there).  The fusing 1x1 conv over cat([up(stage0..3), f]) is computed as Wf . f with the pyramid term
+// sum_I up(W_I . stage_I) as its pre-ReLU residual: pool f into 50 bins per image, run the stage convs and the W_I slices on those 50
+// pixels, expand bilinearly into a 512-channel PF tensor.  Then the 3x3 head on one stored line of output channels and the bilinear x8.
+constexpr int PSP_WIDTH = 512, PSP_BINS_PER_IMAGE = 50;
+struct PspPlan {
+    size_t x0, pooled, mid, proj, pyr, fused, head, total;
+    int fh, fw, fc, line;                             // the feature map and its channels; channels of one stored line
+};
+static int psp_plan(const int ec[5], const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes, PspPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    u.fh = h / 8; u.fw = w / 8; u.fc = ec[2]; u.line = planes == 1 ? 64 : 32;
+    if (dw->feat_c != u.fc || !wsi_psp_width_ok(u.fc) || dw->cin[0] != u.fc || dw->cout[0] != PSP_WIDTH || dw->cin[1] != PSP_WIDTH ||
+        dw->cout[1] != u.line || dw->classes <= 0 || dw->classes > 16)
+        return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    u.pooled = take((size_t)n * PSP_BINS_PER_IMAGE * u.fc * sizeof(float));
+    u.mid = take((size_t)n * PSP_BINS_PER_IMAGE * (u.fc / 4) * sizeof(float));
+    u.proj = take((size_t)n * PSP_BINS_PER_IMAGE * PSP_WIDTH * sizeof(float));
+    u.pyr = take(wsi_pf_bytes(n, u.fh, u.fw, PSP_WIDTH, planes));
+    u.fused = take(wsi_pf_bytes(n, u.fh, u.fw, PSP_WIDTH, planes));
+    u.head = take(wsi_pf_bytes(n, u.fh, u.fw, u.line, planes));
+    u.total = off;
+    return WSI_OK;
+}
+static bool psp_ready(const wsi_pspnet_decoder_weights* dw) {
+    for (int i = 0; i < 2; ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    for (int i = 0; i < 4; ++i) if (!dw->stage_w[i] || !dw->stage_b[i] || !dw->proj_w[i]) return false;
+    return true;
+}
+// wsi_prof kinds: the four memory-bound kinds of csrc/pspnet.hip, which carry no FLOPs - 18 = pyramid pool, 19 = stage projection,
+// 20 = pyramid expand, 21 = head x8 upsample - and 12 = the fusing 1x1 conv, 6 = the 3x3 head conv (over its stored output channels)
+static int psp_decoder_run(const wsi_pspnet_decoder_weights* dw, const PspPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                           float* logits_out, hipStream_t st) {
+    const void* f = enc[2];
+    float *pooled = (float*)(dec + u.pooled), *mid = (float*)(dec + u.mid), *proj = (float*)(dec + u.proj);
+    int rc;
+    { ProfScope ps(st, 18, 0.0); rc = wsi_psp_pool_dispatch(f, pooled, n, u.fh, u.fw, u.fc, planes, st); }
+    if (rc) return rc;
+    { ProfScope ps(st, 19, 0.0); rc = wsi_psp_project_dispatch(pooled, dw->stage_w, dw->stage_b, dw->proj_w, mid, proj, n, u.fc, st); }
+    if (rc) return rc;
+    { ProfScope ps(st, 20, 0.0); rc = wsi_psp_expand_dispatch(proj, dec + u.pyr, n, u.fh, u.fw, planes, st); }
+    if (rc) return rc;
+    // relu(Wf . f + shift + pyramid term): the pyramid tensor is the 1x1 conv's residual, added before the ReLU
+    rc = run_conv(st, 12, ConvCall{.in = f, .out = dec + u.fused, .resid = dec + u.pyr, .wpk = dw->conv_w[0], .bias = dw->conv_b[0], .n = n,
+                                   .h = u.fh, .w = u.fw, .cin = u.fc, .cout = PSP_WIDTH, .stride = 1, .ksize = 1, .relu = 1, .planes = planes,
+                                   .stream = st});
+    if (rc) return rc;
+    // the head's output channels are zero-padded to one line (zero weights, zero bias): signed logits at / 8, no ReLU
+    rc = run_conv(st, 6, ConvCall{.in = dec + u.fused, .out = dec + u.head, .wpk = dw->conv_w[1], .bias = dw->conv_b[1], .n = n, .h = u.fh,
+                                  .w = u.fw, .cin = PSP_WIDTH, .cout = u.line, .stride = 1, .ksize = 3, .relu = 0, .planes = planes, .stream = st});
+    if (rc) return rc;
+    ProfScope ps(st, 21, 0.0);
+    return wsi_psp_up_dispatch(dec + u.head, logits_out, n, u.fh, u.fw, dw->classes, 8, planes, st);
+}
+struct PspDec {
+    using Weights = wsi_pspnet_decoder_weights;
+    using Plan = PspPlan;
+    static constexpr auto plan = psp_plan;
+    static constexpr auto ready = psp_ready;
+    static constexpr auto run = psp_decoder_run;
+    static constexpr bool needs_x0 = false;
+    static constexpr int only_stage = 2;
+};
+
+size_t wsi_pspnet_workspace_bytes(const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BasicNet, PspDec>(dw, n, h, w, planes);
+}
+int wsi_pspnet_workspace_init(const wsi_pspnet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BasicNet, PspDec>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_pspnet_forward(const wsi_trunk_weights* wt, const wsi_pspnet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                       long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                       int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BasicNet, PspDec>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace,
+                                          workspace_n, logits_out, enc_out, stream);
+}
+int wsi_pspnet_decoder(const wsi_pspnet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes, void* workspace,
+                       int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BasicNet, PspDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
+}
+size_t wsi_pspnet_bneck_workspace_bytes(const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes) {
+    return unet_workspace_bytes<BneckNet, PspDec>(dw, n, h, w, planes);
+}
+int wsi_pspnet_bneck_workspace_init(const wsi_pspnet_decoder_weights* dw, void* workspace, int n, int h, int w, int planes, void* stream) {
+    return unet_workspace_init<BneckNet, PspDec>(dw, workspace, n, h, w, planes, stream);
+}
+int wsi_pspnet_bneck_forward(const wsi_bneck_weights* wt, const wsi_pspnet_decoder_weights* dw, const float* in_f32, const uint8_t* slide,
+                             long long slide_pitch_bytes, int slide_h, int slide_w, const int* tile_xy, const float* lut, int n, int h,
+                             int w, void* workspace, int workspace_n, float* logits_out, float* enc_out[5], void* stream) {
+    return unet_forward<BneckNet, PspDec>(wt, dw, {in_f32, slide, slide_pitch_bytes, slide_h, slide_w, tile_xy, lut}, n, h, w, workspace,
+                                          workspace_n, logits_out, enc_out, stream);
+}
+int wsi_pspnet_bneck_decoder(const wsi_pspnet_decoder_weights* dw, const float* const enc_nchw[5], int n, int h, int w, int planes,
+                             void* workspace, int workspace_n, float* logits_out, void* stream) {
+    return unet_decoder<BneckNet, PspDec>(dw, enc_nchw, n, h, w, planes, workspace, workspace_n, logits_out, stream);
 }
 
 size_t wsi_unet_workspace_bytes(const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes) {

@@ -921,6 +921,49 @@ def upsample2_nearest(x_pf, n, h, w, c, planes=2):
     return out
 
 
+def pyramid_pool(x_pf, n, h, w, c, planes=2):
+    """wsi_pyramid_pool: PF (n, h, w, c) -> fp32 (n, 50, c), the adaptive average pools of sizes 1, 2, 3, 6 (bins row-major within a size)."""
+    lib = native.load()
+    out = torch.empty((n, 50, c), dtype=torch.float32, device=x_pf.device)
+    native.check(lib.wsi_pyramid_pool(_ptr(x_pf), _ptr(out), n, h, w, c, planes, _stream()), 'wsi_pyramid_pool')
+    return out
+
+
+def pspnet_stage_project(pooled, stage_w, stage_b, proj_w):
+    """wsi_pspnet_stage_project: pooled fp32 (n, 50, c) and per stage stage_w (c, c / 4), stage_b (c / 4,), proj_w (c / 4, 512) fp32 GPU
+    tensors (the transposed matrices of `unet.pspnet_fold`) -> fp32 (n, 50, 512)."""
+    lib = native.load()
+    n, _, c = pooled.shape
+    mats = [[t.to(torch.float32).contiguous() for t in group] for group in (stage_w, stage_b, proj_w)]
+    mid = torch.empty((n, 50, c // 4), dtype=torch.float32, device=pooled.device)
+    out = torch.empty((n, 50, 512), dtype=torch.float32, device=pooled.device)
+    ptrs = [(C.c_void_p * 4)(*[t.data_ptr() for t in group]) for group in mats]
+    native.check(lib.wsi_pspnet_stage_project(_ptr(pooled.contiguous()), *[C.byref(p) for p in ptrs], _ptr(mid), _ptr(out), n, c, _stream()),
+                 'wsi_pspnet_stage_project')
+    return out
+
+
+def pyramid_expand(proj, n, h, w, planes=2, out=None):
+    """wsi_pyramid_expand: fp32 (n, 50, 512) -> PF (n, h, w, 512) in `out` (a zeroed PF buffer is made when None): per pixel the sum of the
+    bilinear samples (align_corners=True) of the four grids."""
+    lib = native.load()
+    if out is None:
+        out = pf_zeros(n, 512, h, w, planes, proj.device)
+    native.check(lib.wsi_pyramid_expand(_ptr(proj.contiguous()), _ptr(out), n, h, w, 512, planes, _stream()), 'wsi_pyramid_expand')
+    return out
+
+
+def pspnet_head_up8(x_pf, wpk, bias, n, h, w, classes, planes=2):
+    """wsi_pspnet_head_up8: PF (n, h, w, 512), the packed 3x3 head (output channels padded to one line) and its padded bias -> fp32 logits
+    (n, classes, 8h, 8w), bilinear x8 with align_corners=True."""
+    lib = native.load()
+    scratch = pf_zeros(n, 64 if planes == 1 else 32, h, w, planes, x_pf.device)
+    out = torch.empty((n, classes, 8 * h, 8 * w), dtype=torch.float32, device=x_pf.device)
+    native.check(lib.wsi_pspnet_head_up8(_ptr(x_pf), _ptr(wpk), _ptr(bias), _ptr(scratch), _ptr(out), n, h, w, 512, classes, planes, _stream()),
+                 'wsi_pspnet_head_up8')
+    return out
+
+
 def conv1x1_bn_act(x_pf, n, h, w, cin, cout, wpk, bias, stride=1, resid_pf=None, relu=True, planes=2, out=None, check=True):
     """wsi_conv1x1_bn_act (the Bottleneck 1x1 convs: pointwise kernel at stride 1 unless ConvMode.PW_GATHER) into `out` (a zeroed PF
     buffer is made when None).  check=False returns (out, return code) instead of raising."""

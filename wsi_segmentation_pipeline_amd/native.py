@@ -68,6 +68,17 @@ class WsiFpnDecoderWeights(C.Structure):
     ]
 
 
+class WsiPspnetDecoderWeights(C.Structure):
+    """wsi_pspnet_decoder_weights: conv slot 0 = the feature-map columns of decoder.conv (1x1, BatchNorm folded), slot 1 = decoder.final_conv
+    (3x3, output channels padded to one line); per pyramid stage the transposed stage conv [feat_c][feat_c / 4] with its BatchNorm scale
+    folded in, its bias [feat_c / 4] and the transposed column slice of decoder.conv [feat_c / 4][512]."""
+    _fields_ = [
+        ('conv_w', C.c_void_p * 2), ('conv_b', C.c_void_p * 2), ('cin', C.c_int * 2), ('cout', C.c_int * 2),
+        ('stage_w', C.c_void_p * 4), ('stage_b', C.c_void_p * 4), ('proj_w', C.c_void_p * 4),
+        ('classes', C.c_int), ('feat_c', C.c_int),
+    ]
+
+
 _vp, _i, _ll, _sz, _f, _d =C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double
 # name -> (restype, argtypes); must list every symbol include/wsi_hip.h declares
 SIGNATURES = {
@@ -191,6 +202,20 @@ SIGNATURES = {
     'wsi_fpn_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiFpnDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
                                    _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
     'wsi_fpn_bneck_decoder': (_i, [C.POINTER(WsiFpnDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'wsi_pyramid_pool': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'wsi_pspnet_stage_project': (_i, [_vp, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4), _vp, _vp, _i, _i, _vp]),
+    'wsi_pyramid_expand': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    'wsi_pspnet_head_up8': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    'wsi_pspnet_workspace_bytes': (_sz, [C.POINTER(WsiPspnetDecoderWeights), _i, _i, _i, _i]),
+    'wsi_pspnet_workspace_init': (_i, [C.POINTER(WsiPspnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_pspnet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiPspnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                                _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_pspnet_decoder': (_i, [C.POINTER(WsiPspnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    'wsi_pspnet_bneck_workspace_bytes': (_sz, [C.POINTER(WsiPspnetDecoderWeights), _i, _i, _i, _i]),
+    'wsi_pspnet_bneck_workspace_init': (_i, [C.POINTER(WsiPspnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
+    'wsi_pspnet_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiPspnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
+                                      _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
+    'wsi_pspnet_bneck_decoder': (_i, [C.POINTER(WsiPspnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_resize_nearest_f32': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _vp]),
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),

@@ -314,3 +314,30 @@ def make_fpn_bottleneck_state_dict(seed, layers=RESNET50_LAYERS, classes=4):
     sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
           if not k.startswith('fc')}
     return _with_fpn_decoder(sd, seed, classes, ENC_CH['bottleneck'])
+
+
+def _with_pspnet_decoder(sd, seed, classes, enc_ch):
+    from .unet import pspnet_decoder_key_shapes
+    rng = np.random.Generator(np.random.PCG64(seed + 11000))
+    for key, shape, kind in pspnet_decoder_key_shapes(classes, enc_ch):
+        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
+    return sd
+
+
+def make_pspnet_state_dict(seed, layers=RESNET18_LAYERS, classes=4):
+    """Seeded state dict of the PSPNet 'seg' model: encoder.* as make_fpn_state_dict builds it (layers 3 and 4 included: smp checkpoints
+    carry them), decoder.* per wsi_segmentation_pipeline_amd.unet.pspnet_decoder_key_shapes, drawn in state-dict order from
+    PCG64(seed + 11000): 'conv' for the conv weights, 'lin_b' for the two conv biases, the BatchNorm kinds as everywhere."""
+    from .unet import ENC_CH
+    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
+          if not k.startswith('fc')}
+    return _with_pspnet_decoder(sd, seed, classes, ENC_CH['basic'])
+
+
+def make_pspnet_bottleneck_state_dict(seed, layers=RESNET50_LAYERS, classes=4):
+    """make_pspnet_state_dict with a Bottleneck encoder (encoder.* = make_bottleneck_state_dict(seed, layers, with_fc=False) without its
+    heads): the decoder is drawn for a feature map of 512 channels."""
+    from .unet import ENC_CH
+    sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
+          if not k.startswith('fc')}
+    return _with_pspnet_decoder(sd, seed, classes, ENC_CH['bottleneck'])

@@ -2,12 +2,12 @@
 ``smp.Unet('resnet18', classes=C)`` (the reference's eval_tumorbed.py:21-28 and eval.py:22-27), driven by
 ``predict_wsis`` (utils/eval.py:51 ``model(batch_image)``) and ``predict_tumorbed(mode='seg')`` (:196-200
 ``model.decoder(model.encoder(batch_image))``).  The reference picks the model family by name (``eval('smp.' + args.model_name)``,
-``--model_name``) and the encoder by ``--arch_encoder``: this module serves 'Unet', 'Linknet' and 'FPN' on the encoders of `ENCODERS`, so
-``import wsi_segmentation_pipeline_amd.unet as smp`` keeps that line working.
+``--model_name``) and the encoder by ``--arch_encoder``: this module serves all four names the reference lists - 'Unet', 'Linknet', 'FPN'
+and 'PSPNet' - on the encoders of `ENCODERS`, so ``import wsi_segmentation_pipeline_amd.unet as smp`` keeps that line working.
 
 segmentation_models_pytorch is third-party, absent here and un-pinned in the reference, so the architectures and the
 state-dict key names are restated from its published 0.0.x source - **parity unpinned**; the numerical specs are
-oracle/unet_oracle.py, tests/linknet_oracle.py and tests/fpn_oracle.py (torch on the CPU) and the HIP path is held to them:
+oracle/unet_oracle.py, tests/linknet_oracle.py, tests/fpn_oracle.py and tests/pspnet_oracle.py (torch on the CPU) and the HIP path is held to them:
   encoder  a ResNet of `ENCODERS` (torchvision key names ``encoder.layerL.B.*``); forward returns [x4, x3, x2, x1, x0] (deepest first):
            x1..x4 = the LAST block of layer1..4, x0 = relu(bn1(conv1(x))) at half resolution, with `ENC_CH` channels: the same for
            every depth of a block type, so a decoder depends on the block type only
@@ -24,12 +24,20 @@ oracle/unet_oracle.py, tests/linknet_oracle.py and tests/fpn_oracle.py (torch on
              GroupNorm(32), ReLU, and a bilinear x2 upsample with align_corners=True per unit of s5 / s4 / s3), the sum of the four
              branches at 1/4 resolution, Dropout2d, ``decoder.final_conv`` and a bilinear x4 upsample.  x0 is never read.  All four
              encoders, 'parity' and 'speed' only
+    PSPNet   other keys (`pspnet_decoder`): it reads ONE map, f = x2 at 1/8 resolution (psp_in_factor 8) with C = 128 or 512 channels.
+             ``decoder.psp.stages.I.pool.1.block`` for the pool sizes S = (1, 2, 3, 6): AdaptiveAvgPool2d((S, S)), 1x1 conv C -> C / 4
+             (I = 0: with bias, no BatchNorm, keys ``block.0.{weight,bias}``; I = 1..3: no bias, BatchNorm ``block.1.*``), ReLU, bilinear
+             resize back to f's size with align_corners=True; ``decoder.conv.block`` = 1x1 conv 2C -> 512 + BatchNorm + ReLU on
+             ``cat([stage0, ..., stage3, f], 1)``; Dropout2d; ``decoder.final_conv`` = 3x3 conv 512 -> classes with bias; bilinear x8
+             with align_corners=True.  28 decoder keys (2 + 3 x 6 + 6 + 2).  On the device the concatenation is never made (`pspnet_fold`): the fusing conv
+             runs on f alone, and the stages' share is computed on the 50 pooled pixels and expanded; the encoder stops after layer 2
+             unless the five maps are asked for.  All four encoders, 'parity' and 'speed' only
 
-What a decoder consists of is written once, as a `Decoder` description (`unet_decoder`, `linknet_decoder`, `fpn_decoder`): its convs in
+What a decoder consists of is written once, as a `Decoder` description (`unet_decoder`, `linknet_decoder`, `fpn_decoder`, `pspnet_decoder`): its convs in
 state-dict order with real and stored widths and what follows each (BatchNorm, GroupNorm or a bias).  The key lists (`decoder_key_shapes`,
-`linknet_decoder_key_shapes`, `fpn_decoder_key_shapes`), the packing of the device
+`linknet_decoder_key_shapes`, `fpn_decoder_key_shapes`, `pspnet_decoder_key_shapes`), the packing of the device
 weights (`pack_decoder`, host work only) and the layers of the ``nn.Module`` decoders are read from it.
-Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/fpn.hip, csrc/tail.hip behind one entry prefix per model and
+Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/fpn.hip, csrc/pspnet.hip, csrc/tail.hip behind one entry prefix per model and
 encoder block type); training mode uses torch ops so ``train.py``-style callers still run.
 """
 import collections
@@ -80,11 +88,13 @@ def equal_batches(n, cap):
 # bias}``: its statistics come from the data, so it stays a separate device op) or 'bias' (nothing but the conv's own bias: the conv is
 # ``<prefix>.{weight,bias}`` itself).
 Conv = collections.namedtuple('Conv', 'prefix kind real stored place norm', defaults=('bn',))
-KINDS = {'conv3': ('conv', 3), 'conv1': ('conv', 1), 'tconv': ('tconv', 4)}      # -> (kind in the key lists, kernel size); tconv = 4x4 stride 2
+# -> (kind in the key lists, kernel size); tconv = 4x4 stride 2; lin1 = a 1x1 conv the device keeps as a plain fp32 matrix (never packed)
+KINDS = {'conv3': ('conv', 3), 'conv1': ('conv', 1), 'tconv': ('tconv', 4), 'lin1': ('conv', 1)}
 # The last block + head as one kernel on the block's REAL channels, in parity mode up to 4 classes: the prepack entry (its size is
 # ``<entry>_bytes()``), the prefixes of the block's convs and the dimension arguments between the head and `classes`.
 Tail = collections.namedtuple('Tail', 'entry prefixes dims')
-# A decoder: its Conv rows in state-dict order (slot i of the C struct = row i), the head's input width, its Tail and its C struct.
+# A decoder: its Conv rows in state-dict order (slot i of the C struct = row i), the input width of its 1x1 head ``decoder.final_conv``
+# (None: the last row IS the head), its Tail and its C struct.
 Decoder = collections.namedtuple('Decoder', 'rows head_cin tail weights')
 BN_IDENTITY = (1.0, 0.0, 0.0, 1.0)               # BN_KEYS of a padding channel: scale ~1, shift 0 -> relu(0) = 0
 
@@ -141,6 +151,55 @@ def fpn_decoder(enc_ch=ENC_CH['basic']):
     return Decoder(rows, FPN_SEG_CH, None, native.WsiFpnDecoderWeights)
 
 
+PSP_SIZES, PSP_OUT_CH, PSP_BINS = (1, 2, 3, 6), 512, 50                    # smp's PSPNet defaults; 50 = 1 + 4 + 9 + 36 pooled pixels per image
+
+
+def pspnet_decoder(enc_ch=ENC_CH['basic'], planes=PARITY, classes=1):
+    """The PSPNet decoder on an encoder whose map x2 = enc[2] has C = `enc_ch`[2] channels (the other four maps are never read): the four
+    stage convs C -> C / 4 (kind 'lin1': plain fp32 matrices on the device, stage 0 with a bias and no BatchNorm), the fusing 1x1 conv
+    2C -> 512 + BatchNorm, of which the device stores the LAST C input columns only (the feature map's; the stages' columns are folded
+    into the projection matrices, `pspnet_fold`), and the 3x3 head 512 -> classes with bias, stored with its output channels zero-padded
+    to one line (64 in speed mode, 32 otherwise)."""
+    c, line = enc_ch[2], 64 if planes == SPEED else 32
+    rows = [Conv('decoder.psp.stages.0.pool.1.block.0', 'lin1', (c // 4, c), (c // 4, c), [(0, c, 0)], 'bias')]
+    rows += [Conv('decoder.psp.stages.%d.pool.1.block' % i, 'lin1', (c // 4, c), (c // 4, c), [(0, c, 0)]) for i in (1, 2, 3)]
+    rows.append(Conv('decoder.conv.block', 'conv1', (PSP_OUT_CH, 2 * c), (PSP_OUT_CH, c), [(c, 2 * c, 0)]))
+    rows.append(Conv('decoder.final_conv', 'conv3', (classes, PSP_OUT_CH), (line, PSP_OUT_CH), [(0, PSP_OUT_CH, 0)], 'bias'))
+    return Decoder(rows, None, None, native.WsiPspnetDecoderWeights)
+
+
+def pspnet_fold(state_dict, c):
+    """The pyramid term of the PSPNet decoder as the device computes it, folded in float64 on the host.  The fusing 1x1 conv and the
+    bilinear resize are linear, so with a = its BatchNorm's scale gamma / sqrt(var + eps) and W its (512, 2C) weight
+        bn(conv(cat(up(s0..s3), f))) = (a W[:, C:]) f + shift + sum_I up((a W[:, I C/4:(I+1) C/4]) s_I),   s_I = relu(stage_I(pool_I(f))).
+    Returns float64 arrays: stage_w [4] (C/4, C) with the stage's BatchNorm scale folded in, stage_b [4] (C/4,) (stage 0: the conv's bias;
+    1-3: the BatchNorm shift), proj_w [4] = the W_I (512, C/4), wf (512, C) and shift (512,).  The device takes stage_w and proj_w
+    transposed, in fp32; wf reaches it through the conv packer instead (row 4 of `pspnet_decoder`), which folds the same BatchNorm."""
+    def f64(key):
+        return torch.as_tensor(state_dict[key]).detach().cpu().double().numpy()
+
+    def fold(prefix):
+        g, b, m, v = (f64('%s.%s' % (prefix, k)) for k in BN_KEYS)
+        scale = g / np.sqrt(v + BN_EPS)
+        return scale, b - m * scale
+
+    stage_w, stage_b = [], []
+    for i in range(4):
+        pre = 'decoder.psp.stages.%d.pool.1.block' % i
+        w = f64(pre + '.0.weight').reshape(c // 4, c)
+        if i == 0:
+            stage_w.append(w)
+            stage_b.append(f64(pre + '.0.bias'))
+        else:
+            scale, shift = fold(pre + '.1')
+            stage_w.append(w * scale[:, None])
+            stage_b.append(shift)
+    scale, shift = fold('decoder.conv.block.1')
+    w = f64('decoder.conv.block.0.weight').reshape(PSP_OUT_CH, 2 * c) * scale[:, None]
+    proj_w = [w[:, i * (c // 4):(i + 1) * (c // 4)] for i in range(4)]
+    return {'stage_w': stage_w, 'stage_b': stage_b, 'proj_w': proj_w, 'wf': w[:, c:], 'shift': shift}
+
+
 def _key_shapes(dec, classes):
     out = []
     for r in dec.rows:
@@ -154,8 +213,9 @@ def _key_shapes(dec, classes):
             continue
         out += [('%s.1.%s' % (r.prefix, s), (cout,), bn_kind) for s, bn_kind in zip(BN_KEYS, ('bn_w', 'bn_b', 'bn_m', 'bn_v'))]
         out.append((r.prefix + '.1.num_batches_tracked', (), 'bn_n'))
-    out.append(('decoder.final_conv.weight', (classes, dec.head_cin, 1, 1), 'conv'))
-    out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
+    if dec.head_cin is not None:
+        out.append(('decoder.final_conv.weight', (classes, dec.head_cin, 1, 1), 'conv'))
+        out.append(('decoder.final_conv.bias', (classes,), 'lin_b'))
     return out
 
 
@@ -169,6 +229,11 @@ def linknet_decoder_key_shapes(classes):
     return _key_shapes(linknet_decoder(), classes)
 
 
+def pspnet_decoder_key_shapes(classes, enc_ch=ENC_CH['basic']):
+    """[(key, shape, kind)] of the PSPNet decoder in state-dict order: 28 keys (stage 0: 2, stages 1-3: 6 each, the fusing conv: 6, the head: 2)."""
+    return _key_shapes(pspnet_decoder(enc_ch, classes=classes), classes)
+
+
 def fpn_decoder_key_shapes(classes, enc_ch=ENC_CH['basic']):
     """[(key, shape, kind)] of the FPN decoder in state-dict order: 31 keys.  kind 'lin_b' = a conv's bias, 'bn_w' / 'bn_b' = a GroupNorm's
     weight / bias."""
@@ -180,20 +245,27 @@ PackedDecoder = collections.namedtuple('PackedDecoder', 'convs cin cout head_w h
 
 def pack_decoder(lib, state_dict, dec, planes, classes):
     """The device weights of decoder `dec` from the ``decoder.*`` keys, as numpy arrays (host work only): convs = [(packed, bias)] per
-    row, the stored cin / cout tables, the head's (classes, head_cin) weight and its bias, the fused tail's blob or None, and gn =
-    [(weight, bias)] of the rows that a GroupNorm follows.  A row without BatchNorm is packed with scale 1; its bias array is the conv's
-    own bias (zeros where it has none)."""
+    row, the stored cin / cout tables, the head's (classes, head_cin) weight and its bias (None where the last row is the head), the fused
+    tail's blob or None, and gn = [(weight, bias)] of the rows that a GroupNorm follows.  A row without BatchNorm is packed with scale 1;
+    its bias array is the conv's own bias (zeros where it has none).  A bias-only row may be stored wider than it is: the padding holds
+    zero weights and a zero bias (a GroupNorm's statistics would see such padding, so a 'gn' row may not)."""
     convs, gn = [], []
     for r in dec.rows:
         (kind, k), (cout, cin), (cout_s, cin_s) = KINDS[r.kind], r.real, r.stored
         tconv = kind == 'tconv'
         if r.norm != 'bn':
-            if r.real != r.stored:
-                raise ValueError('row %s: a conv without BatchNorm is stored at its real width' % r.prefix)
+            if r.real != r.stored and (r.norm != 'bias' or tconv):
+                raise ValueError('row %s: a conv followed by a GroupNorm is stored at its real width' % r.prefix)
             w = _f32(state_dict, r.prefix + ('.weight' if r.norm == 'bias' else '.0.weight'))
+            if r.real != r.stored:
+                wp = np.zeros((cout_s, cin_s, k, k), np.float32)
+                for lo, hi, at in r.place:
+                    wp[:cout, at:at + hi - lo] = w[:, lo:hi]
+                w = wp
             pk, bias = pack_conv(lib, w, None, planes, tconv)
             if r.norm == 'bias':
-                bias = _f32(state_dict, r.prefix + '.bias')
+                bias = np.zeros(cout_s, np.float32)
+                bias[:cout] = _f32(state_dict, r.prefix + '.bias')
             else:
                 gn.append((_f32(state_dict, r.prefix + '.1.weight'), _f32(state_dict, r.prefix + '.1.bias')))
             convs.append((pk, bias))
@@ -209,8 +281,10 @@ def pack_decoder(lib, state_dict, dec, planes, classes):
             padded[:cout] = a
             bn.append(padded)
         convs.append(pack_conv(lib, wp, bn, planes, tconv))
-    head_w = np.ascontiguousarray(_f32(state_dict, 'decoder.final_conv.weight').reshape(classes, dec.head_cin))
-    head_b = _f32(state_dict, 'decoder.final_conv.bias')
+    head_w = head_b = None
+    if dec.head_cin is not None:
+        head_w = np.ascontiguousarray(_f32(state_dict, 'decoder.final_conv.weight').reshape(classes, dec.head_cin))
+        head_b = _f32(state_dict, 'decoder.final_conv.bias')
     tail = None
     if dec.tail is not None and planes == PARITY and classes <= 4:
         args =[a for p in dec.tail.prefixes for a in [_f32(state_dict, p + '.0.weight')] + _bn(state_dict, p + '.1')]
@@ -401,6 +475,54 @@ class FPNEngine(UNetEngine):
         dw.head_w, dw.head_b, dw.classes = dev(pk.head_w), dev(pk.head_b), self.classes
 
 
+class PSPNetEngine(UNetEngine):
+    """ResNet encoder (either block type) + PSPNet decoder on HIP kernels (wsi_pspnet_* / wsi_pspnet_bneck_*; csrc/pspnet.hip for the
+    pyramid pool, the stage projection, the pyramid expand and the head's x8 upsample, the existing conv kernels for the fusing 1x1 conv
+    and the 3x3 head): the surface of UNetEngine.  The decoder reads x2 only, so a forward that returns logits alone stops the encoder
+    after layer 2; with enc=True the whole encoder runs.  Precision 'parity' or 'speed'."""
+
+    ENTRY = {'basic': 'wsi_pspnet', 'bottleneck': 'wsi_pspnet_bneck'}
+
+    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
+        if planes not in (PARITY, SPEED):
+            raise ValueError("a PSPNet runs in precision 'parity' or 'speed': there is no mx mode")
+        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+
+    def _describe(self):
+        return pspnet_decoder(self.enc_ch, self.planes, self.classes)
+
+    def _pack_decoder(self, state_dict):
+        dec = self._describe()
+        convs = dec._replace(rows=dec.rows[4:])                # the two rows the conv kernels run: the fusing conv's feature columns, the head
+        pk = pack_decoder(self.lib, state_dict, convs, self.planes, self.classes)
+        fold = pspnet_fold(state_dict, self.enc_ch[2])
+
+        def dev(a):
+            self._keep.append(torch.from_numpy(np.ascontiguousarray(a, dtype=a.dtype if a.dtype == np.uint8 else np.float32)).to(self.device))
+            return self._keep[-1].data_ptr()
+
+        dw = self.dw = dec.weights()
+        for i, (w, bias) in enumerate(pk.convs):
+            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
+            dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
+        for i in range(4):                                     # the device walks k with consecutive outputs side by side: [in][out]
+            dw.stage_w[i], dw.stage_b[i], dw.proj_w[i] = dev(fold['stage_w'][i].T), dev(fold['stage_b'][i]), dev(fold['proj_w'][i].T)
+        dw.classes, dw.feat_c = self.classes, self.enc_ch[2]
+
+    def decode(self, enc):
+        """`model.decoder(encoding)`: the decoder reads enc[2] (x2 at 1/8 resolution) only; the other four entries may be None."""
+        f = enc[2]
+        _require_gpu(f, 'encoder map')
+        f = f.to(torch.float32).contiguous()
+        n, h, w = f.shape[0], f.shape[2] * 8, f.shape[3] * 8
+        ws, cap = self._workspace(n, h, w)
+        logits = torch.empty((n, self.classes, h, w), dtype=torch.float32, device=self.device)
+        ptrs = (C.c_void_p * 5)(None, None, f.data_ptr(), None, None)
+        native.check(self._decoder(C.byref(self.dw), C.byref(ptrs), n, h, w, self.planes, _ptr(ws), cap, _ptr(logits), _stream()),
+                     self._decoder.__name__)
+        return logits
+
+
 class LinknetEngine(UNetEngine):
     """BasicBlock ResNet encoder + Linknet decoder on HIP kernels (wsi_linknet_*; csrc/linknet.hip): the surface of UNetEngine -
     forward_f32, forward_tiles, decode, release_workspaces - with the batch sized by the Linknet workspace (~70 MB per 256 x 256 tile in
@@ -554,6 +676,48 @@ class FPNDecoder(nn.Module):
         return F.interpolate(x, scale_factor=4, mode='bilinear', align_corners=True)
 
 
+class _PSPStage(nn.Module):
+    """``.pool`` = Sequential(AdaptiveAvgPool2d(S), module with ``.block`` = Sequential(1x1 conv[, BatchNorm2d], ReLU)) of one 'lin1' row:
+    the keys ``pool.1.block.0.weight`` and, without BatchNorm (pool size 1), ``pool.1.block.0.bias``, else ``pool.1.block.1.*``."""
+
+    def __init__(self, row, size):
+        super().__init__()
+        cout, cin = row.real
+        bn = row.norm == 'bn'
+        unit = nn.Module()
+        unit.block = nn.Sequential(*([nn.Conv2d(cin, cout, 1, bias=not bn)] + ([nn.BatchNorm2d(cout)] if bn else []) + [nn.ReLU(inplace=True)]))
+        self.pool = nn.Sequential(nn.AdaptiveAvgPool2d((size, size)), unit)
+
+    def forward(self, x):
+        y = self.pool[1].block(self.pool[0](x))
+        return F.interpolate(y, size=x.shape[2:], mode='bilinear', align_corners=True)
+
+
+class PSPNetDecoder(nn.Module):
+    """``psp.stages.0-3``, ``conv``, ``dropout`` (no keys) and ``final_conv`` of `pspnet_decoder`.  Eval mode hands the 1/8-resolution map
+    to the owner's HIP engine; training mode runs torch ops, in the literal form: concatenate, then fuse."""
+
+    def __init__(self, classes, owner=None, enc_ch=ENC_CH['basic'], dropout=0.2):
+        super().__init__()
+        rows = pspnet_decoder(enc_ch, classes=classes).rows
+        self.psp = nn.Module()
+        self.psp.stages = nn.ModuleList([_PSPStage(row, size) for row, size in zip(rows[:4], PSP_SIZES)])
+        cout, cin = rows[4].real
+        self.conv = nn.Module()
+        self.conv.block = nn.Sequential(nn.Conv2d(cin, cout, 1, bias=False), nn.BatchNorm2d(cout), nn.ReLU(inplace=True))
+        self.dropout = nn.Dropout2d(dropout)
+        self.final_conv = nn.Conv2d(cout, classes, 3, padding=1)
+        self._owner = [owner]                                  # list: not registered as a sub-module
+
+    def forward(self, enc):
+        f = enc[2]
+        if not self.training:
+            return self._owner[0].hip_engine(f.device).decode(list(enc))
+        x = self.conv.block(torch.cat([stage(f) for stage in self.psp.stages] + [f], 1))
+        x = self.final_conv(self.dropout(x))
+        return F.interpolate(x, scale_factor=8, mode='bilinear', align_corners=True)
+
+
 class UNetEncoder(nn.Module):
     """ResNet-18 / ResNet-34 trunk with the smp encoder surface: forward(x) -> [x4, x3, x2, x1, x0]; ``out_shapes``."""
 
@@ -667,11 +831,9 @@ class LinknetSeg(UNetSeg):
         return LinknetDecoder(classes, self)
 
 
-class FPNSeg(UNetSeg):
-    """Drop-in for ``smp.FPN(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of UNetSeg,
-    so every caller that takes a UNetSeg - utils.eval's fused tile path, multi-rank stitching - takes it too.  Precision 'parity' or 'speed'."""
+class _DropoutSeg(UNetSeg):
+    """A UNetSeg whose decoder has a Dropout2d in front of its head (smp's FPN and PSPNet): `dropout` in [0, 1), 'parity' or 'speed'."""
     PRECISIONS = ('parity', 'speed')
-    ENGINE = FPNEngine
 
     def __init__(self, classes=4, precision='parity', encoder='resnet18', dropout=0.2):
         if not 0.0 <= float(dropout) < 1.0:
@@ -679,12 +841,35 @@ class FPNSeg(UNetSeg):
         object.__setattr__(self, '_dropout_p', float(dropout))           # (read by _make_decoder, which the base constructor calls)
         super().__init__(classes, precision, encoder)
 
+
+class FPNSeg(_DropoutSeg):
+    """Drop-in for ``smp.FPN(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of UNetSeg,
+    so every caller that takes a UNetSeg - utils.eval's fused tile path, multi-rank stitching - takes it too.  Precision 'parity' or 'speed'."""
+    ENGINE = FPNEngine
+
     def _make_decoder(self, classes):
         return FPNDecoder(classes, self, self.encoder.out_shapes, self._dropout_p)
 
 
 class FPNSegBottleneck(FPNSeg):
     """``smp.FPN('resnet50' | 'resnet101', classes=C, activation=None)``: FPNSeg on a Bottleneck encoder."""
+    ENCODER = UNetBottleneckEncoder
+
+    def __init__(self, classes=4, precision='parity', encoder='resnet50', dropout=0.2):
+        super().__init__(classes, precision, encoder, dropout)
+
+
+class PSPNetSeg(_DropoutSeg):
+    """Drop-in for ``smp.PSPNet(encoder, classes=C, activation=None)`` with encoder 'resnet18' (default) or 'resnet34': the surface of UNetSeg,
+    so every caller that takes a UNetSeg - utils.eval's fused tile path, multi-rank stitching - takes it too.  Precision 'parity' or 'speed'."""
+    ENGINE = PSPNetEngine
+
+    def _make_decoder(self, classes):
+        return PSPNetDecoder(classes, self, self.encoder.out_shapes, self._dropout_p)
+
+
+class PSPNetSegBottleneck(PSPNetSeg):
+    """``smp.PSPNet('resnet50' | 'resnet101', classes=C, activation=None)``: PSPNetSeg on a Bottleneck encoder."""
     ENCODER = UNetBottleneckEncoder
 
     def __init__(self, classes=4, precision='parity', encoder='resnet50', dropout=0.2):
@@ -731,3 +916,20 @@ def FPN(encoder_name='resnet34', encoder_weights=None, decoder_pyramid_channels=
             raise ValueError('%s must be %d (got %r): the FPN kernels are built for smp\'s default decoder' % (name, want, got))
     arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
     return {'basic': FPNSeg, 'bottleneck': FPNSegBottleneck}[arch](classes, precision, encoder_name, dropout)
+
+
+def PSPNet(encoder_name='resnet34', encoder_weights=None, psp_in_factor=8, psp_out_channels=512, psp_use_batchnorm=True, psp_aux_output=False,
+           classes=21, dropout=0.2, activation=None, precision='parity'):
+    """smp's factory signature for the PSPNet, so the reference's ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None,
+    classes=C, activation=None)`` serves 'PSPNet' on all four encoders: PSPNetSeg for 'resnet18' / 'resnet34', PSPNetSegBottleneck for
+    'resnet50' / 'resnet101'.  Refusals as `Unet`.  `activation` defaults to None, not smp's 'softmax': smp applies it in its own
+    ``predict`` only, which this module does not have, and the reference always passes None.  The four ``psp_*`` arguments are accepted at
+    smp's defaults only (the kernels are built for them; `psp_aux_output` would add a training-time branch and its keys); `dropout` in
+    [0, 1) (it acts in training mode only)."""
+    _factory_refusals(encoder_weights, activation)
+    for name, got, want in (('psp_in_factor', psp_in_factor, 8), ('psp_out_channels', psp_out_channels, PSP_OUT_CH),
+                            ('psp_use_batchnorm', psp_use_batchnorm, True), ('psp_aux_output', psp_aux_output, False)):
+        if got != want or type(got) is not type(want):
+            raise ValueError('%s must be %r (got %r): the PSPNet kernels are built for smp\'s default decoder' % (name, want, got))
+    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
+    return {'basic': PSPNetSeg, 'bottleneck': PSPNetSegBottleneck}[arch](classes, precision, encoder_name, dropout)
