@@ -78,6 +78,8 @@ def test_factory_refusals_and_model_name_switch():
     with pytest.raises(ValueError, match='encoder_name'):
         smp.FPN('vgg16')
     assert smp.FPN('resnet18', precision='speed', dropout=0.0).decoder.dropout.p == 0.0
+    # the fixed arguments are compared by value: smp's defaults in another number type pass
+    assert type(smp.FPN('resnet18', decoder_pyramid_channels=256.0, decoder_segmentation_channels=128.0, final_upsampling=np.int64(4))) is smp.FPNSeg
 
 
 @pytest.mark.parametrize('name,make', [('resnet18', lambda: W.make_fpn_state_dict(31, R18, 4)),

@@ -3,30 +3,22 @@ bilinear upsamples and the merge + head, the existing conv kernels for the rest;
 tests/fpn_oracle.py: GroupNorm + ReLU with and without the x2 upsample, the merge + head + x4, the lateral path, the whole model under the
 project's ABSOLUTE 1e-3 contract at max |logit| 16, the launches one forward makes, the u8 slide path, speed mode, the module surface and
 predict_tumorbed(mode='seg') with the model the smp-signature factory returns."""
-import ctypes as C
 import json
 import os
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import fpn_oracle as FO
+import seg_model_checks as M
 from oracle import resnet_oracle as R
-from oracle import wsi_oracle as WO
+from seg_model_checks import LOGIT_TOL, NEAR_TIE, SPEED_TOL, TAP_TOL, TOL_PARITY, TOL_SPEED, U8_TOL
 from wsi_segmentation_pipeline_amd import synthetic as W
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R18, R34, R50, B1 = [2, 2, 2, 2], [3, 4, 6, 3], [3, 4, 6, 3], [1, 1, 1, 1]
-TOL_PARITY = 2e-5         # tests/test_gpu_kernels.py: one op, relative to the tensor's maximum, fp16 hi + lo pair
-TOL_SPEED = 3e-2          # ... single-pass bf16
-LOGIT_TOL = 1e-3          # BASELINE.json north_star: absolute, on logits of magnitude 16
-TAP_TOL = {'basic': 7e-6, 'bottleneck': 2e-4}   # tests/test_gpu_resnet34.py TAP_TOL[2] / tests/test_gpu_resnet50.py TAP_TOL: encoder maps, relative to the map's maximum
-U8_TOL = 2e-5             # tests/test_gpu_unet_bottleneck.py: u8 slide path against the f32 path, times the f32 path's maximum
-SPEED_TOL = 0.1           # ... speed mode: finite and within 0.1 of the maximum
-NEAR_TIE = 0.0005         # arg-max flips are asserted only where at most this share of the spec's pixels has a top-two margin < 2 LOGIT_TOL
 # Measured on an MI355X (profiles/fpn_parity.json); the bounds above are the project's own, set before and not derived from these.
 GN_MEASURED = {'1x128x1x1 up2 planes 2': 3.416e-07, '1x128x1x1 up2 planes 1': 2.220e-03, '1x128x1x1 planes 2': 3.416e-07,
                '1x128x1x1 planes 1': 2.220e-03, '1x128x1x2 up2 planes 2': 4.521e-07, '1x128x1x2 up2 planes 1': 2.557e-03,
@@ -73,10 +65,6 @@ def sd():
     return W.make_fpn_state_dict(31, R18, 4)
 
 
-def _rel(got, ref):
-    return float((got.double().cpu() - ref).abs().max() / ref.abs().max())
-
-
 @pytest.mark.parametrize('up2', [1, 0], ids=['up2', 'plain'])
 @pytest.mark.parametrize('name,shape,offset', GN_CASES, ids=[c[0] for c in GN_CASES])
 def test_groupnorm_relu_matches_float64(dev, name, shape, offset, up2):
@@ -100,7 +88,7 @@ def test_groupnorm_relu_matches_float64(dev, name, shape, offset, up2):
                                   n, c, k * h, k * w, planes)
         got = run()
         assert torch.equal(got, run())                                               # a fixed summation order: the same bits every run
-        errs[planes] = _rel(got, ref)
+        errs[planes] = M.rel(got, ref)
         print('groupnorm + relu%s %s planes %d: rel err to max %.3e (bound %.0e)' % (' + up2' if up2 else '', name, planes, errs[planes], tol))
     assert errs[2] <= TOL_PARITY and errs.get(1, 0.0) <= TOL_SPEED
 
@@ -119,8 +107,8 @@ def test_merge_head_up4_matches_float64(dev, name, shape, classes):
     for planes, tol in ((2, TOL_PARITY), (1, TOL_SPEED)):
         got, q = E.fpn_merge_head_up4([E.pf_pack(m.to(dev), planes) for m in maps], hw_.to(dev), hb.to(dev), n, h, w, planes, with_quarter=True)
         assert got.shape == ref.shape == (n, classes, 4 * h, 4 * w)
-        errs[planes] = _rel(got, ref)
-        print('merge + head + x4 %s planes %d: rel err to max %.3e (bound %.0e), quarter map %.3e' % (name, planes, errs[planes], tol, _rel(q, refq)))
+        errs[planes] = M.rel(got, ref)
+        print('merge + head + x4 %s planes %d: rel err to max %.3e (bound %.0e), quarter map %.3e' % (name, planes, errs[planes], tol, M.rel(q, refq)))
         assert torch.equal(got[:, :, 0, 0], q[:, :, 0, 0])
         scale = float(q.abs().max())
         for (yo, xo), (yq, xq) in (((0, -1), (0, -1)), ((-1, 0), (-1, 0)), ((-1, -1), (-1, -1))):
@@ -146,7 +134,7 @@ def test_lateral_path_matches_float64(dev, name, n, cin, h, w):
         assert not zero.any()
         up = E.upsample2_nearest(E.pf_pack(p.to(dev), planes), n, h // 2, w // 2, 256, planes)
         out = E.conv1x1_bn_act(E.pf_pack(ck.to(dev), planes), n, h, w, cin, 256, wpk, b.to(dev), resid_pf=up, relu=False, planes=planes)
-        errs[planes] = _rel(E.pf_unpack(out, n, 256, h, w, planes), ref)
+        errs[planes] = M.rel(E.pf_unpack(out, n, 256, h, w, planes), ref)
         print('lateral %s planes %d: rel err to max %.3e (bound %.0e)' % (name, planes, errs[planes], tol))
         alone = E.conv1x1_bn_act(E.pf_zeros(n, cin, h, w, planes, dev), n, h, w, cin, 256, wpk, b.to(dev), relu=False, planes=planes)
         only_b = E.pf_unpack(alone, n, 256, h, w, planes).cpu()
@@ -158,25 +146,6 @@ def _checkpoint(arch, layers):
     return W.make_fpn_bottleneck_state_dict(31, layers, 4) if arch == 'bottleneck' else W.make_fpn_state_dict(31, layers, 4)
 
 
-def _scaled_to_logit(sd, x, target=16.0):
-    """final_conv scaled until the spec's max |logit| on these inputs is `target` (tests/test_gpu_linknet.py).  Returns (state dict,
-    float64 spec logits, fp32 spec encoder maps, every decoder map)."""
-    with torch.no_grad():
-        ref, enc = FO.forward(sd, x)
-    s = target / float(ref.abs().max())
-    sd = dict(sd)
-    for key in ('decoder.final_conv.weight', 'decoder.final_conv.bias'):
-        sd[key] = sd[key] * s
-    maps = []
-    with torch.no_grad():
-        return sd, FO.decoder(sd, enc, maps=maps), enc, maps
-
-
-def _near_tie_share(ref):
-    top = ref.topk(2, 1).values
-    return float(((top[:, 0] - top[:, 1]) < 2 * LOGIT_TOL).double().mean())
-
-
 @pytest.mark.parametrize('name,arch,layers,shape', LOGIT_CASES, ids=[c[0] for c in LOGIT_CASES])
 def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     """Whole forward, and model.decoder(model.encoder(x)) through fp32 NCHW maps, against the float64 spec at max |logit| 16.  No seeded
@@ -185,7 +154,7 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     from wsi_segmentation_pipeline_amd.unet import FPNEngine
     n, h, w = shape
     x = R.normalize_u8(W.make_u8_patches(41 + h + w, (n, 3, h, w)))
-    sd, ref, ref_enc, maps = _scaled_to_logit(_checkpoint(arch, layers), x)
+    sd, ref, ref_enc, maps = M.scaled_to_logit(FO, _checkpoint(arch, layers), x)
     assert abs(float(ref.abs().max()) - 16.0) < 1e-3
     assert max(float(t.abs().max()) for t in list(ref_enc) + maps) < 6e4             # inside the fp16 range of the line format
     eng = FPNEngine(sd, dev, planes=2)
@@ -196,7 +165,7 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     err, err2 = float((got.cpu().double() - ref).abs().max()), float((two.cpu().double() - ref).abs().max())
     d12 = float((two - got).abs().max())
     enc_err = [float((a.cpu() - b).abs().max() / b.abs().max()) for a, b in zip(enc, ref_enc)]
-    flips, share = float((got.cpu().argmax(1) != ref.argmax(1)).float().mean()), _near_tie_share(ref)
+    flips, share = float((got.cpu().argmax(1) != ref.argmax(1)).float().mean()), M.near_tie_share(ref)
     print('fpn %s parity: max |logit - spec| %.3e (decoder(encoder(x)): %.3e, between the two %.3e) ABSOLUTE at max |logit| 16; '
           'encoder maps rel err %s; arg-max flips %.5f, near-tie share %.5f' % (name, err, err2, d12, ['%.2e' % e for e in enc_err], flips, share))
     assert max(enc_err) <= TAP_TOL[arch]
@@ -205,30 +174,17 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
         assert flips <= 0.002
 
 
-def _prof_kinds(lib, run, cap=256):
-    from wsi_segmentation_pipeline_amd import native
-    native.check(lib.wsi_prof_begin(cap), 'wsi_prof_begin')
-    try:
-        run()
-    finally:
-        ms, kind, fl = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
-        n = lib.wsi_prof_end(*[a.ctypes.data_as(C.c_void_p) for a in (ms, kind, fl)], cap)
-    assert 0 <= n < cap
-    return [(int(kind[i]), float(fl[i])) for i in range(n)]
-
-
 def test_routes_of_one_forward(dev, sd):
     """The profiler's records of one (3, 64, 64) forward: the trunk's, then - with no x0 glue (7) in between, the FPN never reads x0 - the
     pyramid [1x1 (12), then three times upsample (7) + 1x1 (12)], per seg unit [3x3 (6), statistics (15), apply (16)] seven times, and the
     merge + head (17) last.  No refused launch (9).  With enc=True the x0 record is back, in front of the pyramid."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import FPNEngine
-    lib = native.load()
     x = R.normalize_u8(W.make_u8_patches(43, (3, 3, 64, 64))).to(dev)
     eng = FPNEngine(sd, dev, planes=2)
     eng.forward_f32(x)                                                              # (plans the workspace outside the recording)
-    rec = _prof_kinds(lib, lambda: eng.forward_f32(x))
-    rec_enc = _prof_kinds(lib, lambda: eng.forward_f32(x, enc=True))
+    rec = native.profiled(lambda: eng.forward_f32(x))[1]
+    rec_enc = native.profiled(lambda: eng.forward_f32(x, enc=True))[1]
     kinds, kinds_enc = [k for k, _ in rec], [k for k, _ in rec_enc]
     print('prof kinds, fpn resnet18: %r; with enc=True %r' % (kinds, kinds_enc))
     first = kinds.index(12)
@@ -243,114 +199,29 @@ def test_routes_of_one_forward(dev, sd):
 def test_u8_slide_path_equals_f32_path(dev, sd):
     """forward_tiles on a 200 x 260 slide, four 64 x 64 tiles, one hanging over the edge, against forward_f32 of the gathered tiles."""
     from wsi_segmentation_pipeline_amd.unet import FPNEngine
-    rng = np.random.default_rng(7)
-    slide = rng.integers(0, 256, (200, 260, 3), dtype=np.uint8)
-    xy = np.array([[0, 0], [100, 50], [260 - 64, 200 - 64], [230, 170]], np.int32)
-    tiles = np.stack([WO.read_tile(slide, int(x), int(y), 64, 64) for x, y in xy]).transpose(0, 3, 1, 2)
-    x = R.normalize_u8(tiles)
-    sd16 = _scaled_to_logit(sd, x)[0]
-    eng = FPNEngine(sd16, dev, planes=2)
-    b = eng.forward_f32(x.to(dev))[0].clone()
-    a = eng.forward_tiles(torch.from_numpy(slide).to(dev), torch.from_numpy(xy).to(dev), 64, 64).clone()
-    scale, err = float(b.abs().max()), float((a - b).abs().max())
-    print('fpn u8 slide path vs f32 path: %.3e of scale %.3e (bound %.1e)' % (err, scale, U8_TOL * scale))
-    assert a.shape == b.shape == (4, 4, 64, 64)
-    assert err <= U8_TOL * scale
+    M.u8_slide_path_equals_f32_path(FPNEngine, FO, sd, dev)
 
 
 def test_speed_mode_is_sane(dev, sd):
-    """planes 1 (single-pass bf16): outside the contract; finite logits within 0.1 of the spec's maximum."""
+    """planes 1 (single-pass bf16): outside the contract; finite logits, and x4, within 0.1 of the spec's maximum."""
     from wsi_segmentation_pipeline_amd.unet import FPNEngine
-    x = R.normalize_u8(W.make_u8_patches(45, (3, 3, 64, 64)))
-    sd16, ref, ref_enc, _ = _scaled_to_logit(sd, x)
-    eng = FPNEngine(sd16, dev, planes=1)
-    got, enc = eng.forward_f32(x.to(dev), logits=True, enc=True)
-    err = float((got.cpu().double() - ref).abs().max() / ref.abs().max())
-    e4 = float((enc[0].cpu() - ref_enc[0]).abs().max() / ref_enc[0].abs().max())
-    print('fpn speed mode: logits rel err %.2e, x4 rel err %.2e' % (err, e4))
-    assert np.isfinite(err) and err <= SPEED_TOL and np.isfinite(e4) and e4 <= SPEED_TOL
+    M.speed_mode_is_sane(FPNEngine, FO, sd, dev, R.normalize_u8(W.make_u8_patches(45, (3, 3, 64, 64))), enc_index=0)
 
 
 def test_module_surface_and_mx_refusal(dev, sd):
     """model(x), model.encoder(x), model.decoder(encoding) in eval mode run on the engine; a CPU tensor is refused."""
     from wsi_segmentation_pipeline_amd import unet
-    model = unet.FPN('resnet18', encoder_weights=None, classes=4, activation=None)
-    model.load_state_dict(sd, strict=True)
-    model = model.cuda().eval()
-    x = R.normalize_u8(W.make_u8_patches(46, (2, 3, 64, 64)))
-    with torch.no_grad():
-        ref = FO.forward(sd, x)[0]
-        y = model(x.cuda())
-        enc = model.encoder(x.cuda())
-        y2 = model.decoder(enc)
-    assert isinstance(model.hip_engine(dev), unet.FPNEngine)
-    assert [tuple(t.shape[1:]) for t in enc] == [(512, 2, 2), (256, 4, 4), (128, 8, 8), (64, 16, 16), (64, 32, 32)]
-    scale = float(ref.abs().max())
-    assert float((y.cpu().double() - ref).abs().max()) <= 2e-4 * scale and float((y2.cpu().double() - ref).abs().max()) <= 4e-4 * scale
-    with pytest.raises(RuntimeError):
-        model(x)
-    with pytest.raises(ValueError, match='mx'):
-        unet.FPNEngine(sd, dev, planes=3)
+    M.module_surface_and_mx_refusal(unet.FPN, unet.FPNEngine, FO, sd, dev)
 
 
 def test_predict_tumorbed_seg_with_the_factory_model(dev, sd, tmp_path, monkeypatch):
     """predict_tumorbed(mode='seg') with unet.FPN('resnet18', classes=4) on the slide of tests/test_gpu_linknet.py: the fused tile path is
     the one taken (the FPN engine reads the tiles from the device-resident level), the class map and the heat map against the CPU chain
     (float64 spec -> float64 stitch -> threshold / heat map): heat pixels off by more than 1 LSB and class flips at most 0.002 each, where
-    at most NEAR_TIE of the spec's own tile pixels are near-ties."""
-    import myargs
-    import utils.dataset as ds
-    import utils.eval as val
+    at most NEAR_TIE of the spec's own tile pixels are near-ties (the slide seed was picked on the CPU so that the rule applies)."""
     from wsi_segmentation_pipeline_amd import unet
-    from wsi_segmentation_pipeline_amd.slide import ArraySlide
-    a = myargs.args
-    a.scan_level, a.scan_resize, a.num_classes, a.class_probs = 2, 1, 4, [0., 0., 0., 0.]
-    a.tile_w = a.tile_h = 64
-    a.tile_stride_w = a.tile_stride_h = 48
-    a.val_save_pth, a.wsi_mask_pth = str(tmp_path / 'out'), str(tmp_path / 'nomask')
-    rng = np.random.default_rng(13)
-    l2 = np.clip(np.kron(rng.integers(60, 250, (7, 9, 3)), np.ones((32, 32, 1))) + rng.integers(-25, 25, (224, 288, 3)), 0, 255).astype(np.uint8)
-    big = np.repeat(np.repeat(l2, 4, 0), 4, 1)
-    slide = ArraySlide([np.repeat(np.repeat(big, 4, 0), 4, 1)[:8, :8], big[:8, :8], l2], [1.0, 4.0, 16.0])   # only level 2 is read
-    slide.level_dimensions = ((288 * 16, 224 * 16), (288 * 4, 224 * 4), (288, 224))
-    slide.name = 'seg.svs'
     model = unet.FPN('resnet18', encoder_weights=None, classes=4, activation=None)
-    model.load_state_dict(sd)
-    model = model.cuda().eval()
-    model.classifier, model.regressor = torch.nn.Identity(), torch.nn.Identity()
-    calls = {'tiles': 0, 'f32': 0}
-    real_tiles, real_f32 = unet.UNetEngine.forward_tiles, unet.UNetEngine.forward_f32
-
-    def forward_tiles(self, *args, **kw):
-        assert type(self) is unet.FPNEngine
-        calls['tiles'] += int(args[1].shape[0])
-        return real_tiles(self, *args, **kw)
-
-    def forward_f32(self, *args, **kw):
-        calls['f32'] += 1
-        return real_f32(self, *args, **kw)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_tiles', forward_tiles)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_f32', forward_f32)
-    params = {'ph': 64, 'pw': 64, 'sh': 48, 'sw': 48}
-    dataset = ds.Dataset_wsis({'seg.svs': slide}, params, bs=5)
-    tiles = dataset.wsis['seg.svs']['iterator'].dataset.datalist
-    mask = dataset.wsis['seg.svs']['mask']
-    assert len(tiles) >= 12
-    res = val.predict_tumorbed(model, dataset, 1, mode='seg')['seg.svs']
-    assert calls == {'tiles': len(tiles), 'f32': 0}
-    u8 = np.stack([WO.read_tile(l2, x, y, 64, 64) for x, y in tiles]).transpose(0, 3, 1, 2)
-    with torch.no_grad():
-        tp = FO.forward(sd, R.normalize_u8(u8))[0]
-    share = _near_tie_share(tp)
-    pred = WO.stitch_tumorbed(tiles, tp.numpy(), 4, l2.shape[:2], 1.0, 64, 64)
-    ref_cls, ref_probs = WO.threshold_probs(pred)
-    ref_heat = WO.tumorbed_heatmap(ref_probs, mask, 'seg')
-    flips = float((res['classes'] != ref_cls).mean())
-    dheat = np.abs(res['heatmap'].astype(int) - ref_heat.astype(int))
-    print('fpn predict_tumorbed seg: class flips %.5f, heat pixels off by > 1: %d of %d; near-tie share of the spec tiles %.5f'
-          % (flips, int((dheat > 1).sum()), dheat.size, share))
-    assert share <= NEAR_TIE                                                         # (the slide seed was picked on the CPU so that the rule applies)
-    assert flips <= 0.002 and (dheat > 1).mean() <= 0.002
+    M.predict_tumorbed_seg(model, lambda eng: type(eng) is unet.FPNEngine, FO, sd, tmp_path, monkeypatch, heat=True, near_tie_max=NEAR_TIE)
 
 
 def test_recorded_bounds_match_the_profile():

@@ -4,7 +4,6 @@ pyramid pool, the stage projection, the pyramid expand and the head's x8 upsampl
 caller-held map, the whole model under the project's ABSOLUTE 1e-3 contract at max |logit| 16, the launches one forward makes (the encoder
 stops after layer 2), the u8 slide path, speed mode, the module surface and predict_tumorbed(mode='seg') with the model the smp-signature
 factory returns.  Shapes are the smallest at which the code takes each of its paths, not the workload's."""
-import ctypes as C
 import json
 import os
 
@@ -13,20 +12,14 @@ import pytest
 import torch
 
 import pspnet_oracle as PO
+import seg_model_checks as M
 from oracle import resnet_oracle as R
-from oracle import wsi_oracle as WO
+from seg_model_checks import LOGIT_TOL, NEAR_TIE, SPEED_TOL, TAP_TOL, TOL_PARITY, TOL_SPEED, U8_TOL
 from wsi_segmentation_pipeline_amd import synthetic as W
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R18, R34, R50, R101, B1 = [2, 2, 2, 2], [3, 4, 6, 3], [3, 4, 6, 3], [3, 4, 23, 3], [1, 1, 1, 1]
-TOL_PARITY = 2e-5         # tests/test_gpu_kernels.py: one op, relative to the tensor's maximum, fp16 hi + lo pair (and fp32 arithmetic)
-TOL_SPEED = 3e-2          # ... single-pass bf16
-LOGIT_TOL = 1e-3          # BASELINE.json north_star: absolute, on logits of magnitude 16
-TAP_TOL = {'basic': 7e-6, 'bottleneck': 2e-4}   # tests/test_gpu_resnet34.py TAP_TOL[2] / tests/test_gpu_resnet50.py TAP_TOL: encoder maps, relative to the map's maximum
-U8_TOL = 2e-5             # tests/test_gpu_unet_bottleneck.py: u8 slide path against the f32 path, times the f32 path's maximum
-SPEED_TOL = 0.1           # ... speed mode: finite and within 0.1 of the maximum
-NEAR_TIE = 0.0005         # arg-max flips are asserted only where at most this share of the spec's pixels has a top-two margin < 2 LOGIT_TOL
 # (n, c, h, w): every bin the one pixel; a map smaller than 6 bins (bins repeat pixels); odd sizes with overlapping bins; non-square with
 # 8 / 3 and 8 / 6; more images than one, 512 channels, bins of 2 x 2 repeating; more rows than one round of the kernel's 32 (planes 1: 16)
 POOL_CASES = [(1, 128, 1, 1), (1, 128, 4, 4), (1, 128, 5, 7), (2, 128, 8, 12), (3, 512, 2, 2), (1, 128, 32, 32)]
@@ -56,10 +49,6 @@ def sd():
     return W.make_pspnet_state_dict(31, R18, 4)
 
 
-def _rel(got, ref):
-    return float((got.double().cpu() - ref).abs().max() / ref.abs().max())
-
-
 @pytest.mark.parametrize('shape', POOL_CASES, ids=lambda s: 'x'.join(map(str, s)))
 def test_pyramid_pool_matches_float64(dev, shape):
     """The 50 bins of a PF map against float64 F.adaptive_avg_pool2d, in both line formats; the same bits on a second run (a fixed summation
@@ -74,7 +63,7 @@ def test_pyramid_pool_matches_float64(dev, shape):
         run = lambda: E.pyramid_pool(E.pf_pack(x.to(dev), planes), n, h, w, c, planes)
         got = run()
         assert torch.equal(got, run())
-        errs[planes] = _rel(got, ref)
+        errs[planes] = M.rel(got, ref)
         _record('pool_rel_err', '%s planes %d' % ('x'.join(map(str, shape)), planes), errs[planes])
     assert errs[2] <= TOL_PARITY and errs[1] <= TOL_SPEED
 
@@ -94,7 +83,7 @@ def test_stage_projection_matches_float64(dev, n, c):
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     got = E.pspnet_stage_project(pooled.to(dev), [t(a.T) for a in fold['stage_w']], [t(a) for a in fold['stage_b']], [t(a.T) for a in fold['proj_w']])
     assert tuple(got.shape) == tuple(ref.shape) == (n, 50, 512)
-    err = _rel(got, ref)
+    err = M.rel(got, ref)
     _record('project_rel_err', '%dx50x%d' % (n, c), err)
     assert err <= TOL_PARITY
 
@@ -126,7 +115,7 @@ def test_pyramid_expand_matches_float64_and_leaves_the_pad_ring(dev, n, h, w):
         raw = out.cpu().numpy()
         real = _real_byte_mask(lib, n, h, w, 512 * (2 if planes == 1 else 4), raw.size)
         assert (raw[~real] == 0x5A).all() and (~real).sum() > 0
-        errs[planes] = _rel(E.pf_unpack(out, n, 512, h, w, planes), ref)
+        errs[planes] = M.rel(E.pf_unpack(out, n, 512, h, w, planes), ref)
         _record('expand_rel_err', '%dx%dx%d planes %d' % (n, h, w, planes), errs[planes])
     assert errs[2] <= TOL_PARITY and errs[1] <= TOL_SPEED
 
@@ -151,7 +140,7 @@ def test_head_conv_up8_matches_float64(dev, name, shape, classes):
         wpk, zero = E.prepack_conv(wp, None, planes, dev)
         assert not zero.any()
         got = E.pspnet_head_up8(E.pf_pack(x.to(dev), planes), wpk, bp.to(dev), n, h, w, classes, planes)
-        errs[planes] = _rel(got, ref)
+        errs[planes] = M.rel(got, ref)
         _record('head_rel_err', '%s planes %d' % (name, planes), errs[planes])
         scale = float(refq.abs().max())                                             # the output's corners are the 1/8 map's corners
         for yo, xo in ((0, 0), (0, -1), (-1, 0), (-1, -1)):
@@ -163,25 +152,6 @@ def _checkpoint(arch, layers):
     return W.make_pspnet_bottleneck_state_dict(31, layers, 4) if arch == 'bottleneck' else W.make_pspnet_state_dict(31, layers, 4)
 
 
-def _scaled_to_logit(sd, x, target=16.0):
-    """final_conv scaled until the spec's max |logit| on these inputs is `target` (tests/test_gpu_fpn.py).  Returns (state dict, float64
-    spec logits, fp32 spec encoder maps, the decoder's maps at 1/8 resolution)."""
-    with torch.no_grad():
-        ref, enc = PO.forward(sd, x)
-    s = target / float(ref.abs().max())
-    sd = dict(sd)
-    for key in ('decoder.final_conv.weight', 'decoder.final_conv.bias'):
-        sd[key] = sd[key] * s
-    maps = []
-    with torch.no_grad():
-        return sd, PO.decoder(sd, enc, maps=maps), enc, maps
-
-
-def _near_tie_share(ref):
-    top = ref.topk(2, 1).values
-    return float(((top[:, 0] - top[:, 1]) < 2 * LOGIT_TOL).double().mean())
-
-
 @pytest.mark.parametrize('arch', ['basic', 'bottleneck'])
 def test_decoder_on_a_caller_held_map(dev, arch):
     """wsi_pspnet_decoder / wsi_pspnet_bneck_decoder with enc_nchw = {NULL, NULL, x2, NULL, NULL} against pspnet_oracle.decoder on the same
@@ -190,7 +160,7 @@ def test_decoder_on_a_caller_held_map(dev, arch):
     ck = _checkpoint(arch, B1)
     for n in (1, 3):
         x = R.normalize_u8(W.make_u8_patches(51 + n, (n, 3, 32, 96)))
-        ck16, ref, ref_enc, _ = _scaled_to_logit(ck, x)
+        ck16, ref, ref_enc, _ = M.scaled_to_logit(PO, ck, x)
         eng = PSPNetEngine(ck16, dev, planes=2)
         got = eng.decode([None, None, ref_enc[2].to(dev), None, None])
         err = float((got.cpu().double() - ref).abs().max())
@@ -209,7 +179,7 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     from wsi_segmentation_pipeline_amd.unet import PSPNetEngine
     n, h, w = shape
     x = R.normalize_u8(W.make_u8_patches(41 + h + w, (n, 3, h, w)))
-    sd16, ref, ref_enc, maps = _scaled_to_logit(_checkpoint(arch, layers), x)
+    sd16, ref, ref_enc, maps = M.scaled_to_logit(PO, _checkpoint(arch, layers), x)
     assert abs(float(ref.abs().max()) - 16.0) < 1e-3
     assert max(float(t.abs().max()) for t in list(ref_enc[2:]) + maps) < 6e4       # inside the fp16 range of the line format
     eng = PSPNetEngine(sd16, dev, planes=2)
@@ -223,7 +193,7 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     d12 = float((two - got).abs().max())
     # (the maps of layers 3 and 4 are the trunk's business - tests/test_gpu_resnet34.py, test_gpu_resnet50.py; here: what the decoder reads)
     e2 = float((enc[2].cpu() - ref_enc[2]).abs().max() / ref_enc[2].abs().max())
-    flips, share = float((got.cpu().argmax(1) != ref.argmax(1)).float().mean()), _near_tie_share(ref)
+    flips, share = float((got.cpu().argmax(1) != ref.argmax(1)).float().mean()), M.near_tie_share(ref)
     print('pspnet %s parity: max |logit - spec| %.3e (decoder(encoder(x)): %.3e, between the two %.3e) ABSOLUTE at max |logit| 16; x2 rel err '
           '%.2e; arg-max flips %.5f, near-tie share %.5f' % (name, err, err2, d12, e2, flips, share))
     _record('logit_abs_err', name, max(err, err2))
@@ -232,18 +202,6 @@ def test_logits_hold_the_absolute_contract(dev, name, arch, layers, shape):
     assert err <= LOGIT_TOL and err2 <= LOGIT_TOL and d12 <= LOGIT_TOL
     if share <= NEAR_TIE:
         assert flips <= 0.002
-
-
-def _prof_kinds(lib, run, cap=512):
-    from wsi_segmentation_pipeline_amd import native
-    native.check(lib.wsi_prof_begin(cap), 'wsi_prof_begin')
-    try:
-        run()
-    finally:
-        ms, kind, fl = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
-        n = lib.wsi_prof_end(*[a.ctypes.data_as(C.c_void_p) for a in (ms, kind, fl)], cap)
-    assert 0 <= n < cap
-    return [(int(kind[i]), float(fl[i])) for i in range(n)]
 
 
 @pytest.mark.parametrize('arch,layers', [('basic', R34), ('bottleneck', R50)], ids=['resnet34', 'resnet50'])
@@ -255,14 +213,13 @@ def test_routes_of_one_forward(dev, arch, layers):
     logits are bit for bit the same."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import PSPNetEngine
-    lib = native.load()
     ck = _checkpoint(arch, layers)
     x = R.normalize_u8(W.make_u8_patches(43, (2, 3, 64, 64))).to(dev)
     eng = PSPNetEngine(ck, dev, planes=2)
     eng.forward_f32(x)                                                              # (plans the workspace outside the recording)
     out = {}
-    rec = _prof_kinds(lib, lambda: out.update(alone=eng.forward_f32(x)[0].clone()))
-    rec_enc = _prof_kinds(lib, lambda: out.update(full=eng.forward_f32(x, enc=True)))
+    rec = native.profiled(lambda: out.update(alone=eng.forward_f32(x)[0].clone()), 512)[1]
+    rec_enc = native.profiled(lambda: out.update(full=eng.forward_f32(x, enc=True)), 512)[1]
     kinds, kinds_enc = [k for k, _ in rec], [k for k, _ in rec_enc]
     print('prof kinds, pspnet %s: %r; with enc=True %r' % (arch, kinds, kinds_enc))
     decoder = [18, 19, 20, 12, 6, 21]
@@ -287,114 +244,31 @@ def test_routes_of_one_forward(dev, arch, layers):
 def test_u8_slide_path_equals_f32_path(dev, sd):
     """forward_tiles on a 200 x 260 slide, four 64 x 64 tiles, one hanging over the edge, against forward_f32 of the gathered tiles."""
     from wsi_segmentation_pipeline_amd.unet import PSPNetEngine
-    rng = np.random.default_rng(7)
-    slide = rng.integers(0, 256, (200, 260, 3), dtype=np.uint8)
-    xy = np.array([[0, 0], [100, 50], [260 - 64, 200 - 64], [230, 170]], np.int32)
-    tiles = np.stack([WO.read_tile(slide, int(x), int(y), 64, 64) for x, y in xy]).transpose(0, 3, 1, 2)
-    x = R.normalize_u8(tiles)
-    sd16 = _scaled_to_logit(sd, x)[0]
-    eng = PSPNetEngine(sd16, dev, planes=2)
-    b = eng.forward_f32(x.to(dev))[0].clone()
-    a = eng.forward_tiles(torch.from_numpy(slide).to(dev), torch.from_numpy(xy).to(dev), 64, 64).clone()
-    scale, err = float(b.abs().max()), float((a - b).abs().max())
+    err, scale = M.u8_slide_path_equals_f32_path(PSPNetEngine, PO, sd, dev)
     _record('u8_slide_vs_f32_path', 'err over scale', err / scale)
-    assert a.shape == b.shape == (4, 4, 64, 64)
-    assert err <= U8_TOL * scale
 
 
 def test_speed_mode_is_sane(dev, sd):
-    """planes 1 (single-pass bf16): outside the contract; finite logits within 0.1 of the spec's maximum."""
+    """planes 1 (single-pass bf16): outside the contract; finite logits, and x2 (the map the decoder reads), within 0.1 of the spec's maximum."""
     from wsi_segmentation_pipeline_amd.unet import PSPNetEngine
-    x = R.normalize_u8(W.make_u8_patches(45, (3, 3, 64, 64)))
-    sd16, ref, ref_enc, _ = _scaled_to_logit(sd, x)
-    eng = PSPNetEngine(sd16, dev, planes=1)
-    got, enc = eng.forward_f32(x.to(dev), logits=True, enc=True)
-    err = float((got.cpu().double() - ref).abs().max() / ref.abs().max())
-    e2 = float((enc[2].cpu() - ref_enc[2]).abs().max() / ref_enc[2].abs().max())
+    err, _ = M.speed_mode_is_sane(PSPNetEngine, PO, sd, dev, R.normalize_u8(W.make_u8_patches(45, (3, 3, 64, 64))), enc_index=2)
     _record('speed_mode', 'logits rel err', err)
-    assert np.isfinite(err) and err <= SPEED_TOL and np.isfinite(e2) and e2 <= SPEED_TOL
 
 
 def test_module_surface_and_mx_refusal(dev, sd):
     """model(x), model.encoder(x), model.decoder(encoding) in eval mode run on the engine; a CPU tensor is refused."""
     from wsi_segmentation_pipeline_amd import unet
-    model = unet.PSPNet('resnet18', encoder_weights=None, classes=4, activation=None)
-    model.load_state_dict(sd, strict=True)
-    model = model.cuda().eval()
-    x = R.normalize_u8(W.make_u8_patches(46, (2, 3, 64, 64)))
-    with torch.no_grad():
-        ref = PO.forward(sd, x)[0]
-        y = model(x.cuda())
-        enc = model.encoder(x.cuda())
-        y2 = model.decoder(enc)
-    assert isinstance(model.hip_engine(dev), unet.PSPNetEngine)
-    assert [tuple(t.shape[1:]) for t in enc] == [(512, 2, 2), (256, 4, 4), (128, 8, 8), (64, 16, 16), (64, 32, 32)]
-    scale = float(ref.abs().max())
-    assert float((y.cpu().double() - ref).abs().max()) <= 2e-4 * scale and float((y2.cpu().double() - ref).abs().max()) <= 4e-4 * scale
-    with pytest.raises(RuntimeError):
-        model(x)
-    with pytest.raises(ValueError, match='mx'):
-        unet.PSPNetEngine(sd, dev, planes=3)
+    M.module_surface_and_mx_refusal(unet.PSPNet, unet.PSPNetEngine, PO, sd, dev)
 
 
 def test_predict_tumorbed_seg_with_the_factory_model(dev, sd, tmp_path, monkeypatch):
     """predict_tumorbed(mode='seg') with unet.PSPNet('resnet18', classes=4) on the slide of tests/test_gpu_fpn.py: the fused tile path is the
     one taken (the PSPNet engine reads the tiles from the device-resident level), the class map and the heat map against the CPU chain
     (float64 spec -> float64 stitch -> threshold / heat map): heat pixels off by more than 1 LSB and class flips at most 0.002 each, where
-    at most NEAR_TIE of the spec's own tile pixels are near-ties."""
-    import myargs
-    import utils.dataset as ds
-    import utils.eval as val
+    at most NEAR_TIE of the spec's own tile pixels are near-ties (checked on the CPU for this slide seed: 4e-5, so the rule applies)."""
     from wsi_segmentation_pipeline_amd import unet
-    from wsi_segmentation_pipeline_amd.slide import ArraySlide
-    a = myargs.args
-    a.scan_level, a.scan_resize, a.num_classes, a.class_probs = 2, 1, 4, [0., 0., 0., 0.]
-    a.tile_w = a.tile_h = 64
-    a.tile_stride_w = a.tile_stride_h = 48
-    a.val_save_pth, a.wsi_mask_pth = str(tmp_path / 'out'), str(tmp_path / 'nomask')
-    rng = np.random.default_rng(13)
-    l2 = np.clip(np.kron(rng.integers(60, 250, (7, 9, 3)), np.ones((32, 32, 1))) + rng.integers(-25, 25, (224, 288, 3)), 0, 255).astype(np.uint8)
-    big = np.repeat(np.repeat(l2, 4, 0), 4, 1)
-    slide = ArraySlide([np.repeat(np.repeat(big, 4, 0), 4, 1)[:8, :8], big[:8, :8], l2], [1.0, 4.0, 16.0])   # only level 2 is read
-    slide.level_dimensions = ((288 * 16, 224 * 16), (288 * 4, 224 * 4), (288, 224))
-    slide.name = 'seg.svs'
     model = unet.PSPNet('resnet18', encoder_weights=None, classes=4, activation=None)
-    model.load_state_dict(sd)
-    model = model.cuda().eval()
-    model.classifier, model.regressor = torch.nn.Identity(), torch.nn.Identity()
-    calls = {'tiles': 0, 'f32': 0}
-    real_tiles, real_f32 = unet.UNetEngine.forward_tiles, unet.UNetEngine.forward_f32
-
-    def forward_tiles(self, *args, **kw):
-        assert type(self) is unet.PSPNetEngine
-        calls['tiles'] += int(args[1].shape[0])
-        return real_tiles(self, *args, **kw)
-
-    def forward_f32(self, *args, **kw):
-        calls['f32'] += 1
-        return real_f32(self, *args, **kw)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_tiles', forward_tiles)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_f32', forward_f32)
-    params = {'ph': 64, 'pw': 64, 'sh': 48, 'sw': 48}
-    dataset = ds.Dataset_wsis({'seg.svs': slide}, params, bs=5)
-    tiles = dataset.wsis['seg.svs']['iterator'].dataset.datalist
-    mask = dataset.wsis['seg.svs']['mask']
-    assert len(tiles) >= 12
-    res = val.predict_tumorbed(model, dataset, 1, mode='seg')['seg.svs']
-    assert calls == {'tiles': len(tiles), 'f32': 0}
-    u8 = np.stack([WO.read_tile(l2, x, y, 64, 64) for x, y in tiles]).transpose(0, 3, 1, 2)
-    with torch.no_grad():
-        tp = PO.forward(sd, R.normalize_u8(u8))[0]
-    share = _near_tie_share(tp)
-    pred = WO.stitch_tumorbed(tiles, tp.numpy(), 4, l2.shape[:2], 1.0, 64, 64)
-    ref_cls, ref_probs = WO.threshold_probs(pred)
-    ref_heat = WO.tumorbed_heatmap(ref_probs, mask, 'seg')
-    flips = float((res['classes'] != ref_cls).mean())
-    dheat = np.abs(res['heatmap'].astype(int) - ref_heat.astype(int))
-    print('pspnet predict_tumorbed seg: class flips %.5f, heat pixels off by > 1: %d of %d; near-tie share of the spec tiles %.5f'
-          % (flips, int((dheat > 1).sum()), dheat.size, share))
-    assert share <= NEAR_TIE                                                         # (checked on the CPU for this slide seed: 4e-5, so the rule applies)
-    assert flips <= 0.002 and (dheat > 1).mean() <= 0.002
+    M.predict_tumorbed_seg(model, lambda eng: type(eng) is unet.PSPNetEngine, PO, sd, tmp_path, monkeypatch, heat=True, near_tie_max=NEAR_TIE)
 
 
 def test_recorded_bounds_match_the_profile():

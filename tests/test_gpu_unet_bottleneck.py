@@ -5,23 +5,24 @@ path, and predict_tumorbed(mode='seg') with the model the smp-signature factory 
 import ctypes as C
 import json
 import os
+import types
 
 import numpy as np
 import pytest
 import torch
 
+import seg_model_checks as M
 import unet_bottleneck_oracle as UB
 from oracle import resnet_oracle as R
-from oracle import wsi_oracle as WO
+from seg_model_checks import LOGIT_TOL, SPEED_TOL, U8_TOL
 from wsi_segmentation_pipeline_amd import synthetic as W
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R50, R101 = [3, 4, 6, 3], [3, 4, 23, 3]
-LOGIT_TOL = 1e-3          # BASELINE.json north_star: absolute, on logits of magnitude 16
-TAP_TOL = 2e-4            # tests/test_gpu_resnet50.py TAP_TOL: relative to the map's maximum
-U8_TOL = 2e-5             # tests/test_gpu_resnet50.py::test_u8_slide_path_equals_f32_path: times the f32 path's maximum
-SPEED_TOL = 0.1           # tests/test_gpu_resnet50.py::test_speed_mode_is_sane: finite and within 0.1 of the maximum
+# the spec under the names the shared checks use (its decoder lists no maps)
+SPEC = types.SimpleNamespace(forward=UB.unet_forward, decoder=lambda sd, enc, maps=None: UB.U.decoder(sd, enc))
+TAP_TOL = M.TAP_TOL['bottleneck']      # tests/test_gpu_resnet50.py TAP_TOL: relative to the map's maximum
 # Measured on an MI355X (profiles/unet_resnet50_parity.json); the bounds above were set before and are not derived from these.
 ENC_MEASURED = {'x1 vs fixture': 1.27e-06, 'x2 vs fixture': 1.88e-06, 'x3 vs fixture': 1.80e-06, 'x4 vs fixture': 1.91e-06,
                 'x4': 1.63e-06, 'x3': 1.22e-06, 'x2': 1.23e-06, 'x1': 9.63e-07, 'x0': 7.24e-07}
@@ -53,19 +54,6 @@ def bag6():
 
 def _rel(got, ref):
     return float((got.cpu() - ref).abs().max() / ref.abs().max())
-
-
-def _scaled_to_logit(sd, x, target=16.0):
-    """final_conv scaled until the spec's max |logit| on these inputs is `target` (tests/test_gpu_unet.py: the contract is absolute on
-    logits of the size trained heads produce).  Returns (state dict, spec logits, spec encoder maps)."""
-    with torch.no_grad():
-        ref, enc = UB.unet_forward(sd, x)
-    s = target / float(ref.abs().max())
-    sd = dict(sd)
-    for key in ('decoder.final_conv.weight', 'decoder.final_conv.bias'):
-        sd[key] = sd[key] * s
-    with torch.no_grad():
-        return sd, UB.U.decoder(sd, enc), enc
 
 
 def test_encoder_maps_vs_reference_fixture(dev, sd, bag6, golden_dir):
@@ -114,7 +102,7 @@ def test_logits_hold_the_absolute_contract(dev, name, layers, shape):
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
     n, h, w = shape
     x = R.normalize_u8(W.make_u8_patches(41 + h + w, (n, 3, h, w)))
-    sd, ref, ref_enc = _scaled_to_logit(_checkpoint(layers), x)
+    sd, ref, ref_enc, _ = M.scaled_to_logit(SPEC, _checkpoint(layers), x)
     assert abs(float(ref.abs().max()) - 16.0) < 1e-3
     assert max(float(t.abs().max()) for t in ref_enc) < 6e4                         # inside the fp16 range of the line format
     eng = UNetEngine(sd, dev, planes=2)
@@ -136,19 +124,7 @@ def test_u8_slide_path_equals_f32_path(dev, sd):
     """forward_tiles on a 200 x 260 slide, four 64 x 64 tiles, one hanging over the edge (the integer stem, which also stores x0),
     against forward_f32 of the gathered tiles."""
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
-    rng = np.random.default_rng(7)
-    slide = rng.integers(0, 256, (200, 260, 3), dtype=np.uint8)
-    xy = np.array([[0, 0], [100, 50], [260 - 64, 200 - 64], [230, 170]], np.int32)
-    tiles = np.stack([WO.read_tile(slide, int(x), int(y), 64, 64) for x, y in xy]).transpose(0, 3, 1, 2)
-    x = R.normalize_u8(tiles)
-    sd16 = _scaled_to_logit(sd, x)[0]
-    eng = UNetEngine(sd16, dev, planes=2)
-    b = eng.forward_f32(x.to(dev))[0].clone()
-    a = eng.forward_tiles(torch.from_numpy(slide).to(dev), torch.from_numpy(xy).to(dev), 64, 64).clone()
-    scale, err = float(b.abs().max()), float((a - b).abs().max())
-    print('unet resnet50 u8 slide path vs f32 path: %.3e of scale %.3e (bound %.1e)' % (err, scale, U8_TOL * scale))
-    assert a.shape == b.shape == (4, 4, 64, 64)
-    assert err <= U8_TOL * scale
+    M.u8_slide_path_equals_f32_path(UNetEngine, SPEC, sd, dev)
 
 
 @pytest.mark.parametrize('shape', [(2, 2048, 1024, 256, 4, 4), (1, 2048, 1024, 256, 6, 10), (2, 256, 512, 128, 8, 8), (2, 128, 256, 64, 16, 16)])
@@ -186,30 +162,16 @@ def test_fused_upsample_concat_conv_is_bit_identical_at_the_bottleneck_shapes(de
     assert err <= 2e-4
 
 
-def _prof_records(lib, run, cap=256):
-    """kinds of every launch `run` makes between wsi_prof_begin and wsi_prof_end (a ResNet-50 U-Net forward makes 66)"""
-    from wsi_segmentation_pipeline_amd import native
-    native.check(lib.wsi_prof_begin(cap), 'wsi_prof_begin')
-    try:
-        run()
-    finally:
-        ms, kind, fl = np.zeros(cap, np.float32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
-        n = lib.wsi_prof_end(*[a.ctypes.data_as(C.c_void_p) for a in (ms, kind, fl)], cap)
-    assert 0 <= n < cap
-    return [int(k) for k in kind[:n]]
-
-
 def test_routes_of_one_forward(dev, sd):
     """The profiler's record kinds of one (3, 64, 64) forward: the encoder's 1x1 convs on the pointwise kernel (kind 11: two per block and
     layer 1's downsample), every decoder block's first conv on the fused upsample + concat route (no refused launch, kind 9, and no concat
     pass, kind 7, once the decoder has begun - the one 7 before it is the stem conv for x0), the fused tail (10) last."""
     from wsi_segmentation_pipeline_amd import native
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
-    lib = native.load()
     x = R.normalize_u8(W.make_u8_patches(43, (3, 3, 64, 64))).to(dev)
     eng = UNetEngine(sd, dev, planes=2)
     eng.forward_f32(x)                                                              # (plans the workspace outside the recording)
-    kinds = _prof_records(lib, lambda: eng.forward_f32(x))
+    kinds = [k for k, _ in native.profiled(lambda: eng.forward_f32(x))[1]]       # (a ResNet-50 U-Net forward makes 66 launches)
     print('prof kinds, unet resnet50:', kinds)
     first_dec = kinds.index(6)
     assert 9 not in kinds and 7 not in kinds[first_dec:] and kinds[:first_dec].count(7) == 1
@@ -220,67 +182,20 @@ def test_routes_of_one_forward(dev, sd):
 
 
 def test_speed_mode_is_sane(dev, sd, bag6):
-    """planes 1 (single-pass bf16): outside the contract; finite logits within 0.1 of the spec's maximum."""
+    """planes 1 (single-pass bf16): outside the contract; finite logits, and x4, within 0.1 of the spec's maximum, on the first three
+    images of the fixture's bag."""
     from wsi_segmentation_pipeline_amd.unet import UNetEngine
-    sd16, ref, ref_enc = _scaled_to_logit(sd, bag6[:3])
-    eng = UNetEngine(sd16, dev, planes=1)
-    got, enc = eng.forward_f32(bag6[:3].to(dev), logits=True, enc=True)
-    err, e4 = _rel(got, ref), _rel(enc[0], ref_enc[0])
-    print('unet resnet50 speed mode: logits rel err %.2e, x4 rel err %.2e' % (err, e4))
-    assert np.isfinite(err) and err <= SPEED_TOL and np.isfinite(e4) and e4 <= SPEED_TOL
+    M.speed_mode_is_sane(UNetEngine, SPEC, sd, dev, bag6[:3], enc_index=0)
 
 
 def test_predict_tumorbed_seg_with_the_factory_model(dev, sd, tmp_path, monkeypatch):
     """predict_tumorbed(mode='seg') with unet.Unet('resnet50', ...) on the smallest slide of
     tests/test_gpu_unet.py::test_predict_tumorbed_seg_and_predict_wsis_with_unet: the class map against the CPU chain (spec -> float64
-    stitch -> threshold), and the fused tile path (the engine reads the tiles from the device-resident level) is the one taken."""
-    import myargs
-    import utils.dataset as ds
-    import utils.eval as val
+    stitch -> threshold), and the fused tile path (the engine reads the tiles from the device-resident level) is the one taken.  The
+    class map only: no heat map and no near-tie rule here."""
     from wsi_segmentation_pipeline_amd import unet
-    from wsi_segmentation_pipeline_amd.slide import ArraySlide
-    a = myargs.args
-    a.scan_level, a.scan_resize, a.num_classes, a.class_probs = 2, 1, 4, [0., 0., 0., 0.]
-    a.tile_w = a.tile_h = 64
-    a.tile_stride_w = a.tile_stride_h = 48
-    a.val_save_pth, a.wsi_mask_pth = str(tmp_path / 'out'), str(tmp_path / 'nomask')
-    rng = np.random.default_rng(13)
-    l2 = np.clip(np.kron(rng.integers(60, 250, (7, 9, 3)), np.ones((32, 32, 1))) + rng.integers(-25, 25, (224, 288, 3)), 0, 255).astype(np.uint8)
-    big = np.repeat(np.repeat(l2, 4, 0), 4, 1)
-    slide = ArraySlide([np.repeat(np.repeat(big, 4, 0), 4, 1)[:8, :8], big[:8, :8], l2], [1.0, 4.0, 16.0])   # only level 2 is read
-    slide.level_dimensions = ((288 * 16, 224 * 16), (288 * 4, 224 * 4), (288, 224))
-    slide.name = 'seg.svs'
     model = unet.Unet('resnet50', encoder_weights=None, classes=4, activation=None)
-    model.load_state_dict(sd)
-    model = model.cuda().eval()
-    model.classifier, model.regressor = torch.nn.Identity(), torch.nn.Identity()
-    calls = {'tiles': 0, 'f32': 0}
-    real_tiles, real_f32 = unet.UNetEngine.forward_tiles, unet.UNetEngine.forward_f32
-
-    def forward_tiles(self, *args, **kw):
-        assert self.arch == 'bottleneck'
-        calls['tiles'] += int(args[1].shape[0])
-        return real_tiles(self, *args, **kw)
-
-    def forward_f32(self, *args, **kw):
-        calls['f32'] += 1
-        return real_f32(self, *args, **kw)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_tiles', forward_tiles)
-    monkeypatch.setattr(unet.UNetEngine, 'forward_f32', forward_f32)
-    params = {'ph': 64, 'pw': 64, 'sh': 48, 'sw': 48}
-    dataset = ds.Dataset_wsis({'seg.svs': slide}, params, bs=5)
-    tiles = dataset.wsis['seg.svs']['iterator'].dataset.datalist
-    assert len(tiles) >= 12
-    res = val.predict_tumorbed(model, dataset, 1, mode='seg')['seg.svs']
-    assert calls == {'tiles': len(tiles), 'f32': 0}
-    u8 = np.stack([WO.read_tile(l2, x, y, 64, 64) for x, y in tiles]).transpose(0, 3, 1, 2)
-    with torch.no_grad():
-        tp = UB.unet_forward(sd, R.normalize_u8(u8))[0].numpy()
-    pred = WO.stitch_tumorbed(tiles, tp, 4, l2.shape[:2], 1.0, 64, 64)
-    ref_cls = WO.threshold_probs(pred)[0]
-    flips = float((res['classes'] != ref_cls).mean())
-    print('unet resnet50 predict_tumorbed seg: class flips %.5f of %d pixels' % (flips, ref_cls.size))
-    assert flips <= 0.002
+    M.predict_tumorbed_seg(model, lambda eng: eng.arch == 'bottleneck', SPEC, sd, tmp_path, monkeypatch, heat=False, near_tie_max=None)
 
 
 def test_recorded_bounds_match_the_profile():

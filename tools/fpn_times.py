@@ -31,7 +31,7 @@ COPY_RATE = 6.29e12                      # bytes / s of a device-to-device copy 
 KINDS = {1: '3x3 stride 1 (encoder)', 2: '3x3 stride 2 (encoder)', 3: '1x1 stride-2 downsample', 4: 'stem + max pool', 5: '3x3 stride 1 (layer 1)',
          6: 'seg unit 3x3 conv', 7: 'nearest x2 upsample of the pyramid', 9: 'refused fused launch', 11: '1x1 stride 1 (encoder)',
          12: 'lateral 1x1 conv', 15: 'GroupNorm statistics', 16: 'GroupNorm apply (+ upsample)', 17: 'merge + head + x4'}
-UNIT_LEVEL = (0, 1, 2, 1, 2, 2, 3)       # the pyramid level (/ 32 ... / 4) each of the seven seg units reads (csrc/trunk.hip FPN_UNIT_LEVEL)
+UNIT_LEVEL = (0, 1, 2, 1, 2, 2, 3)       # the pyramid level (/ 32 ... / 4) each of the seven seg units reads (csrc/fpn.hip FPN_UNIT_LEVEL)
 
 
 def new_kind_bytes(n, patch, classes, bytes_per_channel=4):

@@ -1,6 +1,6 @@
 // extern "C" surface of libwsi_hip.so (include/wsi_hip.h) below the model level: the route switches, the single-op conv and stem
-// entries and the argument-checking wrappers of the slide, proposal and post-process ops.  Weight packing: prepack.hip; trunk and
-// U-Net: trunk.hip.  No device allocation, no synchronisation, no exceptions.
+// entries and the argument-checking wrappers of the slide, proposal and post-process ops.  Weight packing: prepack.hip; the trunks:
+// trunk.hip; the segmentation models: seg_host.h and the decoder files.  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "../../include/wsi_hip.h"
 

@@ -11,9 +11,10 @@
 //   fpn_head / up4        : sum of the four quarter-resolution 128-channel maps, final_conv 1x1 + bias into fp32 [n][classes][h][w], then
 //                           bilinear x4 (align_corners=True) into the fp32 NCHW logits
 // All read and write whole 16-byte pieces of the 128-byte lines (planes 1 and 2) and never touch the pad ring.
+// Below the kernels and the single-op entries: the FPN decoder on the host - its workspace plan, its launch sequence, `FpnDec` and the exported
+// wsi_fpn_* / wsi_fpn_bneck_* entries (seg_host.h WSI_SEG_ENTRIES).
 #include "pf_lines.h"
-#include "internal.h"
-#include "../../include/wsi_hip.h"
+#include "seg_host.h"
 
 constexpr int FPN_C = 128;                            // channels of every tensor these kernels take
 constexpr int GN_GROUPS = 32;                         // 4 channels per group
@@ -219,14 +220,14 @@ static bool gn_shape_ok(int n, int h, int w, int planes) {
            (long long)n * chunks_of(h, w, GN_CHUNK) < (1ll << 30);
 }
 
-size_t wsi_gn_scratch_size(int n, int h, int w) {
+static size_t wsi_gn_scratch_size(int n, int h, int w) {
     if (n <= 0 || h <= 0 || w <= 0 || (long long)h * w >= (1ll << 30) || (long long)n * chunks_of(h, w, GN_CHUNK) >= (1ll << 30)) return 0;
     return ((size_t)n * chunks_of(h, w, GN_CHUNK) + (size_t)n) * GN_GROUPS * 2 * sizeof(float);
 }
 // where the (mean, rstd) table sits in a scratch buffer planned for (n, h, w): behind the partials of the planning bound
 static float* gn_stat(float* scratch, int n, int h, int w) { return scratch + (size_t)n * chunks_of(h, w, GN_CHUNK) * GN_GROUPS * 2; }
 
-int wsi_gn_stats_dispatch(const void* in, int n, int h, int w, float eps, float* scratch, int planes, hipStream_t st) {
+static int wsi_gn_stats_dispatch(const void* in, int n, int h, int w, float eps, float* scratch, int planes, hipStream_t st) {
     if (!in || !scratch || !gn_shape_ok(n, h, w, planes) || !(eps > 0.f)) return WSI_EINVAL;
     const PFGeom g = pf_geom(n, h, w, FPN_C);
     const int cp = planes == 2 ? GN_CHUNK : 2 * GN_CHUNK, chunks = chunks_of(h, w, cp);
@@ -237,7 +238,7 @@ int wsi_gn_stats_dispatch(const void* in, int n, int h, int w, float eps, float*
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
-int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const float* beta, const float* scratch, int n, int h, int w, int up2,
+static int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const float* beta, const float* scratch, int n, int h, int w, int up2,
                           int planes, hipStream_t st) {
     if (!in || !out || in == out || !gamma || !beta || !scratch || !gn_shape_ok(n, h, w, planes) || (up2 & ~1)) return WSI_EINVAL;
     const int ho = up2 ? 2 * h : h, wo = up2 ? 2 * w : w;
@@ -253,7 +254,7 @@ int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const f
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
-int wsi_fpn_head_dispatch(const void* const m[4], const float* head_w, const float* head_b, int n, int h, int w, int classes, float* q,
+static int wsi_fpn_head_dispatch(const void* const m[4], const float* head_w, const float* head_b, int n, int h, int w, int classes, float* q,
                           float* logits, int planes, hipStream_t st) {
     if (!m || !head_w || !head_b || !q || !logits || q == logits || n <= 0 || h <= 0 || w <= 0 || classes <= 0 || classes > 16 ||
         (planes != 1 && planes != 2) || (long long)h * w >= (1ll << 26))
@@ -293,3 +294,95 @@ int wsi_upsample2_nearest(const void* in_pf, void* out_pf, int n, int h, int w, 
     if (!in_pf || !out_pf || in_pf == out_pf || (planes != 1 && planes != 2)) return WSI_EINVAL;
     return wsi_upsample_concat_dispatch(in_pf, nullptr, out_pf, n, h, w, c, 0, planes, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------ FPN (dense 'seg' path, GroupNorm + bilinear decoder)
+// smp's FPN decoder on either trunk (include/wsi_hip.h "FPN"): a top-down pyramid p5 ... p2 of 256 channels (1x1 laterals with bias, the
+// coarser level added after a nearest x2 upsample), four seg branches of [3x3 conv -> 128, GroupNorm(32), ReLU, bilinear x2] units that
+// all end at 1/4 resolution, their sum, the 1x1 head and a bilinear x4.  Level k = 0 ... 3 is the map at / 32 ... / 4.  The seven units in
+// state-dict order (s5.0-2, s4.0-1, s3.0, s2.0): the level a unit reads, and whether it reads the pyramid (else the unit before it).
+// Every unit but s2's upsamples, so a unit at level L writes level L + 1.
+static const int FPN_UNIT_LEVEL[7] = {0, 1, 2, 1, 2, 2, 3};
+static const int FPN_UNIT_FIRST[7] = {1, 0, 0, 1, 0, 1, 1};
+static const int FPN_MERGED[4] = {2, 4, 5, 6};        // the last unit of s5, s4, s3, s2
+static const int FPN_CIN[11] = {0, 0, 0, 0, 256, 128, 128, 256, 128, 256, 256};       // (slots 0-3: the encoder's channels)
+constexpr int FPN_PYRAMID = 256, FPN_SEG = 128;
+struct FpnPlan {
+    size_t x0, p[4], up[3], raw[7], out[7], stat, q, total;      // pyramid levels, their upsampled copies, the units' conv outputs and results
+    int lh[4], lw[4];
+};
+static int fpn_plan(const int ec[5], const wsi_fpn_decoder_weights* dw, int n, int h, int w, int planes, FpnPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    for (int i = 0; i < 11; ++i)
+        if (dw->cin[i] != (i < 4 ? ec[i] : FPN_CIN[i]) || dw->cout[i] != (i < 4 ? FPN_PYRAMID : FPN_SEG)) return WSI_EINVAL;
+    if (dw->groups != 32 || !(dw->eps > 0.f) || dw->classes <= 0 || dw->classes > 16) return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    for (int k = 0; k < 4; ++k) {
+        u.lh[k] = (h / 32) << k; u.lw[k] = (w / 32) << k;
+        u.p[k] = take(wsi_pf_bytes(n, u.lh[k], u.lw[k], FPN_PYRAMID, planes));
+        if (k) u.up[k - 1] = take(wsi_pf_bytes(n, u.lh[k], u.lw[k], FPN_PYRAMID, planes));
+    }
+    for (int i = 0; i < 7; ++i) {
+        const int L = FPN_UNIT_LEVEL[i], Lo = L < 3 ? L + 1 : 3;
+        u.raw[i] = take(wsi_pf_bytes(n, u.lh[L], u.lw[L], FPN_SEG, planes));
+        u.out[i] = take(wsi_pf_bytes(n, u.lh[Lo], u.lw[Lo], FPN_SEG, planes));
+    }
+    const size_t stat = wsi_gn_scratch_size(n, u.lh[3], u.lw[3]);
+    if (!stat) return WSI_EINVAL;
+    u.stat = take(stat);
+    u.q = take((size_t)n * dw->classes * u.lh[3] * u.lw[3] * sizeof(float));
+    u.total = off;
+    return WSI_OK;
+}
+static bool fpn_ready(const wsi_fpn_decoder_weights* dw) {
+    for (int i = 0; i < 11; ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    for (int i = 0; i < 7; ++i) if (!dw->gn_w[i] || !dw->gn_b[i]) return false;
+    return dw->head_w && dw->head_b;
+}
+// wsi_prof kinds: 12 = a 1x1 lateral conv, 7 = a nearest x2 upsample of the pyramid, 6 = a seg unit's 3x3 conv, and the three memory-bound
+// kinds of csrc/fpn.hip, which carry no FLOPs: 15 = GroupNorm statistics, 16 = GroupNorm apply (+ upsample), 17 = merge + head + x4
+static int fpn_decoder_run(const wsi_fpn_decoder_weights* dw, const FpnPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                           float* logits_out, hipStream_t st) {
+    int rc = WSI_OK;
+    // p5 = conv1(c5) + bias; p_k = skip_conv(c_k) + bias + nearest_x2(p_{k+1}): the upsampled level is the 1x1's residual, no ReLU
+    for (int k = 0; k < 4 && !rc; ++k) {
+        if (k) {
+            ProfScope ps(st, 7, 0.0);
+            rc = wsi_upsample_concat_dispatch(dec + u.p[k - 1], nullptr, dec + u.up[k - 1], n, u.lh[k - 1], u.lw[k - 1], FPN_PYRAMID, 0, planes, st);
+        }
+        if (!rc) rc = run_conv(st, 12, ConvCall{.in = enc[k], .out = dec + u.p[k], .resid = k ? dec + u.up[k - 1] : nullptr, .wpk = dw->conv_w[k],
+                                                .bias = dw->conv_b[k], .n = n, .h = u.lh[k], .w = u.lw[k], .cin = dw->cin[k], .cout = FPN_PYRAMID,
+                                                .stride = 1, .ksize = 1, .relu = 0, .planes = planes, .stream = st});
+    }
+    float* stat = (float*)(dec + u.stat);
+    for (int i = 0; i < 7 && !rc; ++i) {
+        const int L = FPN_UNIT_LEVEL[i], H = u.lh[L], W = u.lw[L];
+        const void* in = FPN_UNIT_FIRST[i] ? dec + u.p[L] : dec + u.out[i - 1];
+        // the raw conv output is signed: the line formats carry it, as they carry the downsample branch's
+        rc = run_conv(st, 6, ConvCall{.in = in, .out = dec + u.raw[i], .wpk = dw->conv_w[4 + i], .bias = dw->conv_b[4 + i], .n = n, .h = H, .w = W,
+                                      .cin = dw->cin[4 + i], .cout = FPN_SEG, .stride = 1, .ksize = 3, .relu = 0, .planes = planes, .stream = st});
+        if (rc) break;
+        { ProfScope ps(st, 15, 0.0); rc = wsi_gn_stats_dispatch(dec + u.raw[i], n, H, W, dw->eps, stat, planes, st); }
+        if (rc) break;
+        ProfScope ps(st, 16, 0.0);
+        rc = wsi_gn_apply_dispatch(dec + u.raw[i], dec + u.out[i], dw->gn_w[i], dw->gn_b[i], stat, n, H, W, L < 3, planes, st);
+    }
+    if (rc) return rc;
+    const void* merged[4];
+    for (int i = 0; i < 4; ++i) merged[i] = dec + u.out[FPN_MERGED[i]];
+    ProfScope ps(st, 17, 0.0);
+    return wsi_fpn_head_dispatch(merged, dw->head_w, dw->head_b, n, u.lh[3], u.lw[3], dw->classes, (float*)(dec + u.q), logits_out, planes, st);
+}
+// The FPN as a decoder of the segmentation sequence (seg_host.h): it reads the four stage outputs, never x0.
+struct FpnDec {
+    using Weights = wsi_fpn_decoder_weights;
+    using Plan = FpnPlan;
+    static constexpr auto plan = fpn_plan;
+    static constexpr auto ready = fpn_ready;
+    static constexpr auto run = fpn_decoder_run;
+    static constexpr bool needs_x0 = false;
+    static constexpr int only_stage = 0;
+};
+WSI_SEG_ENTRIES(wsi_fpn, BasicNet, FpnDec)
+WSI_SEG_ENTRIES(wsi_fpn_bneck, BneckNet, FpnDec)

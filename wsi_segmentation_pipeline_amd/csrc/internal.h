@@ -1,5 +1,7 @@
 // Internal to libwsi_hip.so: every function one translation unit defines and another calls, declared once (default arguments
-// live here only), and what the host layer's files (capi.hip, trunk.hip) share.  Definer and callers include it.
+// live here only), and what the host layer's files (capi.hip, trunk.hip, the decoder files) share.  Definer and callers include it.  A
+// launcher whose only callers sit in the file that defines it is `static` there and not declared here (fpn.hip, pspnet.hip, the Linknet's
+// fused tail); what the trunk and the decoders share beyond this is seg_host.h.
 #pragma once
 #include <type_traits>
 #include "common.h"
@@ -59,29 +61,6 @@ int wsi_resize_nearest_dispatch(const float* src, long long planes_n, int hs, in
 int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w, int classes, float* logits, hipStream_t st);
 // linknet.hip: ConvTranspose2d(4, stride 2, padding 1) + folded BN + ReLU; a.gi = the (n, h, w, c) input, a.go = (n, 2h, 2w, c), a.ksize = 4
 int wsi_tconv_dispatch(const ConvArgs& a, int planes, hipStream_t st);
-// ... and the fused last block + head (planes 2): x = PF (n, hh, wh, 64), blob = wsi_linknet_tail_prepack's; WSI_EINVAL outside its range
-int wsi_linknet_tail_dispatch(const void* x, const void* blob, int n, int hh, int wh, int classes, float* logits, hipStream_t st);
-// fpn.hip (it also holds the C entries wsi_groupnorm_relu_up2, wsi_fpn_merge_head_up4 and wsi_upsample2_nearest): GroupNorm(32, 128)
-// statistics of a PF tensor (n, h, w, 128) into `scratch` (wsi_gn_scratch_size(n, h, w) bytes, or one planned for a larger n, h, w),
-// relu(groupnorm(x)) (+ bilinear x2, align_corners) from those statistics, and the sum of four such maps + 1x1 head into q
-// [n][classes][h][w] fp32 + bilinear x4 into logits [n][classes][4h][4w]; planes 1 / 2
-size_t wsi_gn_scratch_size(int n, int h, int w);
-int wsi_gn_stats_dispatch(const void* in, int n, int h, int w, float eps, float* scratch, int planes, hipStream_t st);
-int wsi_gn_apply_dispatch(const void* in, void* out, const float* gamma, const float* beta, const float* scratch, int n, int h, int w, int up2,
-                          int planes, hipStream_t st);
-int wsi_fpn_head_dispatch(const void* const m[4], const float* head_w, const float* head_b, int n, int h, int w, int classes, float* q,
-                          float* logits, int planes, hipStream_t st);
-// pspnet.hip (it also holds the C entries wsi_pyramid_pool, wsi_pspnet_stage_project, wsi_pyramid_expand and wsi_pspnet_head_up8): the 50
-// adaptive-average bins (sizes 1, 2, 3, 6) of a PF tensor (n, h, w, c) as fp32 [n][50][c]; per bin relu(stage conv + folded BatchNorm) into
-// mid [n][50][c / 4] and its slice of the fusing conv into proj [n][50][512] (c = 128 or 512: wsi_psp_width_ok); the bilinear expansion
-// (align_corners) of the four grids, summed, into a PF tensor (n, h, w, 512); and the first `classes` channels of a one-line PF tensor
-// (n, h, w) as fp32 NCHW logits, bilinear x `factor`; planes 1 / 2
-bool wsi_psp_width_ok(int c);
-int wsi_psp_pool_dispatch(const void* in, float* pooled, int n, int h, int w, int c, int planes, hipStream_t st);
-int wsi_psp_project_dispatch(const float* pooled, const float* const stage_w[4], const float* const stage_b[4], const float* const proj_w[4],
-                             float* mid, float* proj, int n, int c, hipStream_t st);
-int wsi_psp_expand_dispatch(const float* proj, void* out, int n, int h, int w, int planes, hipStream_t st);
-int wsi_psp_up_dispatch(const void* in, float* logits, int n, int h, int w, int classes, int factor, int planes, hipStream_t st);
 // slide_ops.hip
 int wsi_tile_gather_dispatch(const uint8_t* slide, long long pitch, int SH, int SW, const int* origins, const float* lut,
                              float* out, int N, int ph, int pw, hipStream_t st);
@@ -119,7 +98,7 @@ int wsi_iou_counts_dispatch(const uint8_t* a, const uint8_t* b, long long n, uns
 int wsi_score_counts_dispatch(const uint8_t* p, const uint8_t* gt, const uint8_t* mask, long long n, unsigned long long* out, hipStream_t st);
 int wsi_esp_dispatch(const double* pts, int n, int num, double* out, double* scratch, hipStream_t st);
 
-// ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip)
+// ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // torch's area_pixel_compute_scale with align_corners=True: the source step per output pixel of a bilinear resize from `in` to `out` (fpn.hip, pspnet.hip)
 static inline float corner_scale(int in, int out) { return out > 1 ? (float)(in - 1) / (float)(out - 1) : 0.f; }

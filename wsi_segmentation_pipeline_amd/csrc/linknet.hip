@@ -16,8 +16,10 @@
 // element at its widest), so the form is the gather kernel's: no prefetch, two barriers per staging.
 // Weights: the conv pack with 16 taps (prepack.hip wsi_prepack_tconv), tap ky * 4 + kx; planes 2 ends in the per-channel scales.
 // Tail: conv_epilogue_q per phase on the output positions (2i + a, 2j + b) - bias, planes-2 scales, ReLU, fp16 clamp at +-65504.
+// Below the kernels: the Linknet decoder on the host - its workspace plan, its launch sequence, `LinknetDec` and the exported wsi_linknet_*
+// entries (seg_host.h WSI_SEG_ENTRIES).
 #include "conv_dev.h"
-#include "internal.h"
+#include "seg_host.h"
 
 template <int MT, int WM, int WN, int PLANES>
 __global__ __launch_bounds__(WM* WN * 64) void tconv4x4s2_kernel(ConvArgs a) {
@@ -283,10 +285,94 @@ __global__ __launch_bounds__(256) void linknet_tail_kernel(const char* x, PFGeom
 
 // x: PF (n, hh, wh, 64) at planes 2 = layer 4's output; logits [n][classes][2 hh][2 wh] fp32.  WSI_EINVAL outside the kernel's range
 // (hh no multiple of LT_R, wh over LINKNET_TAIL_MAX_W, classes over 4): the caller's three launches.
-int wsi_linknet_tail_dispatch(const void* x, const void* blob, int n, int hh, int wh, int classes, float* logits, hipStream_t st) {
+static int wsi_linknet_tail_dispatch(const void* x, const void* blob, int n, int hh, int wh, int classes, float* logits, hipStream_t st) {
     if (!x || !blob || !logits || n <= 0 || hh <= 0 || wh <= 0 || hh % LT_R || wh > LINKNET_TAIL_MAX_W || classes < 1 || classes > 4) return WSI_EINVAL;
     const long long grid = (long long)n * (hh / LT_R);
     if (grid > 0x7fffffffll) return WSI_EINVAL;
     const size_t lds = ((size_t)LT_MID0 + (size_t)16 * (LT_R + 2) * (wh + 2)) * sizeof(float);
     return conv_launch(linknet_tail_kernel, (int)grid, 256, lds, st, (const char*)x, pf_geom(n, hh, wh, 64), (const float*)blob, classes, logits);
 }
+
+// ------------------------------------------------------------------------------------ Linknet (dense 'seg' path, light decoder)
+// smp's Linknet decoder on the BasicBlock trunk (include/wsi_hip.h "Linknet"): five blocks of [1x1 conv cin -> cin / 4, ConvTranspose2d
+// 4x4 stride 2, 1x1 conv -> cout], each + BN + ReLU, the next encoder map added AFTER the block (no ReLU behind the add), 1x1 head.
+// Stored widths: every tensor at least 64 channels wide (mid 32 and 16, cout 32: zero weights in the padding, whose outputs are
+// relu(0) = 0), so the 1x1 convs keep the existing routes - the pointwise kernel where cout % 128 == 0, the gather kernel otherwise.
+// Block L (0-based) reads an (h / 32 << L) map: a[L] = its first 1x1 at that size, b[L] and c[L] the transposed conv and the second 1x1
+// at twice the size.
+static const int LINKNET_CIN[15] = {512, 128, 128, 256, 64, 64, 128, 64, 64, 64, 64, 64, 64, 64, 64};
+static const int LINKNET_COUT[15] = {128, 128, 256, 64, 64, 128, 64, 64, 64, 64, 64, 64, 64, 64, 64};
+constexpr int LINKNET_HEAD_CIN = 32;                  // real channels of the last block
+struct LinknetPlan {
+    size_t x0, a[5], b[5], c[5], total;
+    int r_h[5], r_w[5];                               // the map block L reads
+};
+static int linknet_plan(const int ec[5], const wsi_linknet_decoder_weights* dw, int n, int h, int w, int planes, LinknetPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    for (int i = 0; i < 15; ++i) if (dw->cin[i] != LINKNET_CIN[i] || dw->cout[i] != LINKNET_COUT[i]) return WSI_EINVAL;
+    if (ec[0] != LINKNET_CIN[0] || dw->head_cin != LINKNET_HEAD_CIN || dw->classes <= 0 || dw->classes > 16) return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    for (int L = 0; L < 5; ++L) {
+        u.r_h[L] = (h / 32) << L; u.r_w[L] = (w / 32) << L;
+        if (L < 4 && ec[L + 1] != LINKNET_COUT[3 * L + 2]) return WSI_EINVAL;         // the skip is added channel for channel
+        u.a[L] = take(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], LINKNET_COUT[3 * L], planes));
+        u.b[L] = take(wsi_pf_bytes(n, 2 * u.r_h[L], 2 * u.r_w[L], LINKNET_COUT[3 * L + 1], planes));
+        u.c[L] = take(wsi_pf_bytes(n, 2 * u.r_h[L], 2 * u.r_w[L], LINKNET_COUT[3 * L + 2], planes));
+    }
+    u.total = off;
+    return WSI_OK;
+}
+// every pointer a decoder run reads: the convs of blocks 1-4 always; the last block's three and the head unless the fused tail's blob
+// stands in for them (where the tail then does not apply, conv_common refuses the null pointer)
+static bool linknet_ready(const wsi_linknet_decoder_weights* dw) {
+    for (int i = 0; i < (dw->tail_w ? 12 : 15); ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    return dw->tail_w || (dw->head_w && dw->head_b);
+}
+// wsi_prof kinds: 12 = a Linknet 1x1 conv (2 * N * H * W * cin_stored * cout_stored), 13 = transposed conv (per output pixel 4 of the 16
+// taps: 2 * N * 2H * 2W * c * c * 4), 14 = the fused last block + head (the FLOPs of its REAL channels), 8 = the 1x1 head
+static int linknet_decoder_run(const wsi_linknet_decoder_weights* dw, const LinknetPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                               float* logits_out, hipStream_t st) {
+    const void* x = enc[0];
+    int rc = WSI_OK;
+    // parity mode runs the last block and the head as ONE kernel (linknet.hip linknet_tail_kernel) when the caller prepacked its weights
+    // (wsi_linknet_tail_prepack -> dw->tail_w), the tile is at most 256 wide and the head has at most 4 classes; A/B: WSI_CONV_MODE_LINKNET_NO_TAIL
+    const bool tail = planes == 2 && dw->tail_w && g_routes.linknet_tail && dw->classes <= 4 && u.r_w[4] <= 128 && u.r_h[4] % 4 == 0;
+    for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
+        const int H = u.r_h[L], W = u.r_w[L], i = 3 * L, mid = dw->cout[i];
+        auto conv1 = [&](const void* in, void* out, const void* skip, int j, int hh, int ww) {
+            return ConvCall{.in = in, .out = out, .resid = skip, .wpk = dw->conv_w[j], .bias = dw->conv_b[j], .n = n, .h = hh, .w = ww,
+                            .cin = dw->cin[j], .cout = dw->cout[j], .stride = 1, .ksize = 1, .relu = 1, .planes = planes, .stream = st,
+                            .resid_post = skip ? 1 : 0};
+        };
+        if ((rc = run_conv(st, 12, conv1(x, dec + u.a[L], nullptr, i, H, W)))) break;
+        {
+            ProfScope ps(st, 13, conv_flops(n, 2 * H, 2 * W, mid, mid, 4));
+            rc = wsi_tconv4x4s2_bn_relu(dec + u.a[L], dec + u.b[L], dw->conv_w[i + 1], dw->conv_b[i + 1], n, H, W, mid, planes, st);
+        }
+        if (rc) break;
+        rc = run_conv(st, 12, conv1(dec + u.b[L], dec + u.c[L], L < 4 ? enc[L + 1] : nullptr, i + 2, 2 * H, 2 * W));
+        x = dec + u.c[L];
+    }
+    if (rc) return rc;
+    if (tail) {                                           // per output pixel: a quarter of the 64 -> 16 conv, 4 taps x 16 x 16, 16 -> 32, the head
+        ProfScope ps(st, 14, 2.0 * n * (2 * u.r_h[4]) * (2 * u.r_w[4]) * (64.0 * 16.0 / 4.0 + 4.0 * 16.0 * 16.0 + 16.0 * 32.0 + 32.0 * dw->classes));
+        return wsi_linknet_tail_dispatch(x, dw->tail_w, n, u.r_h[4], u.r_w[4], dw->classes, logits_out, st);
+    }
+    if (!dw->head_w || !dw->head_b) return WSI_EINVAL;    // (a blob without the plain head, on a shape the fused kernel does not take)
+    ProfScope ps(st, 8, 2.0 * n * (2 * u.r_h[4]) * (2 * u.r_w[4]) * (double)dw->head_cin * dw->classes);
+    return wsi_unet_head_dispatch(x, n, 2 * u.r_h[4], 2 * u.r_w[4], dw->cout[14], dw->head_w, dw->head_b, dw->head_cin, dw->classes, logits_out,
+                                  planes, st);
+}
+// The Linknet as a decoder of the segmentation sequence (seg_host.h): it reads all five maps; BasicBlock encoders only.
+struct LinknetDec {
+    using Weights = wsi_linknet_decoder_weights;
+    using Plan = LinknetPlan;
+    static constexpr auto plan = linknet_plan;
+    static constexpr auto ready = linknet_ready;
+    static constexpr auto run = linknet_decoder_run;
+    static constexpr bool needs_x0 = true;
+    static constexpr int only_stage = 0;
+};
+WSI_SEG_ENTRIES(wsi_linknet, BasicNet, LinknetDec)

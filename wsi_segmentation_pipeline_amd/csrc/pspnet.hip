@@ -13,9 +13,10 @@
 //                 src = dst * (S - 1) / (L - 1) in fp32, 0 where L = 1 or S = 1, neighbours clamped) of that size's S x S grid.
 //   psp_up      : the first `classes` channels of a PF map (n, h, w, one line) -> fp32 NCHW [n][classes][8h][8w], bilinear, align_corners=True.
 // PF tensors are read and written in whole 16-byte pieces (planes 1 and 2); the pad ring is never written.
+// Below the kernels and the single-op entries: the PSPNet decoder on the host - its workspace plan, its launch sequence, `PspDec` and the
+// exported wsi_pspnet_* / wsi_pspnet_bneck_* entries (seg_host.h WSI_SEG_ENTRIES).
 #include "pf_lines.h"
-#include "internal.h"
-#include "../../include/wsi_hip.h"
+#include "seg_host.h"
 
 constexpr int PSP_STAGES = 4, PSP_BINS = 50, PSP_COLS = 12, PSP_OUT = 512;
 static __host__ __device__ constexpr int psp_size(int s) { return s == 0 ? 1 : s == 1 ? 2 : s == 2 ? 3 : 6; }
@@ -258,9 +259,9 @@ static bool psp_map_ok(int n, int h, int w, int planes) {
     return n > 0 && h > 0 && w > 0 && (planes == 1 || planes == 2) && (long long)h * w < (1ll << 26) && (long long)n * h * w < (1ll << 31) / 64;
 }
 
-bool wsi_psp_width_ok(int c) { return c == 128 || c == 512; }      // the feature map's channels: x2 of a BasicBlock / Bottleneck encoder
+static bool wsi_psp_width_ok(int c) { return c == 128 || c == 512; }      // the feature map's channels: x2 of a BasicBlock / Bottleneck encoder
 
-int wsi_psp_pool_dispatch(const void* in, float* pooled, int n, int h, int w, int c, int planes, hipStream_t st) {
+static int wsi_psp_pool_dispatch(const void* in, float* pooled, int n, int h, int w, int c, int planes, hipStream_t st) {
     if (!in || !pooled || !psp_map_ok(n, h, w, planes) || c <= 0 || c % (planes == 1 ? 64 : 32) || (long long)n * c >= (1ll << 30)) return WSI_EINVAL;
     const PFGeom g = pf_geom(n, h, w, c);
     if (planes == 2) hipLaunchKernelGGL(psp_pool_kernel<2>, dim3(n * (c / 32)), dim3(128), 0, st, (const char*)in, g, pooled);
@@ -282,7 +283,7 @@ static int psp_linear(const float* X, const PspMats& m, float* Y, int n, int K, 
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
-int wsi_psp_project_dispatch(const float* pooled, const float* const stage_w[4], const float* const stage_b[4], const float* const proj_w[4],
+static int wsi_psp_project_dispatch(const float* pooled, const float* const stage_w[4], const float* const stage_b[4], const float* const proj_w[4],
                              float* mid, float* proj, int n, int c, hipStream_t st) {
     if (!pooled || !stage_w || !stage_b || !proj_w || !mid || !proj || mid == proj || pooled == mid || pooled == proj || n <= 0 ||
         n > (1 << 24) || !wsi_psp_width_ok(c))
@@ -297,7 +298,7 @@ int wsi_psp_project_dispatch(const float* pooled, const float* const stage_w[4],
     return rc ? rc : psp_linear(mid, b, proj, n, c / 4, PSP_OUT, 0, st);
 }
 
-int wsi_psp_expand_dispatch(const float* proj, void* out, int n, int h, int w, int planes, hipStream_t st) {
+static int wsi_psp_expand_dispatch(const float* proj, void* out, int n, int h, int w, int planes, hipStream_t st) {
     if (!proj || !out || !psp_map_ok(n, h, w, planes)) return WSI_EINVAL;
     const PFGeom g = pf_geom(n, h, w, PSP_OUT);
     PspScales sc;
@@ -308,7 +309,7 @@ int wsi_psp_expand_dispatch(const float* proj, void* out, int n, int h, int w, i
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
-int wsi_psp_up_dispatch(const void* in, float* logits, int n, int h, int w, int classes, int factor, int planes, hipStream_t st) {
+static int wsi_psp_up_dispatch(const void* in, float* logits, int n, int h, int w, int classes, int factor, int planes, hipStream_t st) {
     if (!in || !logits || !psp_map_ok(n, h, w, planes) || classes <= 0 || classes > 16 || (factor != 4 && factor != 8) ||
         (long long)h * w * factor * factor >= (1ll << 31) || (long long)n * classes >= (1ll << 31))
         return WSI_EINVAL;
@@ -348,3 +349,74 @@ int wsi_pspnet_head_up8(const void* in_pf, const void* head_wpk, const float* he
                                 .cout = planes == 1 ? 64 : 32, .stride = 1, .ksize = 3, .relu = 0, .planes = planes, .stream = stream});
     return rc ? rc : wsi_psp_up_dispatch(head_scratch_pf, logits_out, n, h, w, classes, 8, planes, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------ PSPNet (dense 'seg' path, pyramid-pooling decoder)
+// smp's PSPNet decoder on either trunk (include/wsi_hip.h "PSPNet") at psp_in_factor 8: it reads one map, f = the last block of layer 2 at
+// / 8 (only_stage = 2: the net stops there).  The fusing 1x1 conv over cat([up(stage0..3), f]) is computed as Wf . f with the pyramid term
+// sum_I up(W_I . stage_I) as its pre-ReLU residual: pool f into 50 bins per image, run the stage convs and the W_I slices on those 50
+// pixels, expand bilinearly into a 512-channel PF tensor.  Then the 3x3 head on one stored line of output channels and the bilinear x8.
+constexpr int PSP_WIDTH = 512, PSP_BINS_PER_IMAGE = 50;
+struct PspPlan {
+    size_t x0, pooled, mid, proj, pyr, fused, head, total;
+    int fh, fw, fc, line;                             // the feature map and its channels; channels of one stored line
+};
+static int psp_plan(const int ec[5], const wsi_pspnet_decoder_weights* dw, int n, int h, int w, int planes, PspPlan& u) {
+    if (!dw || n <= 0 || h <= 0 || w <= 0 || h % 32 || w % 32 || planes < 1 || planes > 2) return WSI_EINVAL;
+    u.fh = h / 8; u.fw = w / 8; u.fc = ec[2]; u.line = planes == 1 ? 64 : 32;
+    if (dw->feat_c != u.fc || !wsi_psp_width_ok(u.fc) || dw->cin[0] != u.fc || dw->cout[0] != PSP_WIDTH || dw->cin[1] != PSP_WIDTH ||
+        dw->cout[1] != u.line || dw->classes <= 0 || dw->classes > 16)
+        return WSI_EINVAL;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { const size_t o = off; off += align_up(bytes, 256); return o; };
+    u.x0 = take(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes));
+    u.pooled = take((size_t)n * PSP_BINS_PER_IMAGE * u.fc * sizeof(float));
+    u.mid = take((size_t)n * PSP_BINS_PER_IMAGE * (u.fc / 4) * sizeof(float));
+    u.proj = take((size_t)n * PSP_BINS_PER_IMAGE * PSP_WIDTH * sizeof(float));
+    u.pyr = take(wsi_pf_bytes(n, u.fh, u.fw, PSP_WIDTH, planes));
+    u.fused = take(wsi_pf_bytes(n, u.fh, u.fw, PSP_WIDTH, planes));
+    u.head = take(wsi_pf_bytes(n, u.fh, u.fw, u.line, planes));
+    u.total = off;
+    return WSI_OK;
+}
+static bool psp_ready(const wsi_pspnet_decoder_weights* dw) {
+    for (int i = 0; i < 2; ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    for (int i = 0; i < 4; ++i) if (!dw->stage_w[i] || !dw->stage_b[i] || !dw->proj_w[i]) return false;
+    return true;
+}
+// wsi_prof kinds: the four memory-bound kinds of csrc/pspnet.hip, which carry no FLOPs - 18 = pyramid pool, 19 = stage projection,
+// 20 = pyramid expand, 21 = head x8 upsample - and 12 = the fusing 1x1 conv, 6 = the 3x3 head conv (over its stored output channels)
+static int psp_decoder_run(const wsi_pspnet_decoder_weights* dw, const PspPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                           float* logits_out, hipStream_t st) {
+    const void* f = enc[2];
+    float *pooled = (float*)(dec + u.pooled), *mid = (float*)(dec + u.mid), *proj = (float*)(dec + u.proj);
+    int rc;
+    { ProfScope ps(st, 18, 0.0); rc = wsi_psp_pool_dispatch(f, pooled, n, u.fh, u.fw, u.fc, planes, st); }
+    if (rc) return rc;
+    { ProfScope ps(st, 19, 0.0); rc = wsi_psp_project_dispatch(pooled, dw->stage_w, dw->stage_b, dw->proj_w, mid, proj, n, u.fc, st); }
+    if (rc) return rc;
+    { ProfScope ps(st, 20, 0.0); rc = wsi_psp_expand_dispatch(proj, dec + u.pyr, n, u.fh, u.fw, planes, st); }
+    if (rc) return rc;
+    // relu(Wf . f + shift + pyramid term): the pyramid tensor is the 1x1 conv's residual, added before the ReLU
+    rc = run_conv(st, 12, ConvCall{.in = f, .out = dec + u.fused, .resid = dec + u.pyr, .wpk = dw->conv_w[0], .bias = dw->conv_b[0], .n = n,
+                                   .h = u.fh, .w = u.fw, .cin = u.fc, .cout = PSP_WIDTH, .stride = 1, .ksize = 1, .relu = 1, .planes = planes,
+                                   .stream = st});
+    if (rc) return rc;
+    // the head's output channels are zero-padded to one line (zero weights, zero bias): signed logits at / 8, no ReLU
+    rc = run_conv(st, 6, ConvCall{.in = dec + u.fused, .out = dec + u.head, .wpk = dw->conv_w[1], .bias = dw->conv_b[1], .n = n, .h = u.fh,
+                                  .w = u.fw, .cin = PSP_WIDTH, .cout = u.line, .stride = 1, .ksize = 3, .relu = 0, .planes = planes, .stream = st});
+    if (rc) return rc;
+    ProfScope ps(st, 21, 0.0);
+    return wsi_psp_up_dispatch(dec + u.head, logits_out, n, u.fh, u.fw, dw->classes, 8, planes, st);
+}
+// The PSPNet as a decoder of the segmentation sequence (seg_host.h): it reads the last block of layer 2 alone.
+struct PspDec {
+    using Weights = wsi_pspnet_decoder_weights;
+    using Plan = PspPlan;
+    static constexpr auto plan = psp_plan;
+    static constexpr auto ready = psp_ready;
+    static constexpr auto run = psp_decoder_run;
+    static constexpr bool needs_x0 = false;
+    static constexpr int only_stage = 2;
+};
+WSI_SEG_ENTRIES(wsi_pspnet, BasicNet, PspDec)
+WSI_SEG_ENTRIES(wsi_pspnet_bneck, BneckNet, PspDec)

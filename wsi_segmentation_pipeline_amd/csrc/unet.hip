@@ -8,8 +8,10 @@
 //                     64-channel, half-resolution skip connection x0 that the fused stem + maxpool kernel never materialises
 //   unet_head       : final_conv (1x1, <= 64 input channels, K classes) from PF lines straight to fp32 NCHW logits
 // All three are plain HBM-bound copies / dot products.
+// Below the kernels: the U-Net decoder on the host - its workspace plan, its launch sequence, `UnetDec` and the exported wsi_unet_* /
+// wsi_unet_bneck_* entries (seg_host.h WSI_SEG_ENTRIES).
 #include "pf_lines.h"
-#include "internal.h"
+#include "seg_host.h"
 
 // out (N, 2h, 2w, Cx + Cs) <- x (N, h, w, Cx) upsampled x2 | skip (N, 2h, 2w, Cs); one 16-byte piece per thread
 __global__ __launch_bounds__(256) void upsample_concat_kernel(const char* x, const char* skip, char* out, PFGeom gx, PFGeom go,
@@ -186,3 +188,97 @@ int wsi_resize_nearest_dispatch(const float* src, long long planes_n, int hs, in
     hipLaunchKernelGGL(resize_nearest_kernel, dim3(grid_for(planes_n * hd * wd)), dim3(256), 0, st, src, planes_n, hs, ws, dst, hd, wd);
     return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
+
+// ------------------------------------------------------------------------------------ the decoder's host sequence (dense 'seg' path)
+// smp-style decoder on either trunk (any depth: the five encoder maps keep their channels, Net::enc_c): five blocks of [nearest x2 upsample,
+// concat skip, 2 x (3x3 conv + BN + ReLU)] at channels 256/128/64/32/16 (stored padded to whole 128-byte lines - 32 channels in the
+// split-precision modes, 64 in speed mode; the padding channels carry zero weights), 1x1 head.  Everything below reads the encoder's
+// channels from the one table it is handed: block L takes the previous block's output (x4 = ec[0] for the first) and skips ec[L + 1].
+struct UnetPlan {
+    size_t x0, cat[5], mid[5], out[5], total;
+    int r_h[5], r_w[5], cx[5], cs[5];                        // resolution of block L; channels of its upsampled input and of its skip (0: none)
+};
+static int unet_plan(const int ec[5], const wsi_unet_decoder_weights* dw, int n, int h, int w, int planes, UnetPlan& u) {
+    if (!dw || n <= 0 || h % 32 || w % 32 || planes < 1 || planes > 3) return WSI_EINVAL;
+    size_t off = 0;
+    u.x0 = off; off += align_up(wsi_pf_bytes(n, h / 2, w / 2, ec[4], planes), 256);
+    int cprev = ec[0];
+    for (int L = 0; L < 5; ++L) {
+        u.r_h[L] = (h / 16) << L; u.r_w[L] = (w / 16) << L; u.cx[L] = cprev; u.cs[L] = L < 4 ? ec[L + 1] : 0;
+        const int cin = cprev + u.cs[L], cout = dw->cout[2 * L];
+        if (dw->cin[2 * L] != cin || dw->cin[2 * L + 1] != cout || dw->cout[2 * L + 1] != cout || cout % (planes == 1 ? 64 : 32) || cout <= 0) return WSI_EINVAL;
+        u.cat[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cin, planes), 256);
+        u.mid[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cout, planes), 256);
+        u.out[L] = off; off += align_up(wsi_pf_bytes(n, u.r_h[L], u.r_w[L], cout, planes), 256);
+        cprev = cout;
+    }
+    if (dw->head_cin <= 0 || dw->head_cin > cprev || dw->classes <= 0) return WSI_EINVAL;
+    u.total = off;
+    return WSI_OK;
+}
+// every pointer a decoder run reads: the eight convs of blocks 1-4 always; the last block's two and the head unless the fused tail's blob
+// stands in for them (where the tail then does not apply, conv_common refuses the null pointer)
+static bool decoder_ready(const wsi_unet_decoder_weights* dw) {
+    for (int i = 0; i < (dw->tail_w ? 8 : 10); ++i) if (!dw->conv_w[i] || !dw->conv_b[i]) return false;
+    return dw->tail_w || (dw->head_w && dw->head_b);
+}
+
+// the decoder on five PF encoder maps (x4 deepest ... x0 = stem output at half resolution), `dec` = decoder part of the workspace
+static int unet_decoder_run(const wsi_unet_decoder_weights* dw, const UnetPlan& u, const void* const enc[5], int n, int planes, char* dec,
+                            float* logits_out, hipStream_t st) {
+    const void* x = enc[0];
+    int rc = WSI_OK;
+    // wsi_prof kinds of the decoder (bench.py --workload seg): 6 = decoder 3x3 conv (algorithmic FLOPs over REAL channels are the
+    // caller's business: the record carries 2 * N * H * W * cin_stored * cout_stored * 9), 7 = upsample + concat glue, 8 = 1x1 head
+    // r05: parity mode runs the last block and the head as ONE kernel (tail.hip) when the caller prepacked its weights
+    // (wsi_unet_tail_prepack -> dw->tail_w) and the map is at most 256 wide; A/B: WSI_CONV_MODE_UNET_NO_TAIL
+    const bool tail = planes == 2 && dw->tail_w && g_routes.unet_tail && u.cx[4] == 32 && u.cs[4] == 0 && dw->classes <= 4 &&
+                      u.r_w[3] % 32 == 0 && u.r_w[3] <= 128 &&
+                      (size_t)pf_alloc_pixels(n, u.r_h[3], u.r_w[3]) * 128 <= (size_t)0x7fffffff;      // (32-bit buffer offsets into x4: ~1000 tiles of 256 x 256)
+    for (int L = 0; L < (tail ? 4 : 5) && !rc; ++L) {
+        const int H = u.r_h[L], W = u.r_w[L], cin = dw->cin[2 * L], cout = dw->cout[2 * L];
+        // r04: the block's first conv reads the low-resolution tensor and the skip directly (ConvArgs.in_up: nearest x2 upsample +
+        // concat as source addresses of its slab DMA) where the shape's kernel is the slab3 kernel; otherwise (EINVAL) the
+        // upsample_concat pass writes the concatenated tensor first, as in r02-r03
+        // conv j of the decoder (3x3, stride 1, ReLU) at this block's resolution
+        auto conv3 = [&](const void* in, void* out, int j, int ci) {
+            return ConvCall{.in = in, .out = out, .wpk = dw->conv_w[j], .bias = dw->conv_b[j], .n = n, .h = H, .w = W, .cin = ci, .cout = cout,
+                            .stride = 1, .ksize = 3, .relu = 1, .planes = planes, .stream = st};
+        };
+        {
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            rc = g_routes.unet_fuse_up ? wsi_conv3x3_up_concat_bn_act(x, L < 4 ? enc[L + 1] : nullptr, dec + u.mid[L], dw->conv_w[2 * L], dw->conv_b[2 * L],
+                                                                      n, H, W, u.cx[L], u.cs[L], cout, 1, planes, st)
+                                       : WSI_EINVAL;
+            if (rc == WSI_EINVAL) ps.relabel(9);          // (a refused launch: its empty record is not a decoder conv)
+        }
+        if (rc == WSI_EINVAL) {
+            { ProfScope ps(st, 7, 0.0); rc = wsi_upsample_concat_dispatch(x, L < 4 ? enc[L + 1] : nullptr, dec + u.cat[L], n, H / 2, W / 2, u.cx[L], u.cs[L], planes, st); }
+            ProfScope ps(st, 6, conv_flops(n, H, W, cin, cout, 9));
+            if (!rc) rc = conv_common(conv3(dec + u.cat[L], dec + u.mid[L], 2 * L, cin));
+        }
+        ProfScope ps(st, 6, conv_flops(n, H, W, cout, cout, 9));
+        if (!rc) rc = conv_common(conv3(dec + u.mid[L], dec + u.out[L], 2 * L + 1, cout));
+        x = dec + u.out[L];
+    }
+    if (tail) {
+        ProfScope ps(st, 10, 2.0 * n * u.r_h[4] * u.r_w[4] * (9.0 * (32.0 * 16.0 + 16.0 * 16.0) + 16.0 * dw->classes));    // kind 10: the reference formulation's FLOPs over REAL channels
+        if (!rc) rc = wsi_unet_tail_dispatch(x, dw->tail_w, n, u.r_h[3], u.r_w[3], dw->classes, logits_out, st);
+        return rc;
+    }
+    ProfScope ps(st, 8, 2.0 * n * u.r_h[4] * u.r_w[4] * (double)dw->head_cin * dw->classes);
+    if (!rc) rc = wsi_unet_head_dispatch(x, n, u.r_h[4], u.r_w[4], dw->cout[9], dw->head_w, dw->head_b, dw->head_cin, dw->classes, logits_out, planes, st);
+    return rc;
+}
+// The U-Net as a decoder of the segmentation sequence (seg_host.h): it reads all five maps.
+struct UnetDec {
+    using Weights = wsi_unet_decoder_weights;
+    using Plan = UnetPlan;
+    static constexpr auto plan = unet_plan;
+    static constexpr auto ready = decoder_ready;
+    static constexpr auto run = unet_decoder_run;
+    static constexpr bool needs_x0 = true;
+    static constexpr int only_stage = 0;
+};
+WSI_SEG_ENTRIES(wsi_unet, BasicNet, UnetDec)
+WSI_SEG_ENTRIES(wsi_unet_bneck, BneckNet, UnetDec)

@@ -168,60 +168,38 @@ SIGNATURES = {
     'wsi_mask_iou_counts': (_i, [_vp, _vp, _ll, _vp, _vp]),
     'wsi_score_counts': (_i, [_vp, _vp, _vp, _ll, _vp, _vp]),
     'wsi_esp': (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    'wsi_unet_workspace_bytes': (_sz, [C.POINTER(WsiUnetDecoderWeights), _i, _i, _i, _i]),
-    'wsi_unet_workspace_init': (_i, [C.POINTER(WsiUnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_unet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiUnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                              _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_unet_bneck_workspace_bytes': (_sz, [C.POINTER(WsiUnetDecoderWeights), _i, _i, _i, _i]),
-    'wsi_unet_bneck_workspace_init': (_i, [C.POINTER(WsiUnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_unet_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiUnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                                    _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_unet_bneck_decoder': (_i, [C.POINTER(WsiUnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_prepack_tconv_bytes': (_sz, [_i, _i]),
     'wsi_prepack_tconv': (_i, [_vp, _vp, _vp, _vp, _vp, _f, _i, _i, _vp, _vp]),
     'wsi_linknet_tail_prepack_bytes': (_sz, []),
     'wsi_linknet_tail_prepack': (_i, [_vp] * 15 + [_f, _vp, _vp, _i, _i, _i, _i, _vp]),
     'wsi_tconv4x4s2_bn_relu': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'wsi_conv1x1_bn_relu_add': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'wsi_linknet_workspace_bytes': (_sz, [C.POINTER(WsiLinknetDecoderWeights), _i, _i, _i, _i]),
-    'wsi_linknet_workspace_init': (_i, [C.POINTER(WsiLinknetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_linknet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiLinknetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                                 _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_linknet_decoder': (_i, [C.POINTER(WsiLinknetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_groupnorm_scratch_bytes': (_sz, [_i, _i, _i]),
     'wsi_groupnorm_relu_up2': (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _i, _vp, _vp]),
     'wsi_fpn_merge_head_up4': (_i, [C.POINTER(C.c_void_p * 4), _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     'wsi_upsample2_nearest': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
-    'wsi_fpn_workspace_bytes': (_sz, [C.POINTER(WsiFpnDecoderWeights), _i, _i, _i, _i]),
-    'wsi_fpn_workspace_init': (_i, [C.POINTER(WsiFpnDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_fpn_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiFpnDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                             _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_fpn_decoder': (_i, [C.POINTER(WsiFpnDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    'wsi_fpn_bneck_workspace_bytes': (_sz, [C.POINTER(WsiFpnDecoderWeights), _i, _i, _i, _i]),
-    'wsi_fpn_bneck_workspace_init': (_i, [C.POINTER(WsiFpnDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_fpn_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiFpnDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                                   _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_fpn_bneck_decoder': (_i, [C.POINTER(WsiFpnDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_pyramid_pool': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'wsi_pspnet_stage_project': (_i, [_vp, C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4), C.POINTER(C.c_void_p * 4), _vp, _vp, _i, _i, _vp]),
     'wsi_pyramid_expand': (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     'wsi_pspnet_head_up8': (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    'wsi_pspnet_workspace_bytes': (_sz, [C.POINTER(WsiPspnetDecoderWeights), _i, _i, _i, _i]),
-    'wsi_pspnet_workspace_init': (_i, [C.POINTER(WsiPspnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_pspnet_forward': (_i, [C.POINTER(WsiTrunkWeights), C.POINTER(WsiPspnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                                _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_pspnet_decoder': (_i, [C.POINTER(WsiPspnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
-    'wsi_pspnet_bneck_workspace_bytes': (_sz, [C.POINTER(WsiPspnetDecoderWeights), _i, _i, _i, _i]),
-    'wsi_pspnet_bneck_workspace_init': (_i, [C.POINTER(WsiPspnetDecoderWeights), _vp, _i, _i, _i, _i, _vp]),
-    'wsi_pspnet_bneck_forward': (_i, [C.POINTER(WsiBneckWeights), C.POINTER(WsiPspnetDecoderWeights), _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i,
-                                      _vp, _i, _vp, C.POINTER(C.c_void_p * 5), _vp]),
-    'wsi_pspnet_bneck_decoder': (_i, [C.POINTER(WsiPspnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_resize_nearest_f32': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _vp]),
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_mlp_views': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),
-    'wsi_unet_decoder': (_i, [C.POINTER(WsiUnetDecoderWeights), C.POINTER(C.c_void_p * 5), _i, _i, _i, _i, _vp, _i, _vp, _vp]),
 }
+# the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
+_enc5 = C.POINTER(C.c_void_p * 5)
+for _prefix, _trunk, _dec in (('wsi_unet', WsiTrunkWeights, WsiUnetDecoderWeights), ('wsi_unet_bneck', WsiBneckWeights, WsiUnetDecoderWeights),
+                              ('wsi_linknet', WsiTrunkWeights, WsiLinknetDecoderWeights),
+                              ('wsi_fpn', WsiTrunkWeights, WsiFpnDecoderWeights), ('wsi_fpn_bneck', WsiBneckWeights, WsiFpnDecoderWeights),
+                              ('wsi_pspnet', WsiTrunkWeights, WsiPspnetDecoderWeights), ('wsi_pspnet_bneck', WsiBneckWeights, WsiPspnetDecoderWeights)):
+    _wt, _dw = C.POINTER(_trunk), C.POINTER(_dec)
+    SIGNATURES.update({
+        _prefix + '_workspace_bytes': (_sz, [_dw, _i, _i, _i, _i]),
+        _prefix + '_workspace_init': (_i, [_dw, _vp, _i, _i, _i, _i, _vp]),
+        _prefix + '_forward': (_i, [_wt, _dw, _vp, _vp, _ll, _i, _i, _vp, _vp, _i, _i, _i, _vp, _i, _vp, _enc5, _vp]),
+        _prefix + '_decoder': (_i, [_dw, _enc5, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    })
 
 
 def build(verbose=False):
@@ -314,6 +292,22 @@ def stem_mode(fused, rows=64):
         yield
     finally:
         lib.wsi_stem_set_mode(int(StemMode.FUSED), 64)
+
+
+def profiled(run, max_records=256, ms=False):
+    """(what run() returns, the profiler's records of it): wsi_prof_begin(max_records), run(), wsi_prof_end.  One (kind, flops) per launch
+    in launch order, (kind, flops, milliseconds) with `ms`; wsi_prof_end waits for the recorded events.  RuntimeError where the records
+    filled the table (the run may have made more launches than were recorded)."""
+    lib = load()
+    check(lib.wsi_prof_begin(max_records), 'wsi_prof_begin')
+    try:
+        out = run()
+    finally:
+        t, kind, flops = (C.c_float * max_records)(), (C.c_int * max_records)(), (C.c_double * max_records)()
+        n = lib.wsi_prof_end(t, kind, flops, max_records)
+    if not 0 <= n < max_records:
+        raise RuntimeError('wsi_prof_end returned %d of at most %d records' % (n, max_records))
+    return out, [(kind[i], flops[i]) + ((t[i],) if ms else ()) for i in range(n)]
 
 
 def check(rc, what):

@@ -246,98 +246,56 @@ def make_he_patches(seed, n, size=256):
     return out
 
 
+# model -> (offset of the decoder generator's seed, name of the decoder's key-list function in .unet); every golden and every recorded
+# profile depends on these offsets, on the generator and on the draw order
+SEG_DECODERS = {'unet': (5000, 'decoder_key_shapes'), 'linknet': (7000, 'linknet_decoder_key_shapes'),
+                'fpn': (9000, 'fpn_decoder_key_shapes'), 'pspnet': (11000, 'pspnet_decoder_key_shapes')}
+
+
+def make_seg_state_dict(model, seed, arch, layers, classes=4):
+    """Seeded state dict of a 'seg' model ('unet', 'linknet', 'fpn' or 'pspnet') on an encoder of block type `arch` ('basic' or
+    'bottleneck') and depth `layers`: encoder.* = make_resnet_state_dict / make_bottleneck_state_dict(seed, layers) without its heads,
+    decoder.* per the model's key list in wsi_segmentation_pipeline_amd.unet, drawn in state-dict order from PCG64(seed + the model's
+    offset) - 'conv' / 'tconv' for the conv weights, 'lin_b' for conv biases, the BatchNorm kinds as everywhere ('bn_w' / 'bn_b' also for
+    a GroupNorm's weight / bias).  The decoder draw depends on the block type (the encoder maps' channels), not on the depth."""
+    from . import unet
+    offset, key_shapes = SEG_DECODERS[model]
+    make = make_bottleneck_state_dict if arch == 'bottleneck' else make_resnet_state_dict
+    sd = {'encoder.' + k: v for k, v in make(seed, layers, with_fc=False).items() if not k.startswith('fc')}
+    rng = np.random.Generator(np.random.PCG64(seed + offset))
+    for key, shape, kind in getattr(unet, key_shapes)(classes, *([] if model == 'linknet' else [unet.ENC_CH[arch]])):
+        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
+    return sd
+
+
 def make_unet_state_dict(seed, classes=4):
-    """Seeded state dict of the U-Net 'seg' model (encoder.* = the ResNet-18 trunk keys of make_resnet18_state_dict(seed),
-    decoder.* per wsi_segmentation_pipeline_amd.unet.decoder_key_shapes), randomised BN statistics as everywhere."""
-    return make_unet_resnet_state_dict(seed, RESNET18_LAYERS, classes)
+    """make_seg_state_dict('unet', ...) on ResNet-18 (encoder.* = the trunk keys of make_resnet18_state_dict(seed))."""
+    return make_seg_state_dict('unet', seed, 'basic', RESNET18_LAYERS, classes)
 
 
 def make_unet_resnet_state_dict(seed, layers, classes=4):
-    """make_unet_state_dict with a BasicBlock encoder of any depth (encoder.* = make_resnet_state_dict(seed, layers) without its
-    heads); the decoder draw does not depend on the depth: the five encoder maps keep their channels."""
-    from .unet import decoder_key_shapes
-    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    rng = np.random.Generator(np.random.PCG64(seed + 5000))
-    for key, shape, kind in decoder_key_shapes(classes):
-        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
-    return sd
+    return make_seg_state_dict('unet', seed, 'basic', layers, classes)
 
 
 def make_unet_bottleneck_state_dict(seed, layers, classes=4):
-    """make_unet_resnet_state_dict with a Bottleneck encoder (encoder.* = make_bottleneck_state_dict(seed, layers, with_fc=False) without
-    its heads): the decoder is drawn for encoder maps of 2048 / 1024 / 512 / 256 / 64 channels."""
-    from .unet import ENC_CH, decoder_key_shapes
-    sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    rng = np.random.Generator(np.random.PCG64(seed + 5000))
-    for key, shape, kind in decoder_key_shapes(classes, ENC_CH['bottleneck']):
-        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
-    return sd
+    return make_seg_state_dict('unet', seed, 'bottleneck', layers, classes)
 
 
 def make_linknet_state_dict(seed, layers=RESNET18_LAYERS, classes=4):
-    """Seeded state dict of the Linknet 'seg' model: encoder.* = make_resnet_state_dict(seed, layers) without its heads, decoder.* per
-    wsi_segmentation_pipeline_amd.unet.linknet_decoder_key_shapes, drawn in state-dict order from one generator (the decoder draw does
-    not depend on the depth); randomised BN statistics as everywhere."""
-    from .unet import linknet_decoder_key_shapes
-    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    rng = np.random.Generator(np.random.PCG64(seed + 7000))
-    for key, shape, kind in linknet_decoder_key_shapes(classes):
-        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
-    return sd
-
-
-def _with_fpn_decoder(sd, seed, classes, enc_ch):
-    from .unet import fpn_decoder_key_shapes
-    rng = np.random.Generator(np.random.PCG64(seed + 9000))
-    for key, shape, kind in fpn_decoder_key_shapes(classes, enc_ch):
-        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
-    return sd
+    return make_seg_state_dict('linknet', seed, 'basic', layers, classes)
 
 
 def make_fpn_state_dict(seed, layers=RESNET18_LAYERS, classes=4):
-    """Seeded state dict of the FPN 'seg' model: encoder.* as make_linknet_state_dict builds it, decoder.* per
-    wsi_segmentation_pipeline_amd.unet.fpn_decoder_key_shapes, drawn in state-dict order from PCG64(seed + 9000): 'conv' for the conv
-    weights, 'lin_b' for the conv biases, 'bn_w' / 'bn_b' for the GroupNorm weight / bias."""
-    from .unet import ENC_CH
-    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    return _with_fpn_decoder(sd, seed, classes, ENC_CH['basic'])
+    return make_seg_state_dict('fpn', seed, 'basic', layers, classes)
 
 
 def make_fpn_bottleneck_state_dict(seed, layers=RESNET50_LAYERS, classes=4):
-    """make_fpn_state_dict with a Bottleneck encoder (encoder.* = make_bottleneck_state_dict(seed, layers, with_fc=False) without its
-    heads): the four 1x1 laterals are drawn for encoder maps of 2048 / 1024 / 512 / 256 channels."""
-    from .unet import ENC_CH
-    sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    return _with_fpn_decoder(sd, seed, classes, ENC_CH['bottleneck'])
-
-
-def _with_pspnet_decoder(sd, seed, classes, enc_ch):
-    from .unet import pspnet_decoder_key_shapes
-    rng = np.random.Generator(np.random.PCG64(seed + 11000))
-    for key, shape, kind in pspnet_decoder_key_shapes(classes, enc_ch):
-        sd[key] = torch.from_numpy(np.asarray(_fill(rng, shape, kind)))
-    return sd
+    return make_seg_state_dict('fpn', seed, 'bottleneck', layers, classes)
 
 
 def make_pspnet_state_dict(seed, layers=RESNET18_LAYERS, classes=4):
-    """Seeded state dict of the PSPNet 'seg' model: encoder.* as make_fpn_state_dict builds it (layers 3 and 4 included: smp checkpoints
-    carry them), decoder.* per wsi_segmentation_pipeline_amd.unet.pspnet_decoder_key_shapes, drawn in state-dict order from
-    PCG64(seed + 11000): 'conv' for the conv weights, 'lin_b' for the two conv biases, the BatchNorm kinds as everywhere."""
-    from .unet import ENC_CH
-    sd = {'encoder.' + k: v for k, v in make_resnet_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    return _with_pspnet_decoder(sd, seed, classes, ENC_CH['basic'])
+    return make_seg_state_dict('pspnet', seed, 'basic', layers, classes)
 
 
 def make_pspnet_bottleneck_state_dict(seed, layers=RESNET50_LAYERS, classes=4):
-    """make_pspnet_state_dict with a Bottleneck encoder (encoder.* = make_bottleneck_state_dict(seed, layers, with_fc=False) without its
-    heads): the decoder is drawn for a feature map of 512 channels."""
-    from .unet import ENC_CH
-    sd = {'encoder.' + k: v for k, v in make_bottleneck_state_dict(seed, layers, with_fc=False).items()
-          if not k.startswith('fc')}
-    return _with_pspnet_decoder(sd, seed, classes, ENC_CH['bottleneck'])
+    return make_seg_state_dict('pspnet', seed, 'bottleneck', layers, classes)

@@ -37,8 +37,14 @@ What a decoder consists of is written once, as a `Decoder` description (`unet_de
 state-dict order with real and stored widths and what follows each (BatchNorm, GroupNorm or a bias).  The key lists (`decoder_key_shapes`,
 `linknet_decoder_key_shapes`, `fpn_decoder_key_shapes`, `pspnet_decoder_key_shapes`), the packing of the device
 weights (`pack_decoder`, host work only) and the layers of the ``nn.Module`` decoders are read from it.
-Eval-mode forwards run on libwsi_hip.so only (csrc/unet.hip, csrc/linknet.hip, csrc/fpn.hip, csrc/pspnet.hip, csrc/tail.hip behind one entry prefix per model and
-encoder block type); training mode uses torch ops so ``train.py``-style callers still run.
+One engine serves all four models: `UNetEngine` holds the encoder, the workspace, the forwards, `decode`, the one uploader (`_upload`) and
+the one `_pack_decoder`; `LinknetEngine`, `FPNEngine` and `PSPNetEngine` state what differs - the entry prefixes and with them the encoder
+block types (`ENTRY`), the precisions (`PLANES`), how a refusal names the model (`NOUN`), the encoder maps the decoder reads (`READS`),
+the description (`_describe`) and what their C struct holds beyond convs, head and tail (`_pack_own`).  The four smp factories share one
+body (`_factory` over `SEG_MODELS`).
+Eval-mode forwards run on libwsi_hip.so only: per model and encoder block type one entry prefix, whose four entries are defined in the
+file that holds the decoder's kernels and host sequence (csrc/unet.hip + csrc/tail.hip, csrc/linknet.hip, csrc/fpn.hip, csrc/pspnet.hip)
+on the sequence of csrc/seg_host.h; training mode uses torch ops so ``train.py``-style callers still run.
 """
 import collections
 import ctypes as C
@@ -297,19 +303,31 @@ def pack_decoder(lib, state_dict, dec, planes, classes):
 class UNetEngine:
     """ResNet encoder + smp-style decoder on HIP kernels.  state_dict: ``encoder.*`` + ``decoder.*`` keys.  The encoder's block type and
     depth are read from the state dict (`engine.trunk_arch`): BasicBlock nets run on a TrunkEngine and wsi_unet_*, Bottleneck nets on a
-    BottleneckEngine and wsi_unet_bneck_* (parity and speed only).  `encoder` (an smp name), when given, must agree with the state dict."""
+    BottleneckEngine and wsi_unet_bneck_* (parity and speed only).  `encoder` (an smp name), when given, must agree with the state dict.
+    The other models are subclasses that state what differs: the four class attributes, `_describe` and, where the C struct holds more
+    than convs, head and tail, `_pack_own`."""
 
-    ENTRY = {'basic': 'wsi_unet', 'bottleneck': 'wsi_unet_bneck'}      # prefix of the four C entries, per encoder architecture
+    ENTRY = {'basic': 'wsi_unet', 'bottleneck': 'wsi_unet_bneck'}      # prefix of the four C entries per encoder block type; the model runs on these block types only
+    PLANES = (PARITY, MX, SPEED)                             # the precisions it runs in (mx: BasicBlock encoders only)
+    NOUN = 'a U-Net'                                         # how a refusal names it
+    READS = (0, 1, 2, 3, 4)                                  # the encoder maps (deepest first) its decoder reads
 
     def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
         self._ws = {}
         self.lib = native.load()
         self.device = torch.device(device)
+        archs = tuple(self.ENTRY)
+        if MX not in self.PLANES and planes not in self.PLANES:        # (a model with an mx mode leaves a bad value to its trunk engine)
+            raise ValueError("%s runs in precision 'parity' or 'speed': there is no mx mode" % self.NOUN)
+        if encoder is not None and len(archs) == 1:
+            encoder_spec(encoder, archs, where=BLOCK_RESNETS[archs[0]])
         enc_sd = {k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')}
         self.arch = trunk_arch(enc_sd)[0]
+        if self.arch not in archs:
+            raise ValueError('%s runs on BasicBlock encoders only (%s)' % (self.NOUN, sorted(ENCODER_LAYERS)))
         if self.arch == 'bottleneck':
             if planes == MX:
-                raise ValueError("a U-Net on a Bottleneck encoder runs in precision 'parity' or 'speed': there is no mx mode")
+                raise ValueError("%s on a Bottleneck encoder runs in precision 'parity' or 'speed': there is no mx mode" % self.NOUN)
             self.trunk = BottleneckEngine(enc_sd, device, planes=planes)
         else:
             self.trunk = TrunkEngine(enc_sd, device, planes=planes)
@@ -328,22 +346,33 @@ class UNetEngine:
     def _describe(self):
         return unet_decoder(self.enc_ch, self.planes)
 
+    def _upload(self, a):
+        """One array to the device, kept alive; returns its address.  Contiguous; uint8 (packed weights, a tail blob) stays uint8,
+        everything else becomes float32."""
+        a = np.ascontiguousarray(a, dtype=np.uint8 if a.dtype == np.uint8 else np.float32)
+        self._keep.append(torch.from_numpy(a).to(self.device))
+        return self._keep[-1].data_ptr()
+
     def _pack_decoder(self, state_dict):
-        """Fill self.dw from the decoder.* keys: `pack_decoder`'s arrays, uploaded in its order and kept alive."""
+        """Fill self.dw from the decoder.* keys: `pack_decoder`'s arrays of the rows the conv kernels run (a 'lin1' row is a subclass's
+        own), uploaded in its order and kept alive; then what the subclass adds (`_pack_own`); then the head and the tail where the
+        description has them."""
         dec = self._describe()
-        pk = pack_decoder(self.lib, state_dict, dec, self.planes, self.classes)
-
-        def dev(a):
-            self._keep.append(torch.from_numpy(a).to(self.device))
-            return self._keep[-1].data_ptr()
-
+        pk = pack_decoder(self.lib, state_dict, dec._replace(rows=[r for r in dec.rows if r.kind != 'lin1']), self.planes, self.classes)
         dw = self.dw = dec.weights()
         for i, (w, bias) in enumerate(pk.convs):
-            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
+            dw.conv_w[i], dw.conv_b[i] = self._upload(w), self._upload(bias)
             dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
-        dw.head_w, dw.head_b = dev(pk.head_w), dev(pk.head_b)
-        dw.head_cin, dw.classes = dec.head_cin, self.classes
-        dw.tail_w = None if pk.tail is None else dev(pk.tail)
+        dw.classes = self.classes
+        self._pack_own(state_dict, pk)
+        if dec.head_cin is not None:
+            dw.head_w, dw.head_b = self._upload(pk.head_w), self._upload(pk.head_b)
+        if dec.tail is not None:                               # (the structs with a tail slot also carry the head's input width)
+            dw.head_cin = dec.head_cin
+            dw.tail_w = None if pk.tail is None else self._upload(pk.tail)
+
+    def _pack_own(self, state_dict, pk):
+        """What a model's C struct holds beyond convs, head and tail: uploaded after the convs."""
 
     def _workspace(self, n, h, w):
         key = (h, w)
@@ -428,14 +457,18 @@ class UNetEngine:
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
     def decode(self, enc):
-        """`model.decoder(encoding)`: five fp32 NCHW GPU maps (deepest first) -> logits."""
-        for t in enc:
-            _require_gpu(t, 'encoder map')
-        enc = [t.to(torch.float32).contiguous() for t in enc]
-        n, h, w = enc[0].shape[0], enc[0].shape[2] * 32, enc[0].shape[3] * 32
+        """`model.decoder(encoding)`: five fp32 NCHW maps (deepest first) -> logits.  Only the maps of `READS` are read and must be GPU
+        tensors; the other entries may be anything (None included) and reach the library as NULL."""
+        given, enc = list(enc), [None] * 5
+        for i in self.READS:
+            _require_gpu(given[i], 'encoder map')
+            enc[i] = given[i].to(torch.float32).contiguous()
+        first = enc[self.READS[0]]
+        scale = 32 >> self.READS[0]                            # map i of the four stage outputs is at 1 / (32 >> i) resolution
+        n, h, w = first.shape[0], first.shape[2] * scale, first.shape[3] * scale
         ws, cap = self._workspace(n, h, w)
         logits = torch.empty((n, self.classes, h, w), dtype=torch.float32, device=self.device)
-        ptrs = (C.c_void_p * 5)(*[t.data_ptr() for t in enc])
+        ptrs = (C.c_void_p * 5)(*[None if t is None else t.data_ptr() for t in enc])
         native.check(self._decoder(C.byref(self.dw), C.byref(ptrs), n, h, w, self.planes, _ptr(ws), cap, _ptr(logits), _stream()),
                      self._decoder.__name__)
         return logits
@@ -448,79 +481,36 @@ class FPNEngine(UNetEngine):
     in parity mode, ~64 MB on a Bottleneck one).  Precision 'parity' or 'speed'."""
 
     ENTRY = {'basic': 'wsi_fpn', 'bottleneck': 'wsi_fpn_bneck'}
-
-    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
-        if planes not in (PARITY, SPEED):
-            raise ValueError("an FPN runs in precision 'parity' or 'speed': there is no mx mode")
-        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+    PLANES, NOUN, READS = (PARITY, SPEED), 'an FPN', (0, 1, 2, 3)
 
     def _describe(self):
         return fpn_decoder(self.enc_ch)
 
-    def _pack_decoder(self, state_dict):
-        dec = self._describe()
-        pk = pack_decoder(self.lib, state_dict, dec, self.planes, self.classes)
-
-        def dev(a):
-            self._keep.append(torch.from_numpy(np.ascontiguousarray(a)).to(self.device))
-            return self._keep[-1].data_ptr()
-
-        dw = self.dw = dec.weights()
-        for i, (w, bias) in enumerate(pk.convs):
-            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
-            dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
+    def _pack_own(self, state_dict, pk):
         for i, (g, b) in enumerate(pk.gn):
-            dw.gn_w[i], dw.gn_b[i] = dev(g), dev(b)
-        dw.groups, dw.eps = FPN_GROUPS, GN_EPS
-        dw.head_w, dw.head_b, dw.classes = dev(pk.head_w), dev(pk.head_b), self.classes
+            self.dw.gn_w[i], self.dw.gn_b[i] = self._upload(g), self._upload(b)
+        self.dw.groups, self.dw.eps = FPN_GROUPS, GN_EPS
 
 
 class PSPNetEngine(UNetEngine):
     """ResNet encoder (either block type) + PSPNet decoder on HIP kernels (wsi_pspnet_* / wsi_pspnet_bneck_*; csrc/pspnet.hip for the
     pyramid pool, the stage projection, the pyramid expand and the head's x8 upsample, the existing conv kernels for the fusing 1x1 conv
-    and the 3x3 head): the surface of UNetEngine.  The decoder reads x2 only, so a forward that returns logits alone stops the encoder
-    after layer 2; with enc=True the whole encoder runs.  Precision 'parity' or 'speed'."""
+    and the 3x3 head): the surface of UNetEngine.  The decoder reads x2 only (`decode`: enc[2] at 1/8 resolution; the other four entries
+    may be None), so a forward that returns logits alone stops the encoder after layer 2; with enc=True the whole encoder runs.  Precision
+    'parity' or 'speed'."""
 
     ENTRY = {'basic': 'wsi_pspnet', 'bottleneck': 'wsi_pspnet_bneck'}
-
-    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
-        if planes not in (PARITY, SPEED):
-            raise ValueError("a PSPNet runs in precision 'parity' or 'speed': there is no mx mode")
-        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+    PLANES, NOUN, READS = (PARITY, SPEED), 'a PSPNet', (2,)
 
     def _describe(self):
         return pspnet_decoder(self.enc_ch, self.planes, self.classes)
 
-    def _pack_decoder(self, state_dict):
-        dec = self._describe()
-        convs = dec._replace(rows=dec.rows[4:])                # the two rows the conv kernels run: the fusing conv's feature columns, the head
-        pk = pack_decoder(self.lib, state_dict, convs, self.planes, self.classes)
+    def _pack_own(self, state_dict, pk):
         fold = pspnet_fold(state_dict, self.enc_ch[2])
-
-        def dev(a):
-            self._keep.append(torch.from_numpy(np.ascontiguousarray(a, dtype=a.dtype if a.dtype == np.uint8 else np.float32)).to(self.device))
-            return self._keep[-1].data_ptr()
-
-        dw = self.dw = dec.weights()
-        for i, (w, bias) in enumerate(pk.convs):
-            dw.conv_w[i], dw.conv_b[i] = dev(w), dev(bias)
-            dw.cin[i], dw.cout[i] = pk.cin[i], pk.cout[i]
         for i in range(4):                                     # the device walks k with consecutive outputs side by side: [in][out]
-            dw.stage_w[i], dw.stage_b[i], dw.proj_w[i] = dev(fold['stage_w'][i].T), dev(fold['stage_b'][i]), dev(fold['proj_w'][i].T)
-        dw.classes, dw.feat_c = self.classes, self.enc_ch[2]
-
-    def decode(self, enc):
-        """`model.decoder(encoding)`: the decoder reads enc[2] (x2 at 1/8 resolution) only; the other four entries may be None."""
-        f = enc[2]
-        _require_gpu(f, 'encoder map')
-        f = f.to(torch.float32).contiguous()
-        n, h, w = f.shape[0], f.shape[2] * 8, f.shape[3] * 8
-        ws, cap = self._workspace(n, h, w)
-        logits = torch.empty((n, self.classes, h, w), dtype=torch.float32, device=self.device)
-        ptrs = (C.c_void_p * 5)(None, None, f.data_ptr(), None, None)
-        native.check(self._decoder(C.byref(self.dw), C.byref(ptrs), n, h, w, self.planes, _ptr(ws), cap, _ptr(logits), _stream()),
-                     self._decoder.__name__)
-        return logits
+            self.dw.stage_w[i], self.dw.stage_b[i] = self._upload(fold['stage_w'][i].T), self._upload(fold['stage_b'][i])
+            self.dw.proj_w[i] = self._upload(fold['proj_w'][i].T)
+        self.dw.feat_c = self.enc_ch[2]
 
 
 class LinknetEngine(UNetEngine):
@@ -529,15 +519,7 @@ class LinknetEngine(UNetEngine):
     parity mode)."""
 
     ENTRY = {'basic': 'wsi_linknet'}
-
-    def __init__(self, state_dict, device, planes=PARITY, classes=None, max_batch=None, encoder=None):
-        if planes not in (PARITY, SPEED):
-            raise ValueError("a Linknet runs in precision 'parity' or 'speed': there is no mx mode")
-        if encoder is not None:
-            encoder_spec(encoder, ('basic',), where=BLOCK_RESNETS['basic'])
-        if trunk_arch({k[len('encoder.'):]: v for k, v in state_dict.items() if k.startswith('encoder.')})[0] != 'basic':
-            raise ValueError('a Linknet runs on BasicBlock encoders only (%s)' % sorted(ENCODER_LAYERS))
-        super().__init__(state_dict, device, planes, classes, max_batch, encoder)
+    PLANES, NOUN = (PARITY, SPEED), 'a Linknet'
 
     def _describe(self):
         return linknet_decoder()
@@ -877,20 +859,37 @@ class PSPNetSegBottleneck(PSPNetSeg):
 
 
 def _factory_refusals(encoder_weights, activation):
-    """What both smp factories refuse: the model returns logits, as the reference builds it, and nothing is downloaded."""
+    """What every smp factory refuses: the model returns logits, as the reference builds it, and nothing is downloaded."""
     if encoder_weights is not None:
         raise ValueError('encoder_weights must be None (got %r): pretrained weights are not downloaded; load a state dict' % (encoder_weights,))
     if activation is not None:
         raise ValueError('activation must be None (got %r): the model returns logits, as the reference builds it' % (activation,))
 
 
+# smp model name -> (how a refusal names it, the module class per encoder block type)
+SEG_MODELS = {'Unet': ('a U-Net', {'basic': UNetSeg, 'bottleneck': UNetSegBottleneck}), 'Linknet': ('a Linknet', {'basic': LinknetSeg}),
+              'FPN': ('an FPN', {'basic': FPNSeg, 'bottleneck': FPNSegBottleneck}),
+              'PSPNet': ('a PSPNet', {'basic': PSPNetSeg, 'bottleneck': PSPNetSegBottleneck})}
+
+
+def _factory(model, encoder_name, encoder_weights, activation, args, fixed=(), typed=False):
+    """The one body of the smp factories: the refusals, the arguments accepted at smp's defaults only (`fixed`: (name, got, want), compared
+    by value, with `typed` by type as well: a bool is not an int), the encoder lookup among the block types the model runs on, and the
+    module class of that block type built with `args`."""
+    _factory_refusals(encoder_weights, activation)
+    for name, got, want in fixed:
+        if got != want or (typed and type(got) is not type(want)):
+            raise ValueError('%s must be %r (got %r): the %s kernels are built for smp\'s default decoder' % (name, want, got, model))
+    noun, by_arch = SEG_MODELS[model]
+    arch = encoder_spec(encoder_name, tuple(by_arch), 'encoder_name', '' if len(by_arch) == len(ENC_CH) else ' for ' + noun)[0]
+    return by_arch[arch](*args)
+
+
 def Linknet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
     """smp's factory signature for the Linknet, so with ``import wsi_segmentation_pipeline_amd.unet as smp`` the reference's
     ``getattr(smp, args.model_name)(args.arch_encoder, encoder_weights=None, classes=C, activation=None)`` serves 'Unet' and 'Linknet'.
     Refusals as `Unet`; encoders 'resnet18' and 'resnet34' only."""
-    _factory_refusals(encoder_weights, activation)
-    encoder_spec(encoder_name, ('basic',), 'encoder_name', ' for a Linknet')
-    return LinknetSeg(classes, precision, encoder_name)
+    return _factory('Linknet', encoder_name, encoder_weights, activation, (classes, precision, encoder_name))
 
 
 def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=None, precision='parity'):
@@ -898,9 +897,7 @@ def Unet(encoder_name='resnet34', encoder_weights=None, classes=1, activation=No
     activation=None)`` becomes ``unet.Unet(...)``: UNetSeg for 'resnet18' / 'resnet34', UNetSegBottleneck for 'resnet50' / 'resnet101'.
     The model returns logits: `activation` must be None, as the reference passes it; `encoder_weights` must be None (nothing is
     downloaded: load a checkpoint with ``load_state_dict``)."""
-    _factory_refusals(encoder_weights, activation)
-    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
-    return {'basic': UNetSeg, 'bottleneck': UNetSegBottleneck}[arch](classes, precision, encoder_name)
+    return _factory('Unet', encoder_name, encoder_weights, activation, (classes, precision, encoder_name))
 
 
 def FPN(encoder_name='resnet34', encoder_weights=None, decoder_pyramid_channels=256, decoder_segmentation_channels=128, classes=1, dropout=0.2,
@@ -909,13 +906,9 @@ def FPN(encoder_name='resnet34', encoder_weights=None, decoder_pyramid_channels=
     classes=C, activation=None)`` serves 'FPN' on all four encoders: FPNSeg for 'resnet18' / 'resnet34', FPNSegBottleneck for 'resnet50' /
     'resnet101'.  Refusals as `Unet`; the three decoder-size arguments are accepted at smp's defaults only (the kernels are built for
     them); `dropout` in [0, 1) (it acts in training mode only)."""
-    _factory_refusals(encoder_weights, activation)
-    for name, got, want in (('decoder_pyramid_channels', decoder_pyramid_channels, FPN_PYRAMID_CH),
-                            ('decoder_segmentation_channels', decoder_segmentation_channels, FPN_SEG_CH), ('final_upsampling', final_upsampling, 4)):
-        if got != want:
-            raise ValueError('%s must be %d (got %r): the FPN kernels are built for smp\'s default decoder' % (name, want, got))
-    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
-    return {'basic': FPNSeg, 'bottleneck': FPNSegBottleneck}[arch](classes, precision, encoder_name, dropout)
+    fixed = (('decoder_pyramid_channels', decoder_pyramid_channels, FPN_PYRAMID_CH),
+             ('decoder_segmentation_channels', decoder_segmentation_channels, FPN_SEG_CH), ('final_upsampling', final_upsampling, 4))
+    return _factory('FPN', encoder_name, encoder_weights, activation, (classes, precision, encoder_name, dropout), fixed)
 
 
 def PSPNet(encoder_name='resnet34', encoder_weights=None, psp_in_factor=8, psp_out_channels=512, psp_use_batchnorm=True, psp_aux_output=False,
@@ -926,10 +919,6 @@ def PSPNet(encoder_name='resnet34', encoder_weights=None, psp_in_factor=8, psp_o
     ``predict`` only, which this module does not have, and the reference always passes None.  The four ``psp_*`` arguments are accepted at
     smp's defaults only (the kernels are built for them; `psp_aux_output` would add a training-time branch and its keys); `dropout` in
     [0, 1) (it acts in training mode only)."""
-    _factory_refusals(encoder_weights, activation)
-    for name, got, want in (('psp_in_factor', psp_in_factor, 8), ('psp_out_channels', psp_out_channels, PSP_OUT_CH),
-                            ('psp_use_batchnorm', psp_use_batchnorm, True), ('psp_aux_output', psp_aux_output, False)):
-        if got != want or type(got) is not type(want):
-            raise ValueError('%s must be %r (got %r): the PSPNet kernels are built for smp\'s default decoder' % (name, want, got))
-    arch = encoder_spec(encoder_name, tuple(ENC_CH), 'encoder_name')[0]
-    return {'basic': PSPNetSeg, 'bottleneck': PSPNetSegBottleneck}[arch](classes, precision, encoder_name, dropout)
+    fixed = (('psp_in_factor', psp_in_factor, 8), ('psp_out_channels', psp_out_channels, PSP_OUT_CH),
+             ('psp_use_batchnorm', psp_use_batchnorm, True), ('psp_aux_output', psp_aux_output, False))
+    return _factory('PSPNet', encoder_name, encoder_weights, activation, (classes, precision, encoder_name, dropout), fixed, typed=True)
