@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
+#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_*, wsi_stain_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -743,6 +743,43 @@ int wsi_views_f32(const float* in_nchw, int n, int h, int w, const int* views, i
  * -22 before any launch: NULL feat, w2, b2 or mean_out; NULL w1 or b1 with j > 0; n, f or k <= 0; j < 0; nviews outside 1..8. */
 int wsi_mlp_views(const float* feat, int n, int nviews, int f, const float* w1, const float* b1, int j, const float* w2, const float* b2,
                   int k, int clamp, float clamp_lo, float clamp_hi, float* views_out, float* mean_out, void* stream);
+
+/* ---- stain normalisation of resident u8 RGB pixels: Macenko and Reinhard ----------------------
+ * The reference has no counterpart: parity unpinned, own spec.  The spec is tests/stain_oracle.py, the published
+ * algorithms restated so that they are deterministic on a GPU:
+ *   M. Macenko et al., "A method for normalizing histology slides for quantitative analysis", ISBI 2009
+ *   E. Reinhard et al., "Color transfer between images", IEEE Computer Graphics and Applications 21(5), 2001 (Ruderman's l-alpha-beta
+ *   space, the paper's RGB -> LMS and LMS -> RGB matrices)
+ * img / src / dst: n_images images of npix packed RGB pixels, image i at byte i * npix * 3 (no alignment asked for; the slide is
+ *   n_images = 1).  Every array is device memory: od_lut = the 256 fp32 optical densities od[v] = -ln((v + 1) / Io); the per-image
+ *   parameter arrays are dense, image-major.  A pixel is tissue iff max(r, g, b) <= v_max (od >= beta in every channel, as an integer
+ *   test; v_max = floor(Io exp(-beta)) - 1, found by the host).
+ * od_moments / lab_moments: moments_out [n_images][10] float64 = n, sum x (3), sum x (x) x (00 01 02 11 12 22) over the tissue pixels,
+ *   x = (od[r], od[g], od[b]), or l-alpha-beta of rgb = (v + 1) / 256 evaluated in float64.  float64 sums in a fixed order (a partial
+ *   per chunk of 32768 pixels in `scratch`, wsi_stain_moments_scratch_bytes() bytes, merged in chunk order): no float atomics, the
+ *   same input gives the same bits.
+ * angle_hist: hist_out [n_images][bins] u64 (zeroed here) of phi = atan2(od . V2, od . V1) (fp32) over [-pi, pi), plane_3x2 = V as
+ *   [n_images][3][2].  conc_hist: hist_out [n_images][2][bins] u64 of C = P . od (fp32) over [0, conc_max), values outside clamped
+ *   into the end bins, pinv_2x3 = P as [n_images][2][3].  bins <= 4096.  Integer counts: order independent.
+ * macenko_apply: out_c = clamp(floor(io * 2^(m_c . od) + 0.5), 0, 255), m_3x3 [n_images][3][3] = -log2(e) * HERef diag(maxCRef / maxC)
+ *   pinv(HE), folded by the host in float64.  reinhard_apply: log2 LMS' = G . log2 LMS + g, rgb' = (LMS -> RGB) LMS',
+ *   out_c = clamp(floor(256 rgb'_c - 1 + 0.5), 0, 255); g_3x3_3 [n_images][12] = G [3][3] then g [3], the host's float64 fold of
+ *   l-alpha-beta, (x - mean_src) * std_tgt / std_src + mean_tgt and its inverse.  v_max [n_images] ints: a pixel with
+ *   max(r, g, b) > v_max[i] is copied through (255: every pixel is transformed; -1: the image is copied).  dst == src is allowed
+ *   (in place); any other overlap is refused.  Where src and dst differ mod 16 the kernel moves bytes instead of 16-byte pieces.
+ * -22 before any device work: a NULL pointer, npix <= 0 or > 2^40, n_images outside 1..65535, a scalar v_max outside 0..255,
+ *   bins outside 1..4096, conc_max or io <= 0, partially overlapping src and dst. */
+size_t wsi_stain_moments_scratch_bytes(long long npix, int n_images);
+int wsi_stain_od_moments(const uint8_t* img, long long npix, int n_images, int v_max, const float* od_lut, double* moments_out, void* scratch,
+                         void* stream);
+int wsi_stain_lab_moments(const uint8_t* img, long long npix, int n_images, int v_max, double* moments_out, void* scratch, void* stream);
+int wsi_stain_angle_hist(const uint8_t* img, long long npix, int n_images, int v_max, const float* od_lut, const float* plane_3x2, int bins,
+                         unsigned long long* hist_out, void* stream);
+int wsi_stain_conc_hist(const uint8_t* img, long long npix, int n_images, int v_max, const float* od_lut, const float* pinv_2x3, int bins,
+                        float conc_max, unsigned long long* hist_out, void* stream);
+int wsi_stain_macenko_apply(const uint8_t* src, uint8_t* dst, long long npix, int n_images, const int* v_max, const float* od_lut,
+                            const float* m_3x3, float io, void* stream);
+int wsi_stain_reinhard_apply(const uint8_t* src, uint8_t* dst, long long npix, int n_images, const int* v_max, const float* g_3x3_3, void* stream);
 
 #ifdef __cplusplus
 }

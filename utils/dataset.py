@@ -103,14 +103,19 @@ open_slide = _open_slide_default
 
 
 class Dataset_wsi:
-    """Tile list of one slide at args.scan_level (grid + foreground filter as the reference)."""
+    """Tile list of one slide at args.scan_level (grid + foreground filter as the reference).  stain: a
+    wsi_segmentation_pipeline_amd.stain.Normalizer; the scan's resident levels are then stain-normalised (StainedSlide) while
+    read_region - the thumbnail of the nuclei mask - stays raw.  None: the scan as opened."""
 
-    def __init__(self, wsipth, params):
+    def __init__(self, wsipth, params, stain=None):
         self.params = params
         self.datalist = []
         self.wsipth = wsipth
         filename = os.path.basename(str(wsipth)) if not isinstance(wsipth, S.ArraySlide) else getattr(wsipth, 'name', 'slide')
         self.scan = open_slide(wsipth)
+        if stain is not None:
+            from wsi_segmentation_pipeline_amd.stain import StainedSlide
+            self.scan = StainedSlide(self.scan, stain)
         if len(self.scan.level_dimensions) - 1 < args.scan_level:
             return                                                        # too few pyramid levels: slide is skipped
         self.params.iw, self.params.ih = self.scan.level_dimensions[args.scan_level]
@@ -190,16 +195,16 @@ class DeviceTileIterator:
             yield (torch.from_numpy(xy[:, 0].astype(np.float64)), torch.from_numpy(xy[:, 1].astype(np.float64)), img)
 
 
-def GenerateIterator_wsi(wsipth, p, bs):
-    dataset = Dataset_wsi(wsipth, p)
+def GenerateIterator_wsi(wsipth, p, bs, stain=None):
+    dataset = Dataset_wsi(wsipth, p, stain=stain)
     return DeviceTileIterator(dataset, bs) if len(dataset) > 0 else None
 
 
 class Dataset_wsis:
     """All validation slides under ``svs_pth`` (``Case*/*.svs`` like the reference; also
-    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide}`` mapping."""
+    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide}`` mapping.  stain: as Dataset_wsi."""
 
-    def __init__(self, svs_pth, params, bs=args.batch_size):
+    def __init__(self, svs_pth, params, bs=args.batch_size, stain=None):
         self.params = preprocessing.DotDict(params)
         self.wsis = {}
         if isinstance(svs_pth, dict):
@@ -209,7 +214,7 @@ class Dataset_wsis:
                            + glob.glob('{}/*.npy'.format(svs_pth)))
             entries = [(os.path.basename(p), p) for p in paths]
         for filename, src in entries:
-            itr = GenerateIterator_wsi(src, preprocessing.DotDict(dict(self.params.__dict__, **self.params)), bs)
+            itr = GenerateIterator_wsi(src, preprocessing.DotDict(dict(self.params.__dict__, **self.params)), bs, stain=stain)
             if itr is not None:
                 self.wsis[filename] = {'iterator': itr, 'wsipath': src, 'scan': itr.dataset.scan,
                                        'maskpath': '{}/{}.png'.format(args.wsi_mask_pth, filename),

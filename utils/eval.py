@@ -511,13 +511,15 @@ def breastpathq_image(dataset_path, image_id, region_id):
     return np.asarray(image.resize((args.tile_w, args.tile_h), Image.BILINEAR))
 
 
-def predict_breastpathq(model, ep, dataset_path, label_csv_path, out_csv=None, batch=None, score=None):
+def predict_breastpathq(model, ep, dataset_path, label_csv_path, out_csv=None, batch=None, score=None, stain=None):
     """BreastPathQ submission table (reference utils/eval.py:354-412): every <image>_<region>.tif of the label file, in its row order,
     resized to (tile_h, tile_w), scored as the mean of `model.regressor` over the reference's four views and clamped to [0, 1];
     writes Ozan_Results_<ep>.csv (or `out_csv`) with the header slide,rid,p and returns the rows [(image id, region id, p)].
     The regions travel as u8: `batch` of them (default: what fills the engine's batch with four views each) are uploaded as one
     packed-RGB stack and scored through the u8 view path, the clamp inside wsi_mlp_views; a model without the fused heads gets the
-    normalised fp32 batch and the module loop.  `score(u8 (B, tile_h, tile_w, 3) ndarray) -> B scores` replaces the scoring (tests)."""
+    normalised fp32 batch and the module loop.  `score(u8 (B, tile_h, tile_w, 3) ndarray) -> B scores` replaces the scoring (tests).
+    stain: a wsi_segmentation_pipeline_amd.stain.Normalizer; every uploaded u8 batch is stain-normalised on the device, each region fitted
+    on itself, ahead of the view path (a region whose fit fails is scored as it is)."""
     import csv
     views = E.VIEWS_REFERENCE
     was_training = model.training if model is not None else False
@@ -533,6 +535,8 @@ def predict_breastpathq(model, ep, dataset_path, label_csv_path, out_csv=None, b
         def score(u8):
             b, h, w, _ = u8.shape
             stack = S._upload(u8.reshape(b * h, w, 3), torch.uint8, dev)
+            if stain is not None:
+                stain.apply(stack.view(b, h, w, 3), out=stack.view(b, h, w, 3))
             xy = torch.zeros((b, 2), dtype=torch.int32, device=dev)
             xy[:, 1] = torch.arange(b, dtype=torch.int32, device=dev) * h
             if fused:

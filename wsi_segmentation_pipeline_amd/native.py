@@ -186,6 +186,13 @@ SIGNATURES = {
     'wsi_tile_views_u8': (_i, [_vp, _ll, _i, _i, _vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_views_f32': (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp]),
     'wsi_mlp_views': (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _f, _f, _vp, _vp, _vp]),
+    'wsi_stain_moments_scratch_bytes': (_sz, [_ll, _i]),
+    'wsi_stain_od_moments': (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp, _vp]),
+    'wsi_stain_lab_moments': (_i, [_vp, _ll, _i, _i, _vp, _vp, _vp]),
+    'wsi_stain_angle_hist': (_i, [_vp, _ll, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    'wsi_stain_conc_hist': (_i, [_vp, _ll, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
+    'wsi_stain_macenko_apply': (_i, [_vp, _vp, _ll, _i, _vp, _vp, _vp, _f, _vp]),
+    'wsi_stain_reinhard_apply': (_i, [_vp, _vp, _ll, _i, _vp, _vp, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)
