@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_*, wsi_stain_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
+#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_*, wsi_stain_*, wsi_jpeg_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -780,6 +780,94 @@ int wsi_stain_conc_hist(const uint8_t* img, long long npix, int n_images, int v_
 int wsi_stain_macenko_apply(const uint8_t* src, uint8_t* dst, long long npix, int n_images, const int* v_max, const float* od_lut,
                             const float* m_3x3, float io, void* stream);
 int wsi_stain_reinhard_apply(const uint8_t* src, uint8_t* dst, long long npix, int n_images, const int* v_max, const float* g_3x3_3, void* stream);
+
+/* ---- JPEG tiles of a TIFF / SVS pyramid level, decoded into the resident level ------------------
+ * Replaces OpenSlide's read_region under utils/dataset.py:171-185 (the reference reads every patch through OpenSlide, which decodes
+ * the JPEG tiles of the level with libjpeg on the host).  Baseline sequential DCT, Huffman, 8 bit, one scan, 1 or 3 components, luma
+ * sampling 1x1, 2x1 or 2x2 with 1x1 chroma.  The arithmetic is libjpeg's default decode path in integers (jidctint islow IDCT, "fancy"
+ * h2v1 / h2v2 upsampling, jdcolor's 16-bit fixed-point YCbCr -> RGB): the bytes equal libjpeg's; the spec is tests/jpeg_oracle.py.
+ *
+ * Host side (no GPU): wsi_jpeg_parse_tables reads the DQT / DHT segments of a table blob (TIFF tag 347 JPEGTables, or the header of a
+ * complete stream, up to its SOS / EOI) into a table set; wsi_jpeg_walk walks the markers of n tile streams and fills one record each.
+ *   buf / buf_len: the caller's byte buffer; stream i is [off[i], off[i] + len[i]) and must lie inside it (-22 otherwise); the walk reads
+ *     no byte outside a stream's range.  len[i] == 0: status WSI_JPEG_EMPTY (a TIFF tile with byte count 0: white).
+ *   base: the level's JPEGTables set or NULL.  sets[cap] / n_sets (in: sets already held, out: sets held now): a stream without DQT /
+ *     DHT of its own uses `base`, which is entered as a set on first use; a stream that carries tables gets base overlaid by them, and
+ *     equal sets are shared (compared by content).  A stream that needs set number cap + 1: WSI_JPEG_TABLE_CAPACITY.
+ *   a record's scan_off is relative to buf; status != 0 says why the tile cannot go to the device (the other fields are then unspecified).
+ * Device side.  A batch is n tiles of ONE geometry (frame width x height, ncomp 1 or 3, luma sampling hs x vs); a tile whose record
+ * differs gets WSI_JPEG_GEOMETRY.  wsi_jpeg_workspace_bytes: bytes per tile (a multiple of 256; 0 for a geometry out of range): the
+ * workspace of n tiles is n areas of dequantised int16 coefficients [component][block row][block col][64, natural order], then n
+ * areas of u8 component planes; both calls of a batch get the same ws and n.
+ *   wsi_jpeg_entropy: zeroes the coefficients, then one lane per tile decodes its scan (restart intervals honoured) and writes the
+ *     dequantised coefficients; status[i] (device ints) = the record's status if non-zero, else 0 or a WSI_JPEG_* code >= 16.  A lane
+ *     reads only [scan_off, scan_off + scan_len) of `bytes` (records reaching past nbytes: WSI_JPEG_MALFORMED) and writes only its
+ *     tile's coefficient area.  A workgroup is one wave with `lanes` of its 64 lanes at work, tile = workgroup * lanes + lane; lanes 0:
+ *     ceil(n / (4 x compute units)) capped at 64, so that a small batch still covers the chip and a wave serialises few divergent lanes.
+ *   wsi_jpeg_reconstruct: IDCT into the planes, then upsample + colour + store of every tile with status 0 at grid cell tile_index[i]
+ *     (device ints; cell c is at pixel ((c % grid_cols) * width, (c / grid_cols) * height)) of the (H, W, 3) level with `pitch` bytes
+ *     per row, clipped to the level; a tile_index outside the grid is skipped.  transform 1: YCbCr -> RGB, 0: the planes are R, G, B
+ *     (TIFF PhotometricInterpretation 6 / 2); one component is replicated.  16-byte stores where the address allows, bytes at ragged
+ *     ends; no byte outside the level is written.
+ * -22 before any device work: a NULL pointer, n <= 0, geometry out of range (width / height outside 1..4096, ncomp not 1 or 3, sampling
+ *   not 1x1 / 2x1 / 2x2, or not 1x1 with one component), ws not 16-byte aligned or ws_bytes < n * wsi_jpeg_workspace_bytes(), n_sets <= 0 or
+ *   common_set outside [0, n_sets), lanes outside 0..64, H, W or grid_cols / grid_rows <= 0, pitch < 3 W, transform not 0 / 1, or a grid whose last column or
+ *   row starts outside the level ((grid_cols - 1) * width >= W or (grid_rows - 1) * height >= H). */
+enum {
+    WSI_JPEG_OK = 0,
+    WSI_JPEG_PROGRESSIVE = 1,        /* SOF2 */
+    WSI_JPEG_ARITHMETIC = 2,         /* SOF9 - SOF15, and the lossless / differential Huffman frames SOF3, SOF5 - SOF7 */
+    WSI_JPEG_PRECISION = 3,          /* sample precision other than 8 */
+    WSI_JPEG_COMPONENTS = 4,         /* neither 1 nor 3 components */
+    WSI_JPEG_SAMPLING = 5,
+    WSI_JPEG_MULTISCAN = 6,
+    WSI_JPEG_MALFORMED = 7,          /* truncated or malformed segment, missing table, no SOF / SOS / EOI */
+    WSI_JPEG_TABLE_CAPACITY = 8,
+    WSI_JPEG_EMPTY = 9,              /* byte count 0 */
+    WSI_JPEG_BAD_CODE = 16,          /* from here on: set by the entropy kernel */
+    WSI_JPEG_COEF_OVERRUN = 17,      /* a run + size symbol whose run passes coefficient 63 (libjpeg stores at 63 and goes on) */
+    WSI_JPEG_SHORT = 18,             /* a marker before the interval's (or the scan's) blocks were complete */
+    WSI_JPEG_EXHAUSTED = 19,         /* the scan data ended inside a block */
+    WSI_JPEG_EXCESS = 20,            /* data left where a restart marker or the end of the scan was due */
+    WSI_JPEG_RANGE = 21,             /* a dequantised coefficient outside int16 */
+    WSI_JPEG_GEOMETRY = 22           /* the tile's frame is not the batch's */
+};
+#define WSI_JPEG_LOOK_BITS 9
+typedef struct wsi_jpeg_huff {
+    uint16_t look[1 << WSI_JPEG_LOOK_BITS];  /* the next 9 bits -> (code length << 8) | symbol, 0: the code is longer than 9 bits */
+    int32_t maxcode[18];                      /* [l] = largest code of length l (-1: none), [17] = 0x7fffffff */
+    int32_t valoffset[18];                    /* [l] = index of the first symbol of length l minus its first code */
+    uint8_t huffval[256];
+} wsi_jpeg_huff;
+typedef struct wsi_jpeg_tables {
+    uint16_t qt[4][64];                       /* zigzag order, as in the file */
+    wsi_jpeg_huff huff[4];                    /* DC 0, DC 1, AC 0, AC 1 */
+    uint8_t qt_present[4];
+    uint8_t huff_present[4];
+} wsi_jpeg_tables;
+typedef struct wsi_jpeg_tile {
+    unsigned long long scan_off;              /* first byte of entropy-coded data, relative to the walked buffer */
+    unsigned int scan_len;                    /* up to, not including, the marker that ends the scan */
+    int status;
+    int table_set;
+    unsigned short width, height;
+    unsigned short restart;                   /* MCUs per restart interval, 0: none */
+    unsigned char ncomp;
+    unsigned char h[3], v[3], tq[3], td[3], ta[3];      /* per component: sampling factors, quantisation / DC / AC table ids */
+    unsigned char pad[6];
+} wsi_jpeg_tile;
+size_t wsi_jpeg_tables_bytes(void);            /* sizeof(wsi_jpeg_tables), sizeof(wsi_jpeg_tile): a binding checks its mirror */
+size_t wsi_jpeg_tile_bytes(void);
+int wsi_jpeg_parse_tables(const uint8_t* blob, size_t len, wsi_jpeg_tables* out);      /* 0 or a WSI_JPEG_* status; -22: NULL */
+int wsi_jpeg_walk(const uint8_t* buf, size_t buf_len, const unsigned long long* off, const unsigned int* len, int n,
+                  const wsi_jpeg_tables* base, wsi_jpeg_tables* sets, int cap, int* n_sets, wsi_jpeg_tile* tiles_out);
+size_t wsi_jpeg_workspace_bytes(int width, int height, int ncomp, int hs, int vs);
+int wsi_jpeg_entropy(const uint8_t* bytes, size_t nbytes, const wsi_jpeg_tile* tiles, int n, const wsi_jpeg_tables* sets, int n_sets,
+                     int common_set, int width, int height, int ncomp, int hs, int vs, void* ws, size_t ws_bytes, int* status,
+                     int lanes, void* stream);
+int wsi_jpeg_reconstruct(void* ws, size_t ws_bytes, const int* status, const int* tile_index, int n, int width, int height, int ncomp,
+                         int hs, int vs, int transform, int grid_cols, int grid_rows, uint8_t* level, long long pitch, int H, int W,
+                         void* stream);
 
 #ifdef __cplusplus
 }

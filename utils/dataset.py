@@ -6,7 +6,8 @@ The tile producer is MI355X-native: the chosen pyramid level is resident in HBM 
 and batches are produced on the device by wsi_tile_gather (read + ToTensor + Normalize fused), or
 - on the fused fast path used by utils.eval - never materialised at all (the stem kernel reads
 the slide directly).  Slides come from OpenSlide when it is installed, or from in-memory /
-``.npy``/``.npz`` pyramids (`ArraySlide`) otherwise; `open_slide` can be replaced."""
+``.npy``/``.npz`` pyramids (`ArraySlide`) and JPEG-tiled TIFF / SVS files (`TiffSlide`, decoded on
+the GPU) otherwise; `open_slide` can be replaced."""
 import glob
 import os
 
@@ -18,6 +19,7 @@ from myargs import args
 from utils import preprocessing
 from wsi_segmentation_pipeline_amd import engine as E
 from wsi_segmentation_pipeline_amd import slide as S
+from wsi_segmentation_pipeline_amd.tiffslide import TiffSlide
 
 
 class Dataset(torch.utils.data.Dataset):
@@ -63,7 +65,7 @@ def GenerateIterator(impth, eval=False, duplicate_dataset=1):
 
 
 def _open_slide_default(path):
-    if isinstance(path, S.ArraySlide):
+    if isinstance(path, (S.ArraySlide, TiffSlide)):
         return path
     if str(path).endswith('.npz'):
         z = np.load(path)
@@ -74,7 +76,9 @@ def _open_slide_default(path):
     try:
         import openslide
     except ImportError as e:
-        raise RuntimeError('cannot open %r: OpenSlide is not installed; pass an ArraySlide or a .npy/.npz pyramid' % (path,)) from e
+        if str(path).lower().endswith(('.svs', '.tif', '.tiff')):
+            return TiffSlide(path)                                        # JPEG-tiled TIFF / SVS: own reader, decode on the GPU
+        raise RuntimeError('cannot open %r: OpenSlide is not installed; pass an ArraySlide, a TiffSlide or a .npy/.npz pyramid' % (path,)) from e
     return _OpenSlideAdapter(openslide.OpenSlide(path))
 
 
@@ -111,7 +115,7 @@ class Dataset_wsi:
         self.params = params
         self.datalist = []
         self.wsipth = wsipth
-        filename = os.path.basename(str(wsipth)) if not isinstance(wsipth, S.ArraySlide) else getattr(wsipth, 'name', 'slide')
+        filename = os.path.basename(str(wsipth)) if not isinstance(wsipth, (S.ArraySlide, TiffSlide)) else getattr(wsipth, 'name', 'slide')
         self.scan = open_slide(wsipth)
         if stain is not None:
             from wsi_segmentation_pipeline_amd.stain import StainedSlide
@@ -202,7 +206,7 @@ def GenerateIterator_wsi(wsipth, p, bs, stain=None):
 
 class Dataset_wsis:
     """All validation slides under ``svs_pth`` (``Case*/*.svs`` like the reference; also
-    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide}`` mapping.  stain: as Dataset_wsi."""
+    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide-or-TiffSlide}`` mapping.  stain: as Dataset_wsi."""
 
     def __init__(self, svs_pth, params, bs=args.batch_size, stain=None):
         self.params = preprocessing.DotDict(params)

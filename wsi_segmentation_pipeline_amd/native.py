@@ -79,6 +79,45 @@ class WsiPspnetDecoderWeights(C.Structure):
     ]
 
 
+class WsiJpegHuff(C.Structure):
+    """wsi_jpeg_huff: one Huffman table in the look-up form of the entropy kernel."""
+    _fields_ = [('look', C.c_uint16 * 512), ('maxcode', C.c_int32 * 18), ('valoffset', C.c_int32 * 18), ('huffval', C.c_uint8 * 256)]
+
+
+class WsiJpegTables(C.Structure):
+    """wsi_jpeg_tables: up to four quantisation tables (zigzag order) and the DC 0, DC 1, AC 0, AC 1 Huffman tables."""
+    _fields_ = [('qt', (C.c_uint16 * 64) * 4), ('huff', WsiJpegHuff * 4), ('qt_present', C.c_uint8 * 4), ('huff_present', C.c_uint8 * 4)]
+
+
+class WsiJpegTile(C.Structure):
+    """wsi_jpeg_tile: the marker walk's record of one tile stream."""
+    _fields_ = [('scan_off', C.c_ulonglong), ('scan_len', C.c_uint), ('status', C.c_int), ('table_set', C.c_int),
+                ('width', C.c_ushort), ('height', C.c_ushort), ('restart', C.c_ushort), ('ncomp', C.c_ubyte),
+                ('h', C.c_ubyte * 3), ('v', C.c_ubyte * 3), ('tq', C.c_ubyte * 3), ('td', C.c_ubyte * 3), ('ta', C.c_ubyte * 3),
+                ('pad', C.c_ubyte * 6)]
+
+
+class JpegStatus(enum.IntEnum):
+    """include/wsi_hip.h WSI_JPEG_*: why a tile cannot go to the device (1..9, from the marker walk) or what stopped its lane (16..)."""
+    OK = 0
+    PROGRESSIVE = 1
+    ARITHMETIC = 2
+    PRECISION = 3
+    COMPONENTS = 4
+    SAMPLING = 5
+    MULTISCAN = 6
+    MALFORMED = 7
+    TABLE_CAPACITY = 8
+    EMPTY = 9
+    BAD_CODE = 16
+    COEF_OVERRUN = 17
+    SHORT = 18
+    EXHAUSTED = 19
+    EXCESS = 20
+    RANGE = 21
+    GEOMETRY = 22
+
+
 _vp, _i, _ll, _sz, _f, _d =C.c_void_p, C.c_int, C.c_longlong, C.c_size_t, C.c_float, C.c_double
 # name -> (restype, argtypes); must list every symbol include/wsi_hip.h declares
 SIGNATURES = {
@@ -193,6 +232,13 @@ SIGNATURES = {
     'wsi_stain_conc_hist': (_i, [_vp, _ll, _i, _i, _vp, _vp, _i, _f, _vp, _vp]),
     'wsi_stain_macenko_apply': (_i, [_vp, _vp, _ll, _i, _vp, _vp, _vp, _f, _vp]),
     'wsi_stain_reinhard_apply': (_i, [_vp, _vp, _ll, _i, _vp, _vp, _vp]),
+    'wsi_jpeg_tables_bytes': (_sz, []),
+    'wsi_jpeg_tile_bytes': (_sz, []),
+    'wsi_jpeg_parse_tables': (_i, [_vp, _sz, _vp]),
+    'wsi_jpeg_walk': (_i, [_vp, _sz, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    'wsi_jpeg_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'wsi_jpeg_entropy': (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
+    'wsi_jpeg_reconstruct': (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _i, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)
@@ -239,6 +285,8 @@ def load():
         fn.argtypes = args
     if lib.wsi_hip_abi_version() != ABI_VERSION:
         raise RuntimeError('libwsi_hip.so ABI version mismatch')
+    if lib.wsi_jpeg_tables_bytes() != C.sizeof(WsiJpegTables) or lib.wsi_jpeg_tile_bytes() != C.sizeof(WsiJpegTile):
+        raise RuntimeError('libwsi_hip.so wsi_jpeg_tables / wsi_jpeg_tile layout mismatch')
     _lib = lib
     return lib
 
