@@ -115,6 +115,109 @@ def test_abbreviated_streams_with_tables_and_forced_transform(dev):
         assert int((got != full).sum()) == 0
 
 
+def _offsets(streams):
+    lens = np.array([len(s) for s in streams], np.uint64)
+    return np.concatenate([[0], np.cumsum(lens)[:-1]]).astype(np.uint64), lens
+
+
+def longest_code(stream):
+    """the longest Huffman code the stream's DHT segments define, in bits"""
+    return max(l + 1 for counts, _ in O.parse(stream)['huff'].values() for l in range(16) if counts[l])
+
+
+def test_optimised_huffman_tables_one_set_per_tile(dev):
+    """48 complete 48 x 64 streams with Huffman tables made for each image (Pillow's optimize=True): the three sub-samplings x quality
+    30 / 75 / 95 x noise / H&E-like x (no restart, restart interval 3), and quality 50 / 90 without restart.  The walk finds a table set
+    per stream, so all but the common one are read from memory instead of LDS, and codes longer than the 9 look-up bits (up to 13 bits;
+    33 of the 48 streams define one) take huff_decode's slow path."""
+    combos = list(itertools.product((0, 1, 2), (30, 75, 95), ('noise', 'he'), (0, 3))) + list(itertools.product((0, 1, 2), (50, 90), ('noise', 'he'), (0,)))
+    streams = [TF.encode((TF.noise if kind == 'noise' else TF.he_like)(64, 48, 700 + k), q, ss, restart=r, optimize=True)
+               for k, (ss, q, kind, r) in enumerate(combos)]
+    assert len(streams) == 48
+    offs, lens = _offsets(streams)
+    rec, sets, n_sets = ingest.jpeg_walk(np.frombuffer(b''.join(streams), np.uint8), offs, lens)
+    longest = [longest_code(s) for s in streams]
+    print('%d table sets for %d streams, longest code %d bits, %d streams with a code past %d bits' % (
+        n_sets, len(streams), max(longest), sum(l > 9 for l in longest), 9))
+    assert (rec['status'] == 0).all() and n_sets > 1 and len(set(rec['table_set'])) == n_sets and max(longest) > 9
+    got, status = _decode_strip(dev, streams)
+    assert (status == 0).all()
+    for i, s in enumerate(streams):
+        assert int((got[i] != _pillow(s)).sum()) == 0, (i, combos[i])
+
+
+@pytest.mark.parametrize('w,h,ss', [(4096, 16, 0), (4096, 16, 1), (4096, 16, 2), (16, 4096, 0), (16, 4096, 1), (16, 4096, 2), (1032, 520, 2)],
+                         ids=lambda v: str(v))
+def test_frames_at_the_largest_dimension(dev, w, h, ss):
+    """MAX_DIM = 4096 in either direction (769 pieces per row and a plane pitch of 4096 bytes; 512 block rows), and 1032 x 520, 4:2:0:
+    no multiple of 16 in height, 66 x 130 + 2 x 33 x 65 = 12 870 blocks in one tile.  Two streams (H&E-like; noise with restart interval 3)
+    stacked in a level that starts 0, 7 and 16 bytes past a 16-byte boundary inside guard bytes."""
+    streams = [TF.encode(TF.he_like(h, w, 900 + ss), 75, ss), TF.encode(TF.noise(h, w, 910 + ss), 90, ss, restart=3)]
+    ref = np.stack([_pillow(s) for s in streams]).reshape(2 * h, w, 3)
+    buf = np.frombuffer(b''.join(streams), np.uint8)
+    rec, sets, n_sets = ingest.jpeg_walk(buf, *_offsets(streams))
+    assert (rec['status'] == 0).all() and (int(rec['width'][0]), int(rec['height'][0])) == (w, h)
+    nbytes = 2 * h * w * 3
+    for shift in (0, 7, 16):
+        whole = torch.full((2 * GUARD + nbytes + 32,), 0x5A, dtype=torch.uint8, device=dev)
+        view = whole[GUARD + shift:GUARD + shift + nbytes].view(2 * h, w, 3)
+        status = ingest.jpeg_decode_tiles(buf, rec, sets, n_sets, np.arange(2, dtype=np.int32), (1, 2), view, 1)
+        host = whole.cpu().numpy()
+        assert (status == 0).all()
+        assert int((host[GUARD + shift:GUARD + shift + nbytes].reshape(2 * h, w, 3) != ref).sum()) == 0, shift
+        assert (host[:GUARD + shift] == 0x5A).all() and (host[GUARD + shift + nbytes:] == 0x5A).all(), shift
+
+
+def test_second_store_launch_past_65535_tiles(dev):
+    """65 537 tiles of 16 x 16, 4:2:0, in one jpeg_decode_batch: wsi_jpeg_reconstruct launches store_kernel once per 65 535 tiles, so
+    tiles 65 535 and 65 536 run with tile0 = 65 535.  The 24 streams of the large-batch test repeat in the order (i * 7) % 24; tile i goes
+    to cell perm[i] of a 256 x 257 grid (a seeded permutation of its first 65 537 cells), so a tile that takes another's status, planes or
+    cell lands in the wrong place.  Tiles 0 and 65 536 are streams that fail in the decode loop: their status is reported and their
+    cells keep the fill byte, as do the 255 cells no tile is sent to.  (Were the second launch to read the status of tiles 0 and 1, tile
+    65 535 would be left out and the failed tile 65 536 stored.)"""
+    lib = native.load()
+    n, cols, rows, fill = 65537, 256, 257, 0x5A
+    kinds = [TF.encode((TF.noise if k % 2 else TF.he_like)(16, 16, 500 + k), (30, 75, 95)[k % 3], 2, restart=(0, 1, 3)[(k // 2) % 3]) for k in range(24)]
+    bad = TF.bad_scan_streams(2)
+    kinds += [bad['exhausted'][0], bad['bad_code'][0]]
+    ref = np.stack([_pillow(s) for s in kinds[:24]])
+    order = (np.arange(n) * 7) % 24
+    order[0], order[65536] = 24, 25
+    want_status = np.zeros(n, np.int32)
+    want_status[0], want_status[65536] = bad['exhausted'][1], bad['bad_code'][1]
+    assert bad['exhausted'][1] == O.EXHAUSTED and bad['bad_code'][1] == O.BAD_CODE
+    offs, lens = _offsets(kinds)                                # the 26 streams once; the records name them over and over
+    buf = np.frombuffer(b''.join(kinds), np.uint8)
+    rec, sets, n_sets = ingest.jpeg_walk(buf, offs[order], lens[order])
+    assert (rec['status'] == 0).all() and len(rec) == n
+    geom = (16, 16, 3, 2, 2)
+    assert all(ingest._geometry(rec[i]) == geom for i in (0, 1, 65535, 65536))
+    cells = np.random.default_rng(65537).permutation(n).astype(np.int32)
+    data_at, tot, stage = ingest.jpeg_stage(buf, rec, np.arange(n), cells)
+    tile_ws = lib.wsi_jpeg_workspace_bytes(*geom)
+    assert tile_ws == 1280
+    ws = torch.empty(n * tile_ws, dtype=torch.uint8, device=dev)
+    H, W = rows * 16, cols * 16
+    lvl_whole = torch.full((2 * GUARD + H * W * 3,), fill, dtype=torch.uint8, device=dev)
+    level = lvl_whole[GUARD:GUARD + H * W * 3].view(H, W, 3)
+    status = torch.full((n + 2,), -1, dtype=torch.int32, device=dev)
+    sets_dev = torch.from_numpy(sets[:n_sets].view(np.uint8).reshape(-1).copy()).to(dev)
+    common = int(np.bincount(rec['table_set']).argmax())
+    ingest.jpeg_decode_batch(torch.from_numpy(stage).to(dev), tot, n, sets_dev, n_sets, common, geom, ws, status[1:n + 1], 1, (cols, rows), level)
+    torch.cuda.synchronize()
+    st = status.cpu().numpy()
+    assert st[0] == -1 and st[-1] == -1 and np.array_equal(st[1:-1], want_status)
+    host = lvl_whole.cpu().numpy()
+    assert (host[:GUARD] == fill).all() and (host[-GUARD:] == fill).all()
+    got = host[GUARD:-GUARD].reshape(rows, 16, cols, 16, 3).transpose(0, 2, 1, 3, 4).reshape(rows * cols, 16, 16, 3)     # by cell
+    want = np.full_like(got, fill)
+    good = want_status == 0
+    want[cells[good]] = ref[order[good]]
+    wrong = np.nonzero((got != want).reshape(rows * cols, -1).any(1))[0]
+    assert wrong.size == 0, 'cells %s differ (tiles %s)' % (wrong[:8], [int(np.nonzero(cells == c)[0][0]) if c in cells else None for c in wrong[:8]])
+    assert int((got != want).sum()) == 0
+
+
 # ------------------------------------------------------------------------------------------------------------------ level assembly
 @pytest.fixture(scope='module')
 def pyramid_file(tmp_path_factory):
@@ -187,6 +290,30 @@ def test_fallback_progressive_and_empty_tiles(dev, tmp_path):
     s = TiffSlide(bad)
     with pytest.raises(ValueError, match='level 0 tile 3'):
         s.device_level(0, dev)
+    s.close()
+
+
+def test_level_with_more_table_sets_than_the_walk_keeps(dev, tmp_path):
+    """a level of 70 tiles without JPEGTables, every tile with optimised tables of its own: the walk keeps JPEG_TABLE_SETS = 64 sets and
+    turns the tiles that would need more away with TABLE_CAPACITY; level_from_tiff decodes those on the host.  The split is the walk's
+    (two tiles may share a set), the level is libtiff's byte for byte."""
+    lv = TF.he_like(330, 630, 41)
+    lv[:, 540:] = TF.noise(330, 90, 42)                         # he_like's white right edge would give the last column one set
+    path = str(tmp_path / 'own_tables.tif')
+    info = TF.write_tiff(path, [lv], tile=(64, 48), jpegtables=False, optimize=True, subsampling=2)
+    assert len(info['streams'][0]) == 70 and b'\xff\xc4' in info['streams'][0][0]
+    ref = TF.pillow_levels(path, info['frames'])[0]
+    s = TiffSlide(path)
+    l0 = s.levels[0]
+    assert not l0.tables
+    rec, sets, n_sets = ingest.jpeg_walk(np.frombuffer(s._map, np.uint8), l0.offsets, l0.counts, None)
+    n_ok, n_cap = int((rec['status'] == 0).sum()), int((rec['status'] == O.TABLE_CAPACITY).sum())
+    print('%d tiles: %d table sets, %d tiles accepted, %d refused for capacity, longest code %d bits' % (
+        len(rec), n_sets, n_ok, n_cap, max(longest_code(t) for t in info['streams'][0])))
+    assert n_sets == ingest.JPEG_TABLE_SETS == 64 and n_cap > 0 and n_ok + n_cap == 70 and n_ok >= 64
+    got = s.device_level(0, dev)
+    assert got.shape == ref.shape and int((got.cpu().numpy() != ref).sum()) == 0
+    assert s.decode_report[0] == {'ok': n_ok, 'table_capacity': n_cap}
     s.close()
 
 

@@ -478,6 +478,15 @@ def test_stitch_exponent_guard(dev):
         E.check_stitch_exact(E.exponent_span(wide), 4)
     assert [int(t) for t in E.exponent_span(torch.zeros(5, device=dev)).cpu()] == [255, 0]
     E.check_stitch_exact(E.exponent_span(torch.zeros(5, device=dev)), 1000)
+    # 300 000 values: the launch is capped at 1024 workgroups = 262 144 threads, so threads 0 .. 37 855 take a second value and the
+    # workgroups meet in the atomics.  Everything lies in [1, 2) but four values that only a second round reads, each in another workgroup
+    many = (1.0 + torch.rand(300000, generator=torch.Generator().manual_seed(3))).clamp_(max=1.9999999)      # 1 + rand may round to 2
+    many[262144 + 5] = 2.0 ** -20                                       # workgroup 0, second value of thread 5
+    many[262144 + 69 * 256 + 192] = 2.0 ** 15                          # workgroup 69, last wave
+    many[262144 + 130 * 256 + 64] = float('nan')
+    many[299999] = 0.0                                                  # the last value: workgroup 147
+    assert many.numel() > 1024 * 256 and float(many[:262144].min()) >= 1.0 and float(many[:262144].max()) < 2.0
+    assert [int(t) for t in E.exponent_span(many.to(dev)).cpu()] == [127 - 20, 127 + 15]
 
 
 def test_mx_clamp_to_fp16_range(dev):

@@ -315,6 +315,71 @@ def test_entries_declared_mirrored_and_checked(lib):
         assert rcn(**k) == -22, k                                # W = 192 / H = 144: the grid's last column / row starts outside the level
 
 
+def _resize_frame(stream, width, height):
+    """the stream with the frame header's dimensions overwritten (the scan no longer fits them: for the walk alone)"""
+    i = stream.index(b'\xff\xc0')
+    return stream[:i + 5] + struct.pack('>HH', height, width) + stream[i + 9:]
+
+
+def test_walk_and_workspace_stop_at_4096(lib):
+    """MAX_DIM: the walk takes a frame of 4096 in either dimension and refuses 4097; wsi_jpeg_workspace_bytes answers 0 for it"""
+    good = TF.encode(TF.he_like(16, 16, 3), 75, 2)
+    assert _resize_frame(good, 16, 16) == good
+    cases = [(4096, 16, O.OK), (16, 4096, O.OK), (4096, 4096, O.OK), (4097, 16, O.MALFORMED), (16, 4097, O.MALFORMED), (65535, 65535, O.MALFORMED)]
+    rec, _, _, _ = _walk(lib, [_resize_frame(good, w, h) for w, h, _ in cases])
+    assert [int(v) for v in rec['status']] == [st for _, _, st in cases]
+    assert [(int(r['width']), int(r['height'])) for r in rec[:3]] == [c[:2] for c in cases[:3]]
+    for ss, (hs, vs) in enumerate(((1, 1), (2, 1), (2, 2))):
+        for w, h in ((4096, 16), (16, 4096)):
+            mw, mh = -(-w // (8 * hs)) * 8 * hs, -(-h // (8 * vs)) * 8 * vs
+            assert lib.wsi_jpeg_workspace_bytes(w, h, 3, hs, vs) == 3 * (mw * mh + 2 * (mw // hs) * (mh // vs))
+        assert lib.wsi_jpeg_workspace_bytes(4097, 16, 3, hs, vs) == 0 and lib.wsi_jpeg_workspace_bytes(16, 4097, 3, hs, vs) == 0
+
+
+def test_optimised_tables_fixture_and_walk(lib, tmp_path):
+    """TF.encode / TF.write_tiff(optimize=True): off by default (every other stream keeps its bytes), the oracle equals Pillow on such
+    streams, the walk keeps a set per stream and its slow-path tables (maxcode, valoffset, huffval) decode every code of more than 9
+    bits to the oracle's symbol; the colour forms of the bad scan streams keep the header of a good one."""
+    img = TF.noise(64, 48, 5)
+    assert TF.encode(img, 90, 2) == TF.encode(img, 90, 2, optimize=False) != TF.encode(img, 90, 2, optimize=True)
+    streams = [TF.encode(TF.noise(64, 48, 60 + k) if k % 2 else TF.he_like(64, 48, 60 + k), (75, 95)[k % 2], k % 3, restart=(0, 3)[k // 3], optimize=True)
+               for k in range(6)]
+    rec, sets, n_sets, _ = _walk(lib, streams)
+    assert (rec['status'] == 0).all() and n_sets == 6 and list(rec['table_set']) == list(range(6))
+    long_codes = 0
+    for s, r in zip(streams, rec):
+        d = O.parse(s)
+        assert int((O.decode(s) != np.asarray(Image.open(io.BytesIO(s)).convert('RGB'))).sum()) == 0
+        for (cls, tid), (counts, symbols) in d['huff'].items():
+            h = sets[r['table_set']]['huff'][2 * cls + tid]
+            assert np.array_equal(h['look'], _huff_lookup(counts, symbols))
+            for (length, code), sym in O._code_table(counts, symbols).items():
+                if length > 9:
+                    long_codes += 1
+                    assert h['look'][code >> (length - 9)] == 0                              # the look-up sends it to the slow path
+                    assert h['maxcode'][length - 1] < (code >> 1) and code <= h['maxcode'][length]   # which stops at this length
+                    assert h['huffval'][(code + h['valoffset'][length]) & 255] == sym
+    assert long_codes > 0
+    path = str(tmp_path / 'opt.tif')
+    lv = TF.noise(96, 128, 8)
+    info = TF.write_tiff(path, [lv], jpegtables=False, optimize=True)
+    plain = TF.write_tiff(str(tmp_path / 'plain.tif'), [lv], jpegtables=False)
+    assert all(a != b and len(a) < len(b) for a, b in zip(info['streams'][0], plain['streams'][0]))
+    s = TiffSlide(path)
+    assert int((np.asarray(s.read_region((0, 0), 0, (128, 96)))[..., :3] != TF.pillow_levels(path, info['frames'])[0]).sum()) == 0
+    s.close()
+    with pytest.raises(AssertionError):
+        TF.write_tiff(path, [lv], optimize=True)                # abbreviated streams cannot carry tables of their own
+    grey = TF.bad_scan_streams()
+    assert list(grey) == ['exhausted', 'bad_code', 'coef_overrun', 'short', 'zrl_end']
+    for ss in (0, 1, 2):
+        bad = TF.bad_scan_streams(ss)
+        assert list(bad) == ['exhausted', 'bad_code', 'coef_overrun'] and [v[1] for v in bad.values()] == [v[1] for v in list(grey.values())[:3]]
+        rec, _, _, _ = _walk(lib, [v[0] for v in bad.values()])
+        assert (rec['status'] == 0).all()                       # the damage is in the scan; the frame is a 16 x 16 colour tile's
+        assert all((r['width'], r['height'], r['ncomp'], r['h'][0], r['v'][0]) == (16, 16, 3, (1, 2, 2)[ss], (1, 1, 2)[ss]) for r in rec)
+
+
 # ------------------------------------------------------------------------------------------------ the decode loop under sanitizers
 def _fixture_streams():
     """(tables or b'', stream) of every valid kind the fixtures make: complete and abbreviated, the three sub-samplings, grey, restart"""
@@ -353,6 +418,7 @@ def sanitizer_corpus():
             tgt[i + 4 + int(rng.integers(0, ln - 2))] = int(rng.integers(0, 256))
         cases.append((bytes(t2), bytes(s2), None))
     cases += [(b'', s, st) for s, st in TF.bad_scan_streams().values()]
+    cases += [(b'', s, st) for ss in (0, 1, 2) for s, st in TF.bad_scan_streams(ss).values()]      # their three-component forms
     return cases
 
 

@@ -262,3 +262,44 @@ def test_dataset_wsis_without_stain_builds_what_it_built(tmp_path, monkeypatch):
     assert w0['iterator'].batch_size == w1['iterator'].batch_size == 4 and w0['maskpath'] == w1['maskpath']
     assert isinstance(w2['scan'], stain.StainedSlide) and w2['scan'].scan is scan and w2['scan'].normalizer is norm
     assert norm.fits == [] and norm.applies == []               # nothing is normalised before a level is asked for
+
+
+# ------------------------------------------------------------------------------------- the inputs of tests/test_gpu_stain.py
+def test_gpu_case_inputs_and_pairwise_moments():
+    """What the GPU tests' fixture decides on its own: the head of an image by its address (the kernel's closed form), the tissue count
+    of every step, the two constructions (a crop of the parent up to one step, the parent repeated periodically beyond), the condition
+    that every step of every case holds tissue, and the pairwise moments against exactly rounded sums."""
+    import test_gpu_stain as G
+    for a in range(64):
+        h = G.head_pixels(a)
+        assert 0 <= h < 16 and (a + 3 * h) % 16 == 0 and h == (((16 - a % 16) & 15) * 11) & 15     # csrc/stain.hip, head_pixels
+    img = np.full((3, 4096, 3), 255, np.uint8)                  # three steps of background ...
+    img.reshape(-1, 3)[[0, 4, 4095, 4096, 4099, 8191, 12287]] = 100          # ... and seven tissue pixels
+    assert G.step_tissue(img, 0) == ([3, 3, 1], None)
+    assert G.step_tissue(img, 4) == ([4, 1], 1)                 # a head of four pixels: step 0 is pixels 4 .. 4099, two full steps, 12287 in a partial one
+    assert G.step_tissue(img[:1, :4000], 0) == ([], None)       # under one step: nothing to count
+    for h, w, n in G.CASES:
+        case = G.Case(h, w, n)
+        parents = SO.shifted_he(40 + h + w, n, G.PARENT)
+        assert case.imgs.shape == (n, h, w, 3) and len(case.fits) == n
+        for i in range(n):
+            if n == 3 and i == 1:
+                assert (case.imgs[i] == 255).all() and case.n[i] == 0
+            elif h * w > G.STEP_PIXELS:
+                yy, xx = np.mgrid[:h, :w]
+                assert np.array_equal(case.imgs[i], parents[i][yy % G.PARENT, xx % G.PARENT])
+            else:
+                assert case.n[i] > 0 and any(np.array_equal(case.imgs[i], parents[i][y:y + h, x:x + w])
+                                             for y in range(G.PARENT - h + 1) for x in range(G.PARENT - w + 1))
+        if h * w >= G.STEP_PIXELS:
+            assert len(case.step_tissue) == (1 if n == 1 else 2)
+            for full, last in case.step_tissue:
+                assert len(full) >= 1 and min(full) > 0 and (last is None or last > 0)
+    v = SO.lab_of(SO.shifted_he(3, 1, 128)[0])
+    n, s, ss = SO.moments_pairwise(v)
+    assert n == 128 * 128
+    for a in range(3):
+        assert abs(s[a] - math.fsum(v[:, a])) <= 1e-14 * math.fsum(np.abs(v[:, a]))
+        for b in range(3):
+            p = v[:, a] * v[:, b]
+            assert abs(ss[a, b] - math.fsum(p)) <= 1e-14 * math.fsum(np.abs(p)) and ss[a, b] == ss[b, a]

@@ -38,8 +38,9 @@ def strip_app_markers(stream):
     return b''.join(out)
 
 
-def encode(arr, quality=75, subsampling=0, restart=0, rgb=False, streamtype=0, progressive=False, strip=False):
-    """one JPEG stream of a (h, w, 3) or (h, w) u8 array.  rgb: the three planes are stored untransformed (Adobe transform 0)."""
+def encode(arr, quality=75, subsampling=0, restart=0, rgb=False, streamtype=0, progressive=False, strip=False, optimize=False):
+    """one JPEG stream of a (h, w, 3) or (h, w) u8 array.  rgb: the three planes are stored untransformed (Adobe transform 0).
+    optimize: Huffman tables made for this image (libjpeg's optimize_coding) instead of the standard ones."""
     kw = dict(quality=quality, streamtype=streamtype)
     if arr.ndim == 3:
         kw['subsampling'] = subsampling
@@ -49,6 +50,8 @@ def encode(arr, quality=75, subsampling=0, restart=0, rgb=False, streamtype=0, p
         kw['restart_marker_blocks'] = restart
     if progressive:
         kw['progressive'] = True
+    if optimize:
+        kw['optimize'] = True
     b = io.BytesIO()
     Image.fromarray(arr).save(b, 'JPEG', **kw)
     s = b.getvalue()
@@ -67,12 +70,13 @@ def pyramid(h, w, levels=3, seed=0, content=he_like):
 
 
 def write_tiff(path, levels, tile=(64, 48), big=False, endian='<', jpegtables=True, photometric=6, quality=75, subsampling=2, restart=0,
-               strip=False, empty=(), progressive=(), thumbnail=False, compression=7):
+               strip=False, empty=(), progressive=(), thumbnail=False, compression=7, optimize=False):
     """Write the pyramid; returns dict(streams=[per level [tile stream]], tables=[per level blob or None], frames=[Pillow frame index
     of each level]).  tile = (tile_w, tile_h); empty / progressive: sets of (level, tile index) written with byte count 0 / as a
-    complete progressive stream."""
+    complete progressive stream; optimize: every tile stream carries Huffman tables of its own (use with jpegtables=False)."""
     tw, th = tile
     e = endian
+    assert not (optimize and jpegtables), 'abbreviated streams carry no tables: optimised ones go with jpegtables=False'
     rgb = photometric == 2
     if rgb:
         subsampling = 0                                          # Pillow stores untransformed RGB at full resolution only
@@ -110,7 +114,7 @@ def write_tiff(path, levels, tile=(64, 48), big=False, endian='<', jpegtables=Tr
                 elif (k, idx) in progressive:
                     s = encode(t, quality, subsampling, 0, rgb, 0, True, strip)
                 else:
-                    s = encode(t, quality, subsampling, restart, rgb, 2 if jpegtables else 0, False, strip)
+                    s = encode(t, quality, subsampling, restart, rgb, 2 if jpegtables else 0, False, strip, optimize)
                 streams.append(s)
                 offs.append(blob(s) if s else 0)
                 cnts.append(len(s))
@@ -189,16 +193,18 @@ def _code_of(stream, cls, symbol):
     raise KeyError(symbol)
 
 
-def bad_scan_streams():
+def bad_scan_streams(subsampling=None):
     """{name: (stream, status)}: complete 16 x 16 greyscale streams (Pillow's header, the standard Huffman tables) that pass the marker
-    walk and end the decode loop with the WSI_JPEG_* status given.
+    walk and end the decode loop with the WSI_JPEG_* status given.  subsampling 0 / 1 / 2: three-component streams of that sub-sampling
+    instead, for a colour batch - the first three only, which are damaged in the first luma block and do not depend on the MCU layout.
       exhausted   : the scan cut in the middle, EOI put back behind it
       bad_code    : sixteen 1-bits where a DC code is due (the standard DC table has no code of all ones)
       coef_overrun: DC category 0, three ZRL (coefficient 49), then run 15 / size 1: the run passes coefficient 63
       short       : restart markers after every MCU, the DRI segment patched to promise two MCUs per interval
       zrl_end     : status 0 - four blocks of DC category 0 and four ZRL each: the fourth ZRL passes coefficient 63 and ends the block, as
                     in libjpeg; every coefficient is zero"""
-    g16 = encode(noise(16, 16, 6, 1), 75)
+    colour = subsampling is not None
+    g16 = encode(noise(16, 16, 6, 3), 75, subsampling) if colour else encode(noise(16, 16, 6, 1), 75)
     g16r = encode(noise(16, 16, 7, 1), 75, restart=1)
     s16 = _scan_start(g16)
     dc0, zrl, f1 = _code_of(g16, 0, 0), _code_of(g16, 1, 0xF0), _code_of(g16, 1, 0xF1)
@@ -207,6 +213,8 @@ def bad_scan_streams():
     out['exhausted'] = (g16[:s16] + body[:len(body) // 2].rstrip(b'\xff') + b'\xff\xd9', 19)
     out['bad_code'] = (g16[:s16] + b'\xff\x00\xff\x00' + b'\xff\xd9', 16)
     out['coef_overrun'] = (g16[:s16] + _stuffed(dc0 + zrl * 3 + f1 + '1') + b'\xff\xd9', 17)
+    if colour:
+        return out
     at = g16r.index(b'\xff\xdd\x00\x04')
     assert g16r[at + 4:at + 6] == b'\x00\x01'
     out['short'] = (g16r[:at + 4] + b'\x00\x02' + g16r[at + 6:], 18)
