@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_*, wsi_stain_*, wsi_jpeg_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
+#define WSI_HIP_ABI_VERSION 9            /* (additive entry points and structs - wsi_conv1x1_bn_act, wsi_bneck_*, wsi_stain_*, wsi_jpeg_*, wsi_jenc_* - do not bump it: no existing symbol or layout changed) wsi_trunk_weights.blocks + conv tables of WSI_TRUNK_MAX_BLOCKS (8: wsi_s2_slab_images (7: wsi_unet_tail_bands, wsi_unet_tail_timeouts (6, r05: planes 2 = fp16 pair, its packed conv weights end in cout inverse channel scales; wsi_unet_decoder_weights.tail_w))) */
 int wsi_hip_abi_version(void);
 
 /* ---- padded-flat layout helpers (host) -------------------------------------------------------
@@ -868,6 +868,54 @@ int wsi_jpeg_entropy(const uint8_t* bytes, size_t nbytes, const wsi_jpeg_tile* t
 int wsi_jpeg_reconstruct(void* ws, size_t ws_bytes, const int* status, const int* tile_index, int n, int width, int height, int ncomp,
                          int hs, int vs, int transform, int grid_cols, int grid_rows, uint8_t* level, long long pitch, int H, int W,
                          void* stream);
+
+/* ---- The resident level written as JPEG tiles: baseline encode on the device ---------------------
+ * The mirror of the section above: the tiles of a (H, W, 3) or (H, W) u8 level become the scans of a JPEG-tiled TIFF level
+ * (wsi_segmentation_pipeline_amd/tiffwrite.py adds the markers and the container).  Baseline sequential DCT, the standard (Annex K)
+ * Huffman tables, 8 bit, one interleaved scan, 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma.  The arithmetic is
+ * libjpeg's default encode path in integers (jccolor's 16-bit fixed-point RGB -> YCbCr, jcsample's h2v1 / h2v2 box downsampling with
+ * the alternating bias, jfdctint's islow FDCT, jcdctmgr's quantisation, jchuff): the scan bytes equal libjpeg's; the spec is
+ * tests/jpeg_enc_oracle.py.
+ *
+ * Host side (no GPU): wsi_jenc_quality_tables fills the luma and chroma quantisation tables (64 entries each, natural = row-major order)
+ * of a libjpeg quality 1..100 (clamped into it): jpeg_quality_scaling of the Annex K tables with force_baseline.  wsi_jenc_std_huff
+ * gives table 0..3 (DC luma, DC chroma, AC luma, AC chroma) as a DHT segment holds it: 16 code counts, then *n_symbols (<= 162) symbols.
+ * Device side.  A batch is n tiles of ONE geometry (tile width x height, multiples of 16 in 16..4096; ncomp 1 or 3; luma sampling
+ * hs x vs), the grid cells first_cell .. first_cell + n - 1 of the level's grid (cell c is at pixel ((c % grid_cols) * width,
+ * (c / grid_cols) * height)).  The level has `pitch` bytes per row and any base alignment; a tile pixel outside the level takes the
+ * value of the nearest level pixel (coordinate clamp), so every tile is whole and the frame of every stream is the tile.
+ * wsi_jenc_workspace_bytes: bytes per tile (a multiple of 256; 0 for a geometry out of range); the workspace of n tiles is n areas of
+ * quantised int16 coefficients in the order of the scan: MCU by MCU, component by component (a luma MCU's blocks row by row), zigzag.
+ *   wsi_jenc_transform: colour, downsample, FDCT and quantise of the n tiles into ws.  One launch; it reads only the level's bytes.
+ *   wsi_jenc_entropy_size: sizes[i] (device, n entries) = the exact bytes of tile i's scan, byte stuffing and the final 1-padding
+ *     included.  restart: MCUs per restart interval (0: none); RSTn and the predictor reset come from the same lane.
+ *   wsi_jenc_entropy_write: tile i's scan goes to out[offsets[i] .. offsets[i] + sizes[i]); offsets and sizes are HOST arrays (the
+ *     sizes the size pass gave, the offsets the caller's choice) that must stay valid until the stream has passed the call; the entry
+ *     copies them to ranges_dev (device, 12 n bytes, 8-byte aligned).  A lane writes no byte outside its range (a scan longer than
+ *     the size it was given is cut).  Both passes: a workgroup is one wave with `lanes` of its 64 lanes at work, tile = workgroup *
+ *     lanes + lane; lanes 0: the rule of wsi_jpeg_entropy.
+ *   wsi_jenc_downsample: dst[y][x][c] = (sum of the factor x factor block of src + factor^2 / 2) / factor^2 for the
+ *     (H / factor, W / factor) destination (trailing partial blocks are dropped); factor 2 or 4, channels 1 or 3.
+ * -22 before any device work: a NULL pointer, n <= 0, a tile side that is not a multiple of 16 or outside 16..4096, ncomp not 1 or 3,
+ *   sampling not 1x1 / 2x1 / 2x2 (or not 1x1 with one component), a quantiser entry of 0 (the type ends at 255), H, W, grid_cols or
+ *   grid_rows <= 0, pitch below the row's bytes (W * ncomp; the destination's likewise), a grid whose last column or row starts
+ *   outside the level, first_cell < 0 or first_cell + n past the grid, ws not 16-byte aligned or ws_bytes < n *
+ *   wsi_jenc_workspace_bytes(), restart outside 0..65535, lanes outside 0..64, ranges_dev not 8-byte aligned, a range
+ *   offsets[i] + sizes[i] that leaves out_bytes, a batch of more than 2^31 - 1 transform workgroups, table outside 0..3, factor not
+ *   2 / 4, channels not 1 / 3, a destination without a pixel. */
+int wsi_jenc_quality_tables(int quality, uint8_t* luma_natural, uint8_t* chroma_natural);
+int wsi_jenc_std_huff(int table, uint8_t* counts16, uint8_t* symbols, int* n_symbols);
+size_t wsi_jenc_workspace_bytes(int width, int height, int ncomp, int hs, int vs);
+int wsi_jenc_transform(const uint8_t* level, long long pitch, int H, int W, int grid_cols, int grid_rows, int first_cell, int n, int width,
+                       int height, int ncomp, int hs, int vs, const uint8_t* luma_natural, const uint8_t* chroma_natural, void* ws,
+                       size_t ws_bytes, void* stream);
+int wsi_jenc_entropy_size(const void* ws, size_t ws_bytes, int n, int width, int height, int ncomp, int hs, int vs, int restart,
+                          unsigned int* sizes, int lanes, void* stream);
+int wsi_jenc_entropy_write(const void* ws, size_t ws_bytes, int n, int width, int height, int ncomp, int hs, int vs, int restart,
+                           const unsigned long long* offsets, const unsigned int* sizes, void* ranges_dev, uint8_t* out, size_t out_bytes,
+                           int lanes, void* stream);
+int wsi_jenc_downsample(const uint8_t* src, long long src_pitch, int H, int W, int channels, int factor, uint8_t* dst, long long dst_pitch,
+                        void* stream);
 
 #ifdef __cplusplus
 }

@@ -132,9 +132,10 @@ def _dense_batches(model, it, scan, dev, forward):
         yield np.stack((batch_x.numpy(), batch_y.numpy()), 1), forward(batch_image.to(dev))
 
 
-def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True):
+def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False):
     """Tumour-bed heat maps for every slide in ``dataset`` (a utils.dataset.Dataset_wsis).
-    Writes <val_save_pth>/<ep>/<key>_<stride>_heatmap.png and _overlay.png (rank 0) and returns
+    Writes <val_save_pth>/<ep>/<key>_<stride>_heatmap.png and _overlay.png (rank 0; with save_tiff also _heatmap.tif, the heat map as
+    a one-component JPEG-tiled pyramid encoded on the device, wsi_segmentation_pipeline_amd.tiffwrite) and returns
     {key: {'heatmap': u8 (H2,W2) ndarray, 'classes': u8 ndarray, 'logits': (T,C) tensor}}."""
     if mode not in ('cls', 'seg'):
         raise ValueError("mode must be 'cls' or 'seg'")
@@ -230,6 +231,9 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True)
                 thumb = np.asarray(scan.read_region((0, 0), ref_level, scan.level_dimensions[ref_level]).convert('RGB'))
                 over = thumb * 0.75 + 255 * np.repeat((heat > 255 * 0.99)[..., None], 3, -1) * 0.25
                 _save_png(np.uint8(over), '{}/{}_{}_overlay.png'.format(out_dir, key, args.tile_stride_w))
+                if save_tiff:
+                    from wsi_segmentation_pipeline_amd import tiffwrite
+                    tiffwrite.write_pyramid('{}/{}_{}_heatmap.tif'.format(out_dir, key, args.tile_stride_w), r['heatmap'].contiguous(), downsample=2)
             dataset.wsis[key] = None                       # the reference frees each slide after use (:282)
     if was_training:
         model.train()
@@ -249,7 +253,7 @@ def _map_u8(arr, hw, dev):
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(dev)
 
 
-def predict_wsis(model, dataset, ep, save=True):
+def predict_wsis(model, dataset, ep, save=True, save_tiff=False):
     """Dense per-pixel map prediction with the tumour-bed post-process (reference utils/eval.py:22-152).
     `model(batch_image)` must return (B, C, ph, pw) logits on the GPU (the reference drives an smp U-Net here; any GPU
     module works, e.g. wsi_segmentation_pipeline_amd.unet.UNetSeg).  Everything between the tile list and the colour
@@ -260,6 +264,8 @@ def predict_wsis(model, dataset, ep, save=True):
       :100-123  tumour-bed IoU, accuracy / score figures against `entry['gt']` / `entry['tb_gt']` (when the dataset
                 entry carries them: the reference reads <wsipath>_mask.png / _tumor_bed.png)    wsi_score_counts, wsi_mask_iou_counts
       :138-145  colour mask (threshold_probs classes on the foreground mask, tumour-bed outline in white), saved at half size
+    save_tiff (with save): additionally <key>_<stride>.tif, the colour mask at SCAN-LEVEL resolution - the scan-level `classes`, the
+    foreground mask and the outline scaled up by nearest - as a JPEG-tiled pyramid encoded on the device (tiffwrite.write_pyramid).
     Returns {key: {'pred', 'pred_level2', 'classes' (scan level), 'classes_level2', 'tumor_bed', 'outline', 'scores'}}."""
     from wsi_segmentation_pipeline_amd import postprocess as PP
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -310,6 +316,16 @@ def predict_wsis(model, dataset, ep, save=True):
                 from PIL import Image
                 img = Image.fromarray(rgb.cpu().numpy())
                 img.resize((max(1, map_hw[1] // 2), max(1, map_hw[0] // 2))).save('{}/{}_{}.png'.format(out_dir, key, args.tile_stride_w))
+                if save_tiff:
+                    from wsi_segmentation_pipeline_amd import tiffwrite
+                    ys = torch.arange(ih, device=dev) * map_hw[0] // ih          # nearest: scan-level row -> map row
+                    xs = torch.arange(iw, device=dev) * map_hw[1] // iw
+                    keep, edge = (mask_dev > 0)[ys][:, xs], (tb.outline > 0)[ys][:, xs]
+                    full = torch.zeros((ih, iw, 3), dtype=torch.uint8, device=dev)
+                    for cj in range(min(args.num_classes - 1, 3)):
+                        full[..., cj] = ((classes == cj + 1) & keep).to(torch.uint8) * 255
+                    full[edge] = 255
+                    tiffwrite.write_pyramid('{}/{}_{}.tif'.format(out_dir, key, args.tile_stride_w), full, downsample=2)
         if dataset.wsis:
             print('Average tb iou: {:.3f}'.format(ious_tb / len(dataset.wsis)))
     if was_training:

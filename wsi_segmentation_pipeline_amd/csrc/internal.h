@@ -59,6 +59,8 @@ int wsi_unet_head_dispatch(const void* in, int n, int h, int w, int c_pf, const 
                            int planes, hipStream_t st);
 int wsi_resize_nearest_dispatch(const float* src, long long planes_n, int hs, int ws, float* dst, int hd, int wd, hipStream_t st);
 int wsi_unet_tail_dispatch(const void* x4, const void* blob, int n, int h, int w, int classes, float* logits, hipStream_t st);
+// jpeg.hip: lanes per wave of the one-lane-per-tile entropy kernels (jpeg.hip, jpeg_enc.hip); lanes != 0 is returned as it is
+int wsi_entropy_lanes(int n, int lanes);
 // linknet.hip: ConvTranspose2d(4, stride 2, padding 1) + folded BN + ReLU; a.gi = the (n, h, w, c) input, a.go = (n, 2h, 2w, c), a.ksize = 4
 int wsi_tconv_dispatch(const ConvArgs& a, int planes, hipStream_t st);
 // slide_ops.hip

@@ -228,7 +228,10 @@ __global__ __launch_bounds__(256) void store_kernel(StoreArgs a, Geometry g, int
 
 int launched() { return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT; }
 
-int compute_units() {
+}  // namespace
+
+// compute units of the current device (256 where it cannot be asked)
+static int compute_units() {
     static int cus = 0;
     if (cus == 0) {
         int dev = 0, v = 0;
@@ -237,7 +240,14 @@ int compute_units() {
     }
     return cus;
 }
-}  // namespace
+// lanes per wave of a one-lane-per-tile entropy kernel over n tiles (0 = this rule): at least four waves per compute unit where the
+// batch has the tiles for it, and as few lanes per wave as that allows
+int wsi_entropy_lanes(int n, int lanes) {
+    if (lanes != 0) return lanes;
+    const int waves = compute_units() * 4;
+    lanes = (n + waves - 1) / waves;
+    return lanes < 1 ? 1 : lanes > 64 ? 64 : lanes;
+}
 
 size_t wsi_jpeg_tables_bytes(void) { return sizeof(wsi_jpeg_tables); }
 size_t wsi_jpeg_tile_bytes(void) { return sizeof(wsi_jpeg_tile); }
@@ -265,12 +275,7 @@ int wsi_jpeg_entropy(const uint8_t* bytes, size_t nbytes, const wsi_jpeg_tile* t
     if (!wsi_jpeg::geometry_make(width, height, ncomp, hs, vs, &g) || ((uintptr_t)ws & 15u) || ws_bytes / (size_t)g.tile_bytes < (size_t)n) return WSI_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     if (hipMemsetAsync(ws, 0, (size_t)n * (size_t)g.coef_bytes, st) != hipSuccess) return WSI_EFAULT;
-    // at least four waves per compute unit where the batch has the tiles for it, and as few lanes per wave as that allows
-    if (lanes == 0) {
-        const int waves = compute_units() * 4;
-        lanes = (n + waves - 1) / waves;
-        lanes = lanes < 1 ? 1 : lanes > 64 ? 64 : lanes;
-    }
+    lanes = wsi_entropy_lanes(n, lanes);
     hipLaunchKernelGGL(entropy_kernel, dim3((unsigned)((n + lanes - 1) / lanes)), dim3(64), 0, st, bytes, (unsigned long long)nbytes, tiles, n, sets,
                        n_sets, common_set, g, (uint8_t*)ws, status, lanes);
     return launched();

@@ -239,6 +239,13 @@ SIGNATURES = {
     'wsi_jpeg_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
     'wsi_jpeg_entropy': (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _sz, _vp, _i, _vp]),
     'wsi_jpeg_reconstruct': (_i, [_vp, _sz, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _ll, _i, _i, _vp]),
+    'wsi_jenc_quality_tables': (_i, [_i, _vp, _vp]),
+    'wsi_jenc_std_huff': (_i, [_i, _vp, _vp, C.POINTER(_i)]),
+    'wsi_jenc_workspace_bytes': (_sz, [_i, _i, _i, _i, _i]),
+    'wsi_jenc_transform': (_i, [_vp, _ll, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    'wsi_jenc_entropy_size': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp, _i, _vp]),
+    'wsi_jenc_entropy_write': (_i, [_vp, _sz, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
+    'wsi_jenc_downsample': (_i, [_vp, _ll, _i, _i, _i, _i, _vp, _ll, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)
