@@ -917,6 +917,24 @@ int wsi_jenc_entropy_write(const void* ws, size_t ws_bytes, int n, int width, in
 int wsi_jenc_downsample(const uint8_t* src, long long src_pitch, int H, int W, int channels, int factor, uint8_t* dst, long long dst_pitch,
                         void* stream);
 
+/* ---- Annotation polygons rasterised into a sampled label map -------------------------------------
+ * Replaces the ground-truth route of utils/read_xml.py:69-78 and utils/read_xml_sunnybrook.py:93-108 (cv2.fillPoly / polylines on a
+ * full-resolution canvas, then every step-th pixel): coverage is evaluated at the sampled lattice points alone, in exact integers.
+ * The rule (spec: tests/annotations_oracle.py; the shared per-edge test: csrc/poly_dev.h): pixel (x, y) of the W x H u8 map samples
+ * p = (ox + x sx, oy + y sy).  An edge with ends lo, hi sorted by y crosses iff lo.y <= py < hi.y and
+ * (hi.x - lo.x)(py - lo.y) - (px - lo.x)(hi.y - lo.y) > 0; a polygon (n >= 1 vertices, closed implicitly) covers p if p lies on one of
+ * its closed edges or the number of crossings is odd.  Polygons are painted in list order, a covered pixel takes the low 8 bits of
+ * the label of the last polygon covering it (0 erases), an uncovered pixel keeps what `out` held.
+ *   edges: n_edges x 4 int32 (x0, y0, x1, y1), device, 16-byte aligned.  polys: n_polys x 8 int32 (first edge, edge count, box
+ *     xmin, ymin, xmax, ymax - which must contain the polygon's edges -, label, 0), device, 4-byte aligned.  A record whose edges leave
+ *     [0, n_edges) is skipped.  Every coordinate lies in [-2^29, 2^29] (the caller's duty: the arrays are device memory).
+ *   out: pitch_bytes >= W per row, any alignment; whole aligned 16-byte pieces of a row are stored at once, the ragged ends of a row
+ *     byte by byte; no byte outside the H row segments is read or written.  n_polys == 0: nothing is launched.
+ * -22 before any device work: out NULL, edges or polys NULL (or misaligned) with n_polys > 0, a negative count, W or H <= 0, a step
+ *   <= 0, pitch_bytes < W, an origin or a last sampled point outside [-2^29, 2^29], more than 2^31 - 1 tiles of 128 x 32 pixels. */
+int wsi_poly_raster(const int* edges, long long n_edges, const int* polys, int n_polys, uint8_t* out, int W, int H, long long pitch_bytes,
+                    int ox, int oy, int sx, int sy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -206,9 +206,13 @@ def GenerateIterator_wsi(wsipth, p, bs, stain=None):
 
 class Dataset_wsis:
     """All validation slides under ``svs_pth`` (``Case*/*.svs`` like the reference; also
-    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide-or-TiffSlide}`` mapping.  stain: as Dataset_wsi."""
+    ``*.npz``/``*.npy`` pyramids), or an explicit ``{name: path-or-ArraySlide-or-TiffSlide}`` mapping.  stain: as Dataset_wsi.
+    annotations: None (nothing changes), 'imagescope', 'sedeen' or callable(xml path, scan) -> (coords, labels).  A slide given by path
+    whose ``<path without extension>.xml`` exists - or a mapping value ``(slide, xml path)`` - then gets entry['gt'], the class map
+    at level min(2, level_count - 1) that predict_wsis scores at, and entry['tb_gt'], its tumour bed: u8 GPU tensors rasterised by
+    wsi_segmentation_pipeline_amd.annotations (the reference reads <slide>_mask.png / <slide>_tumor_bed.png made by preprocess/mk_gt.py)."""
 
-    def __init__(self, svs_pth, params, bs=args.batch_size, stain=None):
+    def __init__(self, svs_pth, params, bs=args.batch_size, stain=None, annotations=None):
         self.params = preprocessing.DotDict(params)
         self.wsis = {}
         if isinstance(svs_pth, dict):
@@ -218,8 +222,17 @@ class Dataset_wsis:
                            + glob.glob('{}/*.npy'.format(svs_pth)))
             entries = [(os.path.basename(p), p) for p in paths]
         for filename, src in entries:
+            xml = None
+            if annotations is not None:
+                if isinstance(src, tuple):
+                    src, xml = src
+                elif isinstance(src, (str, os.PathLike)) and os.path.exists(os.path.splitext(str(src))[0] + '.xml'):
+                    xml = os.path.splitext(str(src))[0] + '.xml'
             itr = GenerateIterator_wsi(src, preprocessing.DotDict(dict(self.params.__dict__, **self.params)), bs, stain=stain)
             if itr is not None:
                 self.wsis[filename] = {'iterator': itr, 'wsipath': src, 'scan': itr.dataset.scan,
                                        'maskpath': '{}/{}.png'.format(args.wsi_mask_pth, filename),
                                        'mask': itr.dataset.mask}
+                if xml is not None:
+                    from wsi_segmentation_pipeline_amd import annotations as A
+                    self.wsis[filename]['gt'], self.wsis[filename]['tb_gt'] = A.slide_ground_truth(xml, itr.dataset.scan, annotations)

@@ -242,7 +242,15 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
 
 def _map_u8(arr, hw, dev):
     """Ground-truth image -> uint8 (H,W) device tensor at map resolution (nearest-neighbour when the size differs; the
-    reference resizes with PIL's version-dependent default filter, utils/eval.py:77-78)."""
+    reference resizes with PIL's version-dependent default filter, utils/eval.py:77-78).  A GPU tensor (a map rasterised by
+    wsi_segmentation_pipeline_amd.annotations) stays on the device: passed through at equal size, resized by the same rule otherwise."""
+    if isinstance(arr, torch.Tensor) and arr.is_cuda:
+        a = arr[..., 0] if arr.dim() == 3 else arr
+        if tuple(a.shape) != tuple(hw):
+            ys = (torch.arange(hw[0], device=a.device) * a.shape[0] // hw[0]).clamp(0, a.shape[0] - 1)
+            xs = (torch.arange(hw[1], device=a.device) * a.shape[1] // hw[1]).clamp(0, a.shape[1] - 1)
+            a = a[ys][:, xs]
+        return a.to(dev, torch.uint8).contiguous()
     a = np.asarray(arr)
     if a.ndim == 3:
         a = a[..., 0]

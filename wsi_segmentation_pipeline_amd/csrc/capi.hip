@@ -486,4 +486,17 @@ int wsi_resize_nearest_f32(const float* src, long long planes_n, int hs, int ws,
     return wsi_resize_nearest_dispatch(src, planes_n, hs, ws, dst, hd, wd, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------------------------ annotation polygons -> sampled label map
+int wsi_poly_raster(const int* edges, long long n_edges, const int* polys, int n_polys, uint8_t* out, int W, int H, long long pitch_bytes,
+                    int ox, int oy, int sx, int sy, void* stream) {
+    const long long lim = 1LL << 29;
+    if (!out || n_edges < 0 || n_polys < 0 || W <= 0 || H <= 0 || sx <= 0 || sy <= 0 || pitch_bytes < W) return WSI_EINVAL;
+    if (n_polys > 0 && (!edges || !polys || ((uintptr_t)edges & 15) || ((uintptr_t)polys & 3))) return WSI_EINVAL;
+    if (W == 1) sx = 1;                                         // a step no pixel takes
+    if (H == 1) sy = 1;
+    if (ox < -lim || ox > lim || oy < -lim || oy > lim || ox + (long long)(W - 1) * sx > lim || oy + (long long)(H - 1) * sy > lim) return WSI_EINVAL;
+    if (n_polys == 0) return WSI_OK;
+    return wsi_poly_dispatch(edges, n_edges, polys, n_polys, out, W, H, pitch_bytes, ox, oy, sx, sy, (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -99,6 +99,9 @@ int wsi_hull_polygon_dispatch(void* ws, int H, double* out_xy, int cap, hipStrea
 int wsi_iou_counts_dispatch(const uint8_t* a, const uint8_t* b, long long n, unsigned long long* out, hipStream_t st);
 int wsi_score_counts_dispatch(const uint8_t* p, const uint8_t* gt, const uint8_t* mask, long long n, unsigned long long* out, hipStream_t st);
 int wsi_esp_dispatch(const double* pts, int n, int num, double* out, double* scratch, hipStream_t st);
+// poly.hip
+int wsi_poly_dispatch(const int* edges, long long n_edges, const int* polys, int n_polys, uint8_t* out, int W, int H, long long pitch,
+                      int ox, int oy, int sx, int sy, hipStream_t st);
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
