@@ -935,6 +935,46 @@ int wsi_jenc_downsample(const uint8_t* src, long long src_pitch, int H, int W, i
 int wsi_poly_raster(const int* edges, long long n_edges, const int* polys, int n_polys, uint8_t* out, int W, int H, long long pitch_bytes,
                     int ox, int oy, int sx, int sy, void* stream);
 
+/* ---- A label map traced into ordered boundary loops (the way back from a class map to annotation polygons) ----
+ * An own rule (the reference has no such code; spec: tests/contours_oracle.py; the shared per-edge rule: csrc/contour_dev.h), pinned by
+ * an exact round trip through wsi_poly_raster.  Side d of pixel P (0 top heading east, 1 right south, 2 bottom west, 3 left north) is a
+ * boundary edge iff P's label is traced and the pixel across has another label (a pixel outside the map differs from every label).  The
+ * successor of edge (P, d), with F the pixel ahead and A the pixel across side d of F: F differs from P -> (P, d + 1); else A differs ->
+ * (F, d); else (A, d - 1): 4-connected foreground, so loops of all labels never cross.  A loop starts at the tail of its smallest-key
+ * edge (key = (ty (W + 1) + tx) 4 + d of the tail corner) and loops are listed by that key; vertices are the tails of the edges whose
+ * predecessor has another heading.  Map corner (cx, cy) becomes (ox + cx sx - sx / 2, oy + cy sy - sy / 2), each then clamped to
+ * [0, bounds - 1] where bounds > 0.  For steps >= 2 the loops, largest |area2| first, holes (area2 < 0) as label 0 and before outer loops
+ * on a tie, painted by wsi_poly_raster at the same step and origin give back the traced labels of the map, byte for byte.
+ *   map: H rows of W bytes, pitch_bytes >= W, any alignment; read through aligned 16-byte pieces and bytes at the ragged ends, nothing
+ *     outside the H row segments, never written.  traced256: HOST table, byte l != 0: label l is traced.  1 <= W, H; W H <= 2^28.
+ *   wsi_contour_count: the boundary edges per chunk of corners into count_ws (wsi_contour_count_workspace_bytes, device) and their
+ *     number into *n_edges_out (device).  The caller reads it, and stops there when it is 0.
+ *   The next four entries run in this order on one workspace of wsi_contour_workspace_bytes(n_edges) device bytes, 16-byte aligned (no
+ *   hidden allocation), with the same n_edges - the count's - and, where they take it, the same map:
+ *   wsi_contour_build: compact edge ids in key order, and every edge's successor in those ids.
+ *   wsi_contour_ranks: every edge's loop leader (its smallest id) and forward distance to it by pointer doubling: ceil(log2 n_edges)
+ *     rounds, the count taken from n_edges on the host, no convergence read-back.
+ *   wsi_contour_order: loops and their first slots by one prefix sum over the leaders, every edge to its slot, vertices numbered and
+ *     area2 formed by prefix sums there.  counts_out (device): {n_loops, n_vertices}.
+ *   wsi_contour_emit: vertices[n_vertices][2] int32 (x, y) in level-0 coordinates, loop by loop; loops[n_loops][8] int32 {first vertex,
+ *     vertex count, edge count, label, 0, 0, 0, 0}; area2[n_loops] int64 in map-corner units (positive: outer loop, negative: hole).
+ *     Nothing is written past n_vertices / n_loops, nor past cap_vertices / cap_loops.
+ * -22 before any device work: a NULL or misaligned pointer (4 bytes: count_ws and the counts; 16: workspace and loops; 8: vertices and
+ *   area2), W or H < 1, W H > 2^28, pitch_bytes < W, n_edges outside 1 .. 4 W H (1 .. 2^30 where no map is passed), a workspace smaller
+ *   than wsi_contour_workspace_bytes, a step < 1, negative bounds or capacities, an origin or a produced corner coordinate outside
+ *   [-2^29, 2^29].  The *_bytes entries return 0 for sizes outside these limits. */
+size_t wsi_contour_count_workspace_bytes(int W, int H);
+size_t wsi_contour_workspace_bytes(long long n_edges);
+int wsi_contour_count(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, void* count_ws, unsigned int* n_edges_out,
+                      void* stream);
+int wsi_contour_build(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, const void* count_ws, long long n_edges,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int wsi_contour_ranks(void* workspace, size_t workspace_bytes, long long n_edges, void* stream);
+int wsi_contour_order(void* workspace, size_t workspace_bytes, long long n_edges, int W, unsigned int* counts_out, void* stream);
+int wsi_contour_emit(const uint8_t* map, int W, int H, long long pitch_bytes, const void* workspace, size_t workspace_bytes, long long n_edges,
+                     int ox, int oy, int sx, int sy, int bounds_w, int bounds_h, int* vertices, long long cap_vertices, int* loops, long long* area2,
+                     long long cap_loops, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,10 +132,13 @@ def _dense_batches(model, it, scan, dev, forward):
         yield np.stack((batch_x.numpy(), batch_y.numpy()), 1), forward(batch_image.to(dev))
 
 
-def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False):
+def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False, save_xml=False):
     """Tumour-bed heat maps for every slide in ``dataset`` (a utils.dataset.Dataset_wsis).
     Writes <val_save_pth>/<ep>/<key>_<stride>_heatmap.png and _overlay.png (rank 0; with save_tiff also _heatmap.tif, the heat map as
-    a one-component JPEG-tiled pyramid encoded on the device, wsi_segmentation_pipeline_amd.tiffwrite) and returns
+    a one-component JPEG-tiled pyramid encoded on the device, wsi_segmentation_pipeline_amd.tiffwrite; with save_xml also _tb.xml, the
+    tumour bed of the heat map - tumor_bed_overlay's (heat / 255 >= 0.9) -> open 30 x 30 -> convex hull - traced on the device into ImageScope
+    regions named 'Invasive', in level-0 coordinates: wsi_segmentation_pipeline_amd.contours; MicronsPerPixel is the slide's where it
+    states one, `scan.mpp` or openslide's mpp-x property, else 1.0) and returns
     {key: {'heatmap': u8 (H2,W2) ndarray, 'classes': u8 ndarray, 'logits': (T,C) tensor}}."""
     if mode not in ('cls', 'seg'):
         raise ValueError("mode must be 'cls' or 'seg'")
@@ -234,6 +237,11 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
                 if save_tiff:
                     from wsi_segmentation_pipeline_amd import tiffwrite
                     tiffwrite.write_pyramid('{}/{}_{}_heatmap.tif'.format(out_dir, key, args.tile_stride_w), r['heatmap'].contiguous(), downsample=2)
+                if save_xml:
+                    from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT, postprocess as PP
+                    bed = (PP.tumor_bed_from_heatmap(r['heatmap'].contiguous(), 0.9, 30, 20).tb_pred > 0).to(torch.uint8)
+                    traced = CT.trace(bed, [1], AN.level_step(scan, ref_level), bounds=scan.level_dimensions[0])
+                    CT.write_imagescope('{}/{}_{}_tb.xml'.format(out_dir, key, args.tile_stride_w), traced, CT.slide_mpp(scan), {1: 'Invasive'})
             dataset.wsis[key] = None                       # the reference frees each slide after use (:282)
     if was_training:
         model.train()
@@ -261,7 +269,7 @@ def _map_u8(arr, hw, dev):
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(dev)
 
 
-def predict_wsis(model, dataset, ep, save=True, save_tiff=False):
+def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False):
     """Dense per-pixel map prediction with the tumour-bed post-process (reference utils/eval.py:22-152).
     `model(batch_image)` must return (B, C, ph, pw) logits on the GPU (the reference drives an smp U-Net here; any GPU
     module works, e.g. wsi_segmentation_pipeline_amd.unet.UNetSeg).  Everything between the tile list and the colour
@@ -274,6 +282,11 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False):
       :138-145  colour mask (threshold_probs classes on the foreground mask, tumour-bed outline in white), saved at half size
     save_tiff (with save): additionally <key>_<stride>.tif, the colour mask at SCAN-LEVEL resolution - the scan-level `classes`, the
     foreground mask and the outline scaled up by nearest - as a JPEG-tiled pyramid encoded on the device (tiffwrite.write_pyramid).
+    save_xml (with save): additionally <key>_<stride>.xml, ImageScope annotations in level-0 coordinates traced on the device
+    (wsi_segmentation_pipeline_amd.contours): classes 1 - 3 of the thresholded map on the foreground mask, what the PNG shows, as
+    Benign / In situ / Invasive regions, holes as NegativeROA regions, so annotations.read_imagescope(path, negative='erase') rasterised
+    at the map's step restores that map; a second Annotation element, which neither reader visits, holds the tumour bed as 'Invasive'.
+    MicronsPerPixel is the slide's where it states one (`scan.mpp`, or openslide's mpp-x property), else 1.0.
     Returns {key: {'pred', 'pred_level2', 'classes' (scan level), 'classes_level2', 'tumor_bed', 'outline', 'scores'}}."""
     from wsi_segmentation_pipeline_amd import postprocess as PP
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -334,6 +347,13 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False):
                         full[..., cj] = ((classes == cj + 1) & keep).to(torch.uint8) * 255
                     full[edge] = 255
                     tiffwrite.write_pyramid('{}/{}_{}.tif'.format(out_dir, key, args.tile_stride_w), full, downsample=2)
+                if save_xml:
+                    from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT
+                    step, size0 = AN.level_step(scan, ref_level), scan.level_dimensions[0]
+                    shown = (cls_thr * (mask_dev > 0)).to(torch.uint8).contiguous()
+                    bed = CT.trace((tb.tb_pred > 0).to(torch.uint8), [1], step, bounds=size0)
+                    CT.write_imagescope('{}/{}_{}.xml'.format(out_dir, key, args.tile_stride_w), CT.trace(shown, (1, 2, 3), step, bounds=size0),
+                                        CT.slide_mpp(scan), layers=[(bed, {1: 'Invasive'})])
         if dataset.wsis:
             print('Average tb iou: {:.3f}'.format(ious_tb / len(dataset.wsis)))
     if was_training:

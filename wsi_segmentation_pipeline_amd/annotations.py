@@ -28,11 +28,15 @@ SEDEEN_SKIPPED_TYPES = ('point', 'ellipse', 'text')
 
 
 # ------------------------------------------------------------------------------------------------------------------------ parsers
-def read_imagescope(path):
+def read_imagescope(path, negative=None):
     """Aperio ImageScope / BACH XML (reference utils/read_xml.py:29-66) -> (coords, labels, lengths, areas, microns per pixel): the
     regions under root[0][1]; a region's label is its first attribute's `Value`, or its own `Text`, mapped by substring
     (case-insensitive) benign / in situ / invasive -> 1 / 2 / 3.  A label that matches none raises ValueError naming the region (the
-    reference fails later, with a TypeError, when it indexes its colour list)."""
+    reference fails later, with a TypeError, when it indexes its colour list).
+    negative: None reads a region with NegativeROA="1" like any other (the reference's behaviour); 'erase' gives it the label 0, so
+    that painting in file order subtracts it (what contours.write_imagescope(holes='negative') writes for a hole)."""
+    if negative not in (None, 'erase'):
+        raise ValueError("negative must be None or 'erase', not %r" % (negative,))
     root = ET.parse(path).getroot()
     coords, labels, lengths, areas = [], [], [], []
     for k, r in enumerate(root[0][1].findall('Region')):
@@ -47,7 +51,7 @@ def read_imagescope(path):
             raise ValueError('%s: region %s has the label %r, which is none of benign / in situ / invasive' % (path, r.get('Id', k), text))
         areas.append(float(r.get('AreaMicrons')))
         lengths.append(float(r.get('LengthMicrons')))
-        labels.append(label)
+        labels.append(0 if negative == 'erase' and r.get('NegativeROA') == '1' else label)
         coords.append([[int(v.get('X')), int(v.get('Y'))] for v in r[1]])
     return coords, labels, lengths, areas, float(root.get('MicronsPerPixel'))
 

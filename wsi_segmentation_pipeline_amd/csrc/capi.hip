@@ -499,4 +499,56 @@ int wsi_poly_raster(const int* edges, long long n_edges, const int* polys, int n
     return wsi_poly_dispatch(edges, n_edges, polys, n_polys, out, W, H, pitch_bytes, ox, oy, sx, sy, (hipStream_t)stream);
 }
 
+// ------------------------------------------------------------------------------------ label map -> ordered boundary loops
+static bool contour_map_ok(const uint8_t* map, int W, int H, long long pitch) {
+    return map && W >= 1 && H >= 1 && (long long)W * H <= (1LL << 28) && pitch >= W;
+}
+static bool contour_edges_ok(int W, int H, long long n_edges) { return n_edges >= 1 && n_edges <= 4LL * W * H; }
+size_t wsi_contour_count_workspace_bytes(int W, int H) {
+    return W >= 1 && H >= 1 && (long long)W * H <= (1LL << 28) ? wsi_contour_count_ws_bytes(W, H) : 0;
+}
+size_t wsi_contour_workspace_bytes(long long n_edges) { return n_edges >= 1 && n_edges <= (1LL << 30) ? wsi_contour_ws_bytes(n_edges) : 0; }
+int wsi_contour_count(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, void* count_ws, unsigned int* n_edges_out,
+                      void* stream) {
+    if (!contour_map_ok(map, W, H, pitch_bytes) || !traced256 || !count_ws || !n_edges_out) return WSI_EINVAL;
+    if (((uintptr_t)count_ws & 3) || ((uintptr_t)n_edges_out & 3)) return WSI_EINVAL;
+    return wsi_contour_count_dispatch(map, W, H, pitch_bytes, traced256, count_ws, n_edges_out, (hipStream_t)stream);
+}
+static bool contour_ws_ok(const void* workspace, size_t workspace_bytes, long long n_edges) {
+    return workspace && !((uintptr_t)workspace & 15) && n_edges >= 1 && n_edges <= (1LL << 30) && workspace_bytes >= wsi_contour_ws_bytes(n_edges);
+}
+int wsi_contour_build(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, const void* count_ws, long long n_edges,
+                      void* workspace, size_t workspace_bytes, void* stream) {
+    if (!contour_map_ok(map, W, H, pitch_bytes) || !traced256 || !count_ws || ((uintptr_t)count_ws & 3)) return WSI_EINVAL;
+    if (!contour_edges_ok(W, H, n_edges) || !contour_ws_ok(workspace, workspace_bytes, n_edges)) return WSI_EINVAL;
+    return wsi_contour_build_dispatch(map, W, H, pitch_bytes, traced256, count_ws, n_edges, workspace, (hipStream_t)stream);
+}
+int wsi_contour_ranks(void* workspace, size_t workspace_bytes, long long n_edges, void* stream) {
+    if (!contour_ws_ok(workspace, workspace_bytes, n_edges)) return WSI_EINVAL;
+    return wsi_contour_ranks_dispatch(workspace, n_edges, (hipStream_t)stream);
+}
+int wsi_contour_order(void* workspace, size_t workspace_bytes, long long n_edges, int W, unsigned int* counts_out, void* stream) {
+    if (!contour_ws_ok(workspace, workspace_bytes, n_edges) || W < 1 || W > (1 << 28) || !counts_out || ((uintptr_t)counts_out & 3)) return WSI_EINVAL;
+    return wsi_contour_order_dispatch(workspace, n_edges, W, counts_out, (hipStream_t)stream);
+}
+int wsi_contour_emit(const uint8_t* map, int W, int H, long long pitch_bytes, const void* workspace, size_t workspace_bytes, long long n_edges,
+                     int ox, int oy, int sx, int sy, int bounds_w, int bounds_h, int* vertices, long long cap_vertices, int* loops, long long* area2,
+                     long long cap_loops, void* stream) {
+    const long long lim = 1LL << 29;
+    if (!contour_map_ok(map, W, H, pitch_bytes) || !workspace || !vertices || !loops || !area2) return WSI_EINVAL;
+    if (!contour_edges_ok(W, H, n_edges) || workspace_bytes < wsi_contour_ws_bytes(n_edges)) return WSI_EINVAL;
+    if (((uintptr_t)workspace & 15) || ((uintptr_t)vertices & 7) || ((uintptr_t)loops & 15) || ((uintptr_t)area2 & 7)) return WSI_EINVAL;
+    if (sx < 1 || sy < 1 || bounds_w < 0 || bounds_h < 0 || cap_vertices < 0 || cap_loops < 0 || cap_vertices > 0xffffffffLL || cap_loops > 0xffffffffLL)
+        return WSI_EINVAL;
+    if (ox < -lim || ox > lim || oy < -lim || oy > lim) return WSI_EINVAL;
+    const long long ext[4][2] = {{(long long)ox - sx / 2, bounds_w}, {(long long)ox + (long long)W * sx - sx / 2, bounds_w},
+                                 {(long long)oy - sy / 2, bounds_h}, {(long long)oy + (long long)H * sy - sy / 2, bounds_h}};
+    for (const auto& e : ext) {                                 // the first and the last corner each way, clamped as the kernel clamps
+        const long long v = e[1] > 0 ? (e[0] < 0 ? 0 : e[0] > e[1] - 1 ? e[1] - 1 : e[0]) : e[0];
+        if (v < -lim || v > lim) return WSI_EINVAL;
+    }
+    return wsi_contour_emit_dispatch(map, W, H, pitch_bytes, workspace, n_edges, ox, oy, sx, sy, bounds_w, bounds_h, vertices, cap_vertices, loops, area2,
+                                     cap_loops, (hipStream_t)stream);
+}
+
 }  // extern "C"

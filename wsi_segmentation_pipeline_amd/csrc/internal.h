@@ -102,6 +102,17 @@ int wsi_esp_dispatch(const double* pts, int n, int num, double* out, double* scr
 // poly.hip
 int wsi_poly_dispatch(const int* edges, long long n_edges, const int* polys, int n_polys, uint8_t* out, int W, int H, long long pitch,
                       int ox, int oy, int sx, int sy, hipStream_t st);
+// contour.hip
+size_t wsi_contour_count_ws_bytes(int W, int H);
+size_t wsi_contour_ws_bytes(long long n_edges);
+int wsi_contour_count_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, void* count_ws, unsigned* n_edges_out,
+                               hipStream_t st);
+int wsi_contour_build_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, const void* count_ws, long long n_edges,
+                               void* ws, hipStream_t st);
+int wsi_contour_ranks_dispatch(void* ws, long long n_edges, hipStream_t st);
+int wsi_contour_order_dispatch(void* ws, long long n_edges, int W, unsigned* counts_out, hipStream_t st);
+int wsi_contour_emit_dispatch(const uint8_t* map, int W, int H, long long pitch, const void* ws, long long n_edges, int ox, int oy, int sx, int sy,
+                              int bw, int bh, int* vertices, long long cap_vertices, int* loops, long long* area2, long long cap_loops, hipStream_t st);
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
