@@ -170,6 +170,7 @@ enum {
     WSI_CONV_MODE_L1_SLAB3 = 1024,          /* 64-channel layer 1 on the slab3 kernel, not the row-stacked one (mode 3, 64-wide maps; equal to a few ulps: another summation order) */
     WSI_CONV_MODE_NO_DS_FOLD = 2048,        /* strided blocks' 1x1 downsample as its own tensor + residual, not an extra K segment of the block's second conv (mode 3) */
     WSI_CONV_MODE_NO_SLAB_PAIR = 4096,      /* layer-1 slab3 kernel without paired-tile LDS addressing */
+    WSI_CONV_MODE_EPILOGUE_PIECES = 8192,   /* mode-3 conv epilogues: every lane stores the four 16-byte pieces of its own pixel line in every kernel (default: on the row-stacked layer-1 kernel a lane quad stores one 64-byte sector of a line per instruction; byte-identical) */
     WSI_CONV_MODE_L1_LINES128 = 16384,      /* the trunk keeps 128-byte lines for stem output and layer-1 tensors (mode 3 default: 96-byte lines; bit-identical) */
     WSI_CONV_MODE_S2_NT2 = 32768,           /* wide stride-2 kernel with 128, not 256, output channels per workgroup (mode 3; bit-identical) */
     WSI_CONV_MODE_UNET_CONCAT_PASS = 65536, /* U-Net decoder blocks write the upsampled + concatenated tensor before their first conv (bit-identical) */

@@ -43,7 +43,7 @@ static ConvArgs conv_args(const ConvCall& c) {
     a.in = c.in; a.out = c.out; a.resid = c.resid; a.wpk = c.wpk; a.bias = c.bias;
     a.gi = pf_geom_fd(c.n, c.h, c.w, c.cin);
     a.go = pf_geom_fd(c.n, c.h / c.stride, c.w / c.stride, c.cout);
-    a.stride = c.stride; a.ksize = c.ksize; a.relu = c.relu & 1; a.flags = 0;
+    a.stride = c.stride; a.ksize = c.ksize; a.relu = c.relu & 1; a.flags = (g_routes.epi_sectors && c.planes == 3) ? CONV_STORE_SECTORS : 0;
     a.out2 = nullptr; a.wpk2 = nullptr; a.bias2 = nullptr;
     a.in_split_pixels = 0; a.out_split_pixels = 0;
     return a;
@@ -291,6 +291,7 @@ int wsi_conv_set_mode(int mode) {
     r.unet_x0_fused = (mode & WSI_CONV_MODE_UNET_X0_UNFUSED) ? 0 : 1;
     r.pw_gather = (mode & WSI_CONV_MODE_PW_GATHER) ? 1 : 0;
     r.linknet_tail = (mode & WSI_CONV_MODE_LINKNET_NO_TAIL) ? 0 : 1;
+    r.epi_sectors = (mode & WSI_CONV_MODE_EPILOGUE_PIECES) ? 0 : 1;
     return WSI_OK;
 }
 

@@ -167,6 +167,11 @@ enum : int {
     // Stride-1 1x1 convs of planes 1 / 2 only (the gather and the pointwise kernel: conv_dev.h conv_epilogue_q<.., POST>).
     CONV_RESID_POST = 128,
     CONV_ABL_NO_STORE = 1 << 8, CONV_ABL_DISPATCH_ONLY = 1 << 9, CONV_ABL_NO_MAINLOOP = 1 << 10, CONV_NONTEMPORAL = 1 << 11,
+    // mode-3 epilogue: a lane quad stores one 64-byte sector of one pixel's line per instruction (conv_dev.h mx_store_sectors)
+    // instead of every lane the four 16-byte pieces of its own pixel.  Set on every mode-3 launch unless ConvRoutes.epi_sectors is
+    // off; a launcher whose kernel has the sector form picks that instantiation by it (the row-stacked kernel: conv.hip launch_rows),
+    // every other kernel keeps the piece shape
+    CONV_STORE_SECTORS = 1 << 12,
     CONV_WCOPIES_SHIFT = 16,   // bits 16-19: back-to-back copies of the packed weights minus one
 };
 #ifdef WSI_STUDY
@@ -413,5 +418,6 @@ struct ConvRoutes {
     int unet_x0_fused = 1;         // U-Net: the fused stem kernel stores the half-resolution skip x0 itself
     int pw_gather = 0;             // stride-1 1x1 convs (wsi_conv1x1_bn_act, Bottleneck trunk) on the gather kernel, not conv_pw.hip
     int linknet_tail = 1;          // Linknet decoder: last block + head as one kernel (linknet.hip linknet_tail_kernel)
+    int epi_sectors = 1;           // mode-3 conv epilogues store 64-byte sectors per lane quad where the kernel has that form (CONV_STORE_SECTORS); 0: 16-byte pieces per lane everywhere
 };
 extern ConvRoutes g_routes;

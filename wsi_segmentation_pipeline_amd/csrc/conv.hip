@@ -378,8 +378,9 @@ static int launch_slab3(const ConvArgs& a, hipStream_t st) {
 // NCT: input lines known at compile time (2 = the 64-channel layer 1: the line loop unrolls), 0 = any.  IN96: 96-byte input lines
 // (hi6 plane rebuilt in LDS after the slab has landed).  With 128-byte lines there is no rebuild pass whose ~45 temporaries compete
 // with the weight ring for registers, so a line's first column of weights is requested across the line boundary (during the
-// previous line's last column; line 0: before the slab DMA) instead of after the slab wait.
-template <int MINW, int NCT = 0, bool IN96 = true>
+// previous line's last column; line 0: before the slab DMA) instead of after the slab wait.  SECT: the tail stores 64-byte sectors
+// per lane quad (conv_dev.h mx_store_sectors; the default route), otherwise 16-byte pieces per lane.
+template <int MINW, int NCT = 0, bool IN96 = true, bool SECT = false>
 __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int MT = 4, WN = 2, BM = 256, NTHREADS = 256, RESID_NBUF = 2;
@@ -492,7 +493,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3s1_rows_kernel(ConvArgs a) {
         valid[mt] = true;
     }
     if (a.resid) __syncthreads();                             // every wave is done reading pixel fragments: slab memory becomes
-    conv_tail_mx<1, MT, RESID_NBUF>(a, acc, qs, valid, ntile, lane, smem + wave * (RESID_NBUF * 4096), slab0);   // the waves' residual staging
+    conv_tail_mx<1, MT, RESID_NBUF, SECT>(a, acc, qs, valid, ntile, lane, smem + wave * (RESID_NBUF * 4096), slab0);   // the waves' residual staging
     WSTAMP(wide_stamps_report(lane, st_begin, st_setup, st_pro, st_line, st_tap, st_loop_end);)
 }
 
@@ -506,8 +507,12 @@ static int launch_rows(const ConvArgs& a, hipStream_t st) {
     const int mtiles = (int)(R / BM);                        // whole tiles: H % 4 == 0
     const size_t lds = conv_slab_lds(5 * a.gi.P + 66, NTHREADS, 4);
     const bool i96 = a.flags & CONV_IN96;
+    // the store shape of the tail is a template argument: with both shapes in one kernel the 168-register kernels spill accumulators
     auto k = nc2 ? (i96 ? conv3x3s1_rows_kernel<MINW, 2, true> : conv3x3s1_rows_kernel<MINW, 2, false>)
                  : (i96 ? conv3x3s1_rows_kernel<MINW, 0, true> : conv3x3s1_rows_kernel<MINW, 0, false>);
+    if (a.flags & CONV_STORE_SECTORS)
+        k = nc2 ? (i96 ? conv3x3s1_rows_kernel<MINW, 2, true, true> : conv3x3s1_rows_kernel<MINW, 2, false, true>)
+                : (i96 ? conv3x3s1_rows_kernel<MINW, 0, true, true> : conv3x3s1_rows_kernel<MINW, 0, false, true>);
     return conv_launch(k, conv_grid(mtiles, nblocks, a.flags & CONV_XCD_RANGES), NTHREADS, lds, st, a);
 }
 

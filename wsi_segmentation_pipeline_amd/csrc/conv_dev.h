@@ -275,13 +275,94 @@ static __device__ __forceinline__ void acc_init_bias(f32x16 (&acc)[MT], const fl
         for (int r = 0; r < 16; ++r) acc[mt][r] = b[r];
 }
 
+// Sector stores of the mode-3 epilogue (conv_epilogue_mx<.., SECT>; route CONV_STORE_SECTORS).  In: lane (pixel p = lane & 31, h) holds two 32-byte groups of its
+// pixel's line - H = the fp16 bytes at 32h, Q = the two 16-byte pieces of its fp6 plane (128-byte lines: at 64 + 16h and 96 + 16h;
+// 96-byte lines: the h = 0 lane's at 64 and 80, the h = 1 lane's unused) - and `off`, the byte offset of the line in `out`
+// (~0: the pixel is not written; the same in both lanes of a pixel).  The pieces move through registers only:
+//   1. v_permlane32_swap of H against Q: lane (p, 0) then holds the line's fp16 sector (pieces at 0, 16, 32, 48), lane (p, 1) its
+//      fp6 sector in the order 64, 96, 80, 112 (96-byte lines: 64, 80, and two unused pieces);
+//   2. a 4 x 4 transpose of the 16-byte pieces inside every lane quad (two DPP quad_perm exchange steps, quad_xchg1 / 2): lane i of quad k then
+//      holds piece i of the sectors of pixels 4k .. 4k + 3;
+//   3. four stores; in store j the quad writes the 64 bytes of ONE sector of pixel 4k + j (96-byte lines: the fp16 sector, and the
+//      first two lanes of the upper quad the 32 bytes behind it), so a store instruction completes eight lines where the piece form
+//      touches 32 lines with 32 bytes each (tools/probes/store_shape.hip, profiles/epilogue_lines_probe.txt).
+// No LDS, no barrier; the offsets travel by quad broadcasts, so the mask is per pixel and pads stay unwritten.
+template <int CTRL>
+static __device__ __forceinline__ unsigned quad_dpp(unsigned x) {
+    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, CTRL, 0xf, 0xf, true);
+}
+// One exchange step of the quad transpose on two 16-byte pieces: lanes with `bit` clear keep `even` and receive their partner's
+// `even` (-> n0 = own, n1 = partner's), lanes with it set keep `odd` (-> n0 = partner's, n1 = own); the partner is the lane
+// quad_perm names.  v_cndmask_b32_dpp by inline asm, one instruction per dword and result: hipcc (ROCm 7.2) does not fold the DPP
+// move of __builtin_amdgcn_update_dpp into the select (two instructions each, and it issues every move of a step first: 16 more
+// live registers).  Every lane executes the DPP reads; the leading s_nop covers the two wait states between a VALU write and a
+// DPP read of the same register.
+#define MX_QUAD_XCHG(NAME, PERM)                                                                                                     \
+    static __device__ __forceinline__ void NAME(const u32x4& even, const u32x4& odd, unsigned bit, u32x4& n0, u32x4& n1) {         \
+        unsigned p0, p1, p2, p3, q0, q1, q2, q3;                                                                                     \
+        asm volatile("s_nop 1\n\tv_cmp_ne_u32 vcc, 0, %16\n\t"                                                                      \
+                     "v_cndmask_b32_dpp %4, %8, %12, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                       \
+                     "v_cndmask_b32_dpp %5, %9, %13, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                       \
+                     "v_cndmask_b32_dpp %6, %10, %14, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
+                     "v_cndmask_b32_dpp %7, %11, %15, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
+                     "v_cmp_eq_u32 vcc, 0, %16\n\t"                                                                                  \
+                     "v_cndmask_b32_dpp %0, %12, %8, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                       \
+                     "v_cndmask_b32_dpp %1, %13, %9, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                       \
+                     "v_cndmask_b32_dpp %2, %14, %10, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"                      \
+                     "v_cndmask_b32_dpp %3, %15, %11, vcc " PERM " row_mask:0xf bank_mask:0xf bound_ctrl:1"                           \
+                     : "=&v"(p0), "=&v"(p1), "=&v"(p2), "=&v"(p3), "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3)                        \
+                     : "v"(even[0]), "v"(even[1]), "v"(even[2]), "v"(even[3]), "v"(odd[0]), "v"(odd[1]), "v"(odd[2]), "v"(odd[3]),   \
+                       "v"(bit)                                                                                                      \
+                     : "vcc");                                                                                                       \
+        n0 = u32x4{p0, p1, p2, p3};                                                                                                  \
+        n1 = u32x4{q0, q1, q2, q3};                                                                                                  \
+    }
+MX_QUAD_XCHG(quad_xchg1, "quad_perm:[1,0,3,2]")
+MX_QUAD_XCHG(quad_xchg2, "quad_perm:[2,3,0,1]")
+#undef MX_QUAD_XCHG
+static __device__ __forceinline__ void mx_store_sectors(char* out, size_t off, u32x4 (&H)[2], u32x4 (&Q)[2], bool o96, int lane) {
+    {   // (the s_nops: swap32_halves)
+        unsigned a0 = H[0][0], a1 = H[0][1], a2 = H[0][2], a3 = H[0][3], a4 = H[1][0], a5 = H[1][1], a6 = H[1][2], a7 = H[1][3];
+        unsigned b0 = Q[0][0], b1 = Q[0][1], b2 = Q[0][2], b3 = Q[0][3], b4 = Q[1][0], b5 = Q[1][1], b6 = Q[1][2], b7 = Q[1][3];
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %8\n\tv_permlane32_swap_b32 %1, %9\n\tv_permlane32_swap_b32 %2, %10\n\t"
+                     "v_permlane32_swap_b32 %3, %11\n\tv_permlane32_swap_b32 %4, %12\n\tv_permlane32_swap_b32 %5, %13\n\t"
+                     "v_permlane32_swap_b32 %6, %14\n\tv_permlane32_swap_b32 %7, %15\n\ts_nop 1"
+                     : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7),
+                       "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4), "+v"(b5), "+v"(b6), "+v"(b7));
+        H[0] = u32x4{a0, a1, a2, a3}; H[1] = u32x4{a4, a5, a6, a7};
+        Q[0] = u32x4{b0, b1, b2, b3}; Q[1] = u32x4{b4, b5, b6, b7};
+    }
+    asm volatile("" : "+v"(lane));                          // opaque: the lane masks and offsets below are rebuilt per tile, not kept alive across a main loop
+    const int i = lane & 3, h = lane >> 5;
+    // M[s] = piece s of this lane's sector; N[t][u] = piece 2t + (i & 1) of quad lane (i & ~1) | u; T[j] = piece i of quad lane j
+    u32x4 N[2][2], T[4];
+    quad_xchg1(H[0], H[1], lane & 1, N[0][0], N[0][1]);
+    quad_xchg1(Q[0], Q[1], lane & 1, N[1][0], N[1][1]);
+    quad_xchg2(N[0][0], N[1][0], lane & 2, T[0], T[2]);
+    quad_xchg2(N[0][1], N[1][1], lane & 2, T[1], T[3]);
+    const int piece = h == 0 || o96 ? i : ((i & 1) << 1) | (i >> 1);          // (the fp6 sector's pieces lie in the order 64, 96, 80, 112)
+    const int piece_off = 64 * h + 16 * piece;
+    const bool stored = !(o96 && h && i >= 2);
+    const unsigned off_lo = (unsigned)off, off_hi = (unsigned)(off >> 32);
+    const unsigned ol[4] = {quad_dpp<0x00>(off_lo), quad_dpp<0x55>(off_lo), quad_dpp<0xAA>(off_lo), quad_dpp<0xFF>(off_lo)};
+    const unsigned oh[4] = {quad_dpp<0x00>(off_hi), quad_dpp<0x55>(off_hi), quad_dpp<0xAA>(off_hi), quad_dpp<0xFF>(off_hi)};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const size_t oj = ((size_t)oh[j] << 32) | ol[j];
+        if (stored && oj != ~(size_t)0) *(u32x4*)(out + oj + piece_off) = T[j];
+    }
+}
+
 // Mode-3 epilogue (fp16 hi + MX-fp6): acc (bias and residual already inside: acc_init_bias, conv_tail_mx) -> clamp /
 // ReLU -> the next layer's operands, for tiles mt0 .. mt0 + MTN - 1.  Lane (pixel, h) owns line positions 16h .. 16h+15 of the fp16 plane (32 contiguous
 // bytes) and, after one exchange with lane ^ 32 (v_permlane32_swap per register), ALL 32 values of one fp6 plane (h = 0:
 // lo6, h = 1: hi6), which one v_cvt_scalef32_2xpk16_fp6_f32 converts.  Four 16-byte stores per 32x32 tile; the whole
-// 128-byte line is written.  (`a.resid` is not read here: conv_tail_mx adds the residual.)
+// 128-byte line is written - with SECT as 64-byte sectors per lane quad (mx_store_sectors), otherwise by every lane the four pieces
+// of its own pixel; the bytes are the same.  SECT is a template argument, not a test of CONV_STORE_SECTORS in the kernel: with both
+// shapes compiled into one kernel the 168-register kernels spilled whole accumulator tiles in their main loops (NOTEBOOK, "epilogue
+// lines").  (`a.resid` is not read here: conv_tail_mx adds the residual.)
 // stem.hip stem_store_line_mx is the stem kernels' copy of this encode (values already clamped, >= 0): a change to the format is made in both.
-template <int MT, int MTN = MT>
+template <int MT, int MTN = MT, bool SECT = false>
 static __device__ __forceinline__ void conv_epilogue_mx(const ConvArgs& a, f32x16 (&acc)[MT], const int (&qs)[MT],
                                                         const bool (&valid)[MT], int ntile, int lane, int mt0 = 0) {
     const int h = lane >> 5;
@@ -314,6 +395,16 @@ static __device__ __forceinline__ void conv_epilogue_mx(const ConvArgs& a, f32x1
         const int sb = h ? sh : sl;                                                   // this lane's plane: h = 0 lo6, h = 1 hi6
         swap32_halves(lo, hi);                                                        // lo := (h ? partner's hi : own lo), hi := (h ? own hi : partner's lo)
         const u32x6 q = mx6_pack32(lo, hi, sb ? mx_scale_value(sb) : 1.f);
+        if constexpr (SECT) {
+            if (!CONV_STUDY(a, CONV_ABL_NO_STORE)) {
+                size_t off = ~(size_t)0;                                              // pads and rows past the end stay unwritten
+                if (valid[mt]) off = a.out_split_pixels ? pf_out_offset(a.go, a.out_split_pixels, qs[mt], pixstride) + (size_t)ntile * 128 : loff;
+                u32x4 H[2] = {__builtin_bit_cast(u32x4, hv[0]), __builtin_bit_cast(u32x4, hv[1])};
+                u32x4 Q[2] = {u32x4{q[0], q[1], q[2], q[3]}, o96 ? u32x4{q[4], q[5], (unsigned)sl, (unsigned)sh} : u32x4{q[4], q[5], (unsigned)sb, 0u}};
+                mx_store_sectors((char*)a.out, off, H, Q, o96, lane);
+            }
+            continue;
+        }
         if (valid[mt] && !CONV_STUDY(a, CONV_ABL_NO_STORE)) {
             char* ol = (char*)a.out + (a.out_split_pixels ? pf_out_offset(a.go, a.out_split_pixels, qs[mt], pixstride) + (size_t)ntile * 128 : loff);
             *(f16x8*)(ol + 32 * h) = hv[0];
@@ -339,7 +430,7 @@ static __device__ __forceinline__ void conv_epilogue_mx(const ConvArgs& a, f32x1
 // stored, so a wave pays one exposed round trip to memory instead of one per tile (r02: vector decode of ~50 instructions
 // per tile and 4-8 round trips in a row per wave, +20 % on a residual launch).  Only `vmcnt(0)` waits: spill code or
 // stores the compiler places between the DMAs cannot break a counted wait.
-template <int NT, int MT, int NBUF>
+template <int NT, int MT, int NBUF, bool SECT = false>
 static __device__ __forceinline__ void conv_tail_mx(const ConvArgs& a, f32x16 (&acc)[NT][MT], const int (&qs)[MT], const bool (&valid)[MT],
                                                     int ntile0, int lane, char* scratch, int slab0) {
     constexpr int T = NT * MT;
@@ -347,7 +438,7 @@ static __device__ __forceinline__ void conv_tail_mx(const ConvArgs& a, f32x16 (&
     static_assert(NBUF <= T && T % NBUF == 0, "whole batches");
     if (!a.resid) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) conv_epilogue_mx<MT>(a, acc[nt], qs, valid, ntile0 + nt, lane);
+        for (int nt = 0; nt < NT; ++nt) conv_epilogue_mx<MT, MT, SECT>(a, acc[nt], qs, valid, ntile0 + nt, lane);
         return;
     }
     const int h = lane >> 5, l31 = lane & 31;
@@ -414,9 +505,9 @@ static __device__ __forceinline__ void conv_tail_mx(const ConvArgs& a, f32x16 (&
         // encode + store this batch while the next one is in flight
         if constexpr (NBUF >= MT) {
 #pragma unroll
-            for (int nt = b0 / MT; nt < (b0 + NBUF) / MT; ++nt) conv_epilogue_mx<MT>(a, acc[nt], qs, valid, ntile0 + nt, lane);
+            for (int nt = b0 / MT; nt < (b0 + NBUF) / MT; ++nt) conv_epilogue_mx<MT, MT, SECT>(a, acc[nt], qs, valid, ntile0 + nt, lane);
         } else {
-            conv_epilogue_mx<MT, NBUF>(a, acc[b0 / MT], qs, valid, ntile0 + b0 / MT, lane, b0 % MT);
+            conv_epilogue_mx<MT, NBUF, SECT>(a, acc[b0 / MT], qs, valid, ntile0 + b0 / MT, lane, b0 % MT);
         }
     }
 }

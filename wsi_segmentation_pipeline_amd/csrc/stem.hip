@@ -104,7 +104,9 @@ static __device__ __forceinline__ void stem_store4(char* o, int c, const float* 
 // [0, 65504]; the line's other 16 sit in lane ^ 32.  Every lane of the wave takes part in the exchanges; only the stores are
 // predicated.  ol = the line: 128 bytes, or with o96 the 96-byte form [fp16 plane][lo6][lo6 rest, scale_lo, scale_hi] that lane
 // h = 0 completes alone.  conv_dev.h conv_epilogue_mx is the conv kernels' copy of this encode (it clamps inside and takes |hi|,
-// values there can be negative): a change to the format is made in both.
+// values there can be negative): a change to the format is made in both.  The STORE shape is not shared: the row-stacked conv kernel
+// writes 64-byte sectors per lane quad (conv_dev.h mx_store_sectors, ~50 more vector instructions per tile); the stem keeps the
+// piece shape - its kernels are bound by their vector instructions, and the sector shape was not measured here.
 static __device__ __forceinline__ void stem_store_line_mx(const float (&v)[16], int h, char* ol, bool store, bool o96) {
     f32x16 hi, lo;
     f16x8 hv[2];

@@ -321,6 +321,7 @@ class ConvMode(enum.IntFlag):
     L1_SLAB3 = 1024
     NO_DS_FOLD = 2048
     NO_SLAB_PAIR = 4096
+    EPILOGUE_PIECES = 8192
     L1_LINES128 = 16384
     S2_NT2 = 32768
     UNET_CONCAT_PASS = 65536
