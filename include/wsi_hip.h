@@ -976,6 +976,28 @@ int wsi_contour_emit(const uint8_t* map, int W, int H, long long pitch_bytes, co
                      int ox, int oy, int sx, int sy, int bounds_w, int bounds_h, int* vertices, long long cap_vertices, int* loops, long long* area2,
                      long long cap_loops, void* stream);
 
+/* ---- Exact Euclidean distance transform of a u8 map (round structuring elements, margin bands, surface distances) ----
+ * An own rule (the reference has no such code; spec: tests/edt_oracle.py, cross-checked against SciPy on the CPU; the shared per-column
+ * step and per-pixel scan: csrc/edt_dev.h).  A pixel is a feature iff its byte is non-zero (invert = 0) or zero (invert != 0), and
+ *   out[y, x] = min over features (fy, fx) of (y - fy)^2 + (x - fx)^2   as int32, 0x7FFFFFFF everywhere where the map has no feature.
+ * Pixels are isotropic; distances only, no nearest-feature index.  1 <= W, H <= 32768, so the largest value is 2 * 32767^2 < 2^31.
+ * (SciPy's convention is the mirror image: distance_transform_edt(features == 0) ** 2.)
+ *   map: H rows of W bytes, pitch_bytes >= W, any alignment; read through aligned 16-byte pieces and bytes at the ragged ends, nothing
+ *     outside the H row segments, never written.
+ *   The workspace: wsi_edt_workspace_bytes(W, H) device bytes, 16-byte aligned (no hidden allocation).  It starts, at offset 0, with
+ *     the g plane: H rows of u16, rows 2 * ((W + 127) / 128 * 128) bytes apart; g[y][x] = the distance in rows from (y, x) to the
+ *     nearest feature of column x, 0xFFFF where column x has none.  The values past W of a row are never used.  The band tables of
+ *     the column pass follow the plane (csrc/edt_dev.h).
+ *   wsi_edt_columns: map -> the g plane (three launches: band summaries, carries, g).
+ *   wsi_edt_rows: the g plane -> out, H rows of W int32, out_pitch_bytes apart: out[y][x] = min over x' of (x - x')^2 + g[y][x']^2,
+ *     0xFFFF entries skipped, 0x7FFFFFFF where the row has none other.  It reads nothing but the plane, so it can be driven alone.
+ * -22 before any device work: a NULL pointer, W or H outside 1 .. 32768, pitch_bytes < W, out_pitch_bytes < 4 W or no multiple of 4,
+ *   out not 4-byte aligned, a workspace not 16-byte aligned or smaller than wsi_edt_workspace_bytes (which returns 0 for sizes
+ *   outside the limits). */
+size_t wsi_edt_workspace_bytes(int W, int H);
+int wsi_edt_columns(const uint8_t* map, int W, int H, long long pitch_bytes, int invert, void* workspace, size_t workspace_bytes, void* stream);
+int wsi_edt_rows(const void* workspace, size_t workspace_bytes, int W, int H, int32_t* out, long long out_pitch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

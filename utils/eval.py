@@ -269,7 +269,7 @@ def _map_u8(arr, hw, dev):
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(dev)
 
 
-def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False):
+def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False, boundary_scores=False):
     """Dense per-pixel map prediction with the tumour-bed post-process (reference utils/eval.py:22-152).
     `model(batch_image)` must return (B, C, ph, pw) logits on the GPU (the reference drives an smp U-Net here; any GPU
     module works, e.g. wsi_segmentation_pipeline_amd.unet.UNetSeg).  Everything between the tile list and the colour
@@ -287,6 +287,10 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False)
     Benign / In situ / Invasive regions, holes as NegativeROA regions, so annotations.read_imagescope(path, negative='erase') rasterised
     at the map's step restores that map; a second Annotation element, which neither reader visits, holds the tumour bed as 'Invasive'.
     MicronsPerPixel is the slide's where it states one (`scan.mpp`, or openslide's mpp-x property), else 1.0.
+    boundary_scores: where the entry has `tb_gt`, `scores` gains how far the predicted bed's outline lies from the ground truth's
+    (wsi_segmentation_pipeline_amd.distance.surface_distances on the device): 'hd_tb', 'hd95_tb', 'assd_tb' - Hausdorff, its 95th
+    percentile by nearest rank, the mean surface distance - in pixels of the scoring level, and, where the slide states an mpp, the
+    same three with the suffix '_um' (mpp times the level's step).  Unset, `scores` and the printed line are what they were.
     Returns {key: {'pred', 'pred_level2', 'classes' (scan level), 'classes_level2', 'tumor_bed', 'outline', 'scores'}}."""
     from wsi_segmentation_pipeline_amd import postprocess as PP
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -325,6 +329,16 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False)
                     ious_tb += scores['iou_tb']
                 print('{}, {:.3f}({:.3f}), {:.3f}({:.3f}), {:.3f}, tb iou: {:.3f} '.format(
                     key, scores['s_masked'], scores['s'], scores['acc_masked'], scores['acc'], scores['iou_fg'], scores['iou_tb']))
+                if boundary_scores and entry.get('tb_gt') is not None:
+                    from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT, distance as DT
+                    sd = DT.surface_distances((tb.tb_pred > 0).to(torch.uint8), (_map_u8(entry['tb_gt'], map_hw, dev) > 0).to(torch.uint8))
+                    for name in ('hd', 'hd95', 'assd'):
+                        scores[name + '_tb'] = sd[name]
+                    if CT.stated_mpp(scan) is not None:
+                        um = CT.stated_mpp(scan) * AN.level_step(scan, ref_level)
+                        for name in ('hd', 'hd95', 'assd'):
+                            scores[name + '_tb_um'] = sd[name] * um
+                    print('{}, tb outline: hd {:.2f}, hd95 {:.2f}, assd {:.2f} px'.format(key, sd['hd'], sd['hd95'], sd['assd']))
             results[key] = {'pred': pred, 'pred_level2': pred2, 'classes': classes, 'classes_level2': p,
                             'tumor_bed': tb.tb_pred, 'outline': tb.outline, 'scores': scores}
             if save:                                                           # :138-145

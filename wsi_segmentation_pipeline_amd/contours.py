@@ -243,13 +243,19 @@ def write_imagescope(path, c, mpp=1.0, names=None, holes='negative', layers=()):
     return path
 
 
-def slide_mpp(scan):
-    """microns per pixel of level 0 where the slide states it (`scan.mpp`, or openslide's `properties['openslide.mpp-x']`), else 1.0"""
+def stated_mpp(scan):
+    """microns per pixel of level 0 where the slide states it (`scan.mpp`, or openslide's `properties['openslide.mpp-x']`), else None"""
     v = getattr(scan, 'mpp', None)
     if v is None:
         v = (getattr(scan, 'properties', None) or {}).get('openslide.mpp-x')
     try:
         v = float(v)
     except (TypeError, ValueError):
-        return 1.0
-    return v if v > 0 else 1.0
+        return None
+    return v if v > 0 else None
+
+
+def slide_mpp(scan):
+    """stated_mpp, or 1.0 where the slide states none"""
+    v = stated_mpp(scan)
+    return 1.0 if v is None else v

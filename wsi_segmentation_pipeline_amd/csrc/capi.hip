@@ -2,6 +2,7 @@
 // entries and the argument-checking wrappers of the slide, proposal and post-process ops.  Weight packing: prepack.hip; the trunks:
 // trunk.hip; the segmentation models: seg_host.h and the decoder files.  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
+#include "edt_dev.h"
 #include "../../include/wsi_hip.h"
 
 ConvRoutes g_routes;                                  // the one instance of the route switches (common.h), at their defaults
@@ -550,6 +551,22 @@ int wsi_contour_emit(const uint8_t* map, int W, int H, long long pitch_bytes, co
     }
     return wsi_contour_emit_dispatch(map, W, H, pitch_bytes, workspace, n_edges, ox, oy, sx, sy, bounds_w, bounds_h, vertices, cap_vertices, loops, area2,
                                      cap_loops, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ u8 map -> exact squared Euclidean distances
+static bool edt_size_ok(int W, int H) { return W >= 1 && H >= 1 && W <= wsi_edt::LIMIT && H <= wsi_edt::LIMIT; }
+static bool edt_ws_ok(const void* workspace, size_t workspace_bytes, int W, int H) {
+    return workspace && !((uintptr_t)workspace & 15) && workspace_bytes >= wsi_edt::workspace_bytes(W, H);
+}
+size_t wsi_edt_workspace_bytes(int W, int H) { return edt_size_ok(W, H) ? wsi_edt::workspace_bytes(W, H) : 0; }
+int wsi_edt_columns(const uint8_t* map, int W, int H, long long pitch_bytes, int invert, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!map || !edt_size_ok(W, H) || pitch_bytes < W || !edt_ws_ok(workspace, workspace_bytes, W, H)) return WSI_EINVAL;
+    return wsi_edt_columns_dispatch(map, W, H, pitch_bytes, invert, workspace, (hipStream_t)stream);
+}
+int wsi_edt_rows(const void* workspace, size_t workspace_bytes, int W, int H, int32_t* out, long long out_pitch_bytes, void* stream) {
+    if (!edt_size_ok(W, H) || !edt_ws_ok(workspace, workspace_bytes, W, H) || !out || ((uintptr_t)out & 3)) return WSI_EINVAL;
+    if (out_pitch_bytes < 4LL * W || (out_pitch_bytes & 3)) return WSI_EINVAL;
+    return wsi_edt_rows_dispatch(workspace, W, H, out, out_pitch_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -113,6 +113,9 @@ int wsi_contour_ranks_dispatch(void* ws, long long n_edges, hipStream_t st);
 int wsi_contour_order_dispatch(void* ws, long long n_edges, int W, unsigned* counts_out, hipStream_t st);
 int wsi_contour_emit_dispatch(const uint8_t* map, int W, int H, long long pitch, const void* ws, long long n_edges, int ox, int oy, int sx, int sy,
                               int bw, int bh, int* vertices, long long cap_vertices, int* loops, long long* area2, long long cap_loops, hipStream_t st);
+// edt.hip
+int wsi_edt_columns_dispatch(const uint8_t* map, int W, int H, long long pitch, int invert, void* ws, hipStream_t st);
+int wsi_edt_rows_dispatch(const void* ws, int W, int H, int32_t* out, long long out_pitch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

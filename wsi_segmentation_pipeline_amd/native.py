@@ -254,6 +254,9 @@ SIGNATURES = {
     'wsi_contour_ranks': (_i, [_vp, _sz, _ll, _vp]),
     'wsi_contour_order': (_i, [_vp, _sz, _ll, _i, _vp, _vp]),
     'wsi_contour_emit': (_i, [_vp, _i, _i, _ll, _vp, _sz, _ll, _i, _i, _i, _i, _i, _i, _vp, _ll, _vp, _vp, _ll, _vp]),
+    'wsi_edt_workspace_bytes': (_sz, [_i, _i]),
+    'wsi_edt_columns': (_i, [_vp, _i, _i, _ll, _i, _vp, _sz, _vp]),
+    'wsi_edt_rows': (_i, [_vp, _sz, _i, _i, _vp, _ll, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)
