@@ -998,6 +998,54 @@ size_t wsi_edt_workspace_bytes(int W, int H);
 int wsi_edt_columns(const uint8_t* map, int W, int H, long long pitch_bytes, int invert, void* workspace, size_t workspace_bytes, void* stream);
 int wsi_edt_rows(const void* workspace, size_t workspace_bytes, int W, int H, int32_t* out, long long out_pitch_bytes, void* stream);
 
+/* ---- Region tables: a u8 class map labelled into connected regions, every region measured in one pass ----
+ * An own rule (parity unpinned; spec: tests/regions_oracle.py, cross-checked against a flood fill, SciPy and the boundary tracer on the
+ * CPU; the shared per-run arithmetic: csrc/regions_dev.h).  A run is a maximal stretch [x0, x1) of equal bytes in one row whose class is
+ * traced; runs are numbered in raster order.  Two runs of one class in neighbouring rows are joined iff a0 < x1 + d and x0 < a1 + d, d = 0
+ * for connectivity 4 and 1 for 8.  A region is a class of the closure of that relation; regions are numbered 1 .. n by their smallest
+ * run, which is raster order of their first pixel; label 0 is everything else.
+ * A region's record is sixteen int64 (128 bytes): area; x0, y0, x1, y1 (the box, upper ends exclusive); sx, sy, sxx, sxy, syy (sums of
+ * x, y, x^2, x y, y^2 over its pixels, map coordinates); perim (pixel sides that face a pixel outside the region, the map's outside
+ * included); wsum (the sum of the weight map over it, 0 without one); first (y W + x of its first pixel); cls; border (1 iff the box
+ * touches the map's edge); 0.  All integer, the same bytes every run.
+ *   map, weight: H rows of W bytes, pitch_bytes >= W, any alignment; read through aligned 16-byte pieces and bytes at the ragged ends,
+ *     nothing outside the H row segments, never written.  traced256: HOST table, byte l != 0: label l is traced.  1 <= W, H <= 32768.
+ *   wsi_region_count: run starts per chunk of 1024 pixels of a row into count_ws (wsi_region_count_workspace_bytes, device) and their
+ *     number into *n_runs_out (device).  The caller reads it, and stops there when it is 0.
+ *   The other entries run in this order on one workspace of wsi_region_workspace_bytes(W, H, n_runs) device bytes, 16-byte aligned (no
+ *   hidden allocation), with the same W, H and n_runs.  The workspace holds, each rounded up to 256 bytes and in this order:
+ *     runs       n_runs records of four int32 {y, x0, x1, cls}
+ *     row_first  H + 1 u32: the first run of every row, n_runs at H
+ *     parent     n_runs u32: the union-find forest (a root points at itself, every parent is the smaller run)
+ *     up         n_runs u32: shared pixel sides (the d = 0 overlap) with the same-class runs of the row above
+ *     root       n_runs u32: the smallest run of the region
+ *     flag       n_runs + 1 u32: 1 at a root
+ *     rank       n_runs + 1 u32: roots before the run; n_regions at n_runs
+ *     id         n_runs u32: the region's number
+ *     sums       n_runs / 1024 (rounded up) + 1 u32 of scan scratch
+ *   wsi_region_runs: map -> runs, row_first, parent[r] = r.
+ *   wsi_region_link: runs, row_first, parent -> parent united over every join, up.  One launch; it reads nothing else.
+ *   wsi_region_rank: parent (its chains are shortened, its roots kept) -> root, flag, rank, id; counts_out (device) = {n_regions, status}.  status counts the joined pairs whose
+ *     roots differ and is 0 unless the link failed: the caller treats anything else as an error.
+ *   wsi_region_table: runs, row_first, up, root, id (+ weight, may be NULL) -> table[n_regions][16] int64.
+ *   wsi_region_paint: runs, row_first, id -> labels, H rows of W int32, labels_pitch_bytes apart; nothing outside the rows is written.
+ * -22 before any device work: a NULL pointer (weight excepted), W or H outside 1 .. 32768, a pitch below the row size,
+ *   labels_pitch_bytes no multiple of 4, a connectivity other than 4 or 8, n_runs outside 1 .. W H, n_regions outside 1 .. n_runs, a
+ *   misaligned pointer (4 bytes: count_ws, the counts, labels; 8: table; 16: workspace), a workspace smaller than
+ *   wsi_region_workspace_bytes.  The *_bytes entries return 0 for sizes outside these limits. */
+size_t wsi_region_count_workspace_bytes(int W, int H);
+size_t wsi_region_workspace_bytes(int W, int H, long long n_runs);
+int wsi_region_count(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, void* count_ws, unsigned int* n_runs_out,
+                     void* stream);
+int wsi_region_runs(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, const void* count_ws, long long n_runs,
+                    void* workspace, size_t workspace_bytes, void* stream);
+int wsi_region_link(void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int connectivity, void* stream);
+int wsi_region_rank(void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int connectivity, unsigned int* counts_out, void* stream);
+int wsi_region_table(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, long long n_regions, const uint8_t* weight,
+                     long long weight_pitch_bytes, long long* table, void* stream);
+int wsi_region_paint(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int32_t* labels, long long labels_pitch_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,14 +132,18 @@ def _dense_batches(model, it, scan, dev, forward):
         yield np.stack((batch_x.numpy(), batch_y.numpy()), 1), forward(batch_image.to(dev))
 
 
-def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False, save_xml=False):
+def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False, save_xml=False, region_table=False):
     """Tumour-bed heat maps for every slide in ``dataset`` (a utils.dataset.Dataset_wsis).
     Writes <val_save_pth>/<ep>/<key>_<stride>_heatmap.png and _overlay.png (rank 0; with save_tiff also _heatmap.tif, the heat map as
     a one-component JPEG-tiled pyramid encoded on the device, wsi_segmentation_pipeline_amd.tiffwrite; with save_xml also _tb.xml, the
     tumour bed of the heat map - tumor_bed_overlay's (heat / 255 >= 0.9) -> open 30 x 30 -> convex hull - traced on the device into ImageScope
     regions named 'Invasive', in level-0 coordinates: wsi_segmentation_pipeline_amd.contours; MicronsPerPixel is the slide's where it
     states one, `scan.mpp` or openslide's mpp-x property, else 1.0) and returns
-    {key: {'heatmap': u8 (H2,W2) ndarray, 'classes': u8 ndarray, 'logits': (T,C) tensor}}."""
+    {key: {'heatmap': u8 (H2,W2) ndarray, 'classes': u8 ndarray, 'logits': (T,C) tensor}}.
+    region_table: the result gains 'slide_positive' - does the slide hold tumour at all, the reference's rule
+    (paper_tools/check_for_false_positives.py:61-69: heat >= 0.99 * 255 -> open 50 x 50 -> any pixel left) on the device,
+    wsi_segmentation_pipeline_amd.regions.slide_positive - and 'regions', the regions of that opened mask with the heat map as weight;
+    with save, rank 0 also writes <key>_<stride>_heatmap_regions.csv in level-0 coordinates.  Unset, results and files are what they were."""
     if mode not in ('cls', 'seg'):
         raise ValueError("mode must be 'cls' or 'seg'")
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -229,6 +233,9 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
             results[key] = {'heatmap': heat, 'classes': classes_np, 'logits': r['logits'],
                             'precision': r.get('precision'),          # precision='auto': the mode this slide ran in, and why
                             'stitch_exact': stitch_exact}
+            if region_table:
+                from wsi_segmentation_pipeline_amd import regions as RG
+                results[key]['slide_positive'], results[key]['regions'] = RG._slide_positive(r['heatmap'].contiguous(), 0.99, 50, 0.0)
             if save and rank == 0:
                 _save_png(heat, '{}/{}_{}_heatmap.png'.format(out_dir, key, args.tile_stride_w))
                 thumb = np.asarray(scan.read_region((0, 0), ref_level, scan.level_dimensions[ref_level]).convert('RGB'))
@@ -242,6 +249,10 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
                     bed = (PP.tumor_bed_from_heatmap(r['heatmap'].contiguous(), 0.9, 30, 20).tb_pred > 0).to(torch.uint8)
                     traced = CT.trace(bed, [1], AN.level_step(scan, ref_level), bounds=scan.level_dimensions[0])
                     CT.write_imagescope('{}/{}_{}_tb.xml'.format(out_dir, key, args.tile_stride_w), traced, CT.slide_mpp(scan), {1: 'Invasive'})
+                if region_table:
+                    from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT
+                    RG.write_csv('{}/{}_{}_heatmap_regions.csv'.format(out_dir, key, args.tile_stride_w), results[key]['regions'],
+                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), {1: 'Invasive'})
             dataset.wsis[key] = None                       # the reference frees each slide after use (:282)
     if was_training:
         model.train()
@@ -269,7 +280,7 @@ def _map_u8(arr, hw, dev):
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(dev)
 
 
-def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False, boundary_scores=False):
+def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False, boundary_scores=False, region_table=False):
     """Dense per-pixel map prediction with the tumour-bed post-process (reference utils/eval.py:22-152).
     `model(batch_image)` must return (B, C, ph, pw) logits on the GPU (the reference drives an smp U-Net here; any GPU
     module works, e.g. wsi_segmentation_pipeline_amd.unet.UNetSeg).  Everything between the tile list and the colour
@@ -291,6 +302,11 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False,
     (wsi_segmentation_pipeline_amd.distance.surface_distances on the device): 'hd_tb', 'hd95_tb', 'assd_tb' - Hausdorff, its 95th
     percentile by nearest rank, the mean surface distance - in pixels of the scoring level, and, where the slide states an mpp, the
     same three with the suffix '_um' (mpp times the level's step).  Unset, `scores` and the printed line are what they were.
+    region_table: the result gains 'regions', the region table (wsi_segmentation_pipeline_amd.regions.label, connectivity 8) of classes
+    1 - 3 of `classes_level2` on the foreground mask; with save also <key>_<stride>_regions.csv in level-0 coordinates, areas in square
+    microns where the slide states an mpp; where the entry has `gt`, `scores` gains lesions as objects for classes (2, 3), the
+    reference's own tumour rule p >= 2: 'lesions_pred', 'lesions_gt', 'lesion_precision', 'lesion_recall', 'lesion_f1'
+    (regions.lesion_scores, IoU 0.5).  Unset, results, printed lines and files are what they were.
     Returns {key: {'pred', 'pred_level2', 'classes' (scan level), 'classes_level2', 'tumor_bed', 'outline', 'scores'}}."""
     from wsi_segmentation_pipeline_amd import postprocess as PP
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -339,8 +355,21 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False,
                         for name in ('hd', 'hd95', 'assd'):
                             scores[name + '_tb_um'] = sd[name] * um
                     print('{}, tb outline: hd {:.2f}, hd95 {:.2f}, assd {:.2f} px'.format(key, sd['hd'], sd['hd95'], sd['assd']))
+                if region_table:
+                    from wsi_segmentation_pipeline_amd import regions as RG
+                    ls = RG.lesion_scores(p, _map_u8(entry['gt'], map_hw, dev), classes=(2, 3))
+                    scores.update(lesions_pred=ls['n_pred'], lesions_gt=ls['n_gt'], lesion_precision=ls['precision'], lesion_recall=ls['recall'],
+                                  lesion_f1=ls['f1'])
+                    print('{}, lesions: {} predicted, {} annotated, precision {:.3f}, recall {:.3f}, f1 {:.3f}'.format(
+                        key, ls['n_pred'], ls['n_gt'], ls['precision'], ls['recall'], ls['f1']))
             results[key] = {'pred': pred, 'pred_level2': pred2, 'classes': classes, 'classes_level2': p,
                             'tumor_bed': tb.tb_pred, 'outline': tb.outline, 'scores': scores}
+            if region_table:
+                from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT, regions as RG
+                results[key]['regions'] = RG.label((p * (mask_dev > 0)).to(torch.uint8).contiguous(), (1, 2, 3), 8, labels=False)
+                if save:
+                    RG.write_csv('{}/{}_{}_regions.csv'.format(out_dir, key, args.tile_stride_w), results[key]['regions'],
+                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), CT.DEFAULT_NAMES)
             if save:                                                           # :138-145
                 cls_thr = E.softmax_threshold_argmax(pred2, args.class_probs, want_probs=False)[0]      # pred_to_mask
                 rgb = torch.zeros(map_hw + (3,), dtype=torch.uint8, device=dev)

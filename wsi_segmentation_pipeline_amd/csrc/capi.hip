@@ -3,6 +3,7 @@
 // trunk.hip; the segmentation models: seg_host.h and the decoder files.  No device allocation, no synchronisation, no exceptions.
 #include "internal.h"
 #include "edt_dev.h"
+#include "regions_dev.h"
 #include "../../include/wsi_hip.h"
 
 ConvRoutes g_routes;                                  // the one instance of the route switches (common.h), at their defaults
@@ -567,6 +568,48 @@ int wsi_edt_rows(const void* workspace, size_t workspace_bytes, int W, int H, in
     if (!edt_size_ok(W, H) || !edt_ws_ok(workspace, workspace_bytes, W, H) || !out || ((uintptr_t)out & 3)) return WSI_EINVAL;
     if (out_pitch_bytes < 4LL * W || (out_pitch_bytes & 3)) return WSI_EINVAL;
     return wsi_edt_rows_dispatch(workspace, W, H, out, out_pitch_bytes, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ u8 class map -> region table and label map
+static bool region_size_ok(int W, int H) { return W >= 1 && H >= 1 && W <= wsi_region::LIMIT && H <= wsi_region::LIMIT; }
+static bool region_runs_ok(int W, int H, long long n_runs) { return region_size_ok(W, H) && n_runs >= 1 && n_runs <= (long long)W * H; }
+static bool region_ws_ok(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs) {
+    return workspace && !((uintptr_t)workspace & 15) && region_runs_ok(W, H, n_runs) && workspace_bytes >= wsi_region::layout(H, n_runs).bytes;
+}
+size_t wsi_region_count_workspace_bytes(int W, int H) { return region_size_ok(W, H) ? wsi_region::count_workspace_bytes(W, H) : 0; }
+size_t wsi_region_workspace_bytes(int W, int H, long long n_runs) { return region_runs_ok(W, H, n_runs) ? wsi_region::layout(H, n_runs).bytes : 0; }
+int wsi_region_count(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, void* count_ws, unsigned int* n_runs_out,
+                     void* stream) {
+    if (!map || !region_size_ok(W, H) || pitch_bytes < W || !traced256 || !count_ws || !n_runs_out) return WSI_EINVAL;
+    if (((uintptr_t)count_ws & 3) || ((uintptr_t)n_runs_out & 3)) return WSI_EINVAL;
+    return wsi_region_count_dispatch(map, W, H, pitch_bytes, traced256, count_ws, n_runs_out, (hipStream_t)stream);
+}
+int wsi_region_runs(const uint8_t* map, int W, int H, long long pitch_bytes, const uint8_t* traced256, const void* count_ws, long long n_runs,
+                    void* workspace, size_t workspace_bytes, void* stream) {
+    if (!map || !region_size_ok(W, H) || pitch_bytes < W || !traced256 || !count_ws || ((uintptr_t)count_ws & 3)) return WSI_EINVAL;
+    if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs)) return WSI_EINVAL;
+    return wsi_region_runs_dispatch(map, W, H, pitch_bytes, traced256, count_ws, n_runs, workspace, (hipStream_t)stream);
+}
+int wsi_region_link(void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int connectivity, void* stream) {
+    if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs) || (connectivity != 4 && connectivity != 8)) return WSI_EINVAL;
+    return wsi_region_link_dispatch(workspace, H, n_runs, connectivity, (hipStream_t)stream);
+}
+int wsi_region_rank(void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int connectivity, unsigned int* counts_out, void* stream) {
+    if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs) || (connectivity != 4 && connectivity != 8)) return WSI_EINVAL;
+    if (!counts_out || ((uintptr_t)counts_out & 3)) return WSI_EINVAL;
+    return wsi_region_rank_dispatch(workspace, H, n_runs, connectivity, counts_out, (hipStream_t)stream);
+}
+int wsi_region_table(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, long long n_regions, const uint8_t* weight,
+                     long long weight_pitch_bytes, long long* table, void* stream) {
+    if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs) || n_regions < 1 || n_regions > n_runs) return WSI_EINVAL;
+    if (!table || ((uintptr_t)table & 7) || (weight && weight_pitch_bytes < W)) return WSI_EINVAL;
+    return wsi_region_table_dispatch(workspace, W, H, n_runs, n_regions, weight, weight_pitch_bytes, table, (hipStream_t)stream);
+}
+int wsi_region_paint(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int32_t* labels, long long labels_pitch_bytes,
+                     void* stream) {
+    if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs) || !labels || ((uintptr_t)labels & 3)) return WSI_EINVAL;
+    if (labels_pitch_bytes < 4LL * W || (labels_pitch_bytes & 3)) return WSI_EINVAL;
+    return wsi_region_paint_dispatch(workspace, W, H, n_runs, labels, labels_pitch_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -116,6 +116,16 @@ int wsi_contour_emit_dispatch(const uint8_t* map, int W, int H, long long pitch,
 // edt.hip
 int wsi_edt_columns_dispatch(const uint8_t* map, int W, int H, long long pitch, int invert, void* ws, hipStream_t st);
 int wsi_edt_rows_dispatch(const void* ws, int W, int H, int32_t* out, long long out_pitch, hipStream_t st);
+// regions.hip
+int wsi_region_count_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, void* count_ws, unsigned* n_runs_out,
+                              hipStream_t st);
+int wsi_region_runs_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, const void* count_ws, long long n_runs,
+                             void* ws, hipStream_t st);
+int wsi_region_link_dispatch(void* ws, int H, long long n_runs, int connectivity, hipStream_t st);
+int wsi_region_rank_dispatch(void* ws, int H, long long n_runs, int connectivity, unsigned* counts_out, hipStream_t st);
+int wsi_region_table_dispatch(const void* ws, int W, int H, long long n_runs, long long n_regions, const uint8_t* weight, long long weight_pitch,
+                              long long* table, hipStream_t st);
+int wsi_region_paint_dispatch(const void* ws, int W, int H, long long n_runs, int32_t* labels, long long pitch, hipStream_t st);
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -257,6 +257,14 @@ SIGNATURES = {
     'wsi_edt_workspace_bytes': (_sz, [_i, _i]),
     'wsi_edt_columns': (_i, [_vp, _i, _i, _ll, _i, _vp, _sz, _vp]),
     'wsi_edt_rows': (_i, [_vp, _sz, _i, _i, _vp, _ll, _vp]),
+    'wsi_region_count_workspace_bytes': (_sz, [_i, _i]),
+    'wsi_region_workspace_bytes': (_sz, [_i, _i, _ll]),
+    'wsi_region_count': (_i, [_vp, _i, _i, _ll, _vp, _vp, _vp, _vp]),
+    'wsi_region_runs': (_i, [_vp, _i, _i, _ll, _vp, _vp, _ll, _vp, _sz, _vp]),
+    'wsi_region_link': (_i, [_vp, _sz, _i, _i, _ll, _i, _vp]),
+    'wsi_region_rank': (_i, [_vp, _sz, _i, _i, _ll, _i, _vp, _vp]),
+    'wsi_region_table': (_i, [_vp, _sz, _i, _i, _ll, _ll, _vp, _ll, _vp, _vp]),
+    'wsi_region_paint': (_i, [_vp, _sz, _i, _i, _ll, _vp, _ll, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)
