@@ -2,8 +2,10 @@
 shapes at which the kernels of csrc/contour.hip take another path.  NumPy only."""
 import numpy as np
 
-SCAN_CHUNK = 1024                        # csrc/contour.hip CHUNK: items (corners, edges) of one workgroup
-SCAN_SECOND = 1024 * 256                 # CHUNK * SUMS_TILE: items the scanning workgroup covers in one step of its loop
+SCAN_CHUNK = 1024                        # csrc/map_kernels.h CHUNK: items (corners, edges) of one workgroup
+SCAN_SPAN = 256 * 4                      # csrc/map_kernels.h SUMS_TILE: chunk sums the one scanning workgroup takes in one step of its loop
+SCAN_SECOND = SCAN_CHUNK * 256           # an edge count of 256 scan chunks: a scan over many chunks, a quarter of the scanning workgroup's step
+SCAN_STEP = SCAN_CHUNK * SCAN_SPAN       # items the scanning workgroup covers in one step of its loop
 
 
 def noise_map(h, w, labels, seed):
@@ -69,6 +71,34 @@ def edge_count_map(target, h, w):
     ys, xs = np.nonzero(checkerboard(h - 2, w))
     assert target // 4 <= len(ys)
     m[ys[:target // 4] + 2, xs[:target // 4]] = 1
+    return m
+
+
+def isolated_pixels(h, w, label=1):
+    """single pixels at even (x, y): no two touch, not even at a corner, so every pixel is a loop of 4 edges of its own"""
+    m = np.zeros((h, w), np.uint8)
+    m[0::2, 0::2] = label
+    return m
+
+
+def isolated_pixels_trace(h, w, step=(2, 2), origin=(0, 0), label=1):
+    """what the spec gives for isolated_pixels(h, w), in closed form -> dict(vertices, first, count, edges, label, area2): the loops in
+    raster order of their pixels, each from its top-left corner east, south, west (the spec's start and sense), area2 = 2"""
+    ys, xs = np.nonzero(isolated_pixels(h, w, label))           # raster order: ascending smallest key
+    n = len(ys)
+    corners = np.stack((xs, ys), 1)[:, None, :] + np.asarray(((0, 0), (1, 0), (1, 1), (0, 1)))[None]
+    s, o = np.asarray(step, np.int64), np.asarray(origin, np.int64)
+    four = np.full(n, 4, np.int32)
+    return dict(vertices=(o + corners.reshape(-1, 2) * s - s // 2).astype(np.int32), first=(4 * np.arange(n)).astype(np.int32), count=four, edges=four,
+                label=np.full(n, label, np.int32), area2=np.full(n, 2, np.int64))
+
+
+def sparse_rectangles(h, w):
+    """a handful of small rectangles of three labels in an otherwise empty map: in the first rows, round row 1023, in the middle and in
+    the last rows (the last one ends in the map's last row and column)"""
+    m = np.zeros((h, w), np.uint8)
+    for k, (y, x, rh, rw) in enumerate(((0, 3, 2, 5), (1019, 100, 9, 4), (h // 2, w // 2, 3, 3), (h // 3, w - 9, 4, 6), (h - 3, 40, 2, 7), (h - 2, w - 4, 2, 4))):
+        m[max(0, min(y, h - rh)):max(0, min(y, h - rh)) + rh, x:x + rw] = 1 + k % 3
     return m
 
 

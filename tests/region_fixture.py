@@ -6,7 +6,7 @@ import numpy as np
 import contour_fixture as CF
 
 CHUNK = 1024                             # csrc/regions_dev.h CHUNK: pixels of a row one workgroup walks; items of one scan chunk
-SCAN_SPAN = 256 * 4                      # csrc/regions.hip SUMS_TILE: chunk sums the one scanning workgroup takes in one step of its loop
+SCAN_SPAN = 256 * 4                      # csrc/map_kernels.h SUMS_TILE: chunk sums the one scanning workgroup takes in one step of its loop
 SCAN_SECOND = CHUNK * 256                # a run count of 256 scan chunks: the rank stage's scan over more than one chunk of runs
 
 

@@ -5,7 +5,8 @@
 // record, one step per run bisecting the row above and uniting (a sequential union-find in place of the atomics: the larger root goes
 // under the smaller), the roots ranked, the closed forms per run, the weight sums per aligned 16-byte piece and the labels per aligned
 // piece of four, each bisecting into its row's runs - so UBSan sees every product and sum the device forms, and ASan every index into
-// the map (allocated to its last row's last byte, no slack) and into the workspace arrays (sized by wsi_region::layout).
+// the map (allocated to its last row's last byte, no slack) and into the workspace arrays (sized by wsi_region::layout).  Before the
+// corpus it walks the piece arithmetic the map kernels share (csrc/map_dev.h) exhaustively; exit status 5 where that fails.
 //   usage: regions_san CORPUS RESULTS
 //   CORPUS : u32 cases, then per case i32 kind, W, H, connectivity, shift (bytes before the map's first byte), pitch, has_weight, n;
 //            kind 0: 256 bytes of traced table, H x W map bytes, then H x W weight bytes where has_weight;
@@ -28,8 +29,33 @@ static uint32_t find_root(const std::vector<uint32_t>& parent, uint32_t r) {
 
 static int byte_at(const unsigned char* map, long long pitch, int W, int y, int x) { return x < 0 || x >= W ? -1 : (int)map[(long long)y * pitch + x]; }
 
+// The shared piece arithmetic (csrc/map_dev.h), exhaustively over real addresses: a segment of every length 1 .. 48 at every offset of its
+// first byte inside an aligned 16-byte piece, its shift taken from that address as the kernels take it.  The pieces 0 ..
+// pieces_for(len) - 1 cover every byte of [0, len) exactly once and nothing outside it, and the address a whole piece is fetched from,
+// seg + k0, is a multiple of 16.
+static bool pieces_cover_every_segment() {
+    alignas(16) static const unsigned char line[80] = {};
+    for (int offset = 0; offset < 16; ++offset)
+        for (int len = 1; len <= 48; ++len) {
+            const unsigned char* seg = line + offset;
+            const int shift = wsi_map::piece_shift(seg);
+            if (shift != offset) return false;
+            std::vector<int> seen((size_t)len, 0);
+            for (int piece = 0; piece < wsi_map::pieces_for(len); ++piece) {
+                const wsi_map::Piece p = wsi_map::piece_of(shift, piece, len);
+                if (p.ke <= p.kb) continue;
+                if (p.kb < 0 || p.ke > len || p.kb < p.k0 || p.ke > p.k0 + 16) return false;
+                if (p.ke - p.kb == 16 && (uintptr_t)(seg + p.k0) % 16 != 0) return false;
+                for (int k = p.kb; k < p.ke; ++k) ++seen.at((size_t)k);
+            }
+            for (int k = 0; k < len; ++k) if (seen.at((size_t)k) != 1) return false;
+        }
+    return true;
+}
+
 int main(int argc, char** argv) {
     if (argc != 3) { fprintf(stderr, "usage: %s CORPUS RESULTS\n", argv[0]); return 2; }
+    if (!pieces_cover_every_segment()) { fprintf(stderr, "wsi_map::piece_of does not cover a segment exactly once\n"); return 5; }
     FILE* in = fopen(argv[1], "rb");
     FILE* out = fopen(argv[2], "wb");
     if (!in || !out) { fprintf(stderr, "cannot open files\n"); return 2; }
@@ -54,8 +80,7 @@ int main(int argc, char** argv) {
         const int d = conn == 8 ? 1 : 0;
         unsigned char table[256];
         if (!read_n(in, table, 256)) return 2;
-        Traced tr{};
-        for (int l = 0; l < 256; ++l) if (table[l]) tr.bits[l >> 5] |= 1u << (l & 31);
+        const Traced tr = wsi_map::traced_bits(table);
         const size_t bytes = (size_t)shift + (size_t)(H - 1) * pitch + W;
         unsigned char* buf = (unsigned char*)malloc(bytes);
         unsigned char* wbuf = has_weight ? (unsigned char*)malloc(bytes) : nullptr;
@@ -159,12 +184,12 @@ int main(int argc, char** argv) {
             if (root[r] == r) { rec[BOX_Y0] = me.y; rec[FIRST] = (long long)me.y * W + me.x0; rec[CLS] = me.cls; }
         }
         if (weight) {
-            const int pieces = (W + 15) / 16 + 1;
+            const int pieces = wsi_map::pieces_for(W);
             for (int y = 0; y < H; ++y)
                 for (int piece = 0; piece < pieces; ++piece) {
                     const unsigned char* seg = weight + (long long)y * pitch;
-                    const int sh = (int)((uintptr_t)seg & 15u);
-                    const int k0 = piece * 16 - sh, kb = k0 < 0 ? 0 : k0, ke = k0 + 16 < W ? k0 + 16 : W;
+                    const wsi_map::Piece p = wsi_map::piece_of(wsi_map::piece_shift(seg), piece, W);
+                    const int kb = p.kb, ke = p.ke;
                     if (ke <= kb) continue;
                     const uint32_t end = row_first.at(y + 1);
                     for (uint32_t r = first_ending_after(runs.data(), row_first.at(y), end, kb); r < end; ++r) {

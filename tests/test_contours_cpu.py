@@ -91,6 +91,15 @@ def test_hand_written_cases():
         assert len(two.first) == h * w and (two.edges == 4).all() and (two.area2 == 2).all()
 
 
+def test_isolated_pixels_closed_form_is_the_spec():
+    """the closed form the GPU test of a million edges expects (contour_fixture.isolated_pixels_trace), pinned to the spec at small sizes"""
+    for h, w, step, origin in ((6, 10, (2, 2), (0, 0)), (5, 7, (3, 2), (-4, 9)), (1, 1, (16, 16), (0, 0)), (2, 9, (5, 4), (1, -1))):
+        want, got = O.trace(F.isolated_pixels(h, w), None, step, origin), F.isolated_pixels_trace(h, w, step, origin)
+        assert len(want.first) == ((h + 1) // 2) * ((w + 1) // 2)
+        for name in ('vertices', 'first', 'count', 'edges', 'label', 'area2'):
+            assert np.array_equal(getattr(want, name), got[name]) and getattr(want, name).dtype == got[name].dtype, (h, w, name)
+
+
 def test_start_vertex_loop_order_and_area_sign():
     for c in F.random_cases(40, seed=23):
         w = c['m'].shape[1]
@@ -229,12 +238,15 @@ def test_entries_declared_mirrored_and_checked(lib):
     assert int(re.search(r'#define WSI_HIP_ABI_VERSION (\d+)', hdr).group(1)) == native.ABI_VERSION == 9       # additive: the version stays
     dev_h = open(os.path.join(native.CSRC, 'contour_dev.h')).read()
     assert 'constexpr int LIMIT = 1 << 29;' in dev_h and 'constexpr long long MAX_PIXELS = 1LL << 28;' in dev_h
-    src = open(os.path.join(native.CSRC, 'contour.hip')).read()
-    consts = dict(re.findall(r'constexpr int (\w+) = ([^;]+);', src))
-    assert int(consts['THREADS']) * int(consts['PER_THREAD']) == F.SCAN_CHUNK and consts['SUMS_TILE'] == 'THREADS'
-    assert F.SCAN_SECOND == F.SCAN_CHUNK * int(consts['THREADS'])
+    src = open(os.path.join(native.CSRC, 'contour.hip')).read()                 # the scan is the shared one: its constants are map_kernels.h's
+    assert '#include "map_kernels.h"' in src and not re.search(r'constexpr int (THREADS|PER_THREAD|CHUNK|SUMS_TILE)\b', src)
+    consts = dict(re.findall(r'constexpr int (\w+) = ([^;]+);', open(os.path.join(native.CSRC, 'map_kernels.h')).read()))
+    assert int(consts['THREADS']) * int(consts['PER_THREAD']) == F.SCAN_CHUNK and consts['CHUNK'] == 'THREADS * PER_THREAD'
+    assert consts['SUMS_TILE'] == 'THREADS * SUMS_PER_LANE' and int(consts['THREADS']) * int(consts['SUMS_PER_LANE']) == F.SCAN_SPAN
+    assert F.SCAN_SECOND == F.SCAN_CHUNK * int(consts['THREADS']) and F.SCAN_STEP == F.SCAN_CHUNK * F.SCAN_SPAN
     mk = open(os.path.join(native.CSRC, 'Makefile')).read()
     assert re.search(r'^SRCS\s*=.*\bcontour\.hip\b', mk, re.M) and re.search(r'^build/%\.o:.*\bcontour_dev\.h\b', mk, re.M)
+    assert re.search(r'^build/%\.o:.*\bmap_dev\.h\b.*\bmap_kernels\.h\b', mk, re.M)
 
     assert lib.wsi_contour_count_workspace_bytes(0, 5) == lib.wsi_contour_count_workspace_bytes(1 << 15, 1 << 14) == 0
     assert lib.wsi_contour_count_workspace_bytes(1 << 14, 1 << 14) > 0 and lib.wsi_contour_count_workspace_bytes(1, 1) == 256

@@ -105,6 +105,25 @@ def test_edge_counts_round_the_scan_sizes(dev, n_edges):
     assert int(want.edges.sum()) == n_edges
 
 
+@pytest.mark.parametrize('h', (F.SCAN_SPAN - 2, F.SCAN_SPAN - 1, F.SCAN_SPAN, 2 * F.SCAN_SPAN))
+def test_corner_chunk_sums_round_one_workgroups_span(dev, h):
+    """the count stage's chunk sums, as many as the one scanning workgroup takes in one step of its loop - 1, + 0, + 1 and twice that + 1:
+    a 1023-wide map has one corner row of 1024 corners per chunk and H + 1 chunks.  Sparse maps, so the spec is quick."""
+    want = check(dev, F.sparse_rectangles(h, 1023), places=PLACES[1:2])
+    assert len(want.first) == 6 and int(want.edges.sum()) == 102
+
+
+def test_edge_scans_past_one_step_of_the_scanning_workgroup(dev):
+    """n_edges just above SCAN_STEP = 1024 x 1024: the u32 scan of the vertex flags and both u64 scans (loops, cross terms) have more chunk
+    sums than the scanning workgroup takes in one step.  Isolated pixels, expected in closed form (pinned to the spec at small sizes in
+    tests/test_contours_cpu.py); 262 656 loops are too many for the round trip's Python, which other tests make."""
+    h, w = 1024, 1026
+    t = F.isolated_pixels_trace(h, w, (2, 2), (0, 0))
+    want = O.Traced(t['vertices'], t['first'], t['count'], t['edges'], t['label'], t['area2'], (w, h), (2, 2), (0, 0), None)
+    assert F.SCAN_STEP < int(want.edges.sum()) == 4 * 513 * 512 < F.SCAN_STEP + 3 * F.SCAN_CHUNK
+    check(dev, F.isolated_pixels(h, w), want=want, places=PLACES[1:2], round_trip=False)
+
+
 @pytest.mark.parametrize('edges', (4, 6, 8, 510, 512, 514))
 def test_single_loops_round_a_doubling_round(dev, edges):
     """one loop is the whole map, so n_edges is its length: 512 takes 9 rounds and covers the loop exactly, 514 takes the 10th"""

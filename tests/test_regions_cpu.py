@@ -312,7 +312,9 @@ def test_workspace_sizes_are_the_documented_ones(lib):
     dev_h = open(os.path.join(native.CSRC, 'regions_dev.h')).read()
     assert 'constexpr int LIMIT = 32768;' in dev_h and 'constexpr int CHUNK = 1024;' in dev_h and 'constexpr int RECORD_WORDS = 16;' in dev_h
     assert (R.LIMIT, RF.CHUNK, O.CHUNK, O.LIMIT) == (32768, 1024, 1024, 32768) and R.FIELDS == O.FIELDS and len(R.FIELDS) == 16
-    consts = dict(re.findall(r'constexpr int (\w+) = ([^;]+);', open(os.path.join(native.CSRC, 'regions.hip')).read()))
+    src = open(os.path.join(native.CSRC, 'regions.hip')).read()                 # the scan is the shared one: its constants are map_kernels.h's,
+    assert 'wsi_map::CHUNK == CHUNK' in src                                     # pinned to the layout's chunk where both are visible
+    consts = dict(re.findall(r'constexpr int (\w+) = ([^;]+);', open(os.path.join(native.CSRC, 'map_kernels.h')).read()))
     assert int(consts['THREADS']) * int(consts['PER_THREAD']) == RF.CHUNK and consts['SUMS_TILE'] == 'THREADS * SUMS_PER_LANE'
     assert int(consts['THREADS']) * int(consts['SUMS_PER_LANE']) == RF.SCAN_SPAN and RF.SCAN_SECOND == 256 * RF.CHUNK
     fields = re.search(r'enum Field \{([^}]*)\}', dev_h).group(1).replace('= 0', '').replace('BOX_', '').lower().split(',')

@@ -43,7 +43,7 @@ def resource_report():
     text = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True).stdout
     out = {}
     for block in text.split('Function Name: ')[1:]:
-        name = re.match(r'_ZN\d+_GLOBAL__N_1(\d+)', block)
+        name = re.match(r'_ZN(?:\d+_GLOBAL__N_1|7wsi_map)(\d+)', block)
         mangled = block.split()[0]
         short = mangled[name.end():name.end() + int(name.group(1))] if name else mangled
         if 'ILb0E' in mangled or 'ILb1E' in mangled:

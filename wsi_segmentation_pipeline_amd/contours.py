@@ -15,6 +15,7 @@ import torch
 
 from . import native
 from .engine import _ptr, _require_gpu
+from .maps import check_map, stage_marker, step2
 
 LIMIT = 1 << 29                          # csrc/contour_dev.h wsi_contour::LIMIT
 MAX_PIXELS = 1 << 28                     # wsi_contour::MAX_PIXELS: the 4 H W edge slots fit 30 bits
@@ -34,13 +35,6 @@ def traced_table(classes=None):
     return t
 
 
-def _step2(step):
-    sx, sy = (int(step), int(step)) if np.isscalar(step) else (int(step[0]), int(step[1]))
-    if sx < 1 or sy < 1:
-        raise ValueError('step %r must be >= 1 each way' % (step,))
-    return sx, sy
-
-
 def level0_corner(c, origin, step, bound=None):
     """map corner -> level-0 coordinate along one axis (Python ints)"""
     v = int(origin) + int(c) * int(step) - int(step) // 2
@@ -54,7 +48,7 @@ class Contours:
 
     def __init__(self, vertices, first, count, edges, label, area2, size, step, origin=(0, 0), bounds=None):
         self.vertices, self.first, self.count, self.edges, self.label, self.area2 = vertices, first, count, edges, label, area2
-        self.size, self.step, self.origin, self.bounds = (int(size[0]), int(size[1])), _step2(step), (int(origin[0]), int(origin[1])), bounds
+        self.size, self.step, self.origin, self.bounds = (int(size[0]), int(size[1])), step2(step), (int(origin[0]), int(origin[1])), bounds
         self._cache = None
 
     def __len__(self):
@@ -103,35 +97,26 @@ def trace_raw(label_map, table, step, origin=(0, 0), bounds=None, alloc=None, st
     rows are returned.  stages: a dict that receives, per stage name ('count', 'build', 'ranks', 'order', 'emit'), the [begin, end]
     torch.cuda.Event pair recorded round the stage's entry (tools/contour_times.py)."""
     lib = native.load()
-    sx, sy = _step2(step)
+    sx, sy = step2(step)
     ox, oy = int(origin[0]), int(origin[1])
-    if not isinstance(label_map, torch.Tensor) or label_map.dim() != 2 or label_map.dtype != torch.uint8:
-        raise ValueError('the label map must be a 2-D uint8 tensor')
-    h, w = int(label_map.shape[0]), int(label_map.shape[1])
+    h, w, pitch = check_map(label_map, 'the label map')
     _check_geometry(w, h, sx, sy, ox, oy, bounds)
-    if (w > 1 and label_map.stride(1) != 1) or (h > 1 and label_map.stride(0) < w):
-        raise ValueError('the label map must have unit column stride and a row stride >= its width')
     _require_gpu(label_map, 'the label map')
     table = np.ascontiguousarray(table, np.uint8)
     assert table.shape == (256,)
     dev = label_map.device
-    pitch = label_map.stride(0) if h > 1 else w
     bw, bh = (0, 0) if bounds is None else (int(bounds[0]), int(bounds[1]))
     tp = table.ctypes.data_as(native.C.c_void_p)
 
-    def mark(name, _end):
-        if stages is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            stages.setdefault(name, []).append(ev)
+    mark = stage_marker(stages)
 
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         count_ws = torch.empty(lib.wsi_contour_count_workspace_bytes(w, h), dtype=torch.uint8, device=dev)
         n_edges_t = torch.zeros(1, dtype=torch.int32, device=dev)
-        mark('count', False)
+        mark('count')
         native.check(lib.wsi_contour_count(_ptr(label_map), w, h, pitch, tp, _ptr(count_ws), _ptr(n_edges_t), st), 'wsi_contour_count')
-        mark('count', True)
+        mark('count')
         n_edges = int(n_edges_t.item())                             # the one number the workspace is sized by
         if n_edges == 0:
             nv = nl = 0
@@ -139,15 +124,15 @@ def trace_raw(label_map, table, step, origin=(0, 0), bounds=None, alloc=None, st
             ws_bytes = lib.wsi_contour_workspace_bytes(n_edges)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
             counts = torch.zeros(2, dtype=torch.int32, device=dev)
-            mark('build', False)
+            mark('build')
             native.check(lib.wsi_contour_build(_ptr(label_map), w, h, pitch, tp, _ptr(count_ws), n_edges, _ptr(ws), ws_bytes, st), 'wsi_contour_build')
-            mark('build', True)
-            mark('ranks', False)
+            mark('build')
+            mark('ranks')
             native.check(lib.wsi_contour_ranks(_ptr(ws), ws_bytes, n_edges, st), 'wsi_contour_ranks')
-            mark('ranks', True)
-            mark('order', False)
+            mark('ranks')
+            mark('order')
             native.check(lib.wsi_contour_order(_ptr(ws), ws_bytes, n_edges, w, _ptr(counts), st), 'wsi_contour_order')
-            mark('order', True)
+            mark('order')
             nl, nv = (int(v) for v in counts.tolist())
         if alloc is None:
             vertices = torch.empty((nv, 2), dtype=torch.int32, device=dev)
@@ -158,10 +143,10 @@ def trace_raw(label_map, table, step, origin=(0, 0), bounds=None, alloc=None, st
             if vertices.shape[0] < nv or records.shape[0] < nl or area2.shape[0] < nl or not (vertices.is_contiguous() and records.is_contiguous()):
                 raise ValueError('alloc returned buffers smaller than %d vertices / %d loops' % (nv, nl))
         if n_edges:
-            mark('emit', False)
+            mark('emit')
             native.check(lib.wsi_contour_emit(_ptr(label_map), w, h, pitch, _ptr(ws), ws_bytes, n_edges, ox, oy, sx, sy, bw, bh, _ptr(vertices), nv,
                                               _ptr(records), _ptr(area2), nl, st), 'wsi_contour_emit')
-            mark('emit', True)
+            mark('emit')
     return vertices[:nv], records[:nl], area2[:nl], n_edges
 
 

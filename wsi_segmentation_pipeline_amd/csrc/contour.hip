@@ -1,8 +1,9 @@
 // Boundary tracing of a u8 label map into ordered polygon loops (include/wsi_hip.h wsi_contour_*; the per-edge rule: contour_dev.h;
 // spec: tests/contours_oracle.py).  The successor map of the boundary edges is a permutation; its cycles are found and ordered by
 // pointer doubling.  Everything is integer, no workgroup waits on another inside a launch (every dependency between workgroups is a
-// kernel boundary; a prefix sum is three launches: chunk sums, the scan of the sums by one workgroup, apply), no atomics, and the
-// output is the same bits every run.
+// kernel boundary; a prefix sum is the three launches of map_kernels.h: chunk sums, the scan of the sums by one workgroup, apply), no
+// atomics, and the output is the same bits every run.  The workgroup scan, the staging of labels in LDS and the launch helpers are
+// map_kernels.h's, shared with regions.hip.
 //
 //   count   the corners of the (W + 1) x (H + 1) corner grid are cut into chunks of at most CHUNK corners that are consecutive in key
 //           order (corner_geom: a piece of one corner row, or whole rows of a narrow map).  A workgroup stages the pixels round its
@@ -20,15 +21,13 @@
 #include <hip/hip_runtime.h>
 #include "internal.h"
 #include "contour_dev.h"
+#include "map_kernels.h"
 
 using namespace wsi_contour;
+using namespace wsi_map;                                       // THREADS, PER_THREAD; CHUNK: the corners of one workgroup, as its scan items
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int PER_THREAD = 4;
-constexpr int CHUNK = THREADS * PER_THREAD;                    // elements of one workgroup: corners (count, build) or scan items
-constexpr int SUMS_TILE = THREADS;                             // chunk sums the one scanning workgroup takes per step
 constexpr int TILE_CAP = 3072;                                 // staged labels: (rows + 1) x (cw + 1) <= 2 (CHUNK + 1), or 1.5 CHUNK + W + 2 for whole rows
 
 struct Geom { int W, H, rows, cpr; long long chunks; };        // rows: corner rows per chunk (1 where a row is cut into cpr chunks)
@@ -43,81 +42,6 @@ Geom corner_geom(int W, int H) {
         g.chunks = ((long long)H + 1) * g.cpr;
     }
     return g;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- workgroup scan
-template <typename T>
-__device__ inline T block_exclusive(T v, T* total, T* s) {     // s: THREADS slots of LDS; every lane of the workgroup calls
-    const int tid = threadIdx.x;
-    s[tid] = v;
-    __syncthreads();
-    for (int off = 1; off < THREADS; off <<= 1) {
-        const T add = tid >= off ? s[tid - off] : T(0);
-        __syncthreads();
-        s[tid] += add;
-        __syncthreads();
-    }
-    const T incl = s[tid];
-    *total = s[THREADS - 1];
-    __syncthreads();                                            // the slots may be refilled after this
-    return incl - v;
-}
-
-template <typename T>
-__global__ __launch_bounds__(THREADS) void scan_chunk_sums_kernel(const T* __restrict__ in, long long n, T* __restrict__ sums) {
-    __shared__ T s[THREADS];
-    const long long base = (long long)blockIdx.x * CHUNK + (long long)threadIdx.x * PER_THREAD;
-    T v = 0;
-    for (int k = 0; k < PER_THREAD; ++k) if (base + k < n) v += in[base + k];
-    T total;
-    block_exclusive(v, &total, s);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[0 .. nb) become their exclusive prefix, sums[nb] and *total_out the total
-template <typename T>
-__global__ __launch_bounds__(THREADS) void scan_sums_kernel(T* sums, long long nb, T* total_out) {
-    __shared__ T s[THREADS];
-    T carry = 0;
-    for (long long base = 0; base < nb; base += SUMS_TILE) {
-        const long long i = base + threadIdx.x;
-        const T v = i < nb ? sums[i] : T(0);
-        T total;
-        const T ex = block_exclusive(v, &total, s);
-        if (i < nb) sums[i] = carry + ex;
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        sums[nb] = carry;
-        if (total_out) *total_out = carry;
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(THREADS) void scan_apply_kernel(const T* __restrict__ in, long long n, const T* __restrict__ sums, T* __restrict__ out) {
-    __shared__ T s[THREADS];
-    const long long base = (long long)blockIdx.x * CHUNK + (long long)threadIdx.x * PER_THREAD;
-    T v[PER_THREAD], sum = 0;
-    for (int k = 0; k < PER_THREAD; ++k) { v[k] = base + k < n ? in[base + k] : T(0); sum += v[k]; }
-    T total;
-    T run = sums[blockIdx.x] + block_exclusive(sum, &total, s);
-    for (int k = 0; k < PER_THREAD; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-}
-
-// out[0 .. n) = the exclusive prefix sums of in[0 .. n), out[n] = the total; sums: scan_chunks(n) + 1 items
-long long scan_chunks(long long n) { return (n + CHUNK - 1) / CHUNK; }
-
-template <typename T>
-int scan_exclusive(const T* in, long long n, T* out, T* sums, hipStream_t st) {
-    const long long nb = scan_chunks(n);
-    if (nb > 0x7fffffffLL) return WSI_EINVAL;
-    if (nb) hipLaunchKernelGGL(scan_chunk_sums_kernel<T>, dim3((unsigned)nb), dim3(THREADS), 0, st, in, n, sums);
-    hipLaunchKernelGGL(scan_sums_kernel<T>, dim3(1), dim3(THREADS), 0, st, sums, nb, out + n);
-    if (nb) hipLaunchKernelGGL(scan_apply_kernel<T>, dim3((unsigned)nb), dim3(THREADS), 0, st, in, n, (const T*)sums, out);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
 }
 
 // ------------------------------------------------------------------------------------------------------ the corner walk (count, build)
@@ -139,36 +63,6 @@ __device__ inline ChunkPos chunk_pos(const Geom& g, long long b) {
     return p;
 }
 
-// the labels of pixel rows ty0 - 1 .. ty0 + rows - 1, columns cx0 - 1 .. cx0 + cw - 1 into tile[(rows + 1)][cw + 1]; -1 outside the map
-__device__ inline void stage_tile(const uint8_t* __restrict__ map, long long pitch, const Geom& g, const ChunkPos& p, int16_t* tile) {
-    const int tw = p.cw + 1, th = p.rows + 1;
-    for (int i = threadIdx.x; i < tw * th; i += THREADS) tile[i] = -1;
-    __syncthreads();
-    const int xa = p.cx0 - 1 > 0 ? p.cx0 - 1 : 0, xb = p.cx0 + p.cw < g.W ? p.cx0 + p.cw : g.W;      // the map's columns [xa, xb)
-    if (xb > xa) {
-        const int pieces = (xb - xa + 15) / 16 + 1;             // aligned 16-byte pieces a segment of xb - xa bytes can touch
-        for (int item = threadIdx.x; item < th * pieces; item += THREADS) {
-            const int j = item / pieces, piece = item % pieces;
-            const long long py = p.ty0 - 1 + j;
-            if (py < 0 || py >= g.H) continue;
-            const uint8_t* seg = map + py * pitch + xa;         // the segment's first byte
-            const int shift = (int)((uintptr_t)seg & 15u);
-            const int k0 = piece * 16 - shift;                  // the piece's first byte, relative to the segment
-            const int kb = k0 < 0 ? 0 : k0, ke = k0 + 16 < xb - xa ? k0 + 16 : xb - xa;
-            if (ke <= kb) continue;
-            int16_t* dst = tile + j * tw + (xa - (p.cx0 - 1));
-            if (ke - kb == 16) {
-                const uint4 v = *reinterpret_cast<const uint4*>(seg + k0);
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-                for (int k = 0; k < 16; ++k) dst[k0 + k] = (int16_t)((w[k >> 2] >> (8 * (k & 3))) & 255u);
-            } else {
-                for (int k = kb; k < ke; ++k) dst[k] = (int16_t)seg[k];
-            }
-        }
-    }
-    __syncthreads();
-}
-
 __device__ inline Quad tile_quad(const int16_t* tile, int tw, int r, int c) {
     Quad q;
     q.q[0] = tile[r * tw + c];
@@ -182,9 +76,9 @@ template <bool BUILD>
 __global__ __launch_bounds__(THREADS) void contour_corner_kernel(const uint8_t* __restrict__ map, long long pitch, Geom g, Traced tr, uint32_t* sums,
                                                                   long long n_edges, uint32_t* __restrict__ key, uint8_t* __restrict__ flag) {
     __shared__ int16_t tile[TILE_CAP];
-    __shared__ uint32_t s[THREADS];
+    __shared__ uint32_t s[THREADS / WAVE];
     const ChunkPos p = chunk_pos(g, blockIdx.x);
-    stage_tile(map, pitch, g, p, tile);
+    stage_labels(map, pitch, g.W, g.H, p.ty0 - 1, p.rows + 1, p.cx0 - 1, p.cw + 1, tile);
     const int tw = p.cw + 1, n_local = p.rows * p.cw;
     unsigned mask[PER_THREAD], vert[PER_THREAD];
     uint32_t count = 0;
@@ -348,8 +242,6 @@ int rounds_for(long long n) {                                   // ceil(log2 n):
     return r;
 }
 
-unsigned blocks_for(long long n) { return (unsigned)((n + THREADS - 1) / THREADS); }
-
 }  // namespace
 
 size_t wsi_contour_count_ws_bytes(int W, int H) { return align_up(4 * ((size_t)corner_geom(W, H).chunks + 1), 256); }
@@ -360,28 +252,26 @@ int wsi_contour_count_dispatch(const uint8_t* map, int W, int H, long long pitch
                                hipStream_t st) {
     const Geom g = corner_geom(W, H);
     if (g.chunks > 0x7fffffffLL) return WSI_EINVAL;
-    Traced tr{};
-    for (int l = 0; l < 256; ++l) if (traced256[l]) tr.bits[l >> 5] |= 1u << (l & 31);
+    const Traced tr = traced_bits(traced256);
     uint32_t* sums = (uint32_t*)count_ws;
     hipLaunchKernelGGL(contour_corner_kernel<false>, dim3((unsigned)g.chunks), dim3(THREADS), 0, st, map, pitch, g, tr, sums, 0LL, (uint32_t*)nullptr,
                        (uint8_t*)nullptr);
     hipLaunchKernelGGL(scan_sums_kernel<uint32_t>, dim3(1), dim3(THREADS), 0, st, sums, g.chunks, (uint32_t*)n_edges_out);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return launched();
 }
 
 int wsi_contour_build_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, const void* count_ws, long long n_edges,
                                void* ws, hipStream_t st) {
     const Geom g = corner_geom(W, H);
     if (g.chunks > 0x7fffffffLL) return WSI_EINVAL;
-    Traced tr{};
-    for (int l = 0; l < 256; ++l) if (traced256[l]) tr.bits[l >> 5] |= 1u << (l & 31);
+    const Traced tr = traced_bits(traced256);
     const Workspace w = carve(ws, n_edges);
     const uint32_t n = (uint32_t)n_edges;
     hipLaunchKernelGGL(contour_corner_kernel<true>, dim3((unsigned)g.chunks), dim3(THREADS), 0, st, map, pitch, g, tr, (uint32_t*)count_ws, n_edges, w.key,
                        w.flag);
     hipLaunchKernelGGL(contour_succ_kernel, dim3(blocks_for(n_edges)), dim3(THREADS), 0, st, map, pitch, W, H, (const uint32_t*)w.key, n, w.succ, w.word[0],
                        w.jump[0]);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return launched();
 }
 
 int wsi_contour_ranks_dispatch(void* ws, long long n_edges, hipStream_t st) {
@@ -390,7 +280,7 @@ int wsi_contour_ranks_dispatch(void* ws, long long n_edges, hipStream_t st) {
     for (int k = 0; k < rounds; ++k)
         hipLaunchKernelGGL(contour_double_kernel, dim3(blocks_for(n_edges)), dim3(THREADS), 0, st, (const uint64_t*)w.word[k & 1],
                            (const uint32_t*)w.jump[k & 1], w.word[(k + 1) & 1], w.jump[(k + 1) & 1], (uint32_t)n_edges, 1u << k);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return launched();
 }
 
 int wsi_contour_order_dispatch(void* ws, long long n_edges, int W, unsigned* counts_out, hipStream_t st) {
@@ -410,7 +300,7 @@ int wsi_contour_order_dispatch(void* ws, long long n_edges, int W, unsigned* cou
     if (!rc) rc = scan_exclusive<uint64_t>(cross, n_edges, w.CS, w.sums64, st);
     if (rc) return rc;
     hipLaunchKernelGGL(contour_counts_kernel, dim3(1), dim3(64), 0, st, (const uint64_t*)w.S, (const uint32_t*)w.VS, n, (uint32_t*)counts_out);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return launched();
 }
 
 int wsi_contour_emit_dispatch(const uint8_t* map, int W, int H, long long pitch, const void* ws, long long n_edges, int ox, int oy, int sx, int sy,
@@ -422,5 +312,5 @@ int wsi_contour_emit_dispatch(const uint8_t* map, int W, int H, long long pitch,
                        (const uint32_t*)w.VS, n, W, ox, oy, sx, sy, bw, bh, (int2*)vertices, (uint32_t)cap_vertices);
     hipLaunchKernelGGL(contour_emit_loops_kernel, dim3(nb), dim3(THREADS), 0, st, map, pitch, W, H, (const uint64_t*)w.X, (const uint64_t*)w.S,
                        (const uint32_t*)w.VS, (const uint64_t*)w.CS, (const uint32_t*)w.key, n, (int4*)loops, area2, (uint32_t)cap_loops);
-    return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT;
+    return launched();
 }

@@ -14,22 +14,17 @@
 // An edge's key is corner * 4 + d with corner = ty (W + 1) + tx of its tail; 1 <= W, H and H W <= 2^28 keep every key below 2^32.
 #pragma once
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define WSI_HD __host__ __device__
-#else
-#define WSI_HD
-#endif
+#include "map_dev.h"
 
 namespace wsi_contour {
+
+using wsi_map::Traced;                                         // bit l: label l is traced
+using wsi_map::traced;
 
 constexpr int LIMIT = 1 << 29;                                 // every produced coordinate lies in [-LIMIT, LIMIT]
 constexpr long long MAX_PIXELS = 1LL << 28;
 
-struct Traced { uint32_t bits[8]; };                           // bit l: label l is traced
 struct Quad { int q[4]; };                                     // NW, SW, SE, NE; -1 outside the map
-
-WSI_HD inline bool traced(const Traced& t, int label) { return (t.bits[label >> 5] >> (label & 31)) & 1u; }
 
 // the label of pixel (x, y), -1 outside the W x H map: no byte outside the H row segments is read
 WSI_HD inline int label_at(const uint8_t* map, long long pitch, int W, int H, long long x, long long y) {

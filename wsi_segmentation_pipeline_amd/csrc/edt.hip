@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include "internal.h"
 #include "edt_dev.h"
+#include "map_dev.h"
 
 using namespace wsi_edt;
 
@@ -29,17 +30,17 @@ constexpr int ROW_VEC = 8;                                     // u16 values of 
 
 // rows y0 .. y0 + rows - 1, columns x0 .. x0 + cw - 1 into tile: pixel (j, c) at tile[j * TILE_PITCH + row_shift(j) + c]
 __device__ inline int row_shift(const uint8_t* map, long long pitch, int y0, int x0, int j) {
-    return (int)((uintptr_t)(map + (long long)(y0 + j) * pitch + x0) & 15u);
+    return wsi_map::piece_shift(map + (long long)(y0 + j) * pitch + x0);
 }
 
 __device__ inline void stage_band(const uint8_t* __restrict__ map, long long pitch, int y0, int rows, int x0, int cw, uint8_t* tile) {
-    const int pieces = (cw + 15) / 16 + 1;                      // aligned 16-byte pieces a segment of cw bytes can touch
+    const int pieces = wsi_map::pieces_for(cw);                 // aligned 16-byte pieces a segment of cw bytes can touch
     for (int item = threadIdx.x; item < rows * pieces; item += THREADS) {
         const int j = item / pieces, piece = item % pieces;
         const uint8_t* seg = map + (long long)(y0 + j) * pitch + x0;         // the segment's first byte
-        const int shift = (int)((uintptr_t)seg & 15u);
-        const int k0 = piece * 16 - shift;                      // the piece's first byte, relative to the segment
-        const int kb = k0 < 0 ? 0 : k0, ke = k0 + 16 < cw ? k0 + 16 : cw;
+        const int shift = wsi_map::piece_shift(seg);
+        const wsi_map::Piece p = wsi_map::piece_of(shift, piece, cw);
+        const int k0 = p.k0, kb = p.kb, ke = p.ke;
         if (ke <= kb) continue;
         uint8_t* dst = tile + j * TILE_PITCH + shift;           // dst + k0 is 16-byte aligned: j * TILE_PITCH + piece * 16
         if (ke - kb == 16) {

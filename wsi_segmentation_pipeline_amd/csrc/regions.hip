@@ -1,7 +1,8 @@
 // Region tables of a u8 class map (include/wsi_hip.h wsi_region_*; the per-run rule: regions_dev.h; spec: tests/regions_oracle.py).
 // Regions are found over the runs of equal class of every row, not over pixels, so memory and work follow the run count; every sum of a
 // record is a closed form per run.  Everything is integer: the same bits every run.  No workgroup waits on another inside a launch (a
-// prefix sum is three launches as in contour.hip: chunk sums, the scan of the sums by one workgroup, apply), no fences, no polling.
+// prefix sum is the three launches of map_kernels.h: chunk sums, the scan of the sums by one workgroup, apply), no fences, no polling.
+// The workgroup scan, the piece arithmetic and the launch helpers are map_kernels.h's and map_dev.h's, shared with contour.hip.
 //
 //   count   chunks of CHUNK pixels of one row staged in LDS - whole aligned 16-byte pieces of the row's memory as one uint4, the ragged
 //           ends byte by byte, nothing outside the H row segments - with the neighbour byte of the adjoining chunk at either end; a pixel
@@ -20,112 +21,46 @@
 #include <hip/hip_runtime.h>
 #include "internal.h"
 #include "regions_dev.h"
+#include "map_kernels.h"
 
 using namespace wsi_region;
+using wsi_map::THREADS;
+using wsi_map::PER_THREAD;
+using wsi_map::WAVE;
+using wsi_map::block_exclusive;
+using wsi_map::blocks_for;
+using wsi_map::launched;
+using wsi_map::traced_bits;
 
 namespace {
 
-constexpr int THREADS = 256;
-constexpr int PER_THREAD = 4;
-constexpr int WAVE = 64;
-constexpr int SUMS_PER_LANE = 4;
-constexpr int SUMS_TILE = THREADS * SUMS_PER_LANE;             // chunk sums the one scanning workgroup takes per step
 constexpr int SLOTS = 256;                                     // ids one workgroup combines in LDS before it goes to the records
 constexpr int ACC = 11;                                        // combined words per id: 7 sums, 3 box ends, the border flag
-static_assert(THREADS * PER_THREAD == CHUNK, "one workgroup walks one chunk");
+// regions_dev.h's CHUNK and scan_chunks size the workspaces: one workgroup walks one chunk, and the shared scan cuts its items alike
+static_assert(THREADS * PER_THREAD == CHUNK && wsi_map::CHUNK == CHUNK, "one workgroup walks one chunk; the scan's chunk is the layout's");
 
 typedef unsigned long long u64;
 
-// ---------------------------------------------------------------------------------------------------------------- workgroup scan
-// every lane of the workgroup calls; s: one slot of LDS per wave.  The scan inside a wave goes through shuffles, the waves' totals through LDS.
-__device__ inline uint32_t block_exclusive(uint32_t v, uint32_t* total, uint32_t* s) {
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    uint32_t incl = v;
-    for (int off = 1; off < WAVE; off <<= 1) {
-        const uint32_t below = __shfl_up(incl, off, WAVE);
-        if (lane >= off) incl += below;
-    }
-    if (lane == WAVE - 1) s[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    for (int k = 0; k < THREADS / WAVE; ++k) {
-        const uint32_t t = s[k];
-        if (k < wave) before += t;
-        all += t;
-    }
-    *total = all;
-    __syncthreads();                                            // the slots may be refilled after this
-    return before + incl - v;
-}
-
-__global__ __launch_bounds__(THREADS) void region_chunk_sums_kernel(const uint32_t* __restrict__ in, long long n, uint32_t* __restrict__ sums) {
-    __shared__ uint32_t s[THREADS / WAVE];
-    const long long base = (long long)blockIdx.x * CHUNK + (long long)threadIdx.x * PER_THREAD;
-    uint32_t v = 0;
-    for (int k = 0; k < PER_THREAD; ++k) if (base + k < n) v += in[base + k];
-    uint32_t total;
-    block_exclusive(v, &total, s);
-    if (threadIdx.x == 0) sums[blockIdx.x] = total;
-}
-
-// one workgroup: sums[0 .. nb) become their exclusive prefix, sums[nb] and *total_out the total
-__global__ __launch_bounds__(THREADS) void region_scan_sums_kernel(uint32_t* sums, long long nb, uint32_t* total_out) {
-    __shared__ uint32_t s[THREADS / WAVE];
-    uint32_t carry = 0;
-    for (long long base = 0; base < nb; base += SUMS_TILE) {
-        const long long i = base + (long long)threadIdx.x * SUMS_PER_LANE;
-        uint32_t v[SUMS_PER_LANE], sum = 0;
-#pragma unroll
-        for (int k = 0; k < SUMS_PER_LANE; ++k) { v[k] = i + k < nb ? sums[i + k] : 0u; sum += v[k]; }
-        uint32_t total;
-        uint32_t run = carry + block_exclusive(sum, &total, s);
-#pragma unroll
-        for (int k = 0; k < SUMS_PER_LANE; ++k) {
-            if (i + k < nb) sums[i + k] = run;
-            run += v[k];
-        }
-        carry += total;
-    }
-    if (threadIdx.x == 0) {
-        sums[nb] = carry;
-        if (total_out) *total_out = carry;
-    }
-}
-
-__global__ __launch_bounds__(THREADS) void region_scan_apply_kernel(const uint32_t* __restrict__ in, long long n, const uint32_t* __restrict__ sums,
-                                                                     uint32_t* __restrict__ out) {
-    __shared__ uint32_t s[THREADS / WAVE];
-    const long long base = (long long)blockIdx.x * CHUNK + (long long)threadIdx.x * PER_THREAD;
-    uint32_t v[PER_THREAD], sum = 0;
-    for (int k = 0; k < PER_THREAD; ++k) { v[k] = base + k < n ? in[base + k] : 0u; sum += v[k]; }
-    uint32_t total;
-    uint32_t run = sums[blockIdx.x] + block_exclusive(sum, &total, s);
-    for (int k = 0; k < PER_THREAD; ++k) {
-        if (base + k < n) out[base + k] = run;
-        run += v[k];
-    }
-}
-
 // ------------------------------------------------------------------------------------------------------ the row walk (count, runs)
-// the bytes of row y, columns cx0 - 1 .. cx0 + cw, into tile[cw + 2]; -1 outside the row
+// the bytes of row y, columns cx0 - 1 .. cx0 + cw, into tile[cw + 2]; -1 outside the row.  The one-row form of wsi_map::stage_labels,
+// kept here: a row of the map always exists and one lane takes one piece, so it needs neither the row test nor the division of the
+// windowed form.
 __device__ inline void stage_row(const uint8_t* __restrict__ map, long long pitch, int W, int y, int cx0, int cw, int16_t* tile) {
     for (int i = threadIdx.x; i < cw + 2; i += THREADS) tile[i] = -1;
     __syncthreads();
     const int xa = cx0 - 1 > 0 ? cx0 - 1 : 0, xb = cx0 + cw + 1 < W ? cx0 + cw + 1 : W;               // the map's columns [xa, xb)
     const uint8_t* seg = map + (long long)y * pitch + xa;       // the segment's first byte
-    const int shift = (int)((uintptr_t)seg & 15u);
-    const int pieces = (xb - xa + 15) / 16 + 1;                 // aligned 16-byte pieces a segment of xb - xa bytes can touch
+    const int shift = wsi_map::piece_shift(seg);
     int16_t* dst = tile + (xa - (cx0 - 1));
-    for (int piece = threadIdx.x; piece < pieces; piece += THREADS) {
-        const int k0 = piece * 16 - shift;                      // the piece's first byte, relative to the segment
-        const int kb = k0 < 0 ? 0 : k0, ke = k0 + 16 < xb - xa ? k0 + 16 : xb - xa;
-        if (ke <= kb) continue;
-        if (ke - kb == 16) {
-            const uint4 v = *reinterpret_cast<const uint4*>(seg + k0);
+    for (int piece = threadIdx.x; piece < wsi_map::pieces_for(xb - xa); piece += THREADS) {
+        const wsi_map::Piece p = wsi_map::piece_of(shift, piece, xb - xa);
+        if (p.ke <= p.kb) continue;
+        if (p.ke - p.kb == 16) {
+            const uint4 v = *reinterpret_cast<const uint4*>(seg + p.k0);
             const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-            for (int k = 0; k < 16; ++k) dst[k0 + k] = (int16_t)((w[k >> 2] >> (8 * (k & 3))) & 255u);
+            for (int k = 0; k < 16; ++k) dst[p.k0 + k] = (int16_t)((w[k >> 2] >> (8 * (k & 3))) & 255u);
         } else {
-            for (int k = kb; k < ke; ++k) dst[k] = (int16_t)seg[k];
+            for (int k = p.kb; k < p.ke; ++k) dst[k] = (int16_t)seg[k];
         }
     }
     __syncthreads();
@@ -358,9 +293,8 @@ __global__ __launch_bounds__(THREADS) void region_wsum_kernel(const uint8_t* __r
     if (item < (long long)H * pieces) {
         const int y = (int)(item / pieces), piece = (int)(item % pieces);
         const uint8_t* seg = weight + (long long)y * pitch;
-        const int shift = (int)((uintptr_t)seg & 15u);
-        const int k0 = piece * 16 - shift;
-        const int kb = k0 < 0 ? 0 : k0, ke = k0 + 16 < W ? k0 + 16 : W;
+        const wsi_map::Piece p = wsi_map::piece_of(wsi_map::piece_shift(seg), piece, W);
+        const int k0 = p.k0, kb = p.kb, ke = p.ke;
         if (ke > kb) {
             uint8_t* mine = bytes[threadIdx.x];
             if (ke - kb == 16) *reinterpret_cast<uint4*>(mine) = *reinterpret_cast<const uint4*>(seg + k0);
@@ -425,15 +359,6 @@ Workspace carve(void* base, int H, long long n) {
             (uint32_t*)(p + l.flag), (uint32_t*)(p + l.rank), (uint32_t*)(p + l.id), (uint32_t*)(p + l.sums)};
 }
 
-Traced traced_bits(const uint8_t* traced256) {
-    Traced tr{};
-    for (int l = 0; l < 256; ++l) if (traced256[l]) tr.bits[l >> 5] |= 1u << (l & 31);
-    return tr;
-}
-
-unsigned blocks_for(long long n) { return (unsigned)((n + THREADS - 1) / THREADS); }
-int launched() { return hipGetLastError() == hipSuccess ? WSI_OK : WSI_EFAULT; }
-
 }  // namespace
 
 int wsi_region_count_dispatch(const uint8_t* map, int W, int H, long long pitch, const uint8_t* traced256, void* count_ws, unsigned* n_runs_out,
@@ -442,7 +367,7 @@ int wsi_region_count_dispatch(const uint8_t* map, int W, int H, long long pitch,
     uint32_t* sums = (uint32_t*)count_ws;
     hipLaunchKernelGGL(region_walk_kernel<false>, dim3((unsigned)chunks), dim3(THREADS), 0, st, map, pitch, W, H, (int)chunks_per_row(W), traced_bits(traced256),
                        sums, 0LL, (Run*)nullptr, (uint32_t*)nullptr, (uint32_t*)nullptr);
-    hipLaunchKernelGGL(region_scan_sums_kernel, dim3(1), dim3(THREADS), 0, st, sums, chunks, (uint32_t*)n_runs_out);
+    hipLaunchKernelGGL(wsi_map::scan_sums_kernel<uint32_t>, dim3(1), dim3(THREADS), 0, st, sums, chunks, (uint32_t*)n_runs_out);
     return launched();
 }
 
@@ -466,13 +391,11 @@ int wsi_region_rank_dispatch(void* ws, int H, long long n_runs, int connectivity
     const Workspace w = carve(ws, H, n_runs);
     const uint32_t n = (uint32_t)n_runs;
     const unsigned nb = blocks_for(n_runs);
-    const long long chunks = scan_chunks(n_runs);
     if (hipMemsetAsync(counts_out, 0, 2 * sizeof(unsigned), st) != hipSuccess) return WSI_EFAULT;
     hipLaunchKernelGGL(region_flatten_kernel, dim3(nb), dim3(THREADS), 0, st, (const Run*)w.runs, (const uint32_t*)w.row_first, n, H, connectivity == 8 ? 1 : 0,
                        w.parent, w.root, w.flag, (uint32_t*)counts_out + 1);
-    hipLaunchKernelGGL(region_chunk_sums_kernel, dim3((unsigned)chunks), dim3(THREADS), 0, st, (const uint32_t*)w.flag, n_runs, w.sums);
-    hipLaunchKernelGGL(region_scan_sums_kernel, dim3(1), dim3(THREADS), 0, st, w.sums, chunks, w.rank + n);
-    hipLaunchKernelGGL(region_scan_apply_kernel, dim3((unsigned)chunks), dim3(THREADS), 0, st, (const uint32_t*)w.flag, n_runs, (const uint32_t*)w.sums, w.rank);
+    const int rc = wsi_map::scan_exclusive<uint32_t>(w.flag, n_runs, w.rank, w.sums, st);
+    if (rc) return rc;
     hipLaunchKernelGGL(region_id_kernel, dim3(nb), dim3(THREADS), 0, st, (const uint32_t*)w.root, (const uint32_t*)w.rank, n, w.id, (uint32_t*)counts_out);
     return launched();
 }
@@ -486,7 +409,7 @@ int wsi_region_table_dispatch(const void* ws, int W, int H, long long n_runs, lo
     hipLaunchKernelGGL(region_table_kernel, dim3(blocks_for(n_runs)), dim3(THREADS), 0, st, (const Run*)w.runs, (const uint32_t*)w.up, (const uint32_t*)w.root,
                        (const uint32_t*)w.id, n, (uint32_t)n_regions, W, H, table);
     if (weight) {
-        const int pieces = (W + 15) / 16 + 1;                   // aligned 16-byte pieces a row of W bytes can touch
+        const int pieces = wsi_map::pieces_for(W);              // aligned 16-byte pieces a row of W bytes can touch
         hipLaunchKernelGGL(region_wsum_kernel, dim3(blocks_for((long long)H * pieces)), dim3(THREADS), 0, st, weight, weight_pitch, W, H, pieces,
                            (const Run*)w.runs, (const uint32_t*)w.row_first, (const uint32_t*)w.id, n, (uint32_t)n_regions, table);
     }

@@ -9,14 +9,12 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define WSI_HD __host__ __device__
-#else
-#define WSI_HD
-#endif
+#include "map_dev.h"
 
 namespace wsi_region {
+
+using wsi_map::Traced;                                         // bit l: label l is traced
+using wsi_map::traced;
 
 constexpr int LIMIT = 32768;                                   // 1 <= W, H <= LIMIT
 constexpr int CHUNK = 1024;                                    // pixels of one row one workgroup walks; items of one scan chunk
@@ -26,9 +24,6 @@ constexpr int RECORD_WORDS = 16;                               // int64 words of
 enum Field { AREA = 0, BOX_X0, BOX_Y0, BOX_X1, BOX_Y1, SX, SY, SXX, SXY, SYY, PERIM, WSUM, FIRST, CLS, BORDER, RESERVED };
 
 struct Run { int32_t y, x0, x1, cls; };                        // 16 bytes: the run record of the workspace
-struct Traced { uint32_t bits[8]; };                           // bit l: label l is traced
-
-WSI_HD inline bool traced(const Traced& t, int label) { return (t.bits[label >> 5] >> (label & 31)) & 1u; }
 
 // left, c, right: the bytes of a pixel and its row neighbours, -1 outside the row
 WSI_HD inline bool starts_run(int left, int c, const Traced& t) { return c >= 0 && traced(t, c) && left != c; }

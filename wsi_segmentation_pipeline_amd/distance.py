@@ -12,6 +12,7 @@ import torch
 
 from . import native
 from .engine import _ptr, _require_gpu
+from .maps import as_u8, check_map, check_out_i32, stage_marker, take_workspace
 
 EDT_NONE = 0x7FFFFFFF                    # csrc/edt_dev.h wsi_edt::EDT_NONE
 G_NONE = 0xFFFF                          # wsi_edt::G_NONE
@@ -24,45 +25,22 @@ def g_pitch(w):
     return (int(w) + 127) // 128 * 128
 
 
-def _map(features):
-    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.dtype != torch.uint8:
-        raise ValueError('the map must be a 2-D uint8 tensor')
-    h, w = int(features.shape[0]), int(features.shape[1])
-    if not (1 <= w <= LIMIT and 1 <= h <= LIMIT):
-        raise ValueError('a map of %d x %d pixels is outside 1 .. %d each way' % (w, h, LIMIT))
-    if (w > 1 and features.stride(1) != 1) or (h > 1 and features.stride(0) < w):
-        raise ValueError('the map must have unit column stride and a row stride >= its width')
-    return h, w
-
-
 def distance_sq(features, invert=False, out=None, workspace=None, stages=None):
     """Squared Euclidean distance to the nearest feature of a u8 (H, W) CUDA map (unit column stride, any row stride and alignment)
     -> int32 (H, W); EDT_NONE everywhere where the map has no feature.  out: an int32 (H, W) tensor to fill (unit column stride);
     workspace: a u8 tensor of at least wsi_edt_workspace_bytes(W, H) to reuse; stages: a dict that receives, per pass ('columns',
     'rows'), the [begin, end] torch.cuda.Event pair recorded round its entry (tools/edt_times.py)."""
     lib = native.load()
-    h, w = _map(features)
+    h, w, pitch = check_map(features, 'the map', LIMIT)
     _require_gpu(features, 'the map')
     dev = features.device
     if out is None:
         out = torch.empty((h, w), dtype=torch.int32, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (h, w) or out.device != dev
-          or (w > 1 and out.stride(1) != 1) or (h > 1 and out.stride(0) < w)):
-        raise ValueError('out must be an int32 (%d, %d) tensor on the map\'s device with unit column stride' % (h, w))
-    need = lib.wsi_edt_workspace_bytes(w, h)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif workspace.dtype != torch.uint8 or workspace.numel() < need or workspace.device != dev or not workspace.is_contiguous():
-        raise ValueError('the workspace must be a contiguous u8 tensor of at least %d bytes on the map\'s device' % need)
-    pitch = features.stride(0) if h > 1 else w
+    else:
+        check_out_i32(out, h, w, dev)
+    workspace = take_workspace(workspace, lib.wsi_edt_workspace_bytes(w, h), dev)
     out_pitch = 4 * (out.stride(0) if h > 1 else w)
-
-    def mark(name):
-        if stages is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            stages.setdefault(name, []).append(ev)
-
+    mark = stage_marker(stages)
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
         mark('columns')
@@ -81,9 +59,8 @@ def distance(features, invert=False):
 
 
 def _mask(mask):
-    if isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
-        mask = mask.to(torch.uint8)
-    _map(mask)
+    mask = as_u8(mask, 'the map')
+    check_map(mask, 'the map', LIMIT)
     return mask
 
 

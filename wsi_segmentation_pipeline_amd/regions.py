@@ -16,6 +16,7 @@ import torch
 from . import native
 from .contours import traced_table
 from .engine import _ptr, _require_gpu
+from .maps import as_u8, check_map, check_out_i32, stage_marker, step2, take_workspace
 
 LIMIT = 32768                            # csrc/regions_dev.h wsi_region::LIMIT
 FIELDS = ('area', 'x0', 'y0', 'x1', 'y1', 'sx', 'sy', 'sxx', 'sxy', 'syy', 'perim', 'wsum', 'first', 'cls', 'border', 'reserved')
@@ -70,7 +71,7 @@ class Regions:
         """one dict per region: id, class, area_px (map pixels), area_um2 (None without mpp; a map pixel is step x step level-0 pixels
         of mpp microns), the box and the centroid in level-0 coordinates (map pixel x covers origin + x step .. origin + (x + 1) step,
         its centre is origin + (x + 0.5) step), perim (pixel sides), major, minor (map pixels), mean_weight (wsum / area)"""
-        sx, sy = (int(step), int(step)) if np.isscalar(step) else (int(step[0]), int(step[1]))
+        sx, sy = step2(step)
         ox, oy = int(origin[0]), int(origin[1])
         t, c = self.host(), self.centroid()
         major, minor, _ = self.axes()
@@ -105,18 +106,6 @@ def write_csv(path, r, step=1, origin=(0, 0), mpp=None, names=None):
     return path
 
 
-def _check_map(m, what):
-    if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.dtype != torch.uint8:
-        raise ValueError('%s must be a 2-D uint8 tensor' % what)
-    h, w = int(m.shape[0]), int(m.shape[1])
-    if not (1 <= w <= LIMIT and 1 <= h <= LIMIT):
-        raise ValueError('%s of %d x %d pixels is outside 1 .. %d each way' % (what, w, h, LIMIT))
-    if (w > 1 and m.stride(1) != 1) or (h > 1 and m.stride(0) < w):
-        raise ValueError('%s must have unit column stride and a row stride >= its width' % what)
-    _require_gpu(m, what)
-    return h, w, (m.stride(0) if h > 1 else w)
-
-
 def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, workspace=None, stages=None):
     """Label a u8 (H, W) CUDA class map (unit column stride, any row stride and alignment) -> `Regions`.
     classes: None takes labels 1..255, an iterable of ints those labels (0 allowed).  connectivity: 4 or 8.  labels: also paint the
@@ -128,24 +117,18 @@ def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, w
     if connectivity not in (4, 8):
         raise ValueError('connectivity %r is neither 4 nor 8' % (connectivity,))
     table = np.ascontiguousarray(traced_table(classes), np.uint8)
-    h, w, pitch = _check_map(m, 'the class map')
+    h, w, pitch = check_map(m, 'the class map', LIMIT)
+    _require_gpu(m, 'the class map')
     if weight is not None:
         if tuple(weight.shape) != (h, w):
             raise ValueError('the weight map must have the shape of the class map')
-        _, _, wpitch = _check_map(weight, 'the weight map')
+        wpitch = check_map(weight, 'the weight map', LIMIT)[2]
+        _require_gpu(weight, 'the weight map')
     dev = m.device
     if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != torch.int32 or tuple(out.shape) != (h, w) or out.device != dev:
-            raise ValueError('out must be an int32 (H, W) tensor on the map\'s device')
-        if (w > 1 and out.stride(1) != 1) or (h > 1 and out.stride(0) < w):
-            raise ValueError('out must have unit column stride and a row stride >= its width')
+        check_out_i32(out, h, w, dev)
     tp = table.ctypes.data_as(native.C.c_void_p)
-
-    def mark(name):
-        if stages is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            stages.setdefault(name, []).append(ev)
+    mark = stage_marker(stages)
 
     with torch.cuda.device(dev):
         st = torch.cuda.current_stream(dev).cuda_stream
@@ -160,11 +143,7 @@ def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, w
             if labels:
                 lab = torch.zeros((h, w), dtype=torch.int32, device=dev) if out is None else out.zero_()
             return Regions(torch.zeros((0, 16), dtype=torch.int64, device=dev), lab, (w, h))
-        need = lib.wsi_region_workspace_bytes(w, h, n_runs)
-        if workspace is None:
-            workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-        elif workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.device != dev:
-            raise ValueError('the workspace must be a contiguous uint8 tensor of at least %d bytes' % need)
+        workspace = take_workspace(workspace, lib.wsi_region_workspace_bytes(w, h, n_runs), dev)
         ws_bytes = int(workspace.numel())
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
         mark('runs')
@@ -195,17 +174,9 @@ def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, w
 
 
 # ------------------------------------------------------------------------------------------------------------- what follows from it
-def _as_u8(m, what):
-    if isinstance(m, torch.Tensor) and m.dtype == torch.bool:
-        m = m.to(torch.uint8)
-    if not isinstance(m, torch.Tensor) or m.dim() != 2 or m.dtype != torch.uint8:
-        raise ValueError('%s must be a 2-D uint8 tensor' % what)
-    return m
-
-
 def remove_small(m, min_area, connectivity=8, classes=None, fill=0):
     """area opening of a class map: the regions of fewer than min_area pixels become `fill`; everything else is kept"""
-    m = _as_u8(m, 'the class map')
+    m = as_u8(m, 'the class map')
     r = label(m, classes, connectivity, labels=True)
     if r.n == 0:
         return m.clone()
@@ -251,7 +222,7 @@ def lesion_scores(pred, gt, classes=None, connectivity=8, iou=0.5, min_area=0):
     if not 0 <= fr <= 1:
         raise ValueError('iou %r is outside [0, 1]' % (iou,))
     num, den = fr.numerator, fr.denominator
-    pred, gt = _as_u8(pred, 'the prediction'), _as_u8(gt, 'the ground truth')
+    pred, gt = as_u8(pred, 'the prediction'), as_u8(gt, 'the ground truth')
     rp, rg = label(foreground(pred, classes), None, connectivity), label(foreground(gt, classes), None, connectivity)
     ap, ag = rp.host()[:, _F['area']], rg.host()[:, _F['area']]
     keep_p, keep_g = ap >= min_area, ag >= min_area
@@ -279,7 +250,7 @@ def slide_positive(heat_u8, thresh=0.99, open_k=50, min_fraction=0.0):
 
 def _slide_positive(heat_u8, thresh, open_k, min_fraction):
     from . import postprocess as PP
-    heat = _as_u8(heat_u8, 'the heat map').contiguous()
+    heat = as_u8(heat_u8, 'the heat map').contiguous()
     opened = PP.morph_rect((heat >= heat_threshold(thresh)).to(torch.uint8), open_k, 'open')
     r = label(opened, None, 8, labels=False, weight=heat)
     fraction = int(torch.count_nonzero(opened)) / opened.numel()
