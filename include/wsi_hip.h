@@ -1046,6 +1046,56 @@ int wsi_region_table(const void* workspace, size_t workspace_bytes, int W, int H
 int wsi_region_paint(const void* workspace, size_t workspace_bytes, int W, int H, long long n_runs, int32_t* labels, long long labels_pitch_bytes,
                      void* stream);
 
+/* ---- Region hulls: the convex hull and the Feret diameters of every region of a region table ----
+ * An own rule (parity unpinned; spec: tests/region_hulls_oracle.py, cross-checked against SciPy's ConvexHull and the brute-force
+ * definitions on the CPU; the shared arithmetic: csrc/region_hulls_dev.h).  (The entries are wsi_regionhull_*: the prefix wsi_region_
+ * is the closed set of the eight region-table entries above.)  A pixel (x, y) is the unit square (x, y) .. (x + 1, y + 1) in map corner
+ * coordinates; a region's hull is the convex hull of its pixels' squares.  Its vertices are strictly convex (none collinear), start at
+ * the smallest (y, x) and go clockwise as seen with y pointing down; there are at least four.
+ * A hull's record is sixteen int64 (128 bytes): hull_first, hull_n (its vertices are vertices[hull_first .. hull_first + hull_n));
+ * hull_area2 (twice its area); feret_sq, feret_a, feret_b (the largest dx^2 + dy^2 over vertex pairs a < b, ties to the smallest a, then
+ * the smallest b; indices within the hull); width_num, width_den, width_edge, width_vertex (the least c^2 / |e|^2 over the edges e, c the
+ * largest |cross(e, v - v_i)| over the vertices, unreduced, compared exactly in 128 bits, ties to the smallest edge; the farthest vertex
+ * is the smallest index among the maxima); orth_num (largest minus smallest cross(v_b - v_a, v - v_a) of the Feret pair); five zeros.
+ * The entries run in this order after wsi_region_table, on a workspace of their own of wsi_regionhull_workspace_bytes(W, H, n_runs,
+ * n_regions) device bytes, 16-byte aligned, with the same W, H, n_runs, n_regions; the region workspace and the region table are only
+ * read.  rows = n_runs + n_regions bounds the corner rows of all regions (a region's box of h pixel rows holds at least h of its runs
+ * and has h + 1 corner rows).  The workspace holds, each rounded up to 256 bytes and in this order:
+ *     height     n_regions + 1 u32: corner rows of the region's box, y1 - y0 + 1
+ *     row_off    n_regions + 1 u32: corner rows before the region; their total at n_regions
+ *     lo         rows i32: the leftmost corner of the corner row (row j of region k at row_off[k] + j)
+ *     hi         rows i32: the rightmost corner
+ *     st_r       rows u32: the right chain of region k from row_off[k]: the rows j of its points, top to bottom
+ *     st_l       rows u32: the left chain likewise
+ *     seg_r      rows u32: first-level scratch (survivors of the right chain of the segment that starts at this row)
+ *     seg_l      rows u32: the same of the left chain
+ *     n_r        n_regions u32: points of the right chain
+ *     n_l        n_regions u32: points of the left chain
+ *     count      n_regions + 1 u32: vertices of the hull, n_r + n_l
+ *     first      n_regions + 1 u32: vertices before the hull; their total V at n_regions
+ *     sums       (n_regions + 1) / 1024 (rounded up) + 1 u32 of scan scratch
+ *     picks      2 rows records of 32 bytes, one per vertex {u64 feret_sq; u32 feret_b, far_cross, edge_sq, far; i64 shoelace}
+ *   Vertex i of a hull is the left chain's first point for i = 0, point i - 1 of the right chain for 1 <= i <= n_r, and point
+ *   n_r + n_l - i of the left chain after that.
+ *   wsi_regionhull_rows: region workspace (runs, id), region table (y0, y1) -> height, row_off, lo, hi.
+ *   wsi_regionhull_chains: row_off, lo, hi -> st_*, seg_*, n_r, n_l, count, first; counts_out (device) = {V, status}.  status is 0 unless
+ *     a chain outgrew the 4096 points a workgroup stacks (a chain in a 32768^2 box has fewer than 2865): the caller treats anything
+ *     else as an error.  The caller reads V and sizes vertices by it.
+ *   wsi_regionhull_emit: first, row_off, n_r, n_l, st_r, st_l, lo, hi, region table (y0) -> vertices[V][2] int32 (x, y).
+ *   wsi_regionhull_measure: count, first, vertices -> picks, hull_table[n_regions][16] int64.
+ * -22 before any device work: a NULL pointer, W or H outside 1 .. 32768, n_runs outside 1 .. W H, n_regions outside 1 .. n_runs,
+ *   n_vertices outside 4 n_regions .. 2 rows, a misaligned pointer (4 bytes: the counts; 8: the tables, vertices; 16: the workspaces), a
+ *   workspace smaller than its *_workspace_bytes.  wsi_regionhull_workspace_bytes returns 0 for sizes outside these limits. */
+size_t wsi_regionhull_workspace_bytes(int W, int H, long long n_runs, long long n_regions);
+int wsi_regionhull_rows(const void* region_workspace, size_t region_workspace_bytes, const long long* region_table, int W, int H, long long n_runs,
+                        long long n_regions, void* hull_workspace, size_t hull_workspace_bytes, void* stream);
+int wsi_regionhull_chains(void* hull_workspace, size_t hull_workspace_bytes, int W, int H, long long n_runs, long long n_regions,
+                          unsigned int* counts_out, void* stream);
+int wsi_regionhull_emit(const void* hull_workspace, size_t hull_workspace_bytes, const long long* region_table, int W, int H, long long n_runs,
+                        long long n_regions, long long n_vertices, int32_t* vertices, void* stream);
+int wsi_regionhull_measure(void* hull_workspace, size_t hull_workspace_bytes, int W, int H, long long n_runs, long long n_regions,
+                           const int32_t* vertices, long long n_vertices, long long* hull_table, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -132,7 +132,7 @@ def _dense_batches(model, it, scan, dev, forward):
         yield np.stack((batch_x.numpy(), batch_y.numpy()), 1), forward(batch_image.to(dev))
 
 
-def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False, save_xml=False, region_table=False):
+def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True, save_tiff=False, save_xml=False, region_table=False, bed_size=False):
     """Tumour-bed heat maps for every slide in ``dataset`` (a utils.dataset.Dataset_wsis).
     Writes <val_save_pth>/<ep>/<key>_<stride>_heatmap.png and _overlay.png (rank 0; with save_tiff also _heatmap.tif, the heat map as
     a one-component JPEG-tiled pyramid encoded on the device, wsi_segmentation_pipeline_amd.tiffwrite; with save_xml also _tb.xml, the
@@ -143,7 +143,11 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
     region_table: the result gains 'slide_positive' - does the slide hold tumour at all, the reference's rule
     (paper_tools/check_for_false_positives.py:61-69: heat >= 0.99 * 255 -> open 50 x 50 -> any pixel left) on the device,
     wsi_segmentation_pipeline_amd.regions.slide_positive - and 'regions', the regions of that opened mask with the heat map as weight;
-    with save, rank 0 also writes <key>_<stride>_heatmap_regions.csv in level-0 coordinates.  Unset, results and files are what they were."""
+    with save, rank 0 also writes <key>_<stride>_heatmap_regions.csv in level-0 coordinates.  Unset, results and files are what they were.
+    bed_size: the result gains 'bed_size', the two dimensions d1 x d2 of the tumour bed of the heat map (save_xml's bed) in pixels of the
+    map and, where the slide states an mpp, millimetres (wsi_segmentation_pipeline_amd.regions.bed_size: the hull's largest diameter and
+    the extent at right angles to it; None without a bed), 'bed_size_gt' likewise where the entry has `tb_gt`, and one printed line per
+    slide; the regions CSV then also holds the hull columns.  Unset, results, printed lines and files are what they were."""
     if mode not in ('cls', 'seg'):
         raise ValueError("mode must be 'cls' or 'seg'")
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -235,7 +239,12 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
                             'stitch_exact': stitch_exact}
             if region_table:
                 from wsi_segmentation_pipeline_amd import regions as RG
-                results[key]['slide_positive'], results[key]['regions'] = RG._slide_positive(r['heatmap'].contiguous(), 0.99, 50, 0.0)
+                results[key]['slide_positive'], results[key]['regions'] = RG._slide_positive(r['heatmap'].contiguous(), 0.99, 50, 0.0,
+                                                                                             **({'hulls': True} if bed_size else {}))
+            if bed_size:
+                from wsi_segmentation_pipeline_amd import postprocess as PP
+                results[key].update(_bed_size(key, PP.tumor_bed_from_heatmap(r['heatmap'].contiguous(), 0.9, 30, 20).tb_pred, entry.get('tb_gt'), scan,
+                                              ref_level, map_hw, dev))
             if save and rank == 0:
                 _save_png(heat, '{}/{}_{}_heatmap.png'.format(out_dir, key, args.tile_stride_w))
                 thumb = np.asarray(scan.read_region((0, 0), ref_level, scan.level_dimensions[ref_level]).convert('RGB'))
@@ -252,11 +261,34 @@ def predict_tumorbed(model, dataset, ep, mode='seg', rank=0, world=1, save=True,
                 if region_table:
                     from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT
                     RG.write_csv('{}/{}_{}_heatmap_regions.csv'.format(out_dir, key, args.tile_stride_w), results[key]['regions'],
-                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), {1: 'Invasive'})
+                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), {1: 'Invasive'}, **({'hulls': True} if bed_size else {}))
             dataset.wsis[key] = None                       # the reference frees each slide after use (:282)
     if was_training:
         model.train()
     return results
+
+
+def _bed_size(key, bed, tb_gt, scan, ref_level, map_hw, dev, scores=None):
+    """the bed's two dimensions (regions.bed_size) of the predicted bed and, where there is one, of the annotated bed; `scores` gains
+    the differences predicted - annotated.  One printed line per slide.  -> the entries to add to the slide's result"""
+    from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT, regions as RG
+    step, mpp = AN.level_step(scan, ref_level), CT.stated_mpp(scan)
+    out = {'bed_size': RG.bed_size((bed > 0).to(torch.uint8).contiguous(), step, mpp)}
+    line = '{}, tb size: '.format(key) + ('none' if out['bed_size'] is None else '{:.1f} x {:.1f} px'.format(out['bed_size']['d1'], out['bed_size']['d2']))
+    if out['bed_size'] is not None and mpp is not None:
+        line += ' ({:.2f} x {:.2f} mm)'.format(out['bed_size']['d1_mm'], out['bed_size']['d2_mm'])
+    if tb_gt is not None:
+        out['bed_size_gt'] = RG.bed_size((_map_u8(tb_gt, map_hw, dev) > 0).to(torch.uint8).contiguous(), step, mpp)
+        a, b = out['bed_size'], out['bed_size_gt']
+        if scores is not None and a is not None and b is not None:
+            for d in ('d1', 'd2'):
+                scores['tb_%s_err' % d] = a[d] - b[d]
+                if mpp is not None:
+                    scores['tb_%s_err_mm' % d] = a[d + '_mm'] - b[d + '_mm']
+        if b is not None:
+            line += ', annotated {:.1f} x {:.1f} px'.format(b['d1'], b['d2'])
+    print(line)
+    return out
 
 
 def _map_u8(arr, hw, dev):
@@ -280,7 +312,7 @@ def _map_u8(arr, hw, dev):
     return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8))).to(dev)
 
 
-def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False, boundary_scores=False, region_table=False):
+def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False, boundary_scores=False, region_table=False, bed_size=False):
     """Dense per-pixel map prediction with the tumour-bed post-process (reference utils/eval.py:22-152).
     `model(batch_image)` must return (B, C, ph, pw) logits on the GPU (the reference drives an smp U-Net here; any GPU
     module works, e.g. wsi_segmentation_pipeline_amd.unet.UNetSeg).  Everything between the tile list and the colour
@@ -307,6 +339,12 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False,
     microns where the slide states an mpp; where the entry has `gt`, `scores` gains lesions as objects for classes (2, 3), the
     reference's own tumour rule p >= 2: 'lesions_pred', 'lesions_gt', 'lesion_precision', 'lesion_recall', 'lesion_f1'
     (regions.lesion_scores, IoU 0.5).  Unset, results, printed lines and files are what they were.
+    bed_size: the result gains 'bed_size', the two dimensions d1 x d2 a pathologist reports for the tumour bed, of `tumor_bed`
+    (wsi_segmentation_pipeline_amd.regions.bed_size: the hull's largest diameter and the extent at right angles to it, in pixels of the
+    scoring level, d1_mm, d2_mm, area_mm2 where the slide states an mpp; None without a bed); where the entry has `tb_gt` also
+    'bed_size_gt' and, in `scores`, 'tb_d1_err', 'tb_d2_err' (predicted minus annotated, pixels) with '_mm' variants where the slide
+    states an mpp; one printed line per slide.  With region_table and save the regions CSV then also holds the hull columns.  Unset,
+    results, printed lines and files are what they were.
     Returns {key: {'pred', 'pred_level2', 'classes' (scan level), 'classes_level2', 'tumor_bed', 'outline', 'scores'}}."""
     from wsi_segmentation_pipeline_amd import postprocess as PP
     out_dir = '{}/{}'.format(args.val_save_pth, ep)
@@ -366,10 +404,13 @@ def predict_wsis(model, dataset, ep, save=True, save_tiff=False, save_xml=False,
                             'tumor_bed': tb.tb_pred, 'outline': tb.outline, 'scores': scores}
             if region_table:
                 from wsi_segmentation_pipeline_amd import annotations as AN, contours as CT, regions as RG
-                results[key]['regions'] = RG.label((p * (mask_dev > 0)).to(torch.uint8).contiguous(), (1, 2, 3), 8, labels=False)
+                results[key]['regions'] = RG.label((p * (mask_dev > 0)).to(torch.uint8).contiguous(), (1, 2, 3), 8, labels=False,
+                                                   **({'hulls': True} if bed_size else {}))
                 if save:
                     RG.write_csv('{}/{}_{}_regions.csv'.format(out_dir, key, args.tile_stride_w), results[key]['regions'],
-                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), CT.DEFAULT_NAMES)
+                                 AN.level_step(scan, ref_level), (0, 0), CT.stated_mpp(scan), CT.DEFAULT_NAMES, **({'hulls': True} if bed_size else {}))
+            if bed_size:
+                results[key].update(_bed_size(key, tb.tb_pred, entry.get('tb_gt'), scan, ref_level, map_hw, dev, scores))
             if save:                                                           # :138-145
                 cls_thr = E.softmax_threshold_argmax(pred2, args.class_probs, want_probs=False)[0]      # pred_to_mask
                 rgb = torch.zeros(map_hw + (3,), dtype=torch.uint8, device=dev)

@@ -4,6 +4,7 @@
 #include "internal.h"
 #include "edt_dev.h"
 #include "regions_dev.h"
+#include "region_hulls_dev.h"
 #include "../../include/wsi_hip.h"
 
 ConvRoutes g_routes;                                  // the one instance of the route switches (common.h), at their defaults
@@ -610,6 +611,40 @@ int wsi_region_paint(const void* workspace, size_t workspace_bytes, int W, int H
     if (!region_ws_ok(workspace, workspace_bytes, W, H, n_runs) || !labels || ((uintptr_t)labels & 3)) return WSI_EINVAL;
     if (labels_pitch_bytes < 4LL * W || (labels_pitch_bytes & 3)) return WSI_EINVAL;
     return wsi_region_paint_dispatch(workspace, W, H, n_runs, labels, labels_pitch_bytes, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------------------------ region table -> convex hull and diameters per region
+static bool hull_sizes_ok(int W, int H, long long n_runs, long long n_regions) { return region_runs_ok(W, H, n_runs) && n_regions >= 1 && n_regions <= n_runs; }
+static bool hull_ws_ok(const void* ws, size_t ws_bytes, int W, int H, long long n_runs, long long n_regions) {
+    return ws && !((uintptr_t)ws & 15) && hull_sizes_ok(W, H, n_runs, n_regions) && ws_bytes >= wsi_hull::layout(n_runs, n_regions).bytes;
+}
+static bool hull_vertices_ok(const void* vertices, long long n_vertices, long long n_runs, long long n_regions) {
+    return vertices && !((uintptr_t)vertices & 7) && n_vertices >= 4 * n_regions && n_vertices <= 2 * wsi_hull::max_rows(n_runs, n_regions);
+}
+size_t wsi_regionhull_workspace_bytes(int W, int H, long long n_runs, long long n_regions) {
+    return hull_sizes_ok(W, H, n_runs, n_regions) ? wsi_hull::layout(n_runs, n_regions).bytes : 0;
+}
+int wsi_regionhull_rows(const void* region_ws, size_t region_ws_bytes, const long long* region_table, int W, int H, long long n_runs, long long n_regions,
+                         void* hull_ws, size_t hull_ws_bytes, void* stream) {
+    if (!region_ws_ok(region_ws, region_ws_bytes, W, H, n_runs) || !hull_ws_ok(hull_ws, hull_ws_bytes, W, H, n_runs, n_regions)) return WSI_EINVAL;
+    if (!region_table || ((uintptr_t)region_table & 7)) return WSI_EINVAL;
+    return wsi_regionhull_rows_dispatch(region_ws, region_table, H, n_runs, n_regions, hull_ws, (hipStream_t)stream);
+}
+int wsi_regionhull_chains(void* hull_ws, size_t hull_ws_bytes, int W, int H, long long n_runs, long long n_regions, unsigned int* counts_out, void* stream) {
+    if (!hull_ws_ok(hull_ws, hull_ws_bytes, W, H, n_runs, n_regions) || !counts_out || ((uintptr_t)counts_out & 3)) return WSI_EINVAL;
+    return wsi_regionhull_chains_dispatch(hull_ws, n_runs, n_regions, counts_out, (hipStream_t)stream);
+}
+int wsi_regionhull_emit(const void* hull_ws, size_t hull_ws_bytes, const long long* region_table, int W, int H, long long n_runs, long long n_regions,
+                         long long n_vertices, int32_t* vertices, void* stream) {
+    if (!hull_ws_ok(hull_ws, hull_ws_bytes, W, H, n_runs, n_regions) || !region_table || ((uintptr_t)region_table & 7)) return WSI_EINVAL;
+    if (!hull_vertices_ok(vertices, n_vertices, n_runs, n_regions)) return WSI_EINVAL;
+    return wsi_regionhull_emit_dispatch(hull_ws, region_table, n_runs, n_regions, n_vertices, vertices, (hipStream_t)stream);
+}
+int wsi_regionhull_measure(void* hull_ws, size_t hull_ws_bytes, int W, int H, long long n_runs, long long n_regions, const int32_t* vertices,
+                            long long n_vertices, long long* hull_table, void* stream) {
+    if (!hull_ws_ok(hull_ws, hull_ws_bytes, W, H, n_runs, n_regions) || !hull_vertices_ok(vertices, n_vertices, n_runs, n_regions)) return WSI_EINVAL;
+    if (!hull_table || ((uintptr_t)hull_table & 7)) return WSI_EINVAL;
+    return wsi_regionhull_measure_dispatch(hull_ws, n_runs, n_regions, vertices, n_vertices, hull_table, (hipStream_t)stream);
 }
 
 }  // extern "C"

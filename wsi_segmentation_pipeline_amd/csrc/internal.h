@@ -126,6 +126,13 @@ int wsi_region_rank_dispatch(void* ws, int H, long long n_runs, int connectivity
 int wsi_region_table_dispatch(const void* ws, int W, int H, long long n_runs, long long n_regions, const uint8_t* weight, long long weight_pitch,
                               long long* table, hipStream_t st);
 int wsi_region_paint_dispatch(const void* ws, int W, int H, long long n_runs, int32_t* labels, long long pitch, hipStream_t st);
+// region_hulls.hip
+int wsi_regionhull_rows_dispatch(const void* region_ws, const long long* table, int H, long long n_runs, long long n_regions, void* ws, hipStream_t st);
+int wsi_regionhull_chains_dispatch(void* ws, long long n_runs, long long n_regions, unsigned* counts_out, hipStream_t st);
+int wsi_regionhull_emit_dispatch(const void* ws, const long long* table, long long n_runs, long long n_regions, long long n_vertices, int32_t* vertices,
+                                  hipStream_t st);
+int wsi_regionhull_measure_dispatch(void* ws, long long n_runs, long long n_regions, const int32_t* vertices, long long n_vertices, long long* out,
+                                     hipStream_t st);
 
 // ------------------------------------------------------------------------------------ host layer (capi.hip, trunk.hip, seg_host.h)
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

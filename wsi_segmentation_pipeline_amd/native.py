@@ -265,6 +265,11 @@ SIGNATURES = {
     'wsi_region_rank': (_i, [_vp, _sz, _i, _i, _ll, _i, _vp, _vp]),
     'wsi_region_table': (_i, [_vp, _sz, _i, _i, _ll, _ll, _vp, _ll, _vp, _vp]),
     'wsi_region_paint': (_i, [_vp, _sz, _i, _i, _ll, _vp, _ll, _vp]),
+    'wsi_regionhull_workspace_bytes': (_sz, [_i, _i, _ll, _ll]),
+    'wsi_regionhull_rows': (_i, [_vp, _sz, _vp, _i, _i, _ll, _ll, _vp, _sz, _vp]),
+    'wsi_regionhull_chains': (_i, [_vp, _sz, _i, _i, _ll, _ll, _vp, _vp]),
+    'wsi_regionhull_emit': (_i, [_vp, _sz, _vp, _i, _i, _ll, _ll, _ll, _vp, _vp]),
+    'wsi_regionhull_measure': (_i, [_vp, _sz, _i, _i, _ll, _ll, _vp, _ll, _vp, _vp]),
 }
 # the four entries of every (segmentation model, encoder block type) pair: one signature set, generated per prefix
 _enc5 = C.POINTER(C.c_void_p * 5)

@@ -27,9 +27,10 @@ STAGES = ('count', 'runs', 'link', 'rank', 'table', 'paint')
 class Regions:
     """n regions; table (n, 16) int64 on the map's device, one row per region in FIELDS order; labels (H, W) int32 or None."""
 
-    def __init__(self, table, labels, size, n_runs=0):
+    def __init__(self, table, labels, size, n_runs=0, hulls=None):
         self.table, self.labels, self.size, self.n_runs = table, labels, (int(size[0]), int(size[1])), int(n_runs)
         self.n = int(table.shape[0])
+        self.hulls = hulls                                      # a `Hulls` where label(..., hulls=True) made them
         self._host_table = None
 
     def __len__(self):
@@ -67,10 +68,12 @@ class Regions:
         half, diff = (mxx + myy) / 2, np.sqrt(((mxx - myy) / 2) ** 2 + mxy * mxy)
         return 4 * np.sqrt(np.maximum(half + diff, 0)), 4 * np.sqrt(np.maximum(half - diff, 0)), 0.5 * np.arctan2(2 * mxy, mxx - myy)
 
-    def rows(self, step=1, origin=(0, 0), mpp=None):
+    def rows(self, step=1, origin=(0, 0), mpp=None, hulls=False):
         """one dict per region: id, class, area_px (map pixels), area_um2 (None without mpp; a map pixel is step x step level-0 pixels
         of mpp microns), the box and the centroid in level-0 coordinates (map pixel x covers origin + x step .. origin + (x + 1) step,
-        its centre is origin + (x + 0.5) step), perim (pixel sides), major, minor (map pixels), mean_weight (wsum / area)"""
+        its centre is origin + (x + 0.5) step), perim (pixel sides), major, minor (map pixels), mean_weight (wsum / area).
+        hulls: also HULL_COLUMNS from self.hulls - feret_max, feret_min, feret_orth (map pixels), their *_um (length x step x mpp; None
+        without mpp or where the step differs between x and y), solidity, hull_area_px"""
         sx, sy = step2(step)
         ox, oy = int(origin[0]), int(origin[1])
         t, c = self.host(), self.centroid()
@@ -87,32 +90,161 @@ class Regions:
                 'perim': int(t[k, _F['perim']]), 'major': float(major[k]), 'minor': float(minor[k]),
                 'mean_weight': int(t[k, _F['wsum']]) / area,
             })
+        if hulls:
+            if self.hulls is None:
+                raise ValueError('these regions were labelled without hulls=True')
+            h = self.hulls
+            um = None if mpp is None or sx != sy else sx * float(mpp)
+            fmax, fmin, forth, harea = h.feret_max(), h.feret_min(), h.feret_orth(), h.hull_area()
+            solidity = h.solidity(t[:, _F['area']])
+            for k, row in enumerate(out):
+                row.update(feret_max=float(fmax[k]), feret_min=float(fmin[k]), feret_orth=float(forth[k]),
+                           feret_max_um=None if um is None else float(fmax[k]) * um, feret_min_um=None if um is None else float(fmin[k]) * um,
+                           feret_orth_um=None if um is None else float(forth[k]) * um, solidity=float(solidity[k]), hull_area_px=float(harea[k]))
         return out
 
 
 CSV_COLUMNS = ('id', 'class', 'name', 'area_px', 'area_um2', 'x0', 'y0', 'x1', 'y1', 'cx', 'cy', 'perim', 'major', 'minor', 'mean_weight')
 
 
-def write_csv(path, r, step=1, origin=(0, 0), mpp=None, names=None):
+HULL_COLUMNS = ('feret_max', 'feret_min', 'feret_orth', 'feret_max_um', 'feret_min_um', 'feret_orth_um', 'solidity', 'hull_area_px')
+
+
+def write_csv(path, r, step=1, origin=(0, 0), mpp=None, names=None, hulls=False):
     """the rows of `r` as CSV, one line per region under CSV_COLUMNS; names: {class: name} (a class without one gets ''); area_um2 is
-    empty where mpp is None"""
+    empty where mpp is None.  hulls: HULL_COLUMNS follow CSV_COLUMNS."""
     names = names or {}
+    columns = CSV_COLUMNS + HULL_COLUMNS if hulls else CSV_COLUMNS
     with open(path, 'w', newline='', encoding='utf-8') as f:
         w = csv.writer(f)
-        w.writerow(CSV_COLUMNS)
-        for row in r.rows(step, origin, mpp):
+        w.writerow(columns)
+        for row in (r.rows(step, origin, mpp, hulls=True) if hulls else r.rows(step, origin, mpp)):
             row['name'] = names.get(row['class'], '')
-            w.writerow(['' if row[c] is None else ('%.4f' % row[c] if isinstance(row[c], float) else row[c]) for c in CSV_COLUMNS])
+            w.writerow(['' if row[c] is None else ('%.4f' % row[c] if isinstance(row[c], float) else row[c]) for c in columns])
     return path
 
 
-def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, workspace=None, stages=None):
+# ------------------------------------------------------------------------------------------------------------------------- hulls
+HULL_FIELDS = ('hull_first', 'hull_n', 'hull_area2', 'feret_sq', 'feret_a', 'feret_b', 'width_num', 'width_den', 'width_edge', 'width_vertex', 'orth_num')
+_H = {name: k for k, name in enumerate(HULL_FIELDS)}
+HULL_STAGES = ('hull_rows', 'hull_chains', 'hull_emit', 'hull_measure')
+
+
+class Hulls:
+    """The convex hull of every region (spec: tests/region_hulls_oracle.py; kernels: wsi_regionhull_*, csrc/region_hulls.hip).  table
+    (n, 16) int64 on the map's device, one row per region in HULL_FIELDS order and five zero words; vertices (V, 2) int32 (x, y) in map
+    corner coordinates - pixel (x, y) is the square (x, y) .. (x + 1, y + 1) - region k's at hull_first[k] : hull_first[k] + hull_n[k],
+    strictly convex, from the smallest (y, x), clockwise as seen with y pointing down."""
+
+    def __init__(self, table, vertices):
+        self.table, self.vertices = table, vertices
+        self.n = int(table.shape[0])
+        self._host_table = self._host_vertices = None
+
+    def __len__(self):
+        return self.n
+
+    hull_first = property(lambda self: self.table[:, _H['hull_first']])
+    hull_n = property(lambda self: self.table[:, _H['hull_n']])
+    hull_area2 = property(lambda self: self.table[:, _H['hull_area2']])
+    feret_sq = property(lambda self: self.table[:, _H['feret_sq']])
+    feret_pair = property(lambda self: self.table[:, _H['feret_a']:_H['feret_b'] + 1])
+    width = property(lambda self: self.table[:, _H['width_num']:_H['width_den'] + 1])
+    orth_num = property(lambda self: self.table[:, _H['orth_num']])
+
+    def host(self):
+        """the table as a host int64 array, copied once"""
+        if self._host_table is None:
+            self._host_table = np.asarray(torch.as_tensor(self.table).cpu().numpy(), np.int64).reshape(-1, 16)
+        return self._host_table
+
+    def host_vertices(self):
+        if self._host_vertices is None:
+            self._host_vertices = np.asarray(torch.as_tensor(self.vertices).cpu().numpy(), np.int32).reshape(-1, 2)
+        return self._host_vertices
+
+    def polygons(self, step=1, origin=(0, 0)):
+        """[(hull_n, 2) int64 arrays] in level-0 coordinates: corner (cx, cy) becomes origin + (cx sx, cy sy), the true corner of the
+        pixel's footprint, as `Regions.rows` places the box (contours.trace shifts its vertices by half a step; these are not shifted)"""
+        sx, sy = step2(step)
+        t, v = self.host(), self.host_vertices().astype(np.int64)
+        v = v * np.asarray([sx, sy], np.int64) + np.asarray([int(origin[0]), int(origin[1])], np.int64)
+        return [v[int(f):int(f) + int(n)] for f, n in zip(t[:, _H['hull_first']], t[:, _H['hull_n']])]
+
+    def _col(self, name):
+        return self.host()[:, _H[name]].astype(np.float64)       # every word is below 2^61; float64 is only the last step
+
+    def feret_max(self):
+        """the largest distance between two points of the region, sqrt(feret_sq), map pixels"""
+        return np.sqrt(self._col('feret_sq'))
+
+    def feret_min(self):
+        """the least caliper width, sqrt(width_num / width_den)"""
+        return np.sqrt(self._col('width_num') / self._col('width_den'))
+
+    def feret_orth(self):
+        """the extent at right angles to the longest diameter, orth_num / sqrt(feret_sq)"""
+        return self._col('orth_num') / np.sqrt(self._col('feret_sq'))
+
+    def feret_angle(self):
+        """radians of the longest diameter a -> b against x"""
+        t, v = self.host(), self.host_vertices().astype(np.int64)
+        d = v[t[:, _H['hull_first']] + t[:, _H['feret_b']]] - v[t[:, _H['hull_first']] + t[:, _H['feret_a']]]
+        return np.arctan2(d[:, 1].astype(np.float64), d[:, 0].astype(np.float64)).reshape(-1)
+
+    def hull_area(self):
+        return self._col('hull_area2') / 2
+
+    def solidity(self, area):
+        """area / hull_area, at most 1; area: the regions' areas (Regions.area or its host copy)"""
+        a = np.asarray(torch.as_tensor(area).cpu().numpy() if isinstance(area, torch.Tensor) else area, np.float64).reshape(-1)
+        return a / self.hull_area()
+
+    def hull_perimeter(self):
+        """the edge lengths summed in vertex order, float64"""
+        out = np.zeros(self.n, np.float64)
+        for k, p in enumerate(self.polygons()):
+            total = 0.0
+            for e in (np.roll(p, -1, 0) - p).tolist():
+                total += math.sqrt(e[0] * e[0] + e[1] * e[1])
+            out[k] = total
+        return out
+
+
+def _hulls(lib, region_ws, region_ws_bytes, tab, w, h, n_runs, n, dev, st, mark):
+    """the hull stages on a workspace of their own; one synchronisation: the vertex count sizes `vertices`"""
+    need = lib.wsi_regionhull_workspace_bytes(w, h, n_runs, n)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    counts = torch.zeros(2, dtype=torch.int32, device=dev)
+    mark('hull_rows')
+    native.check(lib.wsi_regionhull_rows(_ptr(region_ws), region_ws_bytes, _ptr(tab), w, h, n_runs, n, _ptr(ws), need, st), 'wsi_regionhull_rows')
+    mark('hull_rows')
+    mark('hull_chains')
+    native.check(lib.wsi_regionhull_chains(_ptr(ws), need, w, h, n_runs, n, _ptr(counts), st), 'wsi_regionhull_chains')
+    mark('hull_chains')
+    total, status = (int(v) for v in counts.tolist())             # the one synchronisation the hulls add
+    if status != 0 or not 4 * n <= total <= 2 * (n_runs + n):
+        raise RuntimeError('wsi_regionhull_chains: status %d, %d vertices for %d regions of %d runs' % (status, total, n, n_runs))
+    vertices = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    table = torch.empty((n, 16), dtype=torch.int64, device=dev)
+    mark('hull_emit')
+    native.check(lib.wsi_regionhull_emit(_ptr(ws), need, _ptr(tab), w, h, n_runs, n, total, _ptr(vertices), st), 'wsi_regionhull_emit')
+    mark('hull_emit')
+    mark('hull_measure')
+    native.check(lib.wsi_regionhull_measure(_ptr(ws), need, w, h, n_runs, n, _ptr(vertices), total, _ptr(table), st), 'wsi_regionhull_measure')
+    mark('hull_measure')
+    return Hulls(table, vertices)
+
+
+def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, workspace=None, stages=None, hulls=False):
     """Label a u8 (H, W) CUDA class map (unit column stride, any row stride and alignment) -> `Regions`.
     classes: None takes labels 1..255, an iterable of ints those labels (0 allowed).  connectivity: 4 or 8.  labels: also paint the
     (H, W) int32 label map (into `out` where given: int32, unit column stride, any row stride).  weight: a u8 map of the same shape
     whose sum per region goes into `wsum`.  workspace: a u8 tensor at least wsi_region_workspace_bytes large to work in.
     Two synchronisations: the run count sizes the workspace, the region count sizes the table.  A map without a traced pixel launches
-    nothing after the count.  stages: a dict that receives, per name of STAGES, the [begin, end] torch.cuda.Event pair of the stage."""
+    nothing after the count.  stages: a dict that receives, per name of STAGES, the [begin, end] torch.cuda.Event pair of the stage.
+    hulls: also the convex hull and the Feret diameters of every region, as `Regions.hulls` (a `Hulls`); one more synchronisation - the
+    vertex count sizes the vertex list - and the stages HULL_STAGES."""
     lib = native.load()
     if connectivity not in (4, 8):
         raise ValueError('connectivity %r is neither 4 nor 8' % (connectivity,))
@@ -142,7 +274,8 @@ def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, w
             lab = None
             if labels:
                 lab = torch.zeros((h, w), dtype=torch.int32, device=dev) if out is None else out.zero_()
-            return Regions(torch.zeros((0, 16), dtype=torch.int64, device=dev), lab, (w, h))
+            empty = Hulls(torch.zeros((0, 16), dtype=torch.int64, device=dev), torch.zeros((0, 2), dtype=torch.int32, device=dev)) if hulls else None
+            return Regions(torch.zeros((0, 16), dtype=torch.int64, device=dev), lab, (w, h), hulls=empty)
         workspace = take_workspace(workspace, lib.wsi_region_workspace_bytes(w, h, n_runs), dev)
         ws_bytes = int(workspace.numel())
         counts = torch.zeros(2, dtype=torch.int32, device=dev)
@@ -170,7 +303,8 @@ def label(m, classes=None, connectivity=8, labels=True, weight=None, out=None, w
             native.check(lib.wsi_region_paint(_ptr(workspace), ws_bytes, w, h, n_runs, _ptr(lab), 4 * (lab.stride(0) if h > 1 else w), st),
                          'wsi_region_paint')
             mark('paint')
-    return Regions(tab, lab, (w, h), n_runs)
+        made = _hulls(lib, workspace, ws_bytes, tab, w, h, n_runs, n, dev, st, mark) if hulls else None
+    return Regions(tab, lab, (w, h), n_runs, made)
 
 
 # ------------------------------------------------------------------------------------------------------------- what follows from it
@@ -236,6 +370,24 @@ def lesion_scores(pred, gt, classes=None, connectivity=8, iou=0.5, min_area=0):
     return score_dict(int(keep_p.sum()), int(keep_g.sum()), int((found_p & keep_p).sum()), int((found_g & keep_g).sum()))
 
 
+def bed_size(mask, step=1, mpp=None):
+    """The two dimensions a pathologist reports for the tumour bed, from a u8 (or bool) CUDA mask: of its largest region at connectivity 8
+    (ties: the smallest id) d1 = the largest diameter and d2 = the extent at right angles to it, in map pixels, with area, hull_area and
+    solidity; with mpp (microns per level-0 pixel; a map pixel is `step` of them) also d1_mm, d2_mm, area_mm2.  None on an empty mask."""
+    r = label(as_u8(mask, 'the mask'), None, 8, labels=False, hulls=True)
+    if r.n == 0:
+        return None
+    areas = r.host()[:, _F['area']]
+    k = int(np.argmax(areas))                                   # the first of the largest
+    h = r.hulls
+    area, hull_area = int(areas[k]), float(h.hull_area()[k])
+    out = dict(d1=float(h.feret_max()[k]), d2=float(h.feret_orth()[k]), area=area, hull_area=hull_area, solidity=area / hull_area)
+    if mpp is not None:
+        mm = int(step) * float(mpp) / 1000.0
+        out.update(d1_mm=out['d1'] * mm, d2_mm=out['d2'] * mm, area_mm2=area * mm * mm)
+    return out
+
+
 def heat_threshold(thresh):
     """heat / 255 >= thresh on u8 codes: heat >= ceil(thresh 255) (253 for 0.99)"""
     return int(math.ceil(255.0 * float(thresh) - 1e-9))
@@ -248,11 +400,11 @@ def slide_positive(heat_u8, thresh=0.99, open_k=50, min_fraction=0.0):
     return _slide_positive(heat_u8, thresh, open_k, min_fraction)[0]
 
 
-def _slide_positive(heat_u8, thresh, open_k, min_fraction):
+def _slide_positive(heat_u8, thresh, open_k, min_fraction, hulls=False):
     from . import postprocess as PP
     heat = as_u8(heat_u8, 'the heat map').contiguous()
     opened = PP.morph_rect((heat >= heat_threshold(thresh)).to(torch.uint8), open_k, 'open')
-    r = label(opened, None, 8, labels=False, weight=heat)
+    r = label(opened, None, 8, labels=False, weight=heat, **({'hulls': True} if hulls else {}))
     fraction = int(torch.count_nonzero(opened)) / opened.numel()
     return dict(positive=bool(fraction > min_fraction), fraction=float(fraction), n_regions=r.n,
                 largest_area=int(r.area.max()) if r.n else 0), r
